@@ -11,6 +11,11 @@ sharded by sample index and one RCCL collective per step combines the per-rank i
 Workload (config.workload): SURVEY.md 8(d) config 3 — 65 536 sample attempts per GPU per
 iteration, 2048x2048 occupancy grid at 0.1 m with 10 % blocked, 16 moving obstacles, 5 ribbons,
 TSP(K=2) heuristic; edges = root x kept samples x {rho 8, 16} x {2.5, 0.5 m/s}.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (value, ms_per_step);
+--dump-outputs DIR also writes the last timed step's outputs.  --full adds everything else: per-kernel
+times and roofline, the end-to-end copy legs, the CPU baseline with its parity gate, the first-goal
+check, the 64-open-vertex launch and the plan()-level legs.
 """
 import argparse
 import json
@@ -38,7 +43,7 @@ def parse_args():
     ap.add_argument("--total", type=int, default=262144, help="sample attempts per step over all GPUs with --strong")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--open-vertex-run", action="store_true",
-                    help="(default since round 4) also time the 64-open-vertex x 4096-sample launch of SURVEY config 3; "
+                    help="(part of every --full run since round 4) also time the 64-open-vertex x 4096-sample launch of SURVEY config 3; "
                          "PP_BENCH_PROFILED=1 (set by the rocprofv3 tools) leaves it and the plan()-level legs out")
     ap.add_argument("--no-plan-level", action="store_true", help="skip the 10 Hz replan loop (config 5) and the plan()-level CPU baseline")
     ap.add_argument("--replan-cycles", type=int, default=100)
@@ -47,7 +52,17 @@ def parse_args():
                          "the sampler skip over the lower ranks' slices included).  A projection of the worst rank's step, not a scaling curve")
     ap.add_argument("--of", type=int, default=8, metavar="N")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched ranks are stopped after this many seconds")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel times and roofline, the end-to-end copy legs, the CPU baseline and "
+                         "parity gate, the first-goal check, the 64-open-vertex launch and the plan()-level legs.  Without it the run sets "
+                         "up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its kept samples, its edge records "
+                         "field by field, the best (f, edge) key) as DIR/<name>.npy in float64")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -177,7 +192,7 @@ def run_rank(args):
     ctx.set_grid(w.grid, w.res)
     ctx.set_obstacles(w.obst)
     ctx.set_vertices(w.root(), w.ribbons4)
-    ctx.enable_timing(True)                  # HIP events between the kernels of a costing launch, on this stream
+    ctx.enable_timing(args.full)             # --full: HIP events between the kernels of a costing launch, on this stream
 
     max_edges = 4 * B
     d_res = torch.zeros(max_edges * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
@@ -227,27 +242,32 @@ def run_rank(args):
     marks[0].record(stream)
     # the library's HIP events between its kernels (six per costing launch: what roofline.kernels_ms is read from) are recorded in
     # the LAST eight timed steps only — each record is ~7 us of idle device between two kernels; PP_BENCH_EVENTS=all records them in
-    # every step, =0 in none
-    ev_mode = os.environ.get("PP_BENCH_EVENTS", "last8")
+    # every step, =0 in none.  The per-kernel times are --full's: a plain run records none
+    ev_mode = os.environ.get("PP_BENCH_EVENTS", "last8") if args.full else "0"
     timed_from = 0 if ev_mode == "all" else (args.steps if ev_mode == "0" else max(0, args.steps - 8))
     ctx.enable_timing(timed_from == 0)
     for k in range(args.steps):
         if k == timed_from and k > 0:
             ctx.enable_timing(True)
-        edges += step()
+        ne_last = step()
+        edges += ne_last
         marks[k + 1].record(stream)
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
     step_ms = np.array([marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)])
-    # (solve, pose, cover, heuristic) ms of the last timed steps' launches, from the HIP events the library recorded between its
-    # kernels on this stream inside the timed region (a ring of 8 sets: read back here, so no step waited for its own events)
-    for back in range(min(args.steps - timed_from, 8)):
-        kernel_events.append(ctx.past_timing(back))
-    ctx.enable_timing(True)
-    if not kernel_events:                                   # (PP_BENCH_EVENTS=0: one launch after the clock has stopped, for the breakdown)
-        step(); ctx.synchronize()
-        kernel_events.append(ctx.past_timing(0))
+    if args.dump_outputs and rank == 0:     # (before anything else runs on the device: d_res and d_key2 are the last timed step's)
+        dump_outputs(args.dump_outputs, ctx.get_samples(), d_res[: ne_last * RESULT_DTYPE.itemsize].cpu().numpy().view(RESULT_DTYPE),
+                     d_key2.cpu().numpy().view(np.uint64))
+    if args.full:
+        # (solve, pose, cover, heuristic) ms of the last timed steps' launches, from the HIP events the library recorded between its
+        # kernels on this stream inside the timed region (a ring of 8 sets: read back here, so no step waited for its own events)
+        for back in range(min(args.steps - timed_from, 8)):
+            kernel_events.append(ctx.past_timing(back))
+        ctx.enable_timing(True)
+        if not kernel_events:                               # (PP_BENCH_EVENTS=0: one launch after the clock has stopped, for the breakdown)
+            step(); ctx.synchronize()
+            kernel_events.append(ctx.past_timing(0))
 
     tot = torch.tensor([float(edges), elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
     if world > 1 or use_comm:
@@ -259,149 +279,99 @@ def run_rank(args):
     else:
         total_edges, t = float(edges), elapsed
 
-    # end to end: the same step followed by the D2H copy of its records into pinned host memory (the host A* needs
-    # all of them).  Its own loop after the timed region; never part of `value`.
-    e2e_ms = None
-    if rank == 0:
-        h_res = torch.empty(max_edges * RESULT_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
-    fence()
-    n_e2e = max(1, min(args.steps, 10))
-    t0 = time.perf_counter()
-    for _ in range(n_e2e):
-        ne = step()
+    # the end-to-end legs (--full only: they are not the headline)
+    e2e_ms = e2e_pipe_ms = e2e_sdma_ms = e2e_sdma_err = copy_alone_ms = None
+    if args.full:
+        # end to end: the same step followed by the D2H copy of its records into pinned host memory (the host A* needs
+        # all of them).  Its own loop after the timed region; never part of `value`.
         if rank == 0:
-            h_res[: ne * RESULT_DTYPE.itemsize].copy_(d_res[: ne * RESULT_DTYPE.itemsize], non_blocking=True)
-            stream.synchronize()
-    fence()
-    if rank == 0:
-        e2e_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
-    # the same with the copy of step i overlapped with step i + 1 ("overlap D2H with the next batch"): two record
-    # buffers, the copies on a second stream
-    e2e_pipe_ms = None
-    fence()
-    if rank == 0:
-        d_res2 = torch.zeros_like(d_res)
-        h_res2 = torch.empty_like(h_res).pin_memory()
-        copy_stream = torch.cuda.Stream(dev)
-        bufs, hbufs = [d_res, d_res2], [h_res, h_res2]
-        copied = [None, None]
-    t0 = time.perf_counter()
-    for i in range(n_e2e):
+            h_res = torch.empty(max_edges * RESULT_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        fence()
+        n_e2e = max(1, min(args.steps, 10))
+        t0 = time.perf_counter()
+        for _ in range(n_e2e):
+            ne = step()
+            if rank == 0:
+                h_res[: ne * RESULT_DTYPE.itemsize].copy_(d_res[: ne * RESULT_DTYPE.itemsize], non_blocking=True)
+                stream.synchronize()
+        fence()
         if rank == 0:
-            b = i & 1
-            if copied[b] is not None:
-                stream.wait_event(copied[b])                 # the copy that read this buffer two steps ago
-            ne = step(bufs[b])
-            done = torch.cuda.Event(); done.record(stream)
-            copy_stream.wait_event(done)
-            with torch.cuda.stream(copy_stream):
-                hbufs[b][: ne * RESULT_DTYPE.itemsize].copy_(bufs[b][: ne * RESULT_DTYPE.itemsize], non_blocking=True)
-                copied[b] = torch.cuda.Event(); copied[b].record(copy_stream)
-        else:
-            step()
-    if rank == 0:
-        copy_stream.synchronize()
-    fence()
-    if rank == 0:
-        e2e_pipe_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
-    # ... and with the copy of step i on an SDMA engine (ppgpu_copy_engine_read: hsa_amd_memory_async_copy) while step i + 1 runs.
-    # The hipMemcpyAsync of the two loops above runs as a blit KERNEL (__amd_rocclr_copyBuffer) whatever the SDMA settings say:
-    # tools/copy_engine_ab.sh, profiles/r04_copy_engine.txt.
-    e2e_sdma_ms, e2e_sdma_err = None, None
-    fence()
-    t0 = time.perf_counter()
-    for i in range(n_e2e):
+            e2e_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
+        # the same with the copy of step i overlapped with step i + 1 ("overlap D2H with the next batch"): two record
+        # buffers, the copies on a second stream
+        fence()
+        if rank == 0:
+            d_res2 = torch.zeros_like(d_res)
+            h_res2 = torch.empty_like(h_res).pin_memory()
+            copy_stream = torch.cuda.Stream(dev)
+            bufs, hbufs = [d_res, d_res2], [h_res, h_res2]
+            copied = [None, None]
+        t0 = time.perf_counter()
+        for i in range(n_e2e):
+            if rank == 0:
+                b = i & 1
+                if copied[b] is not None:
+                    stream.wait_event(copied[b])                 # the copy that read this buffer two steps ago
+                ne = step(bufs[b])
+                done = torch.cuda.Event(); done.record(stream)
+                copy_stream.wait_event(done)
+                with torch.cuda.stream(copy_stream):
+                    hbufs[b][: ne * RESULT_DTYPE.itemsize].copy_(bufs[b][: ne * RESULT_DTYPE.itemsize], non_blocking=True)
+                    copied[b] = torch.cuda.Event(); copied[b].record(copy_stream)
+            else:
+                step()
+        if rank == 0:
+            copy_stream.synchronize()
+        fence()
+        if rank == 0:
+            e2e_pipe_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
+        # ... and with the copy of step i on an SDMA engine (ppgpu_copy_engine_read: hsa_amd_memory_async_copy) while step i + 1 runs.
+        # The hipMemcpyAsync of the two loops above runs as a blit KERNEL (__amd_rocclr_copyBuffer) whatever the SDMA settings say:
+        # tools/copy_engine_ab.sh, profiles/r04_copy_engine.txt.
+        fence()
+        t0 = time.perf_counter()
+        for i in range(n_e2e):
+            if rank == 0 and e2e_sdma_err is None:
+                try:
+                    b = i & 1
+                    n_kept = step_sample()                       # (its host wait also means: the records of step i - 1 are complete)
+                    # the bulk copy of step i - 1 is issued AFTER this step's small count read-back, not before: issued first it kept that
+                    # read-back waiting behind 30 MB on the engine, and the step with it (2.53 ms per step that way)
+                    if i > 0:
+                        ctx.copy_engine_read(hbufs[1 - b].data_ptr(), bufs[1 - b].data_ptr(), ne * RESULT_DTYPE.itemsize)
+                    ne = step_cost(n_kept, bufs[b])
+                except Exception as e:                           # the bench line must not depend on this leg
+                    e2e_sdma_err = repr(e)
+            else:
+                step()
         if rank == 0 and e2e_sdma_err is None:
             try:
-                b = i & 1
-                n_kept = step_sample()                       # (its host wait also means: the records of step i - 1 are complete)
-                # the bulk copy of step i - 1 is issued AFTER this step's small count read-back, not before: issued first it kept that
-                # read-back waiting behind 30 MB on the engine, and the step with it (2.53 ms per step that way)
-                if i > 0:
-                    ctx.copy_engine_read(hbufs[1 - b].data_ptr(), bufs[1 - b].data_ptr(), ne * RESULT_DTYPE.itemsize)
-                ne = step_cost(n_kept, bufs[b])
-            except Exception as e:                           # the bench line must not depend on this leg
+                ctx.synchronize()
+                ctx.copy_engine_read(hbufs[(n_e2e - 1) & 1].data_ptr(), bufs[(n_e2e - 1) & 1].data_ptr(), ne * RESULT_DTYPE.itemsize)   # the last step's records
+                ctx.copy_engine_wait()
+            except Exception as e:
                 e2e_sdma_err = repr(e)
-        else:
-            step()
-    if rank == 0 and e2e_sdma_err is None:
-        try:
-            ctx.synchronize()
-            ctx.copy_engine_read(hbufs[(n_e2e - 1) & 1].data_ptr(), bufs[(n_e2e - 1) & 1].data_ptr(), ne * RESULT_DTYPE.itemsize)   # the last step's records
-            ctx.copy_engine_wait()
-        except Exception as e:
-            e2e_sdma_err = repr(e)
-    fence()
-    copy_alone_ms = None
-    if rank == 0 and e2e_sdma_err is None:
-        e2e_sdma_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
-        e2e_sdma_ok = bool(torch.equal(hbufs[(n_e2e - 1) & 1][: ne * RESULT_DTYPE.itemsize], bufs[(n_e2e - 1) & 1][: ne * RESULT_DTYPE.itemsize].cpu()))   # (after the clock)
-        # the two copies on their own (nothing else on the device): the blit kernel and the SDMA engine
-        nb = ne * RESULT_DTYPE.itemsize
-        tt = []
-        for _ in range(3):
-            t1 = time.perf_counter(); hbufs[0][:nb].copy_(bufs[0][:nb], non_blocking=True); stream.synchronize(); tt.append(time.perf_counter() - t1)
-        ts = []
-        for _ in range(3):
-            t1 = time.perf_counter(); ctx.copy_engine_read(hbufs[0].data_ptr(), bufs[0].data_ptr(), nb); ctx.copy_engine_wait(); ts.append(time.perf_counter() - t1)
-        copy_alone_ms = {"bytes": nb, "hipMemcpyAsync_blit_kernel_ms": 1e3 * min(tt), "copy_engine_sdma_ms": 1e3 * min(ts),
-                         "GBps": {"blit": nb / min(tt) / 1e9, "sdma": nb / min(ts) / 1e9}}
+        fence()
+        if rank == 0 and e2e_sdma_err is None:
+            e2e_sdma_ms = 1e3 * (time.perf_counter() - t0) / n_e2e
+            e2e_sdma_ok = bool(torch.equal(hbufs[(n_e2e - 1) & 1][: ne * RESULT_DTYPE.itemsize], bufs[(n_e2e - 1) & 1][: ne * RESULT_DTYPE.itemsize].cpu()))   # (after the clock)
+            # the two copies on their own (nothing else on the device): the blit kernel and the SDMA engine
+            nb = ne * RESULT_DTYPE.itemsize
+            tt = []
+            for _ in range(3):
+                t1 = time.perf_counter(); hbufs[0][:nb].copy_(bufs[0][:nb], non_blocking=True); stream.synchronize(); tt.append(time.perf_counter() - t1)
+            ts = []
+            for _ in range(3):
+                t1 = time.perf_counter(); ctx.copy_engine_read(hbufs[0].data_ptr(), bufs[0].data_ptr(), nb); ctx.copy_engine_wait(); ts.append(time.perf_counter() - t1)
+            copy_alone_ms = {"bytes": nb, "hipMemcpyAsync_blit_kernel_ms": 1e3 * min(tt), "copy_engine_sdma_ms": 1e3 * min(ts),
+                             "GBps": {"blit": nb / min(tt) / 1e9, "sdma": nb / min(ts) / 1e9}}
 
     if rank == 0:
-        solve_ms, pose_ms, cover_ms, heur_ms = [float(x) for x in np.mean(np.array(kernel_events), axis=0)]
-        kern_ms = cover_ms                                               # pp_k_cover_sweep (+ pp_k_cover_finish, its lane-per-edge second half), the dominant kernel
-        launch_ms = solve_ms + pose_ms + cover_ms + heur_ms
-        res = d_res.cpu().numpy().view(RESULT_DTYPE)[: edges // args.steps]
-        n_edges_launch = len(res)
-        steps_mean = float((res["info"] >> 16).mean())
-        feas_frac = float(((res["flags"] & F_INFEASIBLE) == 0).mean())
+        key = d_key2.cpu().numpy().view(np.uint64)
+        best = {"best_f": float(np.array([key[0]], dtype=np.uint64).view(np.float64)[0]), "best_edge": int(key[1])}
+        n_edges_launch = edges // args.steps
         M = 0 if w.obst is None else len(w.obst)
         R = len(w.ribbons4)
-        # algorithmic bytes / flops per edge with the MEASURED mean step count
-        bytes_per_edge = 88 + 32 + 32 * R + 56 * M / 4.0 + 150 + steps_mean / 8.0
-        flops_per_edge = 1000 + steps_mean * (70 + 21 * M) + 4e4        # solve + sweeps + heuristic
-        cover_edges = ctx.last_cover_edges()
-        # "roofline.achieved must be F x edges/s / fp64-vector peak": F x the edges of one costing launch over the
-        # launch's kernel time (HIP events, live).  F is the survey's model of the reference's arithmetic, not a counter.
-        ach_tf = flops_per_edge * n_edges_launch / (launch_ms * 1e-3) / 1e12
-        hbm_model_gbs = bytes_per_edge * n_edges_launch / (launch_ms * 1e-3) / 1e9
-        cover_gbs = bytes_per_edge * cover_edges / (kern_ms * 1e-3) / 1e9
-        traffic = None
-        per_kernel = None
-        sweep_hbm = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")   # written from separate rocprofv3 --pmc passes (tools/traffic.sh)
-        # the PMC passes ran the default per-GPU workload (config 3: 65 536 attempts per step): their per-launch figures say nothing
-        # about a --strong slice or another batch size
-        counters_apply = (not args.strong) and args.batch == 65536
-        if counters_apply and os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                # the counters describe THIS run only if the kernel sources are still the ones they were measured on
-                if tj.get("kernel_sources_sha256") != kernel_sources_sha256():
-                    raise ValueError("profiles/traffic.json was measured on other kernel sources")
-                traffic = tj.get("hbm_bytes_per_costing_launch", tj.get("hbm_bytes_per_launch"))
-                per_kernel = {k: v.get("fetch_size_bytes", 0.0) + v.get("write_size_bytes", 0.0) for k, v in tj["kernels"].items()}
-                # "achieved HBM GB/s on the collision sweep against the chip's peak" (BASELINE north_star): counter bytes of the
-                # pose sweep (collision checks) over its live kernel time.  Low is good here: the sweep is ALU-bound.
-                nbytes = sum(per_kernel.get(k, 0.0) for k in ("pp_k_plan_skips", "pp_k_pose_sweep"))
-                sweep_hbm = {"kernel": "pp_k_plan_skips+pp_k_pose_sweep", "pmc_bytes_per_launch": nbytes, "GBps": nbytes / (pose_ms * 1e-3) / 1e9,
-                             "frac_of_peak": nbytes / (pose_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            except Exception:
-                traffic = per_kernel = sweep_hbm = None
-        # counter-anchored utilisation: profiles/valu.json from its own rocprofv3 --pmc pass (tools/valu.sh),
-        # stamped with the kernel sources it was measured on
-        valu = None
-        vp = os.path.join(ROOT, "profiles", "valu.json")
-        if counters_apply and os.path.exists(vp):
-            try:
-                vj = json.load(open(vp))
-                if vj.get("kernel_sources_sha256") != kernel_sources_sha256():
-                    raise ValueError("profiles/valu.json was measured on other kernel sources")
-                valu = vj
-            except Exception:
-                valu = None
-        key = d_key2.cpu().numpy().view(np.uint64)
-        alg_bytes_launch = bytes_per_edge * n_edges_launch
         out = {
             "metric": "Dubins edges costed/sec on 2048x2048 grid",
             "value": total_edges / t,
@@ -413,15 +383,6 @@ def run_rank(args):
             "ms_per_step_median": float(np.median(step_ms)),
             "ms_per_step_p99": float(np.percentile(step_ms, 99)),
             "ms_per_step_slowest": {"ms": float(step_ms.max()), "index": int(step_ms.argmax())},     # (which timed step, by stream events)
-            "e2e_ms_per_step": e2e_ms,
-            "e2e_pipelined_ms_per_step": e2e_pipe_ms,
-            "e2e_copy_engine_ms_per_step": e2e_sdma_ms,
-            "records_copy_alone": copy_alone_ms,
-            **({"e2e_copy_engine_error": e2e_sdma_err} if e2e_sdma_err else {"e2e_copy_engine_bytes_verified": e2e_sdma_ok}),
-            "e2e_note": f"rank 0, {n_e2e} further steps after the timed region, each followed by the D2H copy of its records "
-                        f"({n_edges_launch * RESULT_DTYPE.itemsize / 1e6:.1f} MB) into pinned host memory; pipelined: the copy of step i on a second stream "
-                        f"while step i + 1 runs (two record buffers) - hipMemcpyAsync runs as a blit kernel on the CUs here; copy_engine: the same "
-                        f"overlap with the copy on an SDMA engine (ppgpu_copy_engine_read); never part of value",
             "higher_is_better": True,
             "scaling": "strong" if args.strong else "weak",
             "vs_baseline": None,
@@ -436,59 +397,121 @@ def run_rank(args):
                        "ribbons": R, "heuristic": "TspPointRobotNoSplitKRibbons K=2",
                        "edges_per_iter_per_gpu": n_edges_launch,
                        "sharding": "sample batch split by rank; one RCCL collective per iteration (ppgpu_allreduce_best: all-gather of 16 B per rank + local min)"},
-            "roofline": {"bound": "fp64_valu", "achieved": ach_tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach_tf / FP64_VECTOR_PEAK_TFLOPS,
-                         "achieved_is": "SURVEY 8(d): algorithmic flops per edge F (model of the reference's arithmetic with the measured mean step count) "
-                                        "x edges of one costing launch / the launch's kernel time, measured live with HIP events between the kernels.  "
-                                        "F counts what the REFERENCE does per edge; the kernels skip chunks and cull obstacles exactly, so frac is not "
-                                        "hardware utilisation and can exceed 1 - valu_issue_frac (counters) is the utilisation figure",
-                         "valu_issue_frac": (valu or {}).get("valu_issue_frac"),
-                         "executed_to_model_flops": ((valu["executed_lane_ops_per_launch"] / (flops_per_edge * n_edges_launch)) if valu else None),
-                         "valu_is": ("profiles/valu.json (rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU and, in its own pass, GRBM_GUI_ACTIVE on these kernel sources, "
-                                     "tools/valu.sh): valu_issue_frac = sum over the costing kernels of SQ_ACTIVE_INST_VALU x 4 (the counter counts quad-cycles) / "
-                                     "(1 024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs); executed = SQ_INSTS_VALU x 64 lanes, an upper bound of the lanes doing arithmetic"
-                                     if valu else ("null: no VALU counter pass on these kernel sources (tools/valu.sh)" if counters_apply else
-                                                   "null: the PMC passes measured the default per-GPU workload (config 3), not this one")),
-                         "valu_per_kernel": (valu or {}).get("kernels"),
-                         "algorithmic_flops_per_edge": flops_per_edge,
-                         "kernel": "the costing launch (pp_k_solve_edges .. pp_k_heuristic_lanes); dominant kernel pp_k_cover_sweep (kernel_ms includes pp_k_cover_finish, which ends its edges one lane each)",
-                         "launch_ms": launch_ms, "kernel_ms": kern_ms, "edges_in_kernel": cover_edges,
-                         "kernels_ms": {"pp_k_solve_edges": solve_ms, "pp_k_plan_skips+pp_k_pose_sweep": pose_ms, "pp_k_cover_sweep+pp_k_cover_finish": cover_ms,
-                                        "others": heur_ms},
-                         "kernels_note": "HIP events between the kernels of each costing launch of the timed region's last 8 steps (recorded in those steps only: a record is ~7 us of idle device between two kernels); "
-                                         "'others' = pp_k_approach_events (finishes the edges whose coverage state machine has nothing to do: "
-                                         "edges_in_kernel is what is left for the cover sweep) + pp_k_deferred_list + pp_k_heuristic_lanes (beside it, on a second stream, "
-                                         "pp_k_heuristic_listed) + pp_k_heuristic_big; the four add up to the launch",
-                         "traffic": traffic,
-                         "traffic_is": ("PMC bytes per costing launch from profiles/traffic.json, measured on these kernel sources"
-                                        if traffic is not None else ("null: no PMC pass on these kernel sources (tools/traffic.sh)" if counters_apply else
-                                                                    "null: the PMC passes measured the default per-GPU workload (config 3), not this one")),
-                         "hbm": {"bound": "hbm", "achieved": hbm_model_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_model_gbs / HBM_PEAK_GBS,
-                                 "achieved_is": "algorithmic bytes per edge (model, SURVEY 8d) x edges of the launch / launch_ms",
-                                 "algorithmic_bytes_per_edge": bytes_per_edge, "algorithmic_bytes_per_launch": alg_bytes_launch,
-                                 "counter_bytes_per_launch": traffic,
-                                 "counter_to_algorithmic": (traffic / alg_bytes_launch if traffic else None),
-                                 "counter_GBps": (traffic / (launch_ms * 1e-3) / 1e9 if traffic else None),
-                                 "counter_bytes_per_kernel": per_kernel,
-                                 "cover_sweep": {"achieved": cover_gbs, "frac": cover_gbs / HBM_PEAK_GBS,
-                                                 "achieved_is": "algorithmic bytes of the edges pp_k_cover_sweep visited / its own time"},
-                                 "collision_sweep": sweep_hbm,
-                                 "note": "reported because BASELINE's north_star asks for it; the path is fp64-VALU bound (SURVEY 8d: 630 flop/B "
-                                         "against a machine balance of 10), so for HBM lower is better"}},
-            "workload_stats": {"mean_sweep_steps_per_edge": steps_mean, "feasible_fraction": feas_frac,
-                               "kernel_edges_per_s": n_edges_launch / (launch_ms * 1e-3),
-                               "best_f": float(np.array([key[0]], dtype=np.uint64).view(np.float64)[0]), "best_edge": int(key[1])},
+            "workload_stats": best,
         }
+        if args.full:
+            solve_ms, pose_ms, cover_ms, heur_ms = [float(x) for x in np.mean(np.array(kernel_events), axis=0)]
+            kern_ms = cover_ms                                               # pp_k_cover_sweep (+ pp_k_cover_finish, its lane-per-edge second half), the dominant kernel
+            launch_ms = solve_ms + pose_ms + cover_ms + heur_ms
+            res = d_res.cpu().numpy().view(RESULT_DTYPE)[: edges // args.steps]
+            steps_mean = float((res["info"] >> 16).mean())
+            feas_frac = float(((res["flags"] & F_INFEASIBLE) == 0).mean())
+            # algorithmic bytes / flops per edge with the MEASURED mean step count
+            bytes_per_edge = 88 + 32 + 32 * R + 56 * M / 4.0 + 150 + steps_mean / 8.0
+            flops_per_edge = 1000 + steps_mean * (70 + 21 * M) + 4e4        # solve + sweeps + heuristic
+            cover_edges = ctx.last_cover_edges()
+            # "roofline.achieved must be F x edges/s / fp64-vector peak": F x the edges of one costing launch over the
+            # launch's kernel time (HIP events, live).  F is the survey's model of the reference's arithmetic, not a counter.
+            ach_tf = flops_per_edge * n_edges_launch / (launch_ms * 1e-3) / 1e12
+            hbm_model_gbs = bytes_per_edge * n_edges_launch / (launch_ms * 1e-3) / 1e9
+            cover_gbs = bytes_per_edge * cover_edges / (kern_ms * 1e-3) / 1e9
+            traffic = None
+            per_kernel = None
+            sweep_hbm = None
+            tp = os.path.join(ROOT, "profiles", "traffic.json")   # written from separate rocprofv3 --pmc passes (tools/traffic.sh)
+            # the PMC passes ran the default per-GPU workload (config 3: 65 536 attempts per step): their per-launch figures say nothing
+            # about a --strong slice or another batch size
+            counters_apply = (not args.strong) and args.batch == 65536
+            if counters_apply and os.path.exists(tp):
+                try:
+                    tj = json.load(open(tp))
+                    # the counters describe THIS run only if the kernel sources are still the ones they were measured on
+                    if tj.get("kernel_sources_sha256") != kernel_sources_sha256():
+                        raise ValueError("profiles/traffic.json was measured on other kernel sources")
+                    traffic = tj.get("hbm_bytes_per_costing_launch", tj.get("hbm_bytes_per_launch"))
+                    per_kernel = {k: v.get("fetch_size_bytes", 0.0) + v.get("write_size_bytes", 0.0) for k, v in tj["kernels"].items()}
+                    # "achieved HBM GB/s on the collision sweep against the chip's peak" (BASELINE north_star): counter bytes of the
+                    # pose sweep (collision checks) over its live kernel time.  Low is good here: the sweep is ALU-bound.
+                    nbytes = sum(per_kernel.get(k, 0.0) for k in ("pp_k_plan_skips", "pp_k_pose_sweep"))
+                    sweep_hbm = {"kernel": "pp_k_plan_skips+pp_k_pose_sweep", "pmc_bytes_per_launch": nbytes, "GBps": nbytes / (pose_ms * 1e-3) / 1e9,
+                                 "frac_of_peak": nbytes / (pose_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                except Exception:
+                    traffic = per_kernel = sweep_hbm = None
+            # counter-anchored utilisation: profiles/valu.json from its own rocprofv3 --pmc pass (tools/valu.sh),
+            # stamped with the kernel sources it was measured on
+            valu = None
+            vp = os.path.join(ROOT, "profiles", "valu.json")
+            if counters_apply and os.path.exists(vp):
+                try:
+                    vj = json.load(open(vp))
+                    if vj.get("kernel_sources_sha256") != kernel_sources_sha256():
+                        raise ValueError("profiles/valu.json was measured on other kernel sources")
+                    valu = vj
+                except Exception:
+                    valu = None
+            alg_bytes_launch = bytes_per_edge * n_edges_launch
+            out.update({
+                "e2e_ms_per_step": e2e_ms,
+                "e2e_pipelined_ms_per_step": e2e_pipe_ms,
+                "e2e_copy_engine_ms_per_step": e2e_sdma_ms,
+                "records_copy_alone": copy_alone_ms,
+                **({"e2e_copy_engine_error": e2e_sdma_err} if e2e_sdma_err else {"e2e_copy_engine_bytes_verified": e2e_sdma_ok}),
+                "e2e_note": f"rank 0, {n_e2e} further steps after the timed region, each followed by the D2H copy of its records "
+                            f"({n_edges_launch * RESULT_DTYPE.itemsize / 1e6:.1f} MB) into pinned host memory; pipelined: the copy of step i on a second stream "
+                            f"while step i + 1 runs (two record buffers) - hipMemcpyAsync runs as a blit kernel on the CUs here; copy_engine: the same "
+                            f"overlap with the copy on an SDMA engine (ppgpu_copy_engine_read); never part of value",
+                "roofline": {"bound": "fp64_valu", "achieved": ach_tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach_tf / FP64_VECTOR_PEAK_TFLOPS,
+                             "achieved_is": "SURVEY 8(d): algorithmic flops per edge F (model of the reference's arithmetic with the measured mean step count) "
+                                            "x edges of one costing launch / the launch's kernel time, measured live with HIP events between the kernels.  "
+                                            "F counts what the REFERENCE does per edge; the kernels skip chunks and cull obstacles exactly, so frac is not "
+                                            "hardware utilisation and can exceed 1 - valu_issue_frac (counters) is the utilisation figure",
+                             "valu_issue_frac": (valu or {}).get("valu_issue_frac"),
+                             "executed_to_model_flops": ((valu["executed_lane_ops_per_launch"] / (flops_per_edge * n_edges_launch)) if valu else None),
+                             "valu_is": ("profiles/valu.json (rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU and, in its own pass, GRBM_GUI_ACTIVE on these kernel sources, "
+                                         "tools/valu.sh): valu_issue_frac = sum over the costing kernels of SQ_ACTIVE_INST_VALU x 4 (the counter counts quad-cycles) / "
+                                         "(1 024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs); executed = SQ_INSTS_VALU x 64 lanes, an upper bound of the lanes doing arithmetic"
+                                         if valu else ("null: no VALU counter pass on these kernel sources (tools/valu.sh)" if counters_apply else
+                                                       "null: the PMC passes measured the default per-GPU workload (config 3), not this one")),
+                             "valu_per_kernel": (valu or {}).get("kernels"),
+                             "algorithmic_flops_per_edge": flops_per_edge,
+                             "kernel": "the costing launch (pp_k_solve_edges .. pp_k_heuristic_lanes); dominant kernel pp_k_cover_sweep (kernel_ms includes pp_k_cover_finish, which ends its edges one lane each)",
+                             "launch_ms": launch_ms, "kernel_ms": kern_ms, "edges_in_kernel": cover_edges,
+                             "kernels_ms": {"pp_k_solve_edges": solve_ms, "pp_k_plan_skips+pp_k_pose_sweep": pose_ms, "pp_k_cover_sweep+pp_k_cover_finish": cover_ms,
+                                            "others": heur_ms},
+                             "kernels_note": "HIP events between the kernels of each costing launch of the timed region's last 8 steps (recorded in those steps only: a record is ~7 us of idle device between two kernels); "
+                                             "'others' = pp_k_approach_events (finishes the edges whose coverage state machine has nothing to do: "
+                                             "edges_in_kernel is what is left for the cover sweep) + pp_k_deferred_list + pp_k_heuristic_lanes (beside it, on a second stream, "
+                                             "pp_k_heuristic_listed) + pp_k_heuristic_big; the four add up to the launch",
+                             "traffic": traffic,
+                             "traffic_is": ("PMC bytes per costing launch from profiles/traffic.json, measured on these kernel sources"
+                                            if traffic is not None else ("null: no PMC pass on these kernel sources (tools/traffic.sh)" if counters_apply else
+                                                                        "null: the PMC passes measured the default per-GPU workload (config 3), not this one")),
+                             "hbm": {"bound": "hbm", "achieved": hbm_model_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_model_gbs / HBM_PEAK_GBS,
+                                     "achieved_is": "algorithmic bytes per edge (model, SURVEY 8d) x edges of the launch / launch_ms",
+                                     "algorithmic_bytes_per_edge": bytes_per_edge, "algorithmic_bytes_per_launch": alg_bytes_launch,
+                                     "counter_bytes_per_launch": traffic,
+                                     "counter_to_algorithmic": (traffic / alg_bytes_launch if traffic else None),
+                                     "counter_GBps": (traffic / (launch_ms * 1e-3) / 1e9 if traffic else None),
+                                     "counter_bytes_per_kernel": per_kernel,
+                                     "cover_sweep": {"achieved": cover_gbs, "frac": cover_gbs / HBM_PEAK_GBS,
+                                                     "achieved_is": "algorithmic bytes of the edges pp_k_cover_sweep visited / its own time"},
+                                     "collision_sweep": sweep_hbm,
+                                     "note": "reported because BASELINE's north_star asks for it; the path is fp64-VALU bound (SURVEY 8d: 630 flop/B "
+                                             "against a machine balance of 10), so for HBM lower is better"}},
+                "workload_stats": {"mean_sweep_steps_per_edge": steps_mean, "feasible_fraction": feas_frac,
+                                   "kernel_edges_per_s": n_edges_launch / (launch_ms * 1e-3), **best},
+            })
         profiled = os.environ.get("PP_BENCH_PROFILED") == "1"     # under rocprofv3 (tools/*.sh): only the headline launches
         if args.as_rank is not None:
             out["as_rank"] = {"rank": emu_rank, "of": emu_world, "attempts_skipped_per_step": sharding.shard_attempts(total_attempts, emu_rank, emu_world)[0],
                               "note": "ONE GPU playing rank R of N: its slice of the batch and the sampler skip over the lower ranks' slices, no "
                                       "communicator, no collective.  A projection of that rank's step time, not a measured scaling curve"}
-        if world == 1 and not args.no_cpu_baseline and args.as_rank is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.as_rank is None:
             out.update(cpu_baseline_and_parity(ctx, w, res))
             out.update(first_goal_check())
-        if world == 1 and not profiled and args.as_rank is None:
+        if args.full and world == 1 and not profiled and args.as_rank is None:
             out.update(open_vertex_run(ctx, w, torch, dev))
-        if world == 1 and not profiled and not args.no_plan_level and args.as_rank is None:
+        if args.full and world == 1 and not profiled and not args.no_plan_level and args.as_rank is None:
             out.update(plan_level(args.replan_cycles, cpu_baseline=not args.no_cpu_baseline))
         print(json.dumps(out), flush=True)
     if world > 1 or use_comm:
@@ -511,6 +534,35 @@ def kernel_sources_sha256():
     for f in KERNEL_SOURCES:
         h.update(open(os.path.join(ROOT, "path_planner_amd", "csrc", f), "rb").read())
     return h.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, samples, res, key):
+    """--dump-outputs DIR: what the last timed step handed back, as float64 .npy files: samples.npy (the kept samples, x y heading
+    speed time), edge_<field>.npy (one per field of the step's edge records, in edge order; edge_param.npy is n x 3), best_f.npy /
+    best_edge.npy (the step's incumbent key) and sample_index.npy / edge_index.npy (which rows were written).  The inputs are fixed
+    by the arguments, so two builds can be compared file by file.  At most DUMP_LIMIT_BYTES in all: rows beyond it are thinned to a
+    fixed, seeded sample (the default workload fits whole)."""
+    import numpy as np
+
+    def rows(n, row_bytes, budget, seed):
+        if n * row_bytes <= budget:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(seed).choice(n, size=budget // row_bytes, replace=False))
+
+    fields = res.dtype.names
+    edge_row = 8 * (1 + sum(int(np.prod(res.dtype[f].shape)) for f in fields))        # (+ its index)
+    si = rows(len(samples), 8 * 6, DUMP_LIMIT_BYTES // 8, 1)
+    ei = rows(len(res), edge_row, DUMP_LIMIT_BYTES - 8 * 6 * len(si) - 4096, 2)
+    os.makedirs(dirname, exist_ok=True)
+    out = {"samples": samples[si], "sample_index": si, "edge_index": ei,
+           "best_f": key[:1].view(np.float64), "best_edge": key[1:2]}
+    for f in fields:
+        out["edge_" + f] = res[f][ei]
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def open_vertex_run(ctx, w, torch, dev):

@@ -6,7 +6,9 @@ stored (doubles as C99 hex strings, so they round-trip bit-exactly); no referenc
 
 Run in the build container only (the reference tree does not travel):  python tests/golden/make_golden.py
 """
+import hashlib
 import json
+import math
 import os
 import sys
 import tempfile
@@ -159,6 +161,65 @@ def state_cases(rng, n):
     return cases
 
 
+def ribbons_digest(a):
+    """First 16 hex digits of the SHA-256 of a ribbon list's float64 bytes (test_golden.py computes the same)."""
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 4).tobytes()).hexdigest()[:16]
+
+
+def cover_sequence_cases():
+    """test_golden.py's 60 random cover sequences (seed 7, 40 covers each): RibbonManager::cover (RibbonManager.cpp:14-22)
+    restated with the reference's own Ribbon::split / covered.  Per step the list's length and digest: the lists themselves
+    would be 2 MB.  The points are not stored: the test draws them from the same generator and the list it has reached."""
+    rng = np.random.default_rng(7)
+    trials = []
+    for trial in range(60):
+        w = [1.5, 2.0][trial % 2]
+        REF.ref_set_ribbon_width(w)
+        ribs = [list(rng.uniform(0, 60, 4)) for _ in range(4)]
+        ribs = [r for r in ribs if math.hypot(r[2] - r[0], r[3] - r[1]) >= 2 * w]
+        theirs = [np.array(r) for r in ribs]
+        steps = []
+        for step in range(40):
+            i = int(rng.integers(0, max(len(theirs), 1)))
+            if theirs:
+                r = theirs[i]
+                t = rng.uniform(0, 1)
+                p = r[:2] + t * (r[2:] - r[:2]) + rng.uniform(-1.0, 1.0, 2)
+            else:
+                p = rng.uniform(0, 60, 2)
+            strict = int(step % 2)
+            k = 0
+            while k < len(theirs):
+                cur = np.ascontiguousarray(theirs[k])
+                front = arr(4)
+                REF.ref_ribbon_split(cur.ctypes.data, p[0], p[1], strict, front.ctypes.data)
+                theirs[k] = cur
+                if not REF.ref_ribbon_covered(front.ctypes.data, strict):
+                    theirs.insert(k, front.copy())
+                    k += 1
+                if REF.ref_ribbon_covered(np.ascontiguousarray(theirs[k]).ctypes.data, strict):
+                    theirs.pop(k)
+                else:
+                    k += 1
+            steps.append([len(theirs), ribbons_digest(np.array(theirs))])
+        trials.append(steps)
+    REF.ref_set_ribbon_width(1.5)
+    return trials
+
+
+def state_pair_cases():
+    """test_host_cpu.py's 300 state pairs (seed 3, the same draws): State::headingDifference and State::distanceTo."""
+    rng = np.random.default_rng(3)
+    cases = []
+    for _ in range(300):
+        a = np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(0, 2 * np.pi), rng.uniform(0, 3), rng.uniform(0, 100)])
+        b = np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(0, 2 * np.pi), rng.uniform(0, 3), a[4] + rng.uniform(0.1, 10)])
+        rng.uniform(0, 1)                       # the test's interpolation time
+        cases.append([float(REF.ref_state_heading_difference(a.ctypes.data, b[2])).hex(),
+                      float(REF.ref_state_distance_to(a.ctypes.data, b[0], b[1])).hex()])
+    return cases
+
+
 def main():
     rng = np.random.default_rng(20261003)
     out = {
@@ -166,6 +227,8 @@ def main():
         "grid_map.json": [grid_cases(rng, MAP_TEXT, 300), grid_cases(rng, RAGGED_MAP_TEXT, 200)],
         "binary_obstacles.json": obstacle_cases(rng, 6, 400),
         "state_ops.json": state_cases(rng, 200),
+        "cover_sequences.json": cover_sequence_cases(),
+        "state_pairs.json": state_pair_cases(),
     }
     bm = arr(4)
     REF.ref_base_map_extremes(bm.ctypes.data)

@@ -20,7 +20,8 @@ def _env():
 
 
 def test_bench_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, BENCH, "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=_env())
+    out = subprocess.run([sys.executable, BENCH, "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600,
+                         env=_env())
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["steps"] == 4 and line["unit"] == "edges/s" and line["dtype"] == "f64"
@@ -31,6 +32,34 @@ def test_bench_line_has_the_contract_fields():
     assert line["ms_per_step_median"] > 0 and line["ms_per_step_p99"] >= line["ms_per_step_median"]
     assert line["e2e_ms_per_step"] > line["ms_per_step_median"]           # the records' D2H copy is in it
     assert line["value"] > 1e7                                            # BASELINE's target on one MI355X
+
+
+def _dump(tmp_path, name, steps, warmup):
+    d = tmp_path / name
+    out = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=600, env=_env())
+    assert out.returncode == 0, out.stderr[-3000:]
+    files = sorted(d.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 * 10**6
+    return json.loads(out.stdout.strip().splitlines()[-1]), {f.stem: np.load(f) for f in files}
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: the headline fields and none of the other legs; --steps timed steps (value x ms_per_step = the edges of
+    one step); --dump-outputs writes the last timed step's kept samples, edge records and best key in float64, the same
+    arrays from a second run with other step counts."""
+    line, a = _dump(tmp_path, "a", 3, 1)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "edges/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert not {"roofline", "e2e_ms_per_step", "cpu_baseline", "parity", "first_goal", "open_vertex_run", "replan", "plan_level"} & set(line)
+    ne = line["config"]["edges_per_iter_per_gpu"]
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - ne) < 1e-6 * ne
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert len(a["samples"]) * 4 == ne == len(a["edge_f"]) == len(a["edge_index"]) and a["edge_param"].shape == (ne, 3)
+    assert np.array_equal(a["edge_index"], np.arange(ne))
+    assert a["best_f"][0] == line["workload_stats"]["best_f"] and a["best_edge"][0] == line["workload_stats"]["best_edge"]
+    assert a["edge_f"][int(a["best_edge"][0])] == a["best_f"][0]
+    _, b = _dump(tmp_path, "b", 2, 0)
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_self_launch_with_more_ranks_than_devices_fails_at_the_device():

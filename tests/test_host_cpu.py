@@ -4,7 +4,9 @@ bit for bit, without a GPU.  The single-object primitives are pinned to the refe
 file covers what only exists as a list operation or an algorithm (cover sequences, coverBetween, the five heuristics,
 nearest endpoint, Brown-path seeds) and the places where the host code is organised differently from both the reference and
 the oracle (index lists + pruning instead of list copies and exhaustive recursion)."""
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -155,14 +157,20 @@ def test_nearest_endpoint_projection_and_brown_seeds():
 
 
 def test_state_helpers_beyond_the_golden_file():
-    """headingDifference / distanceTo against the reference's own object when it is at hand; interpolate and the two string
-    forms against their definitions (State.cpp:27-41,95-121)."""
+    """headingDifference / distanceTo against the reference's own object (its outputs for these pairs are recorded in
+    tests/golden/state_pairs.json; the live object as well when it is at hand); interpolate and the two string forms
+    against their definitions (State.cpp:27-41,95-121)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "state_pairs.json")) as f:
+        golden = [[float.fromhex(v) for v in c] for c in json.load(f)]
+    assert len(golden) == 300
     rng = np.random.default_rng(3)
-    for _ in range(300):
+    for want_hd, want_dist in golden:
         a = np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(0, 2 * math.pi), rng.uniform(0, 3), rng.uniform(0, 100)])
         b = np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(0, 2 * math.pi), rng.uniform(0, 3), a[4] + rng.uniform(0.1, 10)])
         hd = H.pph_state_heading_difference(a.ctypes.data, b[2])
         assert same(hd, math.fmod(math.fmod(b[2] - a[2], 2 * math.pi) + 3 * math.pi, 2 * math.pi) - math.pi)
+        assert same(hd, want_hd)
+        assert same(H.pph_state_distance_to(a.ctypes.data, b[0], b[1]), want_dist)
         if orc.REF is not None:
             assert same(hd, orc.REF.ref_state_heading_difference(a.ctypes.data, b[2]))
             assert same(H.pph_state_distance_to(a.ctypes.data, b[0], b[1]), orc.REF.ref_state_distance_to(a.ctypes.data, b[0], b[1]))
