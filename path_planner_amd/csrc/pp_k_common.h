@@ -56,7 +56,7 @@ struct PPParams {
 };
 
 // Phase 0 of an edge (Vertex::connect + Edge::computeApproxCost: which vertex/target/configuration, the Dubins word and
-// the constants of its curve), solved with one LANE per edge by pp_k_solve_edges and consumed with scalar loads by the
+// the constants of its curve), solved with one LANE per edge (or per pair of edges on one curve) by pp_k_solve_edges and consumed with scalar loads by the
 // one-WAVE-per-edge sweep.  256 bytes (two 128-byte lines; 384 up to round 3: the three segments carried their tprime intervals and
 // offsets, which follow from p0 / p1, and a never-used clear-after parameter), device-only.
 #define PP_SETUP_MALFORMED 1u   // descriptor out of range

@@ -5,7 +5,8 @@
 // Edge costing = four launches over the same edge list (the fourth, pp_k_heuristic, further down), one wavefront-sized piece
 // of work each:
 //
-//   pp_k_solve_edges  (lane per edge)  phase 0: Vertex::connect + Edge::computeApproxCost: Dubins solve, curve constants,
+//   pp_k_solve_edges  (lane per edge,  phase 0: Vertex::connect + Edge::computeApproxCost: Dubins solve, curve constants,
+//                      per curve when a dense launch holds both speeds of a radius)
 //   pp_k_pose_sweep   (wave per edge)  phase A: 64 consecutive collision-check steps at a time: closed-form pose,
 //                                      occupancy lookup, dynamic-obstacle box tests  ->  the edge's "track"
 //   pp_k_cover_sweep  (wave per edge)  phase B: the sequential coverage state machine of Edge.cpp:153-171, visited only
@@ -338,7 +339,7 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
     const ppgpu_vertex* V = p.verts + vi;
     const double srcH = pp_sgpr(V->heading);
     const PPCurveHot hot = pp_curve_hot(S);
-    const double wEnd = PP_SF64(wEnd), wStart = hot.wStart, speed = hot.speed, cvLength = hot.length, cvQx = hot.qx, cvQy = hot.qy;
+    const double wEnd = PP_SF64(wEnd), wStart = hot.wStart, speed = hot.speed;
     const double endTime = fmin(p.horizon + 1e-12 + p.sst, wEnd);    // Edge.cpp:90 (the cover sweep may end the edge earlier)
     const double* tg = p.tgrid + (size_t)vi * p.ng;
     if (p.wedges && p.ng > 0) {
@@ -366,34 +367,25 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
     int limit = 0, blocked = 0;
     // Can any obstacle come near this edge at all?  Every sampled pose lies within `travel` (arc length from the start of
     // the curve) of the curve's first point, and an obstacle moves at most |Speed| * duration during the sweep: the same
-    // kind of exact bound as the per-chunk culling, applied once.
+    // kind of exact bound as the per-chunk culling, applied once — by pp_k_solve_edges, which left the obstacles that pass it in the
+    // record's omask (all ones with more than 64 obstacles: then the per-chunk culling alone decides, which is as exact).
     bool anyObstacle = false;
     // Up to 64 obstacles: lane i keeps obstacle i's motion for the whole sweep (position at the first step's time, velocity,
     // squared culling radius), so the per-chunk culling below is a dozen instructions and no loads.  The bound is the one
     // pp_obstacle_hits_chunk uses (reach + chunk span + |Speed| * chunk time + slack); it only has to be conservative.
     const bool laneCull = p.n_obst <= PP_WAVE;
     double oX0 = 0, oY0 = 0, oVx = 0, oVy = 0, oR2 = -1.0, cullT0 = 0;
-    if (p.n_obst > 0 && p.ng > 0) {
+    if (p.n_obst > 0 && p.ng > 0) anyObstacle = pp_const_u64(&S->omask)[0] != 0ull;
+    if (anyObstacle && laneCull) {
         const double t0 = pp_const_f64(tg)[0];
-        cullT0 = t0;
-        const double duration = fmax(endTime - t0, 0.0) + chunkTime;
-        const double travel = fmin(cvLength, fmax(endTime - wStart, 0.0) * speed) + 1e-3;
-        for (int b = 0; b < p.n_obst && !anyObstacle; b += PP_WAVE) {
-            bool near = false;
-            if (b + lane < p.n_obst) {
-                const PPObst o = p.obst[b + lane];
-                const double dt = t0 - o.Time;
-                const double X = o.X + o.Speed * dt * o.cosYaw, Y = o.Y + o.Speed * dt * o.sinYaw;
-                const double R = o.reach + travel + fabs(o.Speed) * duration + 1e-3;
-                const double dx = cvQx - X, dy = cvQy - Y;
-                near = !(dx * dx + dy * dy > R * R);
-                if (laneCull) {
-                    oX0 = X; oY0 = Y; oVx = o.Speed * o.cosYaw; oVy = o.Speed * o.sinYaw;
-                    const double Rc = o.reach + chunkSpan + fabs(o.Speed) * chunkTime + 2e-3;
-                    oR2 = Rc * Rc;
-                }
-            }
-            anyObstacle = __ballot(near) != 0ull;
+        if (lane < p.n_obst) {
+            cullT0 = t0;
+            const PPObst o = p.obst[lane];
+            const double dt = t0 - o.Time;
+            oX0 = o.X + o.Speed * dt * o.cosYaw; oY0 = o.Y + o.Speed * dt * o.sinYaw;
+            oVx = o.Speed * o.cosYaw; oVy = o.Speed * o.sinYaw;
+            const double Rc = o.reach + chunkSpan + fabs(o.Speed) * chunkTime + 2e-3;
+            oR2 = Rc * Rc;
         }
     }
 
@@ -405,7 +397,7 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
     for (int g0 = 0; !stop; g0 += PP_WAVE) {
         const unsigned sbits = (skipb && g0 + lane < p.nch) ? (unsigned)skipb[g0 + lane] : 0u;
         const unsigned long long skips = __ballot((sbits & PP_SKIP_ALL) != 0u);
-        const unsigned long long gclear = __ballot((sbits & PP_SKIP_GRID) != 0u), oclear = __ballot((sbits & PP_SKIP_OBST) != 0u);
+        const unsigned long long gclear = __ballot((sbits & PP_SKIP_GRID) != 0u), oclear = anyObstacle ? __ballot((sbits & PP_SKIP_OBST) != 0u) : ~0ull;   // (no obstacle near the edge: as good as none near any chunk)
         int ci = 0;
         for (; ci < PP_WAVE; ci++) {
             const int base = (g0 + ci) * PP_WAVE;
@@ -435,9 +427,9 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
                 if (!gridClear) blk = valid & pp_is_blocked(p.grid, x, y);   // Edge.cpp:144 (pp_k_plan_skips may have ruled it out for the whole chunk)
             }
             double dens = 0;
-            if (anyObstacle && obstClear) {
+            if (obstClear) {
                 // pp_k_plan_skips: no obstacle can hold a pose of this chunk
-            } else if (anyObstacle && laneCull) {                         // :150-151
+            } else if (laneCull) {                                        // :150-151
                 // which obstacles can come near this chunk: lane i answers for obstacle i from its registers
                 const double dtc = tFirst - cullT0;
                 const double ddx = pp_readlane(x, 0) - (oX0 + oVx * dtc), ddy = pp_readlane(y, 0) - (oY0 + oVy * dtc);
@@ -449,7 +441,7 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
                     else dens += pp_obstacle_pdf(reinterpret_cast<const PPGauss*>(p.obst)[j], x, y, t);
                 }
                 if (gaussian) { if (dens < 1e-5) dens = 0; if (!valid) dens = 0; }   // GaussianDynamicObstaclesManager.cpp:11
-            } else if (anyObstacle) {
+            } else {
                 if (!gaussian)
                     hits = pp_obstacle_hits_chunk(p.obst, p.n_obst, x, y, t, valid, pp_readlane(x, 0), pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
                 else
