@@ -350,6 +350,44 @@ int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper
                                   ppgpu_edge_result* h_results,
                                   double* h_child_ribbons, int32_t ribbon_stride);
 
+/* ------------------------------------------------------------------ edge traces */
+
+/* What happened ALONG an edge: one record per executed step of the sweep of Edge::computeTrueCost (Edge.cpp:125-175), i.e. per
+ * pass of `while (intermediate.time() < endTime)` whose DubinsWrapper::sample succeeded, the blocked one included — as many as
+ * bits 16-31 of the edge's ppgpu_edge_result.info say.  The costing launch keeps no per-step state; pp_k_trace_steps rebuilds it
+ * from the same solved curve, the same time grid and the same map / obstacle code, without skipping anything. */
+#define PPGPU_S_BLOCKED  0x1u  /* Map::isBlocked at this pose (Edge.cpp:144): only ever the last record of an edge */
+#define PPGPU_S_STRAIGHT 0x2u  /* lastHeading == intermediate.heading() (Edge.cpp:159): covers even when !coverageAllowed */
+typedef struct ppgpu_step_record {          /* 64 bytes */
+    double x, y, heading, time;             /* the State handed to isBlocked / collisionExists / cover (Edge.cpp:127) */
+    double collision;                       /* collisionExists(intermediate, true) (:150-151); 0 on a blocked step */
+    double penalty_before;                  /* collisionPenalty when this step was sampled = the term in gSoFar (:138) */
+    uint32_t flags, step;                   /* PPGPU_S_*; the step's index k */
+    double reserved;                        /* 0 */
+} ppgpu_step_record;
+
+/* Edge::computeTrueCost (Edge.cpp:68-206) step by step for a list of n packed descriptors: first the costing launch of
+ * ppgpu_cost_edges_list on the same list (d_results receives exactly its records), then the trace.  d_counts[i] receives the edge's
+ * step count (0 for an edge flagged PPGPU_F_THROWS or malformed), d_steps[i * step_stride + k] the record of its step k for
+ * k < min(count, step_stride): an edge with more steps than step_stride is cut, not refused, and its count still says how many
+ * there were (as with ribbon_stride); records beyond an edge's count are left untouched.  d_steps must be 16-byte aligned.
+ * Asynchronous on the handle's stream. */
+int ppgpu_trace_edges_list(ppgpu_ctx* ctx, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results,
+                           int32_t step_stride, int32_t* d_counts, ppgpu_step_record* d_steps);
+/* The same with host descriptors in and host arrays out, synchronous.  h_results may be NULL.  The step records pass through a
+ * buffer of the handle that grows like its other buffers (ppgpu_growth_stats counts it); a trace that would exceed the handle's
+ * workspace budget runs as consecutive slices of the list, like a costing launch. */
+int ppgpu_trace_edges_host(ppgpu_ctx* ctx, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results,
+                           int32_t step_stride, int32_t* h_counts, ppgpu_step_record* h_steps);
+/* ... for edges whose curve is given (Vertex::connect(start, DubinsWrapper, coverageAllowed), Vertex.cpp:28-36, as
+ * ppgpu_cost_wrapper_edges_host costs them): the steps of a plan's segments (AStarPlanner.cpp:46-59 walks them the same way).  A
+ * curve that starts after the vertex's first step has no steps (the first sample throws, Edge.cpp:126-133). */
+int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper_edge* h_wedges, ppgpu_edge_result* h_results,
+                                   int32_t step_stride, int32_t* h_counts, ppgpu_step_record* h_steps);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_trace_steps took in the last trace call, summed
+ * over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
+int ppgpu_last_trace_timing(ppgpu_ctx* ctx, double* ms_trace);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

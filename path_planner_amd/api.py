@@ -71,6 +71,10 @@ def _load():
         "ppgpu_cost_edges_list": (C.c_int, [vp, i64, vp, vp, vp, i32]),
         "ppgpu_cost_edges_host": (C.c_int, [vp, i64, vp, vp, vp, i32]),
         "ppgpu_cost_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, i32]),
+        "ppgpu_trace_edges_list": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
+        "ppgpu_trace_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
+        "ppgpu_trace_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
+        "ppgpu_last_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -307,6 +311,37 @@ class Context:
         child = np.zeros((e.shape[0], stride, 4), dtype=np.float64) if stride > 0 else None
         self._ck(LIB.ppgpu_cost_wrapper_edges_host(self._h, e.shape[0], _ptr(e), _ptr(res), _ptr(child), stride), "ppgpu_cost_wrapper_edges_host")
         return (res, child) if stride > 0 else res
+
+    def trace_edges_list(self, n, d_edges, d_results, step_stride, d_counts, d_steps):
+        self._ck(LIB.ppgpu_trace_edges_list(self._h, n, _ptr(d_edges), _ptr(d_results), step_stride, _ptr(d_counts), _ptr(d_steps)),
+                 "ppgpu_trace_edges_list")
+
+    def _trace_host(self, fn, name, e, step_stride, steps):
+        from .types import STEP_DTYPE
+        n = e.shape[0]
+        res = np.zeros(n, dtype=RESULT_DTYPE)
+        counts = np.zeros(n, dtype=np.int32)
+        if steps is None:
+            steps = np.zeros((n, step_stride), dtype=STEP_DTYPE)
+        assert steps.dtype == STEP_DTYPE and steps.shape == (n, step_stride) and steps.flags["C_CONTIGUOUS"]
+        self._ck(fn(self._h, n, _ptr(e), _ptr(res), step_stride, _ptr(counts), _ptr(steps)), name)
+        return res, counts, steps
+
+    def trace_edges(self, edges, step_stride, steps=None):
+        """Edge::computeTrueCost step by step: (records as cost_edges_host returns them, step counts, steps[n, step_stride]).
+        `steps`: an array to write into (entries beyond an edge's count are left as they are); a zeroed one by default."""
+        e = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._trace_host(LIB.ppgpu_trace_edges_host, "ppgpu_trace_edges_host", e, step_stride, steps)
+
+    def trace_wrapper_edges(self, wedges, step_stride, steps=None):
+        from .types import WRAPPER_EDGE_DTYPE
+        e = np.ascontiguousarray(wedges, dtype=WRAPPER_EDGE_DTYPE)
+        return self._trace_host(LIB.ppgpu_trace_wrapper_edges_host, "ppgpu_trace_wrapper_edges_host", e, step_stride, steps)
+
+    def last_trace_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_trace_timing(self._h, C.byref(ms)), "ppgpu_last_trace_timing")
+        return ms.value
 
     @staticmethod
     def dense_edge_count(nv, ns, cfg_mask):

@@ -117,6 +117,12 @@ struct ppgpu_ctx {
     DevBuf<ppgpu_wrapper_edge> tmp_wedges;
     DevBuf<ppgpu_edge_result> tmp_results;
     DevBuf<double> tmp_child, tmp_lengths, tmp_len_out, int_child;
+    DevBuf<ppgpu_step_record> tmp_steps;   // device end of the host forms of ppgpu_trace_*: the step records of one trace slice
+    DevBuf<int> tmp_counts;
+    long long last_slice_edges = 0;     // edges per workspace slice of the last costing launch (>= its edge count: the setup records of the whole list are still there)
+    hipEvent_t ev_trace[2] = {nullptr, nullptr};   // around pp_k_trace_steps (ppgpu_last_trace_timing)
+    double ms_trace_earlier = 0;        // ... of the slices before the last one
+    bool trace_timed = false;
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
@@ -222,7 +228,7 @@ int ppgpu_destroy(ppgpu_ctx* c) {
     c->grid.release(); c->grid_clear.release(); c->grid_rowclear.release(); c->obst.release(); c->verts.release(); c->ribbons.release(); c->tgrid.release();
     c->sx.release(); c->sy.release(); c->sh.release(); c->samp_ribbons.release(); c->samp_pos.release();
     c->s_bytes.release(); c->s_u64.release(); c->s_u32a.release(); c->s_u32b.release(); c->s_cand.release();
-    c->tmp_edges.release(); c->tmp_wedges.release(); c->partial.release(); c->tmp_results.release(); c->tmp_child.release();
+    c->tmp_edges.release(); c->tmp_wedges.release(); c->partial.release(); c->tmp_results.release(); c->tmp_child.release(); c->tmp_steps.release(); c->tmp_counts.release();
     c->ord_key.release(); c->ord_val.release(); c->ord_idx.release(); c->ord_fallbacks.release(); c->ord_len.release();
     c->ord_blockmin.release(); c->ord_blockcnt.release(); c->ord_bound.release(); c->ord_count.release(); c->near_idx.release(); c->near_count.release(); c->probe_bound.release();
     c->tmp_lengths.release(); c->tmp_len_out.release(); c->tmp_idx.release(); c->gather.release(); c->int_child.release();
@@ -232,6 +238,7 @@ int ppgpu_destroy(ppgpu_ctx* c) {
     if (c->stage_in) (void)hipHostFree(c->stage_in);
     if (c->stage_out) (void)hipHostFree(c->stage_out);
     for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < 6; i++) if (c->ev_ring[r][i]) (void)hipEventDestroy(c->ev_ring[r][i]);
+    for (int i = 0; i < 2; i++) if (c->ev_trace[i]) (void)hipEventDestroy(c->ev_trace[i]);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
@@ -251,8 +258,11 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
         for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
+    if (on && !c->ev_trace[0])
+        for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&c->ev_trace[i]));
     c->timing = on != 0;
     c->ev_launches = 0;
+    c->trace_timed = false;
     return PPGPU_OK;
 }
 
@@ -865,6 +875,7 @@ static int launch_cost(ppgpu_ctx* c, PPParams& p) {
     if (slice < PP_WPB) slice = PP_WPB;
     if (slice > total) slice = total;
     const size_t ws = (size_t)slice;
+    c->last_slice_edges = slice;
     {
         int rc;
         if ((rc = c->setup.reserve(ws, false, c->stream)) ||
@@ -1095,6 +1106,151 @@ int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_e
         HIP_TRY(hipMemcpyAsync(h_child, c->tmp_child.p, (size_t)n * stride * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ edge traces
+// The trace of the edge list `p` was just costed with (launch_cost(c, p) returned: p.n_edges = the whole list, the workspace
+// pointers are set).  The trace kernel reads the PPEdgeSetup records of the costing launch: they are all still in the workspace
+// when that launch ran as one slice; a launch that ran as several has only its last slice's left, and pp_k_solve_edges writes
+// them again, slice by slice (a fraction of the time the records take to write).  Host form (h_steps / h_counts != NULL): the
+// records of one pass go through c->tmp_steps, at most the handle's slice budget at a time; what the caller's array holds beyond
+// an edge's count stays as it is (the pass starts from the caller's bytes).
+static int launch_trace(ppgpu_ctx* c, const PPParams& p, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
+    const long long total = p.n_edges;
+    if (total <= 0) return PPGPU_OK;
+    const bool reuse = c->last_slice_edges >= total;
+    long long pass = reuse ? total : c->last_slice_edges;
+    if (h_steps) {
+        long long cap = (long long)(c->slice_bytes / ((size_t)stride * sizeof(ppgpu_step_record)));
+        if (cap < 1) cap = 1;
+        if (pass > cap) pass = cap;
+        int rc = c->tmp_steps.reserve((size_t)pass * stride, false, c->stream);
+        if (rc) return rc;
+    }
+    const bool gauss = p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN;
+    c->ms_trace_earlier = 0;
+    c->trace_timed = false;
+    for (long long e0 = 0; e0 < total; e0 += pass) {
+        PPParams q = p;
+        q.e_base = e0; q.n_edges = (total - e0 < pass) ? (total - e0) : pass;
+        q.ws_base = reuse ? e0 : 0;
+        if (!reuse) {
+            q.live_count = nullptr; q.defer_count = nullptr; q.hw_count = nullptr;     // (counters of the costing launch: ppgpu_last_cover_edges still reads them)
+            hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
+        }
+        ppgpu_step_record* dst = h_steps ? c->tmp_steps.p : d_steps;
+        const size_t bytes = (size_t)q.n_edges * stride * sizeof(ppgpu_step_record);
+        if (h_steps) HIP_TRY(hipMemcpyAsync(dst, h_steps + (size_t)e0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
+        if (c->timing && c->trace_timed) {              // a further slice re-uses the events: bank the one before
+            float ms = 0;
+            HIP_TRY(hipEventSynchronize(c->ev_trace[1]));
+            HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[0], c->ev_trace[1]));
+            c->ms_trace_earlier += ms;
+        }
+        if (c->timing) HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        hipLaunchKernelGGL(gauss ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
+                           dim3(PP_TRACE_WPB * 64), 0, c->stream, q, dst, h_steps ? e0 : 0ll, stride, d_counts);
+        if (c->timing) { HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream)); c->trace_timed = true; }
+        HIP_TRY(hipGetLastError());
+        if (h_steps) {
+            HIP_TRY(hipMemcpyAsync(h_steps + (size_t)e0 * stride, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));   // the next pass writes the same buffer
+        }
+    }
+    return PPGPU_OK;
+}
+
+int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) {
+    if (!c || !ms_trace) return fail(PPGPU_EINVAL, "null argument");
+    if (!c->timing || !c->trace_timed) return fail(PPGPU_ESTATE, "no timed trace launch (ppgpu_enable_timing, then trace edges)");
+    HIP_TRY(hipSetDevice(c->device));
+    float ms = 0;
+    HIP_TRY(hipEventSynchronize(c->ev_trace[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[0], c->ev_trace[1]));
+    *ms_trace = ms + c->ms_trace_earlier;
+    return PPGPU_OK;
+}
+
+static int trace_args(const char* who, int64_t n, const void* edges, int32_t stride, const void* counts, const void* steps) {
+    if (n < 0 || (n > 0 && (!edges || !counts || !steps))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
+    if (stride <= 0 || stride > 65535) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
+    return PPGPU_OK;
+}
+
+int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
+                           int32_t* d_counts, ppgpu_step_record* d_steps) {
+    int rc = require_world(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = trace_args("trace_edges_list", n, d_edges, stride, d_counts, d_steps))) return rc;
+    if (n > 0 && !d_results) return fail(PPGPU_EINVAL, "trace_edges_list: null results");
+    if (((unsigned long long)d_steps & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_edges_list: d_steps must be 16-byte aligned");
+    if (n == 0) return PPGPU_OK;
+    PPParams p;
+    fill_params(c, p);
+    p.edges = (const unsigned long long*)d_edges; p.wedges = nullptr;
+    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
+    p.n_edges = n;
+    p.out = d_results; p.child = nullptr; p.stride = 0;
+    if ((rc = launch_cost(c, p))) return rc;
+    return launch_trace(c, p, stride, d_counts, d_steps, nullptr);
+}
+
+// the tail of both host forms: records and counts home
+static int trace_host_finish(ppgpu_ctx* c, PPParams& p, int64_t n, ppgpu_edge_result* h_results, int32_t stride, int32_t* h_counts,
+                             ppgpu_step_record* h_steps) {
+    int rc;
+    if ((rc = launch_cost(c, p))) return rc;
+    if (h_results) HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = launch_trace(c, p, stride, c->tmp_counts.p, nullptr, h_steps))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_trace_edges_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t stride,
+                           int32_t* h_counts, ppgpu_step_record* h_steps) {
+    int rc = require_world(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = trace_args("trace_edges_host", n, h_edges, stride, h_counts, h_steps))) return rc;
+    if (n == 0) return PPGPU_OK;
+    if ((rc = c->tmp_edges.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_results.reserve((size_t)n, false, c->stream)) ||
+        (rc = c->tmp_counts.reserve((size_t)n, false, c->stream)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->tmp_edges.p, h_edges, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    PPParams p;
+    fill_params(c, p);
+    p.edges = c->tmp_edges.p; p.wedges = nullptr;
+    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
+    p.n_edges = n;
+    p.out = c->tmp_results.p; p.child = nullptr; p.stride = 0;
+    return trace_host_finish(c, p, n, h_results, stride, h_counts, h_steps);
+}
+
+int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
+                                   int32_t stride, int32_t* h_counts, ppgpu_step_record* h_steps) {
+    int rc = require_cfg(c);
+    if (rc) return rc;
+    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = trace_args("trace_wrapper_edges_host", n, h_edges, stride, h_counts, h_steps))) return rc;
+    if (n == 0) return PPGPU_OK;
+    for (int64_t i = 0; i < n; i++) {
+        if (!(h_edges[i].rho > 0) || !(h_edges[i].speed > 0)) return fail(PPGPU_EINVAL, "trace_wrapper_edges_host: rho and speed must be positive");
+        if (h_edges[i].vertex < 0 || h_edges[i].vertex >= c->nverts) return fail(PPGPU_EINVAL, "trace_wrapper_edges_host: vertex out of range");
+    }
+    if ((rc = c->tmp_wedges.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_results.reserve((size_t)n, false, c->stream)) ||
+        (rc = c->tmp_counts.reserve((size_t)n, false, c->stream)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->tmp_wedges.p, h_edges, (size_t)n * sizeof(ppgpu_wrapper_edge), hipMemcpyHostToDevice, c->stream));
+    PPParams p;
+    fill_params(c, p);
+    p.edges = nullptr; p.wedges = c->tmp_wedges.p;
+    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
+    p.n_edges = n;
+    p.out = c->tmp_results.p; p.child = nullptr; p.stride = 0;
+    return trace_host_finish(c, p, n, h_results, stride, h_counts, h_steps);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own

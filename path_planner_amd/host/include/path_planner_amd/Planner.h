@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -40,6 +41,10 @@ public:
         double PlanHValue = 0;
         unsigned long PlanDepth = 0;
         DubinsPlan Plan;
+        // With PlannerConfig::setPlanTrace: Trace[s] = the executed collision-check steps of Plan's segment s as the device swept
+        // them (ppgpu_trace_wrapper_edges_host from the segment's parent vertex; the layout is ppgpu_step_record's).
+        struct TraceStep { double x, y, heading, time, collision, penaltyBefore; uint32_t flags, step; double reserved; };
+        std::vector<std::vector<TraceStep>> Trace;
         // extra, for parity checks against the CPU oracle
         long FirstGoalIteration = -1;
         unsigned long EdgesCosted = 0;
@@ -103,6 +108,11 @@ struct TripBlock {
     std::unique_ptr<double[]> child;              // `stride` x 4 doubles per edge
     size_t edgeCap = 0, childCap = 0;
     int stride = 0;
+    // PlannerConfig::deviceTrajectories with the search dump on (traceStride > 0): how many steps the device traced of every edge
+    // of the round trip, and the ones the dump prints — every tracePer-th, Edge.cpp:135-136 — traceStride slots per edge
+    std::vector<int32_t> traceCounts;
+    std::vector<Planner::Stats::TraceStep> traceSteps;     // [edge][traceStride]: steps tracePer - 1, 2 tracePer - 1, ...
+    int traceStride = 0, tracePer = 1;
     void reserve(size_t nEdges, size_t childDoubles);
 };
 
@@ -269,7 +279,8 @@ private:
     void check(int rc, const char* what) const;
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
-    void visualizeTrajectory(const Node& child);
+    void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);
+    void tracePlanSteps(int v);            // Stats::Trace for the plan that ends at node v
     void visualizePlan(const DubinsPlan& plan);
     void visualizeSamples();
     int costStateEdges(int source, const std::vector<State>& targets, const std::vector<unsigned>& cfgBits,

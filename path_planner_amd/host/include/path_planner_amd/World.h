@@ -216,13 +216,21 @@ public:
     void setDeadlineGuard(bool on) { m_DeadlineGuard = on; }
     int speculation() const { return m_Speculation; }
     void setSpeculation(int n) { m_Speculation = n < 1 ? 1 : n; }
-    // PlannerConfig.h:60-80,116-118: the search dump.  The device keeps no per-step poses, so the planner rebuilds the
-    // "Trajectory:" samples of an edge on the host from the child's curve when (and only when) this is on.
+    // PlannerConfig.h:60-80,116-118: the search dump.  The costing launch keeps no per-step poses, so the planner rebuilds the
+    // "Trajectory:" samples of an edge on the host from the child's curve when (and only when) this is on — or, with
+    // setDeviceTrajectories, asks the device for the steps of a whole round trip's edges at once.
     bool visualizations() const { return m_Visualizations && (m_Visualizer || m_VisualizationStream); }
     void setVisualizations(bool v) { m_Visualizations = v; }
     void setVisualizer(Visualizer::SharedPtr v) { m_Visualizer = std::move(v); }
     void setVisualizationStream(std::ostream* s) { m_VisualizationStream = s; }   // any stream instead of a file
     std::ostream& visualizationStream() const { return m_Visualizer ? m_Visualizer->stream() : *m_VisualizationStream; }
+    // With the search dump on: the "Trajectory:" lines of the children a device round trip costed come from the device's own sweep
+    // (ppgpu_trace_edges_host, one call per round trip) instead of the host loop above.  Same lines, same thinning.
+    bool deviceTrajectories() const { return m_DeviceTrajectories; }
+    void setDeviceTrajectories(bool on) { m_DeviceTrajectories = on; }
+    // The returned plan step by step (Planner::Stats::Trace): where it was sampled, what it hit, the penalty as it accrued.
+    bool planTrace() const { return m_PlanTrace; }
+    void setPlanTrace(bool on) { m_PlanTrace = on; }
 
 private:
     int m_BranchingFactor = 9;
@@ -235,6 +243,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;
     Map::SharedPtr m_Map;

@@ -368,11 +368,22 @@ void GpuAStarPlanner::visualizeVertex(int vi, const char* tag, bool expanded) {
 // What Edge::computeTrueCost streams while it sweeps (Edge.cpp:122-143): "Trajectory:" and every int(1/increment)+1-th sampled
 // state with the cost accrued so far (start g + time so far + collision penalty of the steps before it) and the START vertex's
 // h.  Rebuilt here from the child's curve, the same time grid (:114-120) and the host obstacle manager.
-void GpuAStarPlanner::visualizeTrajectory(const Node& child) {
+// With `steps` (PlannerConfig::deviceTrajectories) the states and the penalty so far are the device's own: the records
+// pp_k_trace_steps wrote for this edge, thinned the same way.
+void GpuAStarPlanner::visualizeTrajectory(const Node& child, const Stats::TraceStep* steps, int count) {
     if (!m_Config.visualizations() || child.parent < 0) return;
     const Node& src = m_Nodes[child.parent];
     std::ostream& o = m_Config.visualizationStream();
     o << "Trajectory:" << std::endl;
+    if (steps) {                               // (already thinned: the steps at which `visCount-- <= 0` holds, :135-136)
+        for (int k = 0; k < count; k++) {
+            const Stats::TraceStep& t = steps[k];
+            const State s(t.x, t.y, t.heading, child.wrapper.getSpeed(), t.time);
+            const double gSoFar = src.g + (t.time - src.state.time()) + t.penaltyBefore;
+            o << "State: (" << s.toStringRad() << "), f: " << gSoFar + src.h << ", g: " << gSoFar << ", h: " << src.h << " trajectory" << std::endl;
+        }
+        return;
+    }
     const double timeIncrement = m_Config.collisionCheckingIncrement() / m_Config.maxSpeed();
     State intermediate(src.state);
     intermediate.time() += std::fmod(intermediate.time() - m_StartStateTime, timeIncrement);
@@ -635,6 +646,8 @@ struct GpuAStarPlanner::Batch {
     double heavy = 0;                      // heavyListAllowance of the batch (part of `predicted`)
     int strideFloor = 0, strideUsed = 0, retries = 0;      // (the child stride earlier round trips of this plan() needed; what this one ended with)
     GpuContext* ctx = nullptr;
+    bool trace = false;                    // bring the edges' steps back too (PlannerConfig::deviceTrajectories with the search dump on)
+    int tracePer = 1;                      // ... of which the dump prints one in int(1 / increment) + 1
     bool threaded = false;                 // running on ctx's thread (wait() before anything else touches ctx)
     // filled by run()
     std::shared_ptr<TripBlock> block;
@@ -698,6 +711,28 @@ void GpuAStarPlanner::runBatch(Batch& b, int k) {
         b.retries++;
     }
     b.strideUsed = stride;
+    b.block->traceStride = 0;
+    if (b.trace && b.n > 0) {
+        // the search is being watched and wants the device's own sweeps: the steps of every edge of this round trip in one call,
+        // while the handle still holds the round trip's vertices and explicit targets
+        TripBlock& blk = *b.block;
+        const ppgpu_edge_result* res = reinterpret_cast<const ppgpu_edge_result*>(blk.records.get());
+        int most = 1;
+        for (int64_t i = 0; i < b.n; i++) most = std::max(most, (int)(res[i].info >> 16));
+        blk.traceCounts.assign((size_t)b.n, 0);
+        std::vector<Stats::TraceStep> all((size_t)b.n * (size_t)most);
+        if (ppgpu_trace_edges_host(h, b.n, blk.edges.get(), nullptr, most, blk.traceCounts.data(),
+                                   reinterpret_cast<ppgpu_step_record*>(all.data())) != PPGPU_OK)
+            throw std::runtime_error(std::string("ppgpu_trace_edges_host: ") + ppgpu_last_error());
+        // the block lives until its last vertex is expanded: it keeps the steps the dump prints, one in b.tracePer
+        const int per = b.tracePer, kept = most / per + 1;
+        blk.traceSteps.resize((size_t)b.n * (size_t)kept);
+        for (int64_t i = 0; i < b.n; i++)
+            for (int j = 0, k = per - 1; k < blk.traceCounts[(size_t)i]; j++, k += per)
+                blk.traceSteps[(size_t)i * kept + j] = all[(size_t)i * most + k];
+        blk.traceStride = kept;
+        blk.tracePer = per;
+    }
     b.took = HostProfile::now() - b.started;
 }
 
@@ -707,6 +742,8 @@ void GpuAStarPlanner::submitBatch(std::shared_ptr<Batch> bp, GpuContext& ctx) {
     b.ctx = &ctx;
     b.samples = (double)m_NumSamples;
     b.strideFloor = m_StrideFloor;
+    b.trace = m_Config.visualizations() && m_Config.deviceTrajectories();
+    b.tracePer = std::max(1, int(1.0 / m_Config.collisionCheckingIncrement()) + 1);
     b.predicted = ctx.predictTrip(b.samples) + b.heavy;
     packBatch(b);
     const int k = m_Config.branchingFactor();
@@ -925,7 +962,13 @@ bool GpuAStarPlanner::expand(int source) {
         const size_t ki = e - costed.first;
         if (ki < costed.ready.size() && costed.ready[ki]) addNode(std::move(costed.kids[ki]));      // built while the planner waited
         else addNode(makeChild(source, cfgBits, r, blk.child.get() + e * (size_t)blk.stride * 4, blk.stride));
-        visualizeTrajectory(m_Nodes.back());   // in the reference each edge streams its sweep, then its vertex is pushed
+        // in the reference each edge streams its sweep, then its vertex is pushed
+        if (watch && blk.traceStride > 0) {
+            if (blk.traceCounts[e] != m_Nodes.back().steps) throw std::runtime_error("the device traced " + std::to_string(blk.traceCounts[e]) + " steps of an edge whose sweep executed " + std::to_string(m_Nodes.back().steps));
+            visualizeTrajectory(m_Nodes.back(), blk.traceSteps.data() + e * (size_t)blk.traceStride, blk.traceCounts[e] / blk.tracePer);
+        } else {
+            visualizeTrajectory(m_Nodes.back());
+        }
         pushVertexQueue((int)m_Nodes.size() - 1);
     }
     m_Stats.Expanded++;
@@ -978,6 +1021,51 @@ DubinsPlan GpuAStarPlanner::tracePlan(int v, bool addToStats) {   // Planner.cpp
     plan.setDangerous(dangerous);
     for (auto it = branch.rbegin(); it != branch.rend(); it++) plan.append(m_Nodes[*it].wrapper);
     return plan;
+}
+
+// PlannerConfig::planTrace: the returned plan's segments swept once more, step by step, in one device call — segment s from its
+// parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
+static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
+void GpuAStarPlanner::tracePlanSteps(int v) {
+    m_Stats.Trace.clear();
+    std::vector<int> branch;
+    for (int cur = v; cur >= 0 && m_Nodes[cur].parent >= 0; cur = m_Nodes[cur].parent) branch.push_back(cur);
+    std::reverse(branch.begin(), branch.end());
+    const size_t n = branch.size();
+    if (n == 0) return;
+    std::vector<ppgpu_vertex> verts(n);
+    std::vector<double> pool;
+    std::vector<ppgpu_wrapper_edge> wedges(n);
+    int most = 1;
+    for (size_t s = 0; s < n; s++) {
+        const Node& c = m_Nodes[branch[s]];
+        const Node& src = m_Nodes[c.parent];
+        verts[s] = makeVertex(src);
+        verts[s].ribbon_offset = (int32_t)(pool.size() / 4);
+        pool.insert(pool.end(), src.ribbons.rows(), src.ribbons.rows() + 4 * (size_t)src.ribbons.count());
+        ppgpu_wrapper_edge& we = wedges[s];
+        we = ppgpu_wrapper_edge{};
+        we.vertex = (int32_t)s;
+        we.coverage_allowed = c.coverageAllowed ? 1 : 0;
+        const DubinsPath& dp = c.wrapper.unwrap();
+        for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
+        we.rho = dp.rho; we.type = (int32_t)dp.type;
+        we.speed = c.wrapper.getSpeed(); we.start_time = c.wrapper.curveStartTime(); we.end_time = c.wrapper.getEndTime();
+        most = std::max(most, c.steps);
+    }
+    ppgpu_ctx* h = m_Ctx->handle();
+    check(ppgpu_set_vertices(h, (int32_t)n, verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
+    std::vector<int32_t> counts(n, 0);
+    std::vector<Stats::TraceStep> steps(n * (size_t)most);
+    check(ppgpu_trace_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), reinterpret_cast<ppgpu_step_record*>(steps.data())),
+          "ppgpu_trace_wrapper_edges_host");
+    m_Stats.Trace.resize(n);
+    for (size_t s = 0; s < n; s++) {
+        if (counts[s] != m_Nodes[branch[s]].steps)
+            throw std::runtime_error("plan trace: segment " + std::to_string(s) + " traced " + std::to_string(counts[s]) + " steps, its edge executed " +
+                                     std::to_string(m_Nodes[branch[s]].steps));
+        m_Stats.Trace[s].assign(steps.begin() + (long)(s * (size_t)most), steps.begin() + (long)(s * (size_t)most) + counts[s]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ plan()
@@ -1200,6 +1288,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
         m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
         m_Stats.PlanHValue = m_Nodes[m_Best].h;
         m_Stats.Plan = tracePlan(m_Best);
+        if (m_Config.planTrace()) tracePlanSteps(m_Best);
     }
     for (const auto& ctx : m_Ctxs) m_Stats.OrderFallbacks += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
     m_Stats.OrderFallbacks -= orderFallbacksBefore;

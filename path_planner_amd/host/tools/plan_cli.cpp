@@ -4,6 +4,7 @@
 //
 // Scenario lines:  cfg <key> <value> | start x y heading speed time | ribbon x1 y1 x2 y2 | heuristic H K radius |
 //                  ribbon_width w | obstacle x y heading speed time width length | gaussian x y heading speed time [c00 c01 c10 c11] | map_file path | clock t0 dt |
+//                  plan_trace_file path (with cfg plan_trace 1: one line per step of the returned plan) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 #include <algorithm>
@@ -42,7 +43,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath;
+    std::string cycleLogPath, planTracePath;
     std::string line;
     while (std::getline(in, line)) {
         std::istringstream s(line);
@@ -61,6 +62,8 @@ int main(int argc, char** argv) {
             else if (name == "initial_samples") config.setInitialSamples((int)v);
             else if (name == "use_brown_paths") config.setUseBrownPaths(v != 0);
             else if (name == "speculation") config.setSpeculation((int)v);
+            else if (name == "plan_trace") config.setPlanTrace(v != 0);
+            else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else { std::fprintf(stderr, "unknown cfg %s\n", name.c_str()); return 2; }
         } else if (k == "start") {
             double x, y, h, v, t; s >> x >> y >> h >> v >> t; start = State(x, y, h, v, t);
@@ -86,6 +89,7 @@ int main(int argc, char** argv) {
         } else if (k == "sharded_batch") { s >> shardedAttempts >> shardedSeed;
         } else if (k == "fail_shard") { s >> failShard;      // tests: this shard of a sharded_batch throws before its work
         } else if (k == "cycle_log") { s >> cycleLogPath;    // replan: one JSON line per cycle (Stats::Budget and what the cycle reached)
+        } else if (k == "plan_trace_file") { s >> planTracePath;   // segment step x y heading time collision penalty_before flags
         } else if (k == "repeat") { s >> repeat;
         } else if (k == "replan") { s >> replans >> replanStep;   // N consecutive cycles, start moved replanStep seconds along the plan
         } else if (k == "real_clock") { int v; s >> v; realClock = v != 0;   // now() = t0 + wall seconds since plan() began
@@ -266,7 +270,21 @@ int main(int argc, char** argv) {
                         p.qi[2], p.param[0], p.param[1], p.param[2], p.rho, (int)p.type, w.getSpeed(), w.getStartTime(), w.getEndTime());
             first = false;
         }
-        std::printf("]}\n");
+        if (config.planTrace()) {
+            size_t nSteps = 0;
+            for (const auto& seg : st.Trace) nSteps += seg.size();
+            std::printf("], \"plan_trace_segments\": %zu, \"plan_trace_steps\": %zu}\n", st.Trace.size(), nSteps);
+            if (!planTracePath.empty()) {
+                FILE* f = std::fopen(planTracePath.c_str(), "w");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", planTracePath.c_str()); return 2; }
+                for (size_t sg = 0; sg < st.Trace.size(); sg++)
+                    for (const auto& t : st.Trace[sg])
+                        std::fprintf(f, "%zu %u %.17g %.17g %.17g %.17g %.17g %.17g %u\n", sg, t.step, t.x, t.y, t.heading, t.time, t.collision, t.penaltyBefore, t.flags);
+                std::fclose(f);
+            }
+        } else {
+            std::printf("]}\n");
+        }
     } catch (const std::exception& e) {
         std::printf("{\"exception\": \"%s\"}\n", e.what());
         return 1;

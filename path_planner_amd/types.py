@@ -62,6 +62,14 @@ WRAPPER_EDGE_DTYPE = np.dtype([
 ])
 assert WRAPPER_EDGE_DTYPE.itemsize == 96
 
+# struct ppgpu_step_record, 64 bytes: one executed step of an edge's sweep (ppgpu_trace_*)
+S_BLOCKED, S_STRAIGHT = 0x1, 0x2
+STEP_DTYPE = np.dtype([
+    ("x", "<f8"), ("y", "<f8"), ("heading", "<f8"), ("time", "<f8"), ("collision", "<f8"), ("penalty_before", "<f8"),
+    ("flags", "<u4"), ("step", "<u4"), ("reserved", "<f8"),
+])
+assert STEP_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
