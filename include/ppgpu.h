@@ -350,6 +350,33 @@ int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper
                                   ppgpu_edge_result* h_results,
                                   double* h_child_ribbons, int32_t ribbon_stride);
 
+/* ---------------------------------------------------------------- plan chains */
+
+/* Why the chain of a plan ended (h_stop of ppgpu_cost_plans_host): the stop rules of AStarPlanner.cpp:53-57 plus the cases the
+ * leg-by-leg host loop throws on. */
+#define PPGPU_CHAIN_LEGS        1u /* every leg was costed: the plan ran out of legs                                   */
+#define PPGPU_CHAIN_INFEASIBLE  2u /* the last costed leg is PPGPU_F_INFEASIBLE (AStarPlanner.cpp:53-56)                 */
+#define PPGPU_CHAIN_GOAL        3u /* the last costed leg's child satisfies goalCondition (AStarPlanner.cpp:57)          */
+#define PPGPU_CHAIN_THROWS      4u /* the last costed leg is PPGPU_F_THROWS: the reference throws out of plan() here     */
+#define PPGPU_CHAIN_CAPACITY    5u /* PPGPU_F_DUBINS_ERR, PPGPU_F_RIBBON_LOST, or a child list that does not fit ribbon_stride */
+
+/* AStarPlanner::plan's walk over the previous plan (AStarPlanner.cpp:46-59) for n_plans plans in ONE call: plan p is the legs
+ * h_legs[h_leg_offsets[p] .. h_leg_offsets[p + 1]); its first leg starts from the open vertex its .vertex names (set with
+ * ppgpu_set_vertices; any number of plans may share one; the .vertex of later legs is not read), every later leg from the vertex
+ * the leg before produced — Vertex::connect(lastPlanEnd, wrapper, coverageAllowed) + Edge::computeTrueCost (Vertex.cpp:28-36,
+ * Edge.cpp:68-206) — end state, g, coverageCompletedTime and child ribbon list, which never leave the device.  The walk of a plan
+ * ends after a leg that is infeasible, reaches a goal, throws or exceeds a capacity, or after its last leg: h_legs_costed[p] legs
+ * were costed and h_stop[p] says why (PPGPU_CHAIN_*).  PPGPU_F_RIBBON_OVF on a record whose child list fits ribbon_stride does not
+ * end it (only h was not enumerated).  Leg k of plan p leaves its record in h_results[h_leg_offsets[p] + k] and its child ribbons
+ * in the same slot of h_child_ribbons (ribbon_stride * 4 doubles, may be NULL), exactly the bytes ppgpu_set_vertices +
+ * ppgpu_cost_wrapper_edges_host give leg by leg; the slots of legs that were not costed are left untouched.  ribbon_stride is
+ * 1 .. 64.  A leg whose rho differs from the radius its coverage flag implies (Edge.cpp:78-80 re-solves it) is refused with
+ * PPGPU_EINVAL: the caller ends the chain before it.  Synchronous: one upload, one launch sequence per depth with no host wait
+ * between depths, one download, one host wait.  The handle's open vertices are unchanged afterwards. */
+int ppgpu_cost_plans_host(ppgpu_ctx* ctx, int32_t n_plans, const int32_t* h_leg_offsets, const ppgpu_wrapper_edge* h_legs,
+                          ppgpu_edge_result* h_results, double* h_child_ribbons, int32_t ribbon_stride,
+                          int32_t* h_legs_costed, uint32_t* h_stop);
+
 /* ------------------------------------------------------------------ edge traces */
 
 /* What happened ALONG an edge: one record per executed step of the sweep of Edge::computeTrueCost (Edge.cpp:125-175), i.e. per

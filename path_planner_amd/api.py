@@ -71,6 +71,7 @@ def _load():
         "ppgpu_cost_edges_list": (C.c_int, [vp, i64, vp, vp, vp, i32]),
         "ppgpu_cost_edges_host": (C.c_int, [vp, i64, vp, vp, vp, i32]),
         "ppgpu_cost_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, i32]),
+        "ppgpu_cost_plans_host": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, vp]),
         "ppgpu_trace_edges_list": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
         "ppgpu_trace_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
         "ppgpu_trace_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
@@ -311,6 +312,28 @@ class Context:
         child = np.zeros((e.shape[0], stride, 4), dtype=np.float64) if stride > 0 else None
         self._ck(LIB.ppgpu_cost_wrapper_edges_host(self._h, e.shape[0], _ptr(e), _ptr(res), _ptr(child), stride), "ppgpu_cost_wrapper_edges_host")
         return (res, child) if stride > 0 else res
+
+    def cost_plans(self, leg_offsets, legs, stride, results=None, child=None, want_child=True):
+        """AStarPlanner.cpp:46-59 for many plans in one call (ppgpu_cost_plans_host): plan p is legs[leg_offsets[p]:leg_offsets[p + 1]],
+        each leg's .vertex its plan's start vertex.  Returns (records, child ribbons or None, legs_costed, stop codes); `results` /
+        `child`: arrays to write into (the slots of legs that were not costed are left as they are), zeroed ones by default."""
+        from .types import WRAPPER_EDGE_DTYPE
+        off = np.ascontiguousarray(leg_offsets, dtype=np.int32)
+        e = np.ascontiguousarray(legs, dtype=WRAPPER_EDGE_DTYPE)
+        n_plans = off.shape[0] - 1
+        assert n_plans >= 0 and (n_plans == 0 or int(off[-1]) <= e.shape[0])
+        if results is None:
+            results = np.zeros(e.shape[0], dtype=RESULT_DTYPE)
+        if child is None and want_child:
+            child = np.zeros((e.shape[0], stride, 4), dtype=np.float64)
+        assert results.dtype == RESULT_DTYPE and results.shape == (e.shape[0],) and results.flags["C_CONTIGUOUS"]
+        assert child is None or (child.dtype == np.float64 and child.shape == (e.shape[0], stride, 4) and child.flags["C_CONTIGUOUS"])
+        costed = np.zeros(n_plans, dtype=np.int32)
+        stop = np.zeros(n_plans, dtype=np.uint32)
+        self._ck(LIB.ppgpu_cost_plans_host(self._h, n_plans, _ptr(off), _ptr(e) if e.shape[0] else None, _ptr(results) if e.shape[0] else None,
+                                           _ptr(child) if child is not None and e.shape[0] else None, stride, _ptr(costed), _ptr(stop)),
+                 "ppgpu_cost_plans_host")
+        return results, child, costed, stop
 
     def trace_edges_list(self, n, d_edges, d_results, step_stride, d_counts, d_steps):
         self._ck(LIB.ppgpu_trace_edges_list(self._h, n, _ptr(d_edges), _ptr(d_results), step_stride, _ptr(d_counts), _ptr(d_steps)),

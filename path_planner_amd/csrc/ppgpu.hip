@@ -6,6 +6,7 @@
 // separately (baseline x86-64), and so must the device code.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1423,6 +1424,124 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
         n++;
     }
     *n_edges = n;
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ plan chains
+// Depth d of the call costs leg d of every plan that has one, as ONE wrapper-edge launch; pp_k_chain_advance then makes each
+// plan's record the open vertex of its next leg and pp_k_time_grid builds that vertex's row.  Plans are handled most legs first,
+// so "the plans with more than d legs" is a prefix [0, n_d) and the legs, records and child slots of a depth are contiguous.
+// Running vertices live BEHIND the caller's open vertices (verts / tgrid rows nverts + j, ribbons from nribbons on, one stride
+// per plan); c->nverts and c->nribbons are never touched, so the handle is what the caller left once the call returns.
+int ppgpu_cost_plans_host(ppgpu_ctx* c, int32_t n_plans, const int32_t* offs, const ppgpu_wrapper_edge* h_legs, ppgpu_edge_result* h_results,
+                          double* h_child, int32_t stride, int32_t* h_costed, uint32_t* h_stop) {
+    int rc = require_cfg(c);
+    if (rc) return rc;
+    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_plans < 0 || (n_plans > 0 && (!offs || !h_costed || !h_stop))) return fail(PPGPU_EINVAL, "cost_plans_host: bad arguments");
+    if (stride <= 0 || stride > PP_WAVE) return fail(PPGPU_EINVAL, "cost_plans_host: ribbon_stride must be in 1 .. 64");
+    if (n_plans == 0) return PPGPU_OK;
+    if (offs[0] < 0) return fail(PPGPU_EINVAL, "cost_plans_host: negative leg offset");
+    for (int p = 0; p < n_plans; p++)
+        if (offs[p + 1] < offs[p]) return fail(PPGPU_EINVAL, "cost_plans_host: leg offsets must not decrease");
+    if (offs[n_plans] > offs[0] && (!h_legs || !h_results)) return fail(PPGPU_EINVAL, "cost_plans_host: null legs or results");
+    for (int i = offs[0]; i < offs[n_plans]; i++) {
+        const ppgpu_wrapper_edge& w = h_legs[i];
+        if (!(w.rho > 0) || !(w.speed > 0)) return fail(PPGPU_EINVAL, "cost_plans_host: rho and speed must be positive");
+        if (w.vertex < 0 || w.vertex >= c->nverts) return fail(PPGPU_EINVAL, "cost_plans_host: vertex out of range");
+        if (w.rho != (w.coverage_allowed ? c->cfg.coverage_turning_radius : c->cfg.turning_radius))
+            return fail(PPGPU_EINVAL, "cost_plans_host: a leg's rho differs from the radius its coverage flag implies (Edge.cpp:78-80 re-solves it: "
+                                      "end the chain before it and route it through ppgpu_cost_edges_*)");
+    }
+    // device order: most legs first (stable, so equal plans keep the caller's order)
+    std::vector<int> order((size_t)n_plans);
+    for (int p = 0; p < n_plans; p++) order[(size_t)p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return offs[a + 1] - offs[a] > offs[b + 1] - offs[b]; });
+    const int maxLegs = offs[order[0] + 1] - offs[order[0]];
+    for (int p = 0; p < n_plans; p++) { h_costed[p] = 0; h_stop[p] = PPGPU_CHAIN_LEGS; }
+    if (maxLegs == 0) return PPGPU_OK;
+    std::vector<int> nAt((size_t)maxLegs, 0);             // plans that have a leg at depth d
+    std::vector<size_t> at((size_t)maxLegs + 1, 0);       // where depth d starts in the device arrays
+    for (int p = 0; p < n_plans; p++)
+        for (int d = 0; d < offs[p + 1] - offs[p]; d++) nAt[(size_t)d]++;
+    for (int d = 0; d < maxLegs; d++) at[(size_t)d + 1] = at[(size_t)d] + (size_t)nAt[(size_t)d];
+    const size_t L = at[(size_t)maxLegs];
+    const int n1 = nAt[0];                                // plans with at least one leg
+    const int run0 = c->nverts, rib0 = c->nribbons;
+    if ((long long)run0 + n1 >= (1 << 24)) return fail(PPGPU_ECAPACITY, "cost_plans_host: open vertices plus plans exceed 2^24-1");
+    hipStream_t st = c->stream;
+    // ---- stage in: legs, depth-major | start vertex per plan
+    const size_t i_s = L * sizeof(ppgpu_wrapper_edge), in_bytes = i_s + (size_t)n1 * sizeof(int);
+    // ---- stage out: records | legs costed | stop | child slots (downloaded only when the caller wants them)
+    const size_t o_n = L * sizeof(ppgpu_edge_result), o_s = o_n + (size_t)n1 * sizeof(int), o_c = (o_s + (size_t)n1 * sizeof(unsigned) + 127) / 128 * 128,
+                 out_bytes = o_c + L * (size_t)stride * 4 * sizeof(double), down_bytes = h_child ? out_bytes : o_c;
+    if ((rc = stage_reserve(&c->stage_in, &c->stage_in_cap, in_bytes)) || (rc = stage_reserve(&c->stage_out, &c->stage_out_cap, down_bytes)) ||
+        (rc = c->dstage_in.reserve(in_bytes, false, st)) || (rc = c->dstage_out.reserve(out_bytes, false, st)) ||
+        (rc = c->verts.reserve((size_t)run0 + n1, true, st)) || (rc = c->ribbons.reserve(((size_t)rib0 + (size_t)n1 * stride) * 4, true, st)) ||
+        (rc = c->tgrid.reserve(((size_t)run0 + n1) * c->ng, true, st)))
+        return rc;
+    char* sin = (char*)c->stage_in;
+    ppgpu_wrapper_edge* sw = (ppgpu_wrapper_edge*)sin;
+    int* sstart = (int*)(sin + i_s);
+    for (int j = 0; j < n1; j++) {
+        const int p = order[(size_t)j];
+        sstart[j] = h_legs[offs[p]].vertex;
+        for (int d = 0; d < offs[p + 1] - offs[p]; d++) {
+            ppgpu_wrapper_edge& w = sw[at[(size_t)d] + (size_t)j];
+            w = h_legs[offs[p] + d];
+            if (d > 0) w.vertex = run0 + j;               // the plan's running vertex
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->dstage_in.p, sin, in_bytes, hipMemcpyHostToDevice, st));
+    // legs costed = 0, stop = 0 (running), child slots zero beyond each list as on the leg-by-leg route
+    HIP_TRY(hipMemsetAsync(c->dstage_out.p + o_n, 0, out_bytes - o_n, st));
+    ppgpu_wrapper_edge* d_legs = (ppgpu_wrapper_edge*)c->dstage_in.p;
+    ppgpu_edge_result* d_results = (ppgpu_edge_result*)c->dstage_out.p;
+    double* d_child = (double*)(c->dstage_out.p + o_c);
+    PPParams p;
+    fill_params(c, p);
+    p.nverts = run0 + n1;
+    p.edges = nullptr;
+    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
+    for (int d = 0; d < maxLegs; d++) {
+        const int nNow = nAt[(size_t)d], nNext = d + 1 < maxLegs ? nAt[(size_t)d + 1] : 0;
+        p.wedges = d_legs + at[(size_t)d];
+        p.n_edges = nNow;
+        p.out = d_results + at[(size_t)d]; p.child = d_child + at[(size_t)d] * (size_t)stride * 4; p.stride = stride;
+        if ((rc = launch_cost(c, p))) return rc;
+        PPChainArgs a;
+        a.results = p.out; a.child = p.child; a.stride = stride;
+        a.next = nNext > 0 ? d_legs + at[(size_t)d + 1] : nullptr;
+        a.n_now = nNow; a.n_next = nNext; a.depth = d;
+        a.start_vertex = (const int*)(c->dstage_in.p + i_s);
+        a.verts = c->verts.p; a.run0 = run0;
+        a.ribbons = c->ribbons.p; a.rib0 = rib0;
+        a.costed = (int*)(c->dstage_out.p + o_n); a.stop = (unsigned*)(c->dstage_out.p + o_s);
+        hipLaunchKernelGGL(pp_k_chain_advance, dim3((unsigned)nNow), dim3(64), 0, st, a);
+        if (nNext > 0)
+            hipLaunchKernelGGL(pp_k_time_grid, dim3((unsigned)nNext), dim3(64), 0, st, c->verts.p + run0, nNext, c->cfg.start_state_time,
+                               c->cfg.collision_checking_increment, c->cfg.max_speed, c->ng, c->tgrid.p + (size_t)run0 * c->ng);
+        HIP_TRY(hipGetLastError());
+    }
+    char* sout = (char*)c->stage_out;
+    HIP_TRY(hipMemcpyAsync(sout, c->dstage_out.p, down_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const ppgpu_edge_result* sr = (const ppgpu_edge_result*)sout;
+    const int* sn = (const int*)(sout + o_n);
+    const unsigned* ss = (const unsigned*)(sout + o_s);
+    const double* sc = (const double*)(sout + o_c);
+    const size_t slot = (size_t)stride * 4;
+    for (int j = 0; j < n1; j++) {
+        const int q = order[(size_t)j];
+        h_costed[q] = sn[j];
+        h_stop[q] = ss[j];
+        for (int d = 0; d < sn[j] && d < offs[q + 1] - offs[q]; d++) {   // (the slots of legs that were not costed stay as the caller left them)
+            const size_t from = at[(size_t)d] + (size_t)j, to = (size_t)(offs[q] + d);
+            h_results[to] = sr[from];
+            if (h_child) std::memcpy(h_child + to * slot, sc + from * slot, slot * sizeof(double));
+        }
+    }
     return PPGPU_OK;
 }
 

@@ -52,6 +52,8 @@ public:
     void setSpeculation(int n) { m_PlannerConfig.setSpeculation(n); }
     // PlannerConfig::setDeadlineGuard: off for a clock that does not advance while the device works (a scripted, counting clock)
     void setDeadlineGuard(bool on) { m_PlannerConfig.setDeadlineGuard(on); }
+    // PlannerConfig::setChainedPreviousPlan: the previous plan is re-costed by one device call per cycle instead of one per leg
+    void setChainedPreviousPlan(bool on) { m_PlannerConfig.setChainedPreviousPlan(on); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

@@ -45,6 +45,9 @@ public:
         // them (ppgpu_trace_wrapper_edges_host from the segment's parent vertex; the layout is ppgpu_step_record's).
         struct TraceStep { double x, y, heading, time, collision, penaltyBefore; uint32_t flags, step; double reserved; };
         std::vector<std::vector<TraceStep>> Trace;
+        // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
+        struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
+        std::vector<PreviousLeg> PreviousPlanLegs;
         // extra, for parity checks against the CPU oracle
         long FirstGoalIteration = -1;
         unsigned long EdgesCosted = 0;
@@ -67,6 +70,7 @@ public:
             unsigned long DeviceGrowths = 0;  // device / pinned buffers the device library grew inside the call (ppgpu_growth_stats) ...
             double DeviceGrowthMs = 0;        // ... and what that took
             unsigned long RoundTrips = 0;
+            unsigned long PrologueTrips = 0;  // device round trips of the previous-plan pass (one per leg, or one for the whole chained prefix)
             unsigned long StrideRetries = 0;  // round trips repeated because a child's ribbon list did not fit the stride they were costed with
             double MaxWakeMs = 0;             // the longest a context's thread took to start a round trip handed to it
             double PickMs = 0, MaxPickMs = 0;  // choosing the open vertices of the round trips (pickBatch): total and the longest single walk
@@ -219,6 +223,25 @@ public:
                double timeRemaining) override;
 
     typedef SearchNode Node;
+
+    // What a whole plan costs in the current world and how far along it is still feasible (evaluatePlans).
+    struct PlanEvaluation {
+        struct Leg { bool feasible = false; double g = 0, collisionPenalty = 0; };
+        enum Stop { RanOutOfLegs = 1, Infeasible = 2, Goal = 3, Throws = 4, Capacity = 5 };     // PPGPU_CHAIN_*
+        int legsCosted = 0;                   // legs walked, the one the walk stopped at included
+        Stop stop = RanOutOfLegs;
+        std::vector<Leg> legs;                // [legsCosted]
+        double g = 0;                         // currentCost of the last feasible vertex reached (0: none)
+        double collisionPenalty = 0;          // summed over the feasible legs
+        double coverageCompletedTime = -1;    // of that vertex's RibbonManager
+        bool goalReached = false;
+        RibbonManager ribbons;                // ... and what it has left to cover
+    };
+    // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
+    // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
+    // configuration no longer has ends its plan's walk before it (legsCosted says how far it got, stop == RanOutOfLegs).
+    std::vector<PlanEvaluation> evaluatePlans(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
+                                              const std::vector<DubinsPlan>& plans);
 
 private:
     std::shared_ptr<GpuContext> m_Ctx;                    // device 0 of this planner: sampling read-back, wrapper edges, explicit targets

@@ -1068,6 +1068,80 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ evaluatePlans()
+// "What does this whole plan cost in the current world, and how far along is it still feasible": the walk plan() makes over its
+// previous plan (AStarPlanner.cpp:46-59), for any number of candidate plans from one start, all in ONE ppgpu_cost_plans_host call.
+std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
+                                                                            const std::vector<DubinsPlan>& plans) {
+    m_Config = std::move(config);
+    m_Config.setStartStateTime(start.time());
+    m_RibbonManager = ribbonManager;
+    m_RibbonManager.changeHeuristicIfTooManyRibbons();
+    if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
+    m_StartStateTime = start.time();
+    drainInFlight();
+    uploadWorld(start);
+    ppgpu_ctx* h = m_Ctx->handle();
+    Node root;                                       // plan()'s root (:35-37)
+    root.state = start;
+    root.state.speed() = m_Config.maxSpeed();
+    root.g = 0;
+    root.ribbons = m_RibbonManager;
+    ppgpu_vertex v = makeVertex(root);
+    std::vector<double> rib;
+    ribbonsToArray(root.ribbons, rib);
+    check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+    std::vector<int32_t> offsets{0};
+    std::vector<ppgpu_wrapper_edge> legs;
+    for (const DubinsPlan& plan : plans) {
+        for (const auto& p : plan.get()) {
+            if (p.getEndTime() <= start.time() || p.getNetTime() == 0) continue;       // :49-50
+            const bool cov = p.getRho() == m_Config.coverageTurningRadius();
+            if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;   // Edge.cpp:78-80 would re-solve it
+            ppgpu_wrapper_edge we{};
+            we.vertex = 0;
+            we.coverage_allowed = cov ? 1 : 0;
+            const DubinsPath& dp = p.unwrap();
+            for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
+            we.rho = dp.rho; we.type = (int32_t)dp.type;
+            we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
+            legs.push_back(we);
+        }
+        offsets.push_back((int32_t)legs.size());
+    }
+    const size_t n = plans.size();
+    std::vector<ppgpu_edge_result> res(legs.size());
+    std::vector<double> child(legs.size() * (size_t)kRibbonStride * 4, 0.0);
+    std::vector<int32_t> costed(n, 0);
+    std::vector<uint32_t> why(n, 0);
+    check(ppgpu_cost_plans_host(h, (int32_t)n, offsets.data(), legs.data(), res.data(), child.data(), kRibbonStride, costed.data(), why.data()),
+          "ppgpu_cost_plans_host");
+    std::vector<PlanEvaluation> out(n);
+    for (size_t i = 0; i < n; i++) {
+        PlanEvaluation& e = out[i];
+        e.legsCosted = costed[i];
+        e.stop = (PlanEvaluation::Stop)why[i];
+        e.goalReached = why[i] == PPGPU_CHAIN_GOAL;
+        e.ribbons = root.ribbons;
+        e.coverageCompletedTime = root.ribbons.coverageCompletedTime();
+        e.legs.resize((size_t)costed[i]);
+        for (int k = 0; k < costed[i]; k++) {
+            const size_t at = (size_t)offsets[i] + (size_t)k;
+            const ppgpu_edge_result& r = res[at];
+            PlanEvaluation::Leg& leg = e.legs[(size_t)k];
+            leg.feasible = !(r.flags & (PPGPU_F_INFEASIBLE | PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST));
+            leg.g = r.g;
+            leg.collisionPenalty = r.collision_penalty;
+            if (!leg.feasible) continue;             // (only ever the last costed leg)
+            e.g = r.g;
+            e.collisionPenalty += r.collision_penalty;
+            e.coverageCompletedTime = r.coverage_completed_time;
+            e.ribbons.assign(child.data() + at * (size_t)kRibbonStride * 4, std::min((int)((r.info >> 8) & 0xff), kRibbonStride), r.coverage_completed_time);
+        }
+    }
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------------ plan()
 Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
                                      const DubinsPlan& previousPlan, double timeRemaining) {   // AStarPlanner.cpp:12-132
@@ -1134,15 +1208,63 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
     int lastPlanEnd = startV;
     std::vector<int> previousPlanNodes;   // the vertices made from it, for the search dump
     if (!previousPlan.empty()) {
-        for (const auto& p : previousPlan.get()) {
-            if (p.getEndTime() <= start.time()) continue;
-            if (p.getNetTime() == 0) continue;
+        const std::vector<DubinsWrapper>& prevLegs = previousPlan.get();
+        auto skipped = [&](const DubinsWrapper& p) { return p.getEndTime() <= start.time() || p.getNetTime() == 0; };   // :49-50
+        auto wrapperEdge = [&](const DubinsWrapper& p, bool cov) {
+            ppgpu_wrapper_edge we{};
+            we.vertex = 0;
+            we.coverage_allowed = cov ? 1 : 0;
+            const DubinsPath& dp = p.unwrap();
+            for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
+            we.rho = dp.rho; we.type = (int32_t)dp.type;
+            we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
+            return we;
+        };
+        // PlannerConfig::chainedPreviousPlan: the legs up to the first one at a radius the configuration no longer has (Edge.cpp:78-80
+        // re-solves that one: not a given curve any more) are costed by ONE call, every leg from the vertex the leg before left on the
+        // device.  The walk below then finds their records here instead of making a round trip per leg; it builds the same nodes.
+        std::vector<long> chainSlot(prevLegs.size(), -1);
+        std::vector<ppgpu_edge_result> chainRes;
+        std::vector<double> chainChild;
+        if (m_Config.chainedPreviousPlan()) {
+            std::vector<ppgpu_wrapper_edge> legs;
+            std::vector<size_t> legOf;
+            for (size_t i = 0; i < prevLegs.size(); i++) {
+                const DubinsWrapper& p = prevLegs[i];
+                if (skipped(p)) continue;
+                const bool cov = p.getRho() == m_Config.coverageTurningRadius();
+                if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;
+                legs.push_back(wrapperEdge(p, cov));
+                legOf.push_back(i);
+            }
+            if (!legs.empty()) {
+                ppgpu_vertex v = makeVertex(m_Nodes[startV]);
+                std::vector<double> rib;
+                ribbonsToArray(m_Nodes[startV].ribbons, rib);
+                check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+                const int32_t offsets[2] = {0, (int32_t)legs.size()};
+                int32_t costed = 0;
+                uint32_t why = 0;
+                chainRes.resize(legs.size());
+                chainChild.assign(legs.size() * (size_t)kRibbonStride * 4, 0.0);
+                check(ppgpu_cost_plans_host(h, 1, offsets, legs.data(), chainRes.data(), chainChild.data(), kRibbonStride, &costed, &why), "ppgpu_cost_plans_host");
+                m_Stats.Budget.PrologueTrips++;
+                for (int k = 0; k < costed; k++) chainSlot[legOf[(size_t)k]] = k;
+            }
+        }
+        for (size_t legIndex = 0; legIndex < prevLegs.size(); legIndex++) {
+            const DubinsWrapper& p = prevLegs[legIndex];
+            if (skipped(p)) continue;
             const bool cov = p.getRho() == m_Config.coverageTurningRadius();
             const double expectRho = cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius();
-            ppgpu_vertex v = makeVertex(m_Nodes[lastPlanEnd]);
-            std::vector<double> rib;
-            ribbonsToArray(m_Nodes[lastPlanEnd].ribbons, rib);
-            check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+            const long slot = chainSlot[legIndex];
+            if (slot < 0) {
+                ppgpu_vertex v = makeVertex(m_Nodes[lastPlanEnd]);
+                std::vector<double> rib;
+                ribbonsToArray(m_Nodes[lastPlanEnd].ribbons, rib);
+                check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+                m_Stats.Budget.PrologueTrips++;
+            }
             const size_t before = m_Nodes.size();
             if (p.getRho() != expectRho) {
                 // Edge.cpp:78-80: a curve at a radius the configuration no longer has is re-solved to the wrapper's end state
@@ -1159,16 +1281,19 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
                 std::make_heap(m_Queue.begin(), m_Queue.end(), [](const QEntry& a, const QEntry& b) { return a.f > b.f; });
                 m_Stats.Generated = gen;
             } else {
-                ppgpu_wrapper_edge we{};
-                we.vertex = 0;
-                we.coverage_allowed = cov ? 1 : 0;
                 const DubinsPath& dp = p.unwrap();
-                for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
-                we.rho = dp.rho; we.type = (int32_t)dp.type;
-                we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
                 ppgpu_edge_result r;
-                std::vector<double> child((size_t)kRibbonStride * 4);
-                check(ppgpu_cost_wrapper_edges_host(h, 1, &we, &r, child.data(), kRibbonStride), "ppgpu_cost_wrapper_edges_host");
+                std::vector<double> ownChild;
+                const double* child;
+                if (slot >= 0) {
+                    r = chainRes[(size_t)slot];
+                    child = chainChild.data() + (size_t)slot * kRibbonStride * 4;
+                } else {
+                    const ppgpu_wrapper_edge we = wrapperEdge(p, cov);
+                    ownChild.assign((size_t)kRibbonStride * 4, 0.0);
+                    check(ppgpu_cost_wrapper_edges_host(h, 1, &we, &r, ownChild.data(), kRibbonStride), "ppgpu_cost_wrapper_edges_host");
+                    child = ownChild.data();
+                }
                 m_Stats.EdgesCosted++;
                 g_dump.write(m_Nodes[lastPlanEnd].state, r, dp.rho, cov);
                 if (r.flags & PPGPU_F_THROWS) throw std::runtime_error("Invalid time in sample for Dubins path (previous plan)");
@@ -1185,7 +1310,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
                 c.steps = (int)(r.info >> 16);
                 c.g = r.g; c.h = r.h;
                 c.ribbons = m_Nodes[lastPlanEnd].ribbons;
-                c.ribbons.assign(child.data(), nChild, r.coverage_completed_time);
+                c.ribbons.assign(child, nChild, r.coverage_completed_time);
                 if (hostHeuristic) {
                     c.h = c.ribbons.approximateDistanceUntilDone(c.state.x(), c.state.y(), c.state.heading()) / m_Config.maxSpeed() * kTimePenaltyFactor;
                     m_Stats.HostHeuristics++;
@@ -1197,6 +1322,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
             if (m_Nodes.size() == before) break;
             lastPlanEnd = (int)m_Nodes.size() - 1;
             previousPlanNodes.push_back(lastPlanEnd);
+            m_Stats.PreviousPlanLegs.push_back({m_Nodes[lastPlanEnd].g, m_Nodes[lastPlanEnd].collisionPenalty, m_Nodes[lastPlanEnd].infeasible});
             if (m_Nodes[lastPlanEnd].infeasible) {
                 lastPlanEnd = startV;
                 break;

@@ -7,6 +7,11 @@
 //                  plan_trace_file path (with cfg plan_trace 1: one line per step of the returned plan) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
+//                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
+//                  prologue_ms and previous_plan_legs to the JSON) | evaluate (instead of plan(): GpuAStarPlanner::evaluatePlans on the `prev`
+//                  plan, or on every prev_begin ... prev_end block of prev lines; one JSON line of PlanEvaluations) |
+//                  replan_clock_calls n (replan under a counting clock: every cycle gets n polls of dt) | plan_log path (replan: one JSON
+//                  line per cycle with the plan and the search counters)
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -14,6 +19,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <string>
 
 #include "path_planner_amd/Planner.h"
 
@@ -43,7 +49,10 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath;
+    std::string cycleLogPath, planTracePath, planLogPath;
+    bool chainNamed = false, evaluate = false, inBlock = false;
+    std::vector<DubinsPlan> candidates;
+    long replanClockCalls = 0;
     std::string line;
     while (std::getline(in, line)) {
         std::istringstream s(line);
@@ -64,6 +73,7 @@ int main(int argc, char** argv) {
             else if (name == "speculation") config.setSpeculation((int)v);
             else if (name == "plan_trace") config.setPlanTrace(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
+            else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else { std::fprintf(stderr, "unknown cfg %s\n", name.c_str()); return 2; }
         } else if (k == "start") {
             double x, y, h, v, t; s >> x >> y >> h >> v >> t; start = State(x, y, h, v, t);
@@ -90,6 +100,11 @@ int main(int argc, char** argv) {
         } else if (k == "fail_shard") { s >> failShard;      // tests: this shard of a sharded_batch throws before its work
         } else if (k == "cycle_log") { s >> cycleLogPath;    // replan: one JSON line per cycle (Stats::Budget and what the cycle reached)
         } else if (k == "plan_trace_file") { s >> planTracePath;   // segment step x y heading time collision penalty_before flags
+        } else if (k == "plan_log") { s >> planLogPath;
+        } else if (k == "replan_clock_calls") { s >> replanClockCalls;
+        } else if (k == "evaluate") { evaluate = true;
+        } else if (k == "prev_begin") { candidates.emplace_back(); inBlock = true;
+        } else if (k == "prev_end") { inBlock = false;
         } else if (k == "repeat") { s >> repeat;
         } else if (k == "replan") { s >> replans >> replanStep;   // N consecutive cycles, start moved replanStep seconds along the plan
         } else if (k == "real_clock") { int v; s >> v; realClock = v != 0;   // now() = t0 + wall seconds since plan() began
@@ -99,7 +114,7 @@ int main(int argc, char** argv) {
             p.type = (DubinsPathType)type;
             DubinsWrapper w; w.fill(p, speed, st);
             if (w.getEndTime() > en) w.updateEndTime(en);
-            prev.append(w);
+            if (inBlock) candidates.back().append(w); else prev.append(w);
         }
     }
     RibbonManager rm((RibbonManager::Heuristic)H, hr, K);
@@ -139,6 +154,31 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
+    if (evaluate) {
+        try {
+            if (candidates.empty()) candidates.push_back(prev);
+            GpuAStarPlanner planner(contexts);
+            const std::vector<GpuAStarPlanner::PlanEvaluation> ev = planner.evaluatePlans(rm, start, config, candidates);
+            static const char* const why[] = {"?", "ran_out_of_legs", "infeasible", "goal", "throws", "capacity"};
+            std::printf("{\"evaluations\": [");
+            for (size_t i = 0; i < ev.size(); i++) {
+                const GpuAStarPlanner::PlanEvaluation& e = ev[i];
+                std::printf("%s{\"legs_costed\": %d, \"stop\": \"%s\", \"stop_code\": %d, \"goal\": %s, \"g\": %.17g, \"collision_penalty\": %.17g, "
+                            "\"coverage_completed_time\": %.17g, \"ribbons_left\": %d, \"legs\": [", i ? ", " : "", e.legsCosted,
+                            why[(int)e.stop >= 1 && (int)e.stop <= 5 ? (int)e.stop : 0], (int)e.stop, e.goalReached ? "true" : "false", e.g, e.collisionPenalty,
+                            e.coverageCompletedTime, (int)e.ribbons.count());
+                for (size_t k = 0; k < e.legs.size(); k++)
+                    std::printf("%s{\"feasible\": %s, \"g\": %.17g, \"collision_penalty\": %.17g}", k ? ", " : "", e.legs[k].feasible ? "true" : "false", e.legs[k].g,
+                                e.legs[k].collisionPenalty);
+                std::printf("]}");
+            }
+            std::printf("]}\n");
+            return 0;
+        } catch (const std::exception& e) {
+            std::printf("{\"exception\": \"%s\"}\n", e.what());
+            return 1;
+        }
+    }
     try {
         Planner::Stats st;
         std::vector<double> wall;
@@ -159,9 +199,13 @@ int main(int argc, char** argv) {
             double worstMs = 0;
             int failureCount = 0, horizonHalvings = 0;  // Executive::planLoop's back-off (executive.cpp:263-277)
             FILE* cycleLog = cycleLogPath.empty() ? nullptr : std::fopen(cycleLogPath.c_str(), "w");
+            FILE* planLog = planLogPath.empty() ? nullptr : std::fopen(planLogPath.c_str(), "w");
+            if (replanClockCalls > 0) { timeRemaining = (double)replanClockCalls * dt; config.setDeadlineGuard(false); }
             for (int cyc = 0; cyc < replans; cyc++) {
                 const auto w0 = std::chrono::steady_clock::now();
-                config.setNowFunction([&]() { return tNow + std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count(); });
+                long calls = 0;
+                if (replanClockCalls > 0) config.setNowFunction([&]() { return tNow + (double)(calls++) * dt; });
+                else config.setNowFunction([&]() { return tNow + std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count(); });
                 GpuAStarPlanner planner(contexts);
                 st = planner.plan(rm, cur, config, prev, timeRemaining);
                 wall.push_back(1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count());
@@ -196,6 +240,20 @@ int main(int argc, char** argv) {
                                  cyc, wall.back(), 1e3 * timeRemaining, b.LoopEndMs, b.LastOpKind, b.LastOpStartMs, b.LastOpPredictedMs, b.LastOpActualMs, b.MarginMs, b.MaxTripMs,
                                  b.WorstUnderPredictionMs, b.NodeRegrowths, b.NodeRegrowthMs, b.DeviceGrowths, b.DeviceGrowthMs, b.PrologueMs, b.PickMs, b.MaxPickMs,
                                  (unsigned long)st.OrderFallbacks, b.MaxWakeMs, (unsigned long)st.Iterations, (unsigned long)st.Samples, (unsigned long)st.Expanded);
+                if (planLog) {
+                    std::fprintf(planLog, "{\"cycle\": %d, \"expanded\": %lu, \"generated\": %lu, \"edges\": %lu, \"iterations\": %lu, \"first_goal_iteration\": %ld, "
+                                 "\"round_trips\": %lu, \"prologue_trips\": %lu, \"prologue_ms\": %.3f, \"previous_plan_legs\": %zu, \"plan\": [", cyc, (unsigned long)st.Expanded,
+                                 (unsigned long)st.Generated, (unsigned long)st.EdgesCosted, (unsigned long)st.Iterations, st.FirstGoalIteration, b.RoundTrips + b.PrologueTrips,
+                                 b.PrologueTrips, b.PrologueMs, st.PreviousPlanLegs.size());
+                    bool firstSeg = true;
+                    for (const auto& w : st.Plan.get()) {
+                        const DubinsPath& p = w.unwrap();
+                        std::fprintf(planLog, "%s[%.17g, %.17g, %.17g, %.17g, %.17g, %.17g, %.17g, %d, %.17g, %.17g, %.17g]", firstSeg ? "" : ", ", p.qi[0], p.qi[1], p.qi[2],
+                                     p.param[0], p.param[1], p.param[2], p.rho, (int)p.type, w.getSpeed(), w.getStartTime(), w.getEndTime());
+                        firstSeg = false;
+                    }
+                    std::fprintf(planLog, "]}\n");
+                }
                 tNow += replanStep;
                 if (st.Plan.empty()) {
                     failures++; failedCycles.push_back(cyc);
@@ -217,6 +275,7 @@ int main(int argc, char** argv) {
                 rm.cover(cur.x(), cur.y(), false);      // Executive::updateCovered: the vehicle covers as it moves
             }
             if (cycleLog) std::fclose(cycleLog);
+            if (planLog) std::fclose(planLog);
             // the first cycle of a process allocates the device buffers (they persist in the contexts): reported on its own,
             // the percentiles are over the cycles after it
             const double firstCycle = wall.front();
@@ -270,10 +329,23 @@ int main(int argc, char** argv) {
                         p.qi[2], p.param[0], p.param[1], p.param[2], p.rho, (int)p.type, w.getSpeed(), w.getStartTime(), w.getEndTime());
             first = false;
         }
+        std::string tail;                     // (only when the scenario names the switch: without it the line is what it always was)
+        if (chainNamed) {
+            char buf[256];
+            std::snprintf(buf, sizeof buf, ", \"round_trips\": %lu, \"prologue_trips\": %lu, \"prologue_ms\": %.3f, \"previous_plan_legs\": [",
+                          st.Budget.RoundTrips + st.Budget.PrologueTrips, st.Budget.PrologueTrips, st.Budget.PrologueMs);
+            tail = buf;
+            for (size_t i = 0; i < st.PreviousPlanLegs.size(); i++) {
+                std::snprintf(buf, sizeof buf, "%s{\"g\": %.17g, \"collision_penalty\": %.17g, \"infeasible\": %s}", i ? ", " : "", st.PreviousPlanLegs[i].g,
+                              st.PreviousPlanLegs[i].collisionPenalty, st.PreviousPlanLegs[i].infeasible ? "true" : "false");
+                tail += buf;
+            }
+            tail += "]";
+        }
         if (config.planTrace()) {
             size_t nSteps = 0;
             for (const auto& seg : st.Trace) nSteps += seg.size();
-            std::printf("], \"plan_trace_segments\": %zu, \"plan_trace_steps\": %zu}\n", st.Trace.size(), nSteps);
+            std::printf("], \"plan_trace_segments\": %zu, \"plan_trace_steps\": %zu%s}\n", st.Trace.size(), nSteps, tail.c_str());
             if (!planTracePath.empty()) {
                 FILE* f = std::fopen(planTracePath.c_str(), "w");
                 if (!f) { std::fprintf(stderr, "cannot write %s\n", planTracePath.c_str()); return 2; }
@@ -283,7 +355,7 @@ int main(int argc, char** argv) {
                 std::fclose(f);
             }
         } else {
-            std::printf("]}\n");
+            std::printf("]%s}\n", tail.c_str());
         }
     } catch (const std::exception& e) {
         std::printf("{\"exception\": \"%s\"}\n", e.what());
