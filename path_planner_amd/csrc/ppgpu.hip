@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -53,10 +54,15 @@ struct GrowthTimer {
         g_growth_ns.fetch_add((unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(), std::memory_order_relaxed);
     }
 };
+// A grow-only device array that frees itself (with its owner: the device must be current then).
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int reserve(size_t n, bool keep, hipStream_t s) {
         if (n <= cap) return PPGPU_OK;
         GrowthTimer growth;
@@ -64,22 +70,32 @@ struct DevBuf {
         while (ncap < n) ncap *= 2;
         T* np = nullptr;
         HIP_TRY(hipMalloc((void**)&np, ncap * sizeof(T)));
+        // from here on a failure gives the new block back: the buffer stays what it was
+        hipError_t e = hipSuccess;
         if (keep && p && cap) {
-            HIP_TRY(hipMemcpyAsync(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
+            e = hipMemcpyAsync(np, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
         }
-        if (p) HIP_TRY(hipFree(p));
+        if (e == hipSuccess && p) e = hipFree(p);
+        if (e != hipSuccess) {
+            (void)hipFree(np);
+            return fail(PPGPU_EHIP, std::string("DevBuf::reserve: ") + hipGetErrorString(e));
+        }
         p = np; cap = ncap;
         return PPGPU_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
 #define PP_TIMING_RING 8
+// The events of one timed costing launch, in stream order except EV_APPROACHED (recorded between EV_POSED and the cover sweep).
+// A sliced launch records EV_BEGIN .. EV_COVERED and EV_APPROACHED once per slice, EV_END once.
+enum { EV_BEGIN, EV_SOLVED, EV_POSED, EV_COVERED, EV_END, EV_APPROACHED, EV_COUNT };
+// The device arrays (DevBuf) free themselves; ~ppgpu_ctx releases the streams, events and pinned blocks.  ppgpu_destroy makes the
+// device current and waits for the stream first.
 struct ppgpu_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
-    hipStream_t side_stream = nullptr;                 // pp_k_heuristic_listed runs beside the lane heuristic (launch_cost)
+    hipStream_t side_stream = nullptr;                 // pp_k_heuristic_listed runs beside the lane heuristic (cost_heuristic_tail)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool have_cfg = false;
     ppgpu_config cfg{};
@@ -120,7 +136,6 @@ struct ppgpu_ctx {
     DevBuf<double> tmp_child, tmp_lengths, tmp_len_out, int_child;
     DevBuf<ppgpu_step_record> tmp_steps;   // device end of the host forms of ppgpu_trace_*: the step records of one trace slice
     DevBuf<int> tmp_counts;
-    long long last_slice_edges = 0;     // edges per workspace slice of the last costing launch (>= its edge count: the setup records of the whole list are still there)
     hipEvent_t ev_trace[2] = {nullptr, nullptr};   // around pp_k_trace_steps (ppgpu_last_trace_timing)
     double ms_trace_earlier = 0;        // ... of the slices before the last one
     bool trace_timed = false;
@@ -147,11 +162,9 @@ struct ppgpu_ctx {
     // optional per-kernel timing of costing launches (ppgpu_enable_timing)
     bool timing = false;
     // a ring of event sets: the last PP_TIMING_RING launches can be read back without a host wait between them
-    hipEvent_t ev_ring[PP_TIMING_RING][6] = {};   // [0..4] as the launch goes; [5] between the approach prepass and the cover sweep
-    double ms_ring[PP_TIMING_RING][4] = {};    // solve / pose / cover / approach time of the slices before the last one of a sliced launch
-    hipEvent_t* ev = ev_ring[0];               // the set of the launch being recorded / recorded last
-    double* ms_earlier_slices = ms_ring[0];
-    int ev_slot = 0;
+    hipEvent_t ev_ring[PP_TIMING_RING][EV_COUNT] = {};
+    double ms_ring[PP_TIMING_RING][4] = {};    // solve / pose / cover / approach time of the slices before the last one of a sliced launch (slice_durations)
+    int ev_slot = 0;                           // the set of the launch being recorded / recorded last
     long long last_launch_edges = 0;           // edges of the last costing launch, and whether its cover sweep took a packed list
     bool last_launch_packed = false;           // (then the list's length is at need_big[12]: last slice)
     long long live_earlier_slices = 0;
@@ -171,6 +184,13 @@ struct ppgpu_ctx {
     // ppgpu_copy_engine_read: the HSA agents of this device and of the host, the completion signal of the copy in flight
     unsigned long long hsa_gpu = 0, hsa_cpu = 0, hsa_signal = 0;
     bool copy_pending = false;
+
+    __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
+        for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
+        for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_trace[0], ev_trace[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
+    }
 };
 
 static int require_cfg(ppgpu_ctx* c) {
@@ -179,6 +199,49 @@ static int require_cfg(ppgpu_ctx* c) {
     return PPGPU_OK;
 }
 
+// the forms that take their curves from the caller need open vertices but no targets
+static int require_vertices(ppgpu_ctx* c) {
+    int rc = require_cfg(c);
+    if (rc) return rc;
+    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
+    return PPGPU_OK;
+}
+
+static int require_world(ppgpu_ctx* c) {
+    int rc = require_vertices(c);
+    if (rc) return rc;
+    if (c->n_samples + c->n_extra <= 0) return fail(PPGPU_ESTATE, "no targets: call ppgpu_sampler_add, ppgpu_set_samples or ppgpu_set_extra_targets");
+    return PPGPU_OK;
+}
+
+// Checks of what an entry point was handed; `who` is its name in the message.
+static int check_open_vertices(const ppgpu_ctx* c, const char* who, int n, const ppgpu_vertex* hv, int n_ribbons, int* max_ribbons) {
+    *max_ribbons = 0;
+    for (int i = 0; i < n; i++) {
+        if (hv[i].ribbon_count < 0 || hv[i].ribbon_offset < 0 || hv[i].ribbon_offset + hv[i].ribbon_count > n_ribbons)
+            return fail(PPGPU_EINVAL, std::string(who) + ": ribbon range outside the pool");
+        if (hv[i].ribbon_count > PP_WAVE) return fail(PPGPU_ECAPACITY, std::string(who) + ": more than 64 ribbons on one vertex");
+        if (hv[i].time < c->cfg.start_state_time) return fail(PPGPU_EINVAL, std::string(who) + ": vertex time before start_state_time");
+        if (hv[i].ribbon_count > *max_ribbons) *max_ribbons = hv[i].ribbon_count;
+    }
+    return PPGPU_OK;
+}
+
+static int check_wrapper_edges(const ppgpu_ctx* c, const char* who, int64_t n, const ppgpu_wrapper_edge* w) {
+    for (int64_t i = 0; i < n; i++) {
+        if (!(w[i].rho > 0) || !(w[i].speed > 0)) return fail(PPGPU_EINVAL, std::string(who) + ": rho and speed must be positive");
+        if (w[i].vertex < 0 || w[i].vertex >= c->nverts) return fail(PPGPU_EINVAL, std::string(who) + ": vertex out of range");
+    }
+    return PPGPU_OK;
+}
+
+static int trace_args(const char* who, int64_t n, const void* edges, int32_t stride, const void* counts, const void* steps) {
+    if (n < 0 || (n > 0 && (!edges || !counts || !steps))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
+    if (stride <= 0 || stride > 65535) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
+    return PPGPU_OK;
+}
+
+namespace { struct CtxDelete { void operator()(ppgpu_ctx* c) const { delete c; } }; }     // (internal linkage: ppgpu_create's guard)
 static void ppgpu_copy_engine_release(ppgpu_ctx* c);      // (further down, with the HSA entry points)
 extern "C" int ppgpu_copy_engine_wait(ppgpu_ctx* c);
 
@@ -197,7 +260,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PPGPU_ENODEV, std::string("device is ") + prop.gcnArchName + ", this library carries gfx950 code only");
-    ppgpu_ctx* c = new ppgpu_ctx();
+    std::unique_ptr<ppgpu_ctx, CtxDelete> c(new ppgpu_ctx());      // (an early return below frees what was made so far)
     c->device = device;
     c->n_cu = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
@@ -215,7 +278,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
     }
-    *out = c;
+    *out = c.release();
     return PPGPU_OK;
 }
 
@@ -226,24 +289,6 @@ int ppgpu_destroy(ppgpu_ctx* c) {
     if (c->comm) (void)ppgpu_comm_destroy(c);
     if (c->copy_pending) (void)ppgpu_copy_engine_wait(c);
     ppgpu_copy_engine_release(c);
-    c->grid.release(); c->grid_clear.release(); c->grid_rowclear.release(); c->obst.release(); c->verts.release(); c->ribbons.release(); c->tgrid.release();
-    c->sx.release(); c->sy.release(); c->sh.release(); c->samp_ribbons.release(); c->samp_pos.release();
-    c->s_bytes.release(); c->s_u64.release(); c->s_u32a.release(); c->s_u32b.release(); c->s_cand.release();
-    c->tmp_edges.release(); c->tmp_wedges.release(); c->partial.release(); c->tmp_results.release(); c->tmp_child.release(); c->tmp_steps.release(); c->tmp_counts.release();
-    c->ord_key.release(); c->ord_val.release(); c->ord_idx.release(); c->ord_fallbacks.release(); c->ord_len.release();
-    c->ord_blockmin.release(); c->ord_blockcnt.release(); c->ord_bound.release(); c->ord_count.release(); c->near_idx.release(); c->near_count.release(); c->probe_bound.release();
-    c->tmp_lengths.release(); c->tmp_len_out.release(); c->tmp_idx.release(); c->gather.release(); c->int_child.release();
-    c->setup.release(); c->track_hits.release(); c->track_eq.release(); c->track_chunk_hits.release();
-    c->track_summary.release(); c->track_far.release(); c->track_skip.release(); c->track_pen.release(); c->track_chunk_pen.release(); c->need_big.release(); c->defer_list.release(); c->live_list.release(); c->hw_list.release(); c->cover_state.release(); c->work.release(); c->dstage_in.release(); c->dstage_out.release();
-    if (c->pinned_counts) (void)hipHostFree(c->pinned_counts);
-    if (c->stage_in) (void)hipHostFree(c->stage_in);
-    if (c->stage_out) (void)hipHostFree(c->stage_out);
-    for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < 6; i++) if (c->ev_ring[r][i]) (void)hipEventDestroy(c->ev_ring[r][i]);
-    for (int i = 0; i < 2; i++) if (c->ev_trace[i]) (void)hipEventDestroy(c->ev_trace[i]);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return PPGPU_OK;
 }
@@ -258,12 +303,22 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
-        for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
+        for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < EV_COUNT; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
     if (on && !c->ev_trace[0])
         for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&c->ev_trace[i]));
     c->timing = on != 0;
     c->ev_launches = 0;
     c->trace_timed = false;
+    return PPGPU_OK;
+}
+
+// Solve, pose sweep, cover sweep and approach prepass of the slice an event set recorded last (its EV_COVERED has been waited for).
+// The cover sweep alone: from EV_APPROACHED.
+static int slice_durations(hipEvent_t* ev, float ms[4]) {
+    HIP_TRY(hipEventElapsedTime(&ms[0], ev[EV_BEGIN], ev[EV_SOLVED]));
+    HIP_TRY(hipEventElapsedTime(&ms[1], ev[EV_SOLVED], ev[EV_POSED]));
+    HIP_TRY(hipEventElapsedTime(&ms[2], ev[EV_APPROACHED], ev[EV_COVERED]));
+    HIP_TRY(hipEventElapsedTime(&ms[3], ev[EV_POSED], ev[EV_APPROACHED]));
     return PPGPU_OK;
 }
 
@@ -274,12 +329,13 @@ int ppgpu_past_timing(ppgpu_ctx* c, int32_t back, double* ms_solve, double* ms_p
     HIP_TRY(hipSetDevice(c->device));
     const int slot = (c->ev_slot - back + PP_TIMING_RING) % PP_TIMING_RING;
     hipEvent_t* ev = c->ev_ring[slot];
-    HIP_TRY(hipEventSynchronize(ev[4]));
-    float t[4] = {0, 0, 0, 0}, ta = 0;
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&t[i], ev[i == 2 ? 5 : i], ev[i + 1]));   // the cover sweep alone: from event 5
-    HIP_TRY(hipEventElapsedTime(&ta, ev[2], ev[5]));                                                   // the approach prepass
+    HIP_TRY(hipEventSynchronize(ev[EV_END]));
+    float t[4] = {0, 0, 0, 0}, tail = 0;
+    int rc = slice_durations(ev, t);
+    if (rc) return rc;
+    HIP_TRY(hipEventElapsedTime(&tail, ev[EV_COVERED], ev[EV_END]));
     *ms_solve = t[0] + c->ms_ring[slot][0]; *ms_pose = t[1] + c->ms_ring[slot][1]; *ms_cover = t[2] + c->ms_ring[slot][2];
-    *ms_heuristic = t[3] + ta + c->ms_ring[slot][3];
+    *ms_heuristic = tail + t[3] + c->ms_ring[slot][3];               // the heuristic tail and the approach prepass
     return PPGPU_OK;
 }
 int ppgpu_last_timing(ppgpu_ctx* c, double* ms_solve, double* ms_pose, double* ms_cover, double* ms_heuristic) {
@@ -480,12 +536,8 @@ int ppgpu_set_vertices(ppgpu_ctx* c, int32_t n, const ppgpu_vertex* hv, int32_t 
     HIP_TRY(hipSetDevice(c->device));
     if (n <= 0 || !hv || n_ribbons < 0 || (n_ribbons > 0 && !hr)) return fail(PPGPU_EINVAL, "vertices: bad arguments");
     if (n >= (1 << 24)) return fail(PPGPU_ECAPACITY, "vertices: at most 2^24-1 open vertices");
-    for (int i = 0; i < n; i++) {
-        if (hv[i].ribbon_count < 0 || hv[i].ribbon_offset < 0 || hv[i].ribbon_offset + hv[i].ribbon_count > n_ribbons)
-            return fail(PPGPU_EINVAL, "vertices: ribbon range outside the pool");
-        if (hv[i].ribbon_count > PP_WAVE) return fail(PPGPU_ECAPACITY, "vertices: more than 64 ribbons on one vertex");
-        if (hv[i].time < c->cfg.start_state_time) return fail(PPGPU_EINVAL, "vertices: vertex time before start_state_time");
-    }
+    int maxr = 0;
+    if ((rc = check_open_vertices(c, "vertices", n, hv, n_ribbons, &maxr))) return rc;
     if ((rc = c->verts.reserve((size_t)n, false, c->stream))) return rc;
     if ((rc = c->ribbons.reserve((size_t)(n_ribbons > 0 ? n_ribbons : 1) * 4, false, c->stream))) return rc;
     if ((rc = c->tgrid.reserve((size_t)n * c->ng, false, c->stream))) return rc;
@@ -496,9 +548,7 @@ int ppgpu_set_vertices(ppgpu_ctx* c, int32_t n, const ppgpu_vertex* hv, int32_t 
                        c->cfg.collision_checking_increment, c->cfg.max_speed, c->ng, c->tgrid.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));  // the host arrays may go away after return
-    c->nverts = n; c->nribbons = n_ribbons;
-    c->max_vertex_ribbons = 0;
-    for (int i = 0; i < n; i++) if (hv[i].ribbon_count > c->max_vertex_ribbons) c->max_vertex_ribbons = hv[i].ribbon_count;
+    c->nverts = n; c->nribbons = n_ribbons; c->max_vertex_ribbons = maxr;
     return PPGPU_OK;
 }
 
@@ -732,14 +782,6 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.sx = c->sx.p; p.sy = c->sy.p; p.sh = c->sh.p; p.n_samples = c->n_samples + c->n_extra;
 }
 
-static int require_world(ppgpu_ctx* c) {
-    int rc = require_cfg(c);
-    if (rc) return rc;
-    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
-    if (c->n_samples + c->n_extra <= 0) return fail(PPGPU_ESTATE, "no targets: call ppgpu_sampler_add, ppgpu_set_samples or ppgpu_set_extra_targets");
-    return PPGPU_OK;
-}
-
 int ppgpu_dubins_lengths(ppgpu_ctx* c, int32_t v0, int32_t nv, double* d_lengths) {
     int rc = require_world(c);
     if (rc) return rc;
@@ -852,170 +894,220 @@ static unsigned resident_grid(ppgpu_ctx* c, int slot, void (*kernel)(PPParams), 
     return (unsigned)(need < c->resident[slot] ? need : c->resident[slot]);
 }
 
-static int launch_cost(ppgpu_ctx* c, PPParams& p) {
-    if (p.n_edges <= 0) return PPGPU_OK;
+// "Cost this list of n edges": packed descriptors on the device (d_edges), or wrapper edges on the device (d_wedges).  Records go
+// to d_out, child ribbon lists to d_child at `stride` ribbons per edge (NULL: the launch keeps them in a scratch of its own).
+static PPParams list_params(ppgpu_ctx* c, long long n, const unsigned long long* d_edges, const ppgpu_wrapper_edge* d_wedges,
+                            ppgpu_edge_result* d_out, double* d_child, int stride) {
+    PPParams p;
+    fill_params(c, p);
+    p.edges = d_edges; p.wedges = d_wedges;
+    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
+    p.n_edges = n;
+    p.out = d_out; p.child = d_child; p.stride = stride;
+    return p;
+}
+
+// One costing launch.  How it runs is decided once (cost_modes), before anything is reserved or launched; once launch_cost has
+// returned, this is also what the code that runs next (launch_trace) may rely on.
+struct CostLaunch {
+    PPParams p;          // the whole list as it is launched: n_edges = all of it, e_base = 0, the workspace pointers wired
+                         // (cost_workspace), child / stride = the launch's own scratch where the caller gave none
+    bool gaussian;       // the Gaussian obstacle model: its own planner and sweeps, two more track arrays, no lane kernels
+    bool prepasses;      // a large launch: pp_k_approach_events runs (a planner round trip of a few hundred edges is latency-bound) ...
+    bool skip_chunks;    // ... and so does the chunk-skip planner
+    bool packed;         // the cover sweep takes the packed list of the edges it still has to visit (live_list)
+    bool lane_finish;    // phase C of those edges: one lane per edge (pp_k_cover_finish)
+    bool fuse_h;         // the cover sweep computes h itself
+    bool defer_h;        // ... but leaves the TSP enumerations to pp_k_heuristic_lanes
+    bool quiet_finish, lane_split;   // what the handle's PPGPU_QUIET_FINISH / PPGPU_LANE_SPLIT switches allow, on large launches
+    bool forked;         // pp_k_heuristic_listed runs on the side stream
+    int nch, ngp;        // 64-step chunks per edge, and the steps they hold
+    long long slice;     // edges per workspace slice (>= p.n_edges: one piece, the setup records of the whole list are still there)
+};
+
+static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
+    const PPParams& p = m.p;
     const long long total = p.n_edges;
-    p.total_edges = total;
-    if ((total + PP_WPB - 1) / PP_WPB > 0x3fffffffll) return fail(PPGPU_ECAPACITY, "cost_edges: too many edges for one launch");
-    if (!p.child) {
-        // the heuristic kernel reads the child ribbon lists: keep them in a scratch the caller never sees
-        int stride = c->max_vertex_ribbons + 8;
-        if (stride > PP_WAVE) stride = PP_WAVE;
-        int rc = c->int_child.reserve((size_t)total * stride * 4, false, c->stream);
-        if (rc) return rc;
-        p.child = c->int_child.p;
-        p.stride = stride;
-    }
-    p.nch = (p.ng + PP_WAVE - 1) / PP_WAVE;
-    if (p.nch < 1) p.nch = 1;
-    p.ngp = p.nch * PP_WAVE;
-    const size_t per_edge = sizeof(PPEdgeSetup) + (size_t)p.ngp * sizeof(unsigned short) +
-                            (size_t)p.nch * (sizeof(unsigned long long) + sizeof(unsigned)) + sizeof(PPTrackSummary) +
-                            ((p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN) ? (size_t)(p.ngp + p.nch) * sizeof(double) : 0);
-    long long slice = (long long)(c->slice_bytes / per_edge);
-    if (slice < PP_WPB) slice = PP_WPB;
-    if (slice > total) slice = total;
-    const size_t ws = (size_t)slice;
-    c->last_slice_edges = slice;
-    {
-        int rc;
-        if ((rc = c->setup.reserve(ws, false, c->stream)) ||
-            (rc = c->track_hits.reserve(ws * p.ngp, false, c->stream)) ||
-            (rc = c->track_eq.reserve(ws * p.nch, false, c->stream)) ||
-            (rc = c->track_chunk_hits.reserve(ws * p.nch, false, c->stream)) ||
-            (rc = c->track_summary.reserve(ws, false, c->stream)) || (rc = c->track_far.reserve(ws, false, c->stream)) ||
-            (rc = c->track_skip.reserve(ws * p.nch, false, c->stream)))
-            return rc;
-        if (p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN &&
-            ((rc = c->track_pen.reserve(ws * p.ngp, false, c->stream)) || (rc = c->track_chunk_pen.reserve(ws * p.nch, false, c->stream))))
-            return rc;
-    }
-    p.setup = c->setup.p; p.track_hits = c->track_hits.p; p.track_eq = c->track_eq.p;
-    p.track_chunk_hits = c->track_chunk_hits.p; p.track_summary = c->track_summary.p; p.track_far = c->track_far.p;   // (cleared below for small launches)
-    // chunk skipping needs the clearance map (or no grid at all) and solved curves (a given curve may start late or end early)
-    // both prepasses pay for themselves on large launches only: a planner round trip of a few hundred edges is latency-bound
-    const bool big = total >= c->prepass_min_edges;
-    p.track_skip = (big && !p.wedges && (c->rows == 0 || c->grid_clear.p) && p.ng >= PP_WAVE) ? c->track_skip.p : nullptr;
-    if (!big) p.track_far = nullptr;
-    p.track_pen = c->track_pen.p; p.track_chunk_pen = c->track_chunk_pen.p;
-    {
-        int rc = c->need_big.reserve(32, false, c->stream);
-        if (rc) return rc;
-        p.need_big = c->need_big.p;   // cleared by the first slice's pp_k_solve_edges
-        if ((rc = c->work.reserve(PP_WORK_WORDS, false, c->stream))) return rc;
-        p.work = c->work.p;
-    }
+    m.gaussian = p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN;
+    m.nch = (p.ng + PP_WAVE - 1) / PP_WAVE;
+    if (m.nch < 1) m.nch = 1;
+    m.ngp = m.nch * PP_WAVE;
+    const size_t per_edge = sizeof(PPEdgeSetup) + (size_t)m.ngp * sizeof(unsigned short) +
+                            (size_t)m.nch * (sizeof(unsigned long long) + sizeof(unsigned)) + sizeof(PPTrackSummary) +
+                            (m.gaussian ? (size_t)(m.ngp + m.nch) * sizeof(double) : 0);
+    m.slice = (long long)(c->slice_bytes / per_edge);
+    if (m.slice < PP_WPB) m.slice = PP_WPB;
+    if (m.slice > total) m.slice = total;
+    // both prepasses pay for themselves on large launches only; chunk skipping also needs the clearance map (or no grid at all)
+    // and solved curves (a given curve may start late or end early)
+    m.prepasses = total >= c->prepass_min_edges;
+    m.skip_chunks = m.prepasses && !p.wedges && (c->rows == 0 || c->grid_clear.p) && p.ng >= PP_WAVE;
     const bool dubinsH = p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K;
-    const bool gaussianSweep = p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN;
-    p.fuse_h = (PP_FUSE_HEUR && !dubinsH && !gaussianSweep) ? 1 : 0;
-    p.defer_h = (p.fuse_h && big && PP_LANE_HEUR && c->lane_heuristic && total < (1ll << 32) &&
-                 (p.heuristic == PPGPU_H_TSP_POINT_ALL || p.heuristic == PPGPU_H_TSP_POINT_K)) ? 1 : 0;
-    p.quiet_finish = (p.track_far && c->quiet_finish) ? 1 : 0;
-    p.lane_split = (p.track_far && c->lane_split && !gaussianSweep) ? 1 : 0;
-    if (p.track_far && total < (1ll << 32)) {
-        int rc = c->live_list.reserve((size_t)slice * 2, false, c->stream);
-        if (rc) return rc;
-        p.live_list = c->live_list.p; p.live_count = c->need_big.p + 12;
-    }
+    m.fuse_h = PP_FUSE_HEUR && !dubinsH && !m.gaussian;
+    m.defer_h = m.fuse_h && m.prepasses && PP_LANE_HEUR && c->lane_heuristic && total < (1ll << 32) &&
+                (p.heuristic == PPGPU_H_TSP_POINT_ALL || p.heuristic == PPGPU_H_TSP_POINT_K);
+    m.quiet_finish = m.prepasses && c->quiet_finish;
+    m.lane_split = m.prepasses && c->lane_split && !m.gaussian;
+    m.packed = m.prepasses && total < (1ll << 32);
 #if defined(PP_DBG_COUNTS)
     const bool laneFinishBuilt = false;     // (those builds keep every edge with its wave: pp_cover_sweep_edge)
 #else
     const bool laneFinishBuilt = true;
 #endif
-    if (laneFinishBuilt && p.live_list && c->lane_finish && !gaussianSweep) {
-        // phase C of the edges the cover sweep's waves visit: one lane per edge (pp_k_cover_finish)
-        int rc;
-        if ((rc = c->cover_state.reserve((size_t)slice, false, c->stream)) || (rc = c->hw_list.reserve((size_t)total, false, c->stream))) return rc;
+    m.lane_finish = laneFinishBuilt && m.packed && c->lane_finish && !m.gaussian;
+    m.forked = m.lane_finish && m.fuse_h && p.heuristic != PPGPU_H_MAX_DISTANCE;
+}
+
+// Reserves the workspace of the launch and wires it, and the modes the kernels look at, into m.p.
+static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
+    PPParams& p = m.p;
+    const size_t total = (size_t)p.n_edges, ws = (size_t)m.slice;
+    hipStream_t st = c->stream;
+    int rc;
+    if (!p.child) {
+        // the heuristic kernel reads the child ribbon lists: keep them in a scratch the caller never sees
+        int stride = c->max_vertex_ribbons + 8;
+        if (stride > PP_WAVE) stride = PP_WAVE;
+        if ((rc = c->int_child.reserve(total * stride * 4, false, st))) return rc;
+        p.child = c->int_child.p;
+        p.stride = stride;
+    }
+    p.nch = m.nch; p.ngp = m.ngp;
+    if ((rc = c->setup.reserve(ws, false, st)) || (rc = c->track_hits.reserve(ws * p.ngp, false, st)) ||
+        (rc = c->track_eq.reserve(ws * p.nch, false, st)) || (rc = c->track_chunk_hits.reserve(ws * p.nch, false, st)) ||
+        (rc = c->track_summary.reserve(ws, false, st)) || (rc = c->track_far.reserve(ws, false, st)) ||
+        (rc = c->track_skip.reserve(ws * p.nch, false, st)))
+        return rc;
+    if (m.gaussian && ((rc = c->track_pen.reserve(ws * p.ngp, false, st)) || (rc = c->track_chunk_pen.reserve(ws * p.nch, false, st))))
+        return rc;
+    if ((rc = c->need_big.reserve(32, false, st)) || (rc = c->work.reserve(PP_WORK_WORDS, false, st))) return rc;
+    p.setup = c->setup.p; p.track_hits = c->track_hits.p; p.track_eq = c->track_eq.p;
+    p.track_chunk_hits = c->track_chunk_hits.p; p.track_summary = c->track_summary.p;
+    p.track_far = m.prepasses ? c->track_far.p : nullptr;
+    p.track_skip = m.skip_chunks ? c->track_skip.p : nullptr;
+    p.track_pen = c->track_pen.p; p.track_chunk_pen = c->track_chunk_pen.p;
+    p.need_big = c->need_big.p;   // cleared by the first slice's pp_k_solve_edges
+    p.work = c->work.p;
+    p.fuse_h = m.fuse_h; p.defer_h = m.defer_h; p.quiet_finish = m.quiet_finish; p.lane_split = m.lane_split;
+    if (m.packed) {
+        if ((rc = c->live_list.reserve(ws * 2, false, st))) return rc;
+        p.live_list = c->live_list.p; p.live_count = c->need_big.p + 12;
+    }
+    if (m.lane_finish) {
+        if ((rc = c->cover_state.reserve(ws, false, st)) || (rc = c->hw_list.reserve(total, false, st))) return rc;
         p.cover_state = c->cover_state.p; p.hw_list = c->hw_list.p; p.hw_count = c->need_big.p + 13;
     }
-    if (p.defer_h) {
-        int rc = c->defer_list.reserve((size_t)total * PP_HL_MAX_N, false, c->stream);
-        if (rc) return rc;
+    if (m.defer_h) {
+        if ((rc = c->defer_list.reserve(total * PP_HL_MAX_N, false, st))) return rc;
         p.defer_list = c->defer_list.p; p.defer_count = c->need_big.p + 16;     // [n] = deferred edges with n ribbons, n = 1 .. PP_HL_MAX_N
     }
-    if (c->timing) {                                  // the next set of the ring
-        c->ev_slot = (int)(c->ev_launches % PP_TIMING_RING);
-        c->ev = c->ev_ring[c->ev_slot];
-        c->ms_earlier_slices = c->ms_ring[c->ev_slot];
+    return PPGPU_OK;
+}
+
+// A sliced launch re-uses its events: bank the durations of the slice before (timing is a measurement aid: the wait costs the
+// overlap between slices, nothing else).
+static int bank_slice_timing(ppgpu_ctx* c, bool packed) {
+    hipEvent_t* ev = c->ev_ring[c->ev_slot];
+    HIP_TRY(hipEventSynchronize(ev[EV_COVERED]));
+    float ms[4] = {0, 0, 0, 0};
+    int rc = slice_durations(ev, ms);
+    if (rc) return rc;
+    for (int i = 0; i < 4; i++) c->ms_ring[c->ev_slot][i] += ms[i];
+    if (packed) { unsigned live = 0; HIP_TRY(hipMemcpy(&live, c->need_big.p + 12, sizeof(unsigned), hipMemcpyDeviceToHost)); c->live_earlier_slices += live; }
+    return PPGPU_OK;
+}
+
+// The kernels of one slice (p.e_base, p.n_edges): solve, [plan skips,] pose sweep, [approach prepass,] cover sweep[, lane finish].
+static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
+    const PPParams& p = m.p;
+    hipStream_t st = c->stream;
+    hipEvent_t* ev = c->ev_ring[c->ev_slot];
+    if (c->timing) HIP_TRY(hipEventRecord(ev[EV_BEGIN], st));
+    hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);
+    if (c->timing) HIP_TRY(hipEventRecord(ev[EV_SOLVED], st));
+    if (m.skip_chunks) {                                         // timed with the pose sweep
+        // one workgroup per epw consecutive edges: as many as give it 256 (edge, chunk) threads
+        int epw = 256 / p.nch;
+        if (epw < 1) epw = 1;
+        if (epw > PP_PLAN_EDGES_MAX) epw = PP_PLAN_EDGES_MAX;
+        const unsigned blocks = (unsigned)((p.n_edges + epw - 1) / epw);
+        const bool many = p.n_obst > PP_WAVE;
+        void (*planner)(PPParams, int) = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : pp_k_plan_skips_gaussian) : (many ? pp_k_plan_skips_many : pp_k_plan_skips);
+        hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, st, p, epw);
     }
-    c->ms_earlier_slices[0] = c->ms_earlier_slices[1] = c->ms_earlier_slices[2] = c->ms_earlier_slices[3] = 0;
-    for (long long e0 = 0; e0 < total; e0 += slice) {
-        p.e_base = e0; p.ws_base = 0; p.n_edges = (total - e0 < slice) ? (total - e0) : slice;
-        if (e0 == 0) c->live_earlier_slices = 0;
-        if (c->timing && e0 > 0) {
-            // a sliced launch re-uses the events: bank the previous slice's three durations first (timing is a measurement aid: the
-            // wait costs the overlap between slices, nothing else)
-            HIP_TRY(hipEventSynchronize(c->ev[3]));
-            for (int i = 0; i < 3; i++) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, c->ev[i == 2 ? 5 : i], c->ev[i + 1]));
-                c->ms_earlier_slices[i] += ms;
-            }
-            float msa = 0;
-            HIP_TRY(hipEventElapsedTime(&msa, c->ev[2], c->ev[5]));
-            c->ms_earlier_slices[3] += msa;
-            if (p.live_list) { unsigned live = 0; HIP_TRY(hipMemcpy(&live, c->need_big.p + 12, sizeof(unsigned), hipMemcpyDeviceToHost)); c->live_earlier_slices += live; }
-        }
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-        hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, c->stream, p);
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-        if (p.track_skip) {                                          // timed with the pose sweep
-            // one workgroup per epw consecutive edges: as many as give it 256 (edge, chunk) threads
-            int epw = 256 / p.nch;
-            if (epw < 1) epw = 1;
-            if (epw > PP_PLAN_EDGES_MAX) epw = PP_PLAN_EDGES_MAX;
-            const unsigned blocks = (unsigned)((p.n_edges + epw - 1) / epw);
-            const bool gauss = p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN, many = p.n_obst > PP_WAVE;
-            void (*planner)(PPParams, int) = gauss ? (many ? pp_k_plan_skips_gaussian_many : pp_k_plan_skips_gaussian) : (many ? pp_k_plan_skips_many : pp_k_plan_skips);
-            hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, c->stream, p, epw);
-        }
-        if (p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN)
-            hipLaunchKernelGGL(pp_k_pose_sweep_gaussian, dim3(resident_grid(c, 0, pp_k_pose_sweep_gaussian, p.n_edges)), dim3(PP_WPB * 64), 0, c->stream, p);
-        else
-            hipLaunchKernelGGL(pp_k_pose_sweep, dim3(resident_grid(c, 1, pp_k_pose_sweep, p.n_edges)), dim3(PP_WPB * 64), 0, c->stream, p);
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-        if (p.track_far) hipLaunchKernelGGL(pp_k_approach_events, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, c->stream, p);
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev[5], c->stream));
-        if (p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN)
-            hipLaunchKernelGGL(pp_k_cover_sweep_gaussian, dim3(resident_grid(c, 2, pp_k_cover_sweep_gaussian, p.n_edges)), dim3(PP_WPB * 64), 0, c->stream, p);
-        else
-            hipLaunchKernelGGL(pp_k_cover_sweep, dim3(resident_grid(c, 3, pp_k_cover_sweep, p.n_edges)), dim3(PP_WPB * 64), 0, c->stream, p);
-        if (p.cover_state)       // (the list's length is on the device: a grid for "every edge of the slice is on it", whose spare workgroups leave at once)
-            hipLaunchKernelGGL(pp_k_cover_finish, dim3((unsigned)((p.n_edges + PP_FINISH_THREADS - 1) / PP_FINISH_THREADS)), dim3(PP_FINISH_THREADS), 0, c->stream, p);
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-    }
-    p.e_base = 0;
-    p.n_edges = total;
+    void (*pose)(PPParams) = m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep;
+    hipLaunchKernelGGL(pose, dim3(resident_grid(c, m.gaussian ? 0 : 1, pose, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
+    if (c->timing) HIP_TRY(hipEventRecord(ev[EV_POSED], st));
+    if (m.prepasses) hipLaunchKernelGGL(pp_k_approach_events, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
+    if (c->timing) HIP_TRY(hipEventRecord(ev[EV_APPROACHED], st));
+    void (*cover)(PPParams) = m.gaussian ? pp_k_cover_sweep_gaussian : pp_k_cover_sweep;
+    hipLaunchKernelGGL(cover, dim3(resident_grid(c, m.gaussian ? 2 : 3, cover, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
+    if (m.lane_finish)       // (the list's length is on the device: a grid for "every edge of the slice is on it", whose spare workgroups leave at once)
+        hipLaunchKernelGGL(pp_k_cover_finish, dim3((unsigned)((p.n_edges + PP_FINISH_THREADS - 1) / PP_FINISH_THREADS)), dim3(PP_FINISH_THREADS), 0, st, p);
+    if (c->timing) HIP_TRY(hipEventRecord(ev[EV_COVERED], st));
+    return PPGPU_OK;
+}
+
+// What is left of h once every slice is swept (p: the whole list again).
+static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
+    const PPParams& p = m.p;
+    const long long total = p.n_edges;
+    hipStream_t st = c->stream;
     if (p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K)
-        hipLaunchKernelGGL(pp_k_heuristic_dubins, dim3(resident_grid(c, 4, pp_k_heuristic_dubins, total)), dim3(PP_H_WPB * 64), 0, c->stream, p);
-    else if (!p.fuse_h)
-        hipLaunchKernelGGL(pp_k_heuristic, dim3(resident_grid(c, 5, pp_k_heuristic, total)), dim3(PP_H_WPB * 64), 0, c->stream, p);
+        hipLaunchKernelGGL(pp_k_heuristic_dubins, dim3(resident_grid(c, 4, pp_k_heuristic_dubins, total)), dim3(PP_H_WPB * 64), 0, st, p);
+    else if (!m.fuse_h)
+        hipLaunchKernelGGL(pp_k_heuristic, dim3(resident_grid(c, 5, pp_k_heuristic, total)), dim3(PP_H_WPB * 64), 0, st, p);
     // The edges whose TSP enumeration the sweeps deferred: packed into one list per ribbon count, then a few lanes each
     // (pp_k_heuristic_lanes).  The rare edge pp_k_cover_finish left to a whole wave (pp_k_heuristic_listed: 7 or 8 child ribbons,
     // ~1 100 of config 3's 236 140 edges, each a single wave's work for ~170 us) runs on a second stream BESIDE it: the lane kernel
     // fills the rest of the machine meanwhile, and the two touch different records.  The main stream waits for the side stream
     // before the launch is over.
-    const bool forked = p.cover_state && p.fuse_h && p.heuristic != PPGPU_H_MAX_DISTANCE;
-    if (forked) {
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+    if (m.forked) {
+        HIP_TRY(hipEventRecord(c->ev_fork, st));
         HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
         // (as many workgroups as pp_k_heuristic keeps resident: same footprint; all but a few leave at once)
         hipLaunchKernelGGL(pp_k_heuristic_listed, dim3(resident_grid(c, 5, pp_k_heuristic, total)), dim3(PP_H_WPB * 64), 0, c->side_stream, p);
         HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
     }
-    if (p.defer_h)
-        hipLaunchKernelGGL(pp_k_deferred_list, dim3((unsigned)((total + 256 * PP_DL_PER - 1) / (256 * PP_DL_PER))), dim3(256), 0, c->stream, p);
-    if (p.defer_h)
-        hipLaunchKernelGGL(pp_k_heuristic_lanes, dim3((unsigned)((total * PP_HL_SPLIT + PP_HL_THREADS - 1) / PP_HL_THREADS) + PP_HL_MAX_N), dim3(PP_HL_THREADS), 0, c->stream, p);
-    // child lists of 9..12 ribbons under the K variant: a second pass that touches only those edges (the others cost it one
-    // 8-byte read each)
-    if (p.heuristic == PPGPU_H_TSP_POINT_K) {
-        const long long need = total;                 // (a workgroup per edge, striding)
-        hipLaunchKernelGGL(pp_k_heuristic_big, dim3((unsigned)(need < PP_BIG_GRID ? need : PP_BIG_GRID)), dim3(PP_BIG_WPB * 64), 0, c->stream, p);
+    if (m.defer_h) {
+        hipLaunchKernelGGL(pp_k_deferred_list, dim3((unsigned)((total + 256 * PP_DL_PER - 1) / (256 * PP_DL_PER))), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(pp_k_heuristic_lanes, dim3((unsigned)((total * PP_HL_SPLIT + PP_HL_THREADS - 1) / PP_HL_THREADS) + PP_HL_MAX_N), dim3(PP_HL_THREADS), 0, st, p);
     }
-    if (forked) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    c->last_launch_edges = total; c->last_launch_packed = p.live_list != nullptr;
-    if (c->timing) { HIP_TRY(hipEventRecord(c->ev[4], c->stream)); c->ev_launches++; }
+    // child lists of 9..12 ribbons under the K variant: a second pass that touches only those edges (the others cost it one
+    // 8-byte read each); a workgroup per edge, striding
+    if (p.heuristic == PPGPU_H_TSP_POINT_K)
+        hipLaunchKernelGGL(pp_k_heuristic_big, dim3((unsigned)(total < PP_BIG_GRID ? total : PP_BIG_GRID)), dim3(PP_BIG_WPB * 64), 0, st, p);
+    if (m.forked) HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
+    return PPGPU_OK;
+}
+
+// Costs the edges `asked` describes (list_params, or the dense form's own): modes, workspace, the slices one after the other, the
+// heuristic tail.  Asynchronous.  `done`: what the launch leaves for a trace of the same list.
+static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = nullptr) {
+    CostLaunch local;
+    CostLaunch& m = done ? *done : local;
+    m.p = asked;
+    PPParams& p = m.p;
+    const long long total = p.n_edges;
+    if (total <= 0) return PPGPU_OK;
+    p.total_edges = total;
+    if ((total + PP_WPB - 1) / PP_WPB > 0x3fffffffll) return fail(PPGPU_ECAPACITY, "cost_edges: too many edges for one launch");
+    cost_modes(c, m);
+    int rc = cost_workspace(c, m);
+    if (rc) return rc;
+    if (c->timing) c->ev_slot = (int)(c->ev_launches % PP_TIMING_RING);     // the next set of the ring
+    for (double& ms : c->ms_ring[c->ev_slot]) ms = 0;
+    c->live_earlier_slices = 0;
+    for (long long e0 = 0; e0 < total; e0 += m.slice) {
+        p.e_base = e0; p.ws_base = 0; p.n_edges = (total - e0 < m.slice) ? (total - e0) : m.slice;
+        if (c->timing && e0 > 0 && (rc = bank_slice_timing(c, m.packed))) return rc;
+        if ((rc = cost_slice(c, m))) return rc;
+    }
+    p.e_base = 0;
+    p.n_edges = total;
+    if ((rc = cost_heuristic_tail(c, m))) return rc;
+    c->last_launch_edges = total; c->last_launch_packed = m.packed;
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev_ring[c->ev_slot][EV_END], c->stream)); c->ev_launches++; }
     HIP_TRY(hipGetLastError());
     return PPGPU_OK;
 }
@@ -1046,81 +1138,20 @@ int ppgpu_cost_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgp
     HIP_TRY(hipSetDevice(c->device));
     if (n < 0 || (n > 0 && (!d_edges || !d_results))) return fail(PPGPU_EINVAL, "cost_edges_list: bad arguments");
     if (d_child && stride <= 0) return fail(PPGPU_EINVAL, "cost_edges_list: ribbon_stride must be positive");
-    PPParams p;
-    fill_params(c, p);
-    p.edges = (const unsigned long long*)d_edges; p.wedges = nullptr;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = n;
-    p.out = d_results; p.child = d_child; p.stride = stride;
-    return launch_cost(c, p);
-}
-
-int ppgpu_cost_edges_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, double* h_child,
-                          int32_t stride) {
-    int rc = require_world(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (n < 0 || (n > 0 && (!h_edges || !h_results))) return fail(PPGPU_EINVAL, "cost_edges_host: bad arguments");
-    if (n == 0) return PPGPU_OK;
-    if (h_child && stride <= 0) return fail(PPGPU_EINVAL, "cost_edges_host: ribbon_stride must be positive");
-    if ((rc = c->tmp_edges.reserve((size_t)n, false, c->stream))) return rc;
-    if ((rc = c->tmp_results.reserve((size_t)n, false, c->stream))) return rc;
-    if (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_edges.p, h_edges, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    if (h_child) HIP_TRY(hipMemsetAsync(c->tmp_child.p, 0, (size_t)n * stride * 4 * sizeof(double), c->stream));
-    if ((rc = ppgpu_cost_edges_list(c, n, (const uint64_t*)c->tmp_edges.p, c->tmp_results.p, h_child ? c->tmp_child.p : nullptr, stride)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, c->stream));
-    if (h_child)
-        HIP_TRY(hipMemcpyAsync(h_child, c->tmp_child.p, (size_t)n * stride * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PPGPU_OK;
-}
-
-int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
-                                  double* h_child, int32_t stride) {
-    int rc = require_cfg(c);
-    if (rc) return rc;
-    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
-    HIP_TRY(hipSetDevice(c->device));
-    if (n < 0 || (n > 0 && (!h_edges || !h_results))) return fail(PPGPU_EINVAL, "cost_wrapper_edges_host: bad arguments");
-    if (n == 0) return PPGPU_OK;
-    if (h_child && stride <= 0) return fail(PPGPU_EINVAL, "cost_wrapper_edges_host: ribbon_stride must be positive");
-    for (int64_t i = 0; i < n; i++) {
-        if (!(h_edges[i].rho > 0) || !(h_edges[i].speed > 0)) return fail(PPGPU_EINVAL, "cost_wrapper_edges_host: rho and speed must be positive");
-        if (h_edges[i].vertex < 0 || h_edges[i].vertex >= c->nverts) return fail(PPGPU_EINVAL, "cost_wrapper_edges_host: vertex out of range");
-    }
-    if ((rc = c->tmp_wedges.reserve((size_t)n, false, c->stream))) return rc;
-    if ((rc = c->tmp_results.reserve((size_t)n, false, c->stream))) return rc;
-    if (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, c->stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_wedges.p, h_edges, (size_t)n * sizeof(ppgpu_wrapper_edge), hipMemcpyHostToDevice, c->stream));
-    if (h_child) HIP_TRY(hipMemsetAsync(c->tmp_child.p, 0, (size_t)n * stride * 4 * sizeof(double), c->stream));
-    PPParams p;
-    fill_params(c, p);
-    p.edges = nullptr; p.wedges = c->tmp_wedges.p;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = n;
-    p.out = c->tmp_results.p; p.child = h_child ? c->tmp_child.p : nullptr; p.stride = stride;
-    if ((rc = launch_cost(c, p))) return rc;
-    HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, c->stream));
-    if (h_child)
-        HIP_TRY(hipMemcpyAsync(h_child, c->tmp_child.p, (size_t)n * stride * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PPGPU_OK;
+    return launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, d_child, stride));
 }
 
 // ------------------------------------------------------------------------------ edge traces
-// The trace of the edge list `p` was just costed with (launch_cost(c, p) returned: p.n_edges = the whole list, the workspace
-// pointers are set).  The trace kernel reads the PPEdgeSetup records of the costing launch: they are all still in the workspace
-// when that launch ran as one slice; a launch that ran as several has only its last slice's left, and pp_k_solve_edges writes
-// them again, slice by slice (a fraction of the time the records take to write).  Host form (h_steps / h_counts != NULL): the
-// records of one pass go through c->tmp_steps, at most the handle's slice budget at a time; what the caller's array holds beyond
-// an edge's count stays as it is (the pass starts from the caller's bytes).
-static int launch_trace(ppgpu_ctx* c, const PPParams& p, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
-    const long long total = p.n_edges;
-    if (total <= 0) return PPGPU_OK;
-    const bool reuse = c->last_slice_edges >= total;
-    long long pass = reuse ? total : c->last_slice_edges;
+// The trace of the list the launch L just costed.  The trace kernel reads the PPEdgeSetup records of the costing launch: they are
+// all still in the workspace when that launch ran as one slice; a launch that ran as several has only its last slice's left, and
+// pp_k_solve_edges writes them again, slice by slice (a fraction of the time the records take to write).  Host form (h_steps !=
+// NULL): the records of one pass go through c->tmp_steps, at most the handle's slice budget at a time; what the caller's array
+// holds beyond an edge's count stays as it is (the pass starts from the caller's bytes).
+static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
+    const PPParams& p = L.p;
+    const long long total = p.n_edges;            // (> 0: an empty list never gets as far as a launch)
+    const bool reuse = L.slice >= total;
+    long long pass = reuse ? total : L.slice;
     if (h_steps) {
         long long cap = (long long)(c->slice_bytes / ((size_t)stride * sizeof(ppgpu_step_record)));
         if (cap < 1) cap = 1;
@@ -1128,7 +1159,6 @@ static int launch_trace(ppgpu_ctx* c, const PPParams& p, int stride, int* d_coun
         int rc = c->tmp_steps.reserve((size_t)pass * stride, false, c->stream);
         if (rc) return rc;
     }
-    const bool gauss = p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN;
     c->ms_trace_earlier = 0;
     c->trace_timed = false;
     for (long long e0 = 0; e0 < total; e0 += pass) {
@@ -1149,7 +1179,7 @@ static int launch_trace(ppgpu_ctx* c, const PPParams& p, int stride, int* d_coun
             c->ms_trace_earlier += ms;
         }
         if (c->timing) HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
-        hipLaunchKernelGGL(gauss ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
+        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
                            dim3(PP_TRACE_WPB * 64), 0, c->stream, q, dst, h_steps ? e0 : 0ll, stride, d_counts);
         if (c->timing) { HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream)); c->trace_timed = true; }
         HIP_TRY(hipGetLastError());
@@ -1172,12 +1202,6 @@ int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) {
     return PPGPU_OK;
 }
 
-static int trace_args(const char* who, int64_t n, const void* edges, int32_t stride, const void* counts, const void* steps) {
-    if (n < 0 || (n > 0 && (!edges || !counts || !steps))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
-    if (stride <= 0 || stride > 65535) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
-    return PPGPU_OK;
-}
-
 int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
                            int32_t* d_counts, ppgpu_step_record* d_steps) {
     int rc = require_world(c);
@@ -1187,71 +1211,74 @@ int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppg
     if (n > 0 && !d_results) return fail(PPGPU_EINVAL, "trace_edges_list: null results");
     if (((unsigned long long)d_steps & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_edges_list: d_steps must be 16-byte aligned");
     if (n == 0) return PPGPU_OK;
-    PPParams p;
-    fill_params(c, p);
-    p.edges = (const unsigned long long*)d_edges; p.wedges = nullptr;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = n;
-    p.out = d_results; p.child = nullptr; p.stride = 0;
-    if ((rc = launch_cost(c, p))) return rc;
-    return launch_trace(c, p, stride, d_counts, d_steps, nullptr);
+    CostLaunch L;
+    if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
+    return launch_trace(c, L, stride, d_counts, d_steps, nullptr);
 }
 
-// the tail of both host forms: records and counts home
-static int trace_host_finish(ppgpu_ctx* c, PPParams& p, int64_t n, ppgpu_edge_result* h_results, int32_t stride, int32_t* h_counts,
-                             ppgpu_step_record* h_steps) {
-    int rc;
-    if ((rc = launch_cost(c, p))) return rc;
-    if (h_results) HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = launch_trace(c, p, stride, c->tmp_counts.p, nullptr, h_steps))) return rc;
-    HIP_TRY(hipMemcpyAsync(h_counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+// ------------------------------------------------------------------------------ host lists
+// The host arrays of a trace form: step records at `stride` per edge, and how many steps each edge has.
+struct TraceOut { int32_t stride; int32_t* counts; ppgpu_step_record* steps; };
+
+// A host list in, host records out: `who`'s n packed descriptors, or wrapper edges (`wrapper`), go up to tmp_edges / tmp_wedges,
+// are costed into tmp_results (child ribbons into a zeroed tmp_child when the caller wants them) and, for the trace forms, traced;
+// records, child ribbons and counts come home; one synchronise at the end.  h_results may be NULL for a trace.
+static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n, const void* h_list, ppgpu_edge_result* h_results,
+                          double* h_child, int32_t stride, const TraceOut* trace = nullptr) {
+    int rc = wrapper ? require_vertices(c) : require_world(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (trace) {
+        if ((rc = trace_args(who, n, h_list, trace->stride, trace->counts, trace->steps))) return rc;
+    } else if (n < 0 || (n > 0 && (!h_list || !h_results))) {
+        return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
+    }
+    if (n == 0) return PPGPU_OK;
+    if (h_child && stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
+    if (wrapper && (rc = check_wrapper_edges(c, who, n, (const ppgpu_wrapper_edge*)h_list))) return rc;
+    hipStream_t st = c->stream;
+    const size_t child_bytes = h_child ? (size_t)n * stride * 4 * sizeof(double) : 0;
+    if ((rc = wrapper ? c->tmp_wedges.reserve((size_t)n, false, st) : c->tmp_edges.reserve((size_t)n, false, st)) ||
+        (rc = c->tmp_results.reserve((size_t)n, false, st)) || (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, st))) ||
+        (trace && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        return rc;
+    if (wrapper) HIP_TRY(hipMemcpyAsync(c->tmp_wedges.p, h_list, (size_t)n * sizeof(ppgpu_wrapper_edge), hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpyAsync(c->tmp_edges.p, h_list, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (h_child) HIP_TRY(hipMemsetAsync(c->tmp_child.p, 0, child_bytes, st));
+    CostLaunch L;
+    if ((rc = launch_cost(c, list_params(c, n, wrapper ? nullptr : c->tmp_edges.p, wrapper ? c->tmp_wedges.p : nullptr, c->tmp_results.p,
+                                         h_child ? c->tmp_child.p : nullptr, stride), &L)))
+        return rc;
+    if (h_results) HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, st));
+    if (h_child) HIP_TRY(hipMemcpyAsync(h_child, c->tmp_child.p, child_bytes, hipMemcpyDeviceToHost, st));
+    if (trace) {
+        if ((rc = launch_trace(c, L, trace->stride, c->tmp_counts.p, nullptr, trace->steps))) return rc;
+        HIP_TRY(hipMemcpyAsync(trace->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     return PPGPU_OK;
+}
+
+int ppgpu_cost_edges_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, double* h_child,
+                          int32_t stride) {
+    return cost_host_list(c, "cost_edges_host", false, n, h_edges, h_results, h_child, stride);
+}
+
+int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
+                                  double* h_child, int32_t stride) {
+    return cost_host_list(c, "cost_wrapper_edges_host", true, n, h_edges, h_results, h_child, stride);
 }
 
 int ppgpu_trace_edges_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t stride,
                            int32_t* h_counts, ppgpu_step_record* h_steps) {
-    int rc = require_world(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = trace_args("trace_edges_host", n, h_edges, stride, h_counts, h_steps))) return rc;
-    if (n == 0) return PPGPU_OK;
-    if ((rc = c->tmp_edges.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_results.reserve((size_t)n, false, c->stream)) ||
-        (rc = c->tmp_counts.reserve((size_t)n, false, c->stream)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_edges.p, h_edges, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    PPParams p;
-    fill_params(c, p);
-    p.edges = c->tmp_edges.p; p.wedges = nullptr;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = n;
-    p.out = c->tmp_results.p; p.child = nullptr; p.stride = 0;
-    return trace_host_finish(c, p, n, h_results, stride, h_counts, h_steps);
+    const TraceOut trace{stride, h_counts, h_steps};
+    return cost_host_list(c, "trace_edges_host", false, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
                                    int32_t stride, int32_t* h_counts, ppgpu_step_record* h_steps) {
-    int rc = require_cfg(c);
-    if (rc) return rc;
-    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = trace_args("trace_wrapper_edges_host", n, h_edges, stride, h_counts, h_steps))) return rc;
-    if (n == 0) return PPGPU_OK;
-    for (int64_t i = 0; i < n; i++) {
-        if (!(h_edges[i].rho > 0) || !(h_edges[i].speed > 0)) return fail(PPGPU_EINVAL, "trace_wrapper_edges_host: rho and speed must be positive");
-        if (h_edges[i].vertex < 0 || h_edges[i].vertex >= c->nverts) return fail(PPGPU_EINVAL, "trace_wrapper_edges_host: vertex out of range");
-    }
-    if ((rc = c->tmp_wedges.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_results.reserve((size_t)n, false, c->stream)) ||
-        (rc = c->tmp_counts.reserve((size_t)n, false, c->stream)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(c->tmp_wedges.p, h_edges, (size_t)n * sizeof(ppgpu_wrapper_edge), hipMemcpyHostToDevice, c->stream));
-    PPParams p;
-    fill_params(c, p);
-    p.edges = nullptr; p.wedges = c->tmp_wedges.p;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = n;
-    p.out = c->tmp_results.p; p.child = nullptr; p.stride = 0;
-    return trace_host_finish(c, p, n, h_results, stride, h_counts, h_steps);
+    const TraceOut trace{stride, h_counts, h_steps};
+    return cost_host_list(c, "trace_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own
@@ -1336,13 +1363,7 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
     if (h_child && stride <= 0) return fail(PPGPU_EINVAL, "expand_host: ribbon_stride must be positive");
     if (nv > 65535) return fail(PPGPU_ECAPACITY, "expand_host: at most 65535 vertices per call");
     int maxr = 0;
-    for (int i = 0; i < nv; i++) {
-        if (hv[i].ribbon_count < 0 || hv[i].ribbon_offset < 0 || hv[i].ribbon_offset + hv[i].ribbon_count > n_ribbons)
-            return fail(PPGPU_EINVAL, "expand_host: ribbon range outside the pool");
-        if (hv[i].ribbon_count > PP_WAVE) return fail(PPGPU_ECAPACITY, "expand_host: more than 64 ribbons on one vertex");
-        if (hv[i].time < c->cfg.start_state_time) return fail(PPGPU_EINVAL, "expand_host: vertex time before start_state_time");
-        if (hv[i].ribbon_count > maxr) maxr = hv[i].ribbon_count;
-    }
+    if ((rc = check_open_vertices(c, "expand_host", nv, hv, n_ribbons, &maxr))) return rc;
     const long long ns = c->n_samples;
     const bool select = ns > 0 && k > 0;
     const int E = 4 + 4 * k;
@@ -1393,13 +1414,7 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
     HIP_TRY(hipGetLastError());
     // ---- cost the whole list.  (The child block is NOT cleared on the device: an edge's slots beyond its own ribbon count are
     // written by nobody and read by nobody there; the copy-out below hands the caller zeros for them.)
-    PPParams p;
-    fill_params(c, p);
-    p.edges = d_edges; p.wedges = nullptr;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
-    p.n_edges = cap;
-    p.out = d_results; p.child = d_child; p.stride = stride;
-    if ((rc = launch_cost(c, p))) return rc;
+    if ((rc = launch_cost(c, list_params(c, cap, d_edges, nullptr, d_results, d_child, stride)))) return rc;
     if ((rc = stage_reserve(&c->stage_out, &c->stage_out_cap, out_bytes))) return rc;
     char* sout = (char*)c->stage_out;
     HIP_TRY(hipMemcpyAsync(sout, c->dstage_out.p, out_bytes, hipMemcpyDeviceToHost, st));
@@ -1435,9 +1450,8 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
 // per plan); c->nverts and c->nribbons are never touched, so the handle is what the caller left once the call returns.
 int ppgpu_cost_plans_host(ppgpu_ctx* c, int32_t n_plans, const int32_t* offs, const ppgpu_wrapper_edge* h_legs, ppgpu_edge_result* h_results,
                           double* h_child, int32_t stride, int32_t* h_costed, uint32_t* h_stop) {
-    int rc = require_cfg(c);
+    int rc = require_vertices(c);
     if (rc) return rc;
-    if (c->nverts <= 0) return fail(PPGPU_ESTATE, "ppgpu_set_vertices must be called (after ppgpu_set_config)");
     HIP_TRY(hipSetDevice(c->device));
     if (n_plans < 0 || (n_plans > 0 && (!offs || !h_costed || !h_stop))) return fail(PPGPU_EINVAL, "cost_plans_host: bad arguments");
     if (stride <= 0 || stride > PP_WAVE) return fail(PPGPU_EINVAL, "cost_plans_host: ribbon_stride must be in 1 .. 64");
@@ -1446,10 +1460,9 @@ int ppgpu_cost_plans_host(ppgpu_ctx* c, int32_t n_plans, const int32_t* offs, co
     for (int p = 0; p < n_plans; p++)
         if (offs[p + 1] < offs[p]) return fail(PPGPU_EINVAL, "cost_plans_host: leg offsets must not decrease");
     if (offs[n_plans] > offs[0] && (!h_legs || !h_results)) return fail(PPGPU_EINVAL, "cost_plans_host: null legs or results");
+    if (offs[n_plans] > offs[0] && (rc = check_wrapper_edges(c, "cost_plans_host", offs[n_plans] - offs[0], h_legs + offs[0]))) return rc;
     for (int i = offs[0]; i < offs[n_plans]; i++) {
         const ppgpu_wrapper_edge& w = h_legs[i];
-        if (!(w.rho > 0) || !(w.speed > 0)) return fail(PPGPU_EINVAL, "cost_plans_host: rho and speed must be positive");
-        if (w.vertex < 0 || w.vertex >= c->nverts) return fail(PPGPU_EINVAL, "cost_plans_host: vertex out of range");
         if (w.rho != (w.coverage_allowed ? c->cfg.coverage_turning_radius : c->cfg.turning_radius))
             return fail(PPGPU_EINVAL, "cost_plans_host: a leg's rho differs from the radius its coverage flag implies (Edge.cpp:78-80 re-solves it: "
                                       "end the chain before it and route it through ppgpu_cost_edges_*)");
@@ -1499,16 +1512,10 @@ int ppgpu_cost_plans_host(ppgpu_ctx* c, int32_t n_plans, const int32_t* offs, co
     ppgpu_wrapper_edge* d_legs = (ppgpu_wrapper_edge*)c->dstage_in.p;
     ppgpu_edge_result* d_results = (ppgpu_edge_result*)c->dstage_out.p;
     double* d_child = (double*)(c->dstage_out.p + o_c);
-    PPParams p;
-    fill_params(c, p);
-    p.nverts = run0 + n1;
-    p.edges = nullptr;
-    p.v0 = 0; p.nv = 0; p.s0 = 0; p.ns = 1; p.cfg_mask = 0; p.per = 1;
     for (int d = 0; d < maxLegs; d++) {
         const int nNow = nAt[(size_t)d], nNext = d + 1 < maxLegs ? nAt[(size_t)d + 1] : 0;
-        p.wedges = d_legs + at[(size_t)d];
-        p.n_edges = nNow;
-        p.out = d_results + at[(size_t)d]; p.child = d_child + at[(size_t)d] * (size_t)stride * 4; p.stride = stride;
+        PPParams p = list_params(c, nNow, nullptr, d_legs + at[(size_t)d], d_results + at[(size_t)d], d_child + at[(size_t)d] * (size_t)stride * 4, stride);
+        p.nverts = run0 + n1;                             // the running vertices count as open ones
         if ((rc = launch_cost(c, p))) return rc;
         PPChainArgs a;
         a.results = p.out; a.child = p.child; a.stride = stride;

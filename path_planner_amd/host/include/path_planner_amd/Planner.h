@@ -300,6 +300,7 @@ private:
     int depth(int v) const;
     DubinsPlan tracePlan(int v, bool addToStats = true);
     void check(int rc, const char* what) const;
+    void setOpenVertex(const Node& n);     // ppgpu_set_vertices on the planner's own device: this node alone
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
     void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);

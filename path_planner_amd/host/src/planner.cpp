@@ -253,6 +253,26 @@ static ppgpu_vertex makeVertex(const GpuAStarPlanner::Node& n) {
     return v;
 }
 
+// The device's open vertices := this node alone, with its own ribbons.
+void GpuAStarPlanner::setOpenVertex(const Node& n) {
+    const ppgpu_vertex v = makeVertex(n);
+    std::vector<double> rib;
+    ribbonsToArray(n.ribbons, rib);
+    check(ppgpu_set_vertices(m_Ctx->handle(), 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+}
+
+// Vertex::connect(start, DubinsWrapper, coverageAllowed) for the device: the curve `p` as given, from open vertex `vertex`.
+static ppgpu_wrapper_edge wrapperEdge(const DubinsWrapper& p, int32_t vertex, bool coverageAllowed) {
+    ppgpu_wrapper_edge we{};
+    we.vertex = vertex;
+    we.coverage_allowed = coverageAllowed ? 1 : 0;
+    const DubinsPath& dp = p.unwrap();
+    for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
+    we.rho = dp.rho; we.type = (int32_t)dp.type;
+    we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
+    return we;
+}
+
 int GpuAStarPlanner::depth(int v) const {
     int d = 0;
     for (int p = m_Nodes[v].parent; p >= 0; p = m_Nodes[p].parent) d++;
@@ -1043,14 +1063,7 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
         verts[s] = makeVertex(src);
         verts[s].ribbon_offset = (int32_t)(pool.size() / 4);
         pool.insert(pool.end(), src.ribbons.rows(), src.ribbons.rows() + 4 * (size_t)src.ribbons.count());
-        ppgpu_wrapper_edge& we = wedges[s];
-        we = ppgpu_wrapper_edge{};
-        we.vertex = (int32_t)s;
-        we.coverage_allowed = c.coverageAllowed ? 1 : 0;
-        const DubinsPath& dp = c.wrapper.unwrap();
-        for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
-        we.rho = dp.rho; we.type = (int32_t)dp.type;
-        we.speed = c.wrapper.getSpeed(); we.start_time = c.wrapper.curveStartTime(); we.end_time = c.wrapper.getEndTime();
+        wedges[s] = wrapperEdge(c.wrapper, (int32_t)s, c.coverageAllowed);
         most = std::max(most, c.steps);
     }
     ppgpu_ctx* h = m_Ctx->handle();
@@ -1087,10 +1100,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
     root.state.speed() = m_Config.maxSpeed();
     root.g = 0;
     root.ribbons = m_RibbonManager;
-    ppgpu_vertex v = makeVertex(root);
-    std::vector<double> rib;
-    ribbonsToArray(root.ribbons, rib);
-    check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+    setOpenVertex(root);
     std::vector<int32_t> offsets{0};
     std::vector<ppgpu_wrapper_edge> legs;
     for (const DubinsPlan& plan : plans) {
@@ -1098,14 +1108,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
             if (p.getEndTime() <= start.time() || p.getNetTime() == 0) continue;       // :49-50
             const bool cov = p.getRho() == m_Config.coverageTurningRadius();
             if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;   // Edge.cpp:78-80 would re-solve it
-            ppgpu_wrapper_edge we{};
-            we.vertex = 0;
-            we.coverage_allowed = cov ? 1 : 0;
-            const DubinsPath& dp = p.unwrap();
-            for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
-            we.rho = dp.rho; we.type = (int32_t)dp.type;
-            we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
-            legs.push_back(we);
+            legs.push_back(wrapperEdge(p, 0, cov));
         }
         offsets.push_back((int32_t)legs.size());
     }
@@ -1210,16 +1213,6 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
     if (!previousPlan.empty()) {
         const std::vector<DubinsWrapper>& prevLegs = previousPlan.get();
         auto skipped = [&](const DubinsWrapper& p) { return p.getEndTime() <= start.time() || p.getNetTime() == 0; };   // :49-50
-        auto wrapperEdge = [&](const DubinsWrapper& p, bool cov) {
-            ppgpu_wrapper_edge we{};
-            we.vertex = 0;
-            we.coverage_allowed = cov ? 1 : 0;
-            const DubinsPath& dp = p.unwrap();
-            for (int i = 0; i < 3; i++) { we.qi[i] = dp.qi[i]; we.param[i] = dp.param[i]; }
-            we.rho = dp.rho; we.type = (int32_t)dp.type;
-            we.speed = p.getSpeed(); we.start_time = p.curveStartTime(); we.end_time = p.getEndTime();
-            return we;
-        };
         // PlannerConfig::chainedPreviousPlan: the legs up to the first one at a radius the configuration no longer has (Edge.cpp:78-80
         // re-solves that one: not a given curve any more) are costed by ONE call, every leg from the vertex the leg before left on the
         // device.  The walk below then finds their records here instead of making a round trip per leg; it builds the same nodes.
@@ -1234,14 +1227,11 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
                 if (skipped(p)) continue;
                 const bool cov = p.getRho() == m_Config.coverageTurningRadius();
                 if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;
-                legs.push_back(wrapperEdge(p, cov));
+                legs.push_back(wrapperEdge(p, 0, cov));
                 legOf.push_back(i);
             }
             if (!legs.empty()) {
-                ppgpu_vertex v = makeVertex(m_Nodes[startV]);
-                std::vector<double> rib;
-                ribbonsToArray(m_Nodes[startV].ribbons, rib);
-                check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+                setOpenVertex(m_Nodes[startV]);
                 const int32_t offsets[2] = {0, (int32_t)legs.size()};
                 int32_t costed = 0;
                 uint32_t why = 0;
@@ -1259,10 +1249,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
             const double expectRho = cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius();
             const long slot = chainSlot[legIndex];
             if (slot < 0) {
-                ppgpu_vertex v = makeVertex(m_Nodes[lastPlanEnd]);
-                std::vector<double> rib;
-                ribbonsToArray(m_Nodes[lastPlanEnd].ribbons, rib);
-                check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+                setOpenVertex(m_Nodes[lastPlanEnd]);
                 m_Stats.Budget.PrologueTrips++;
             }
             const size_t before = m_Nodes.size();
@@ -1289,7 +1276,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
                     r = chainRes[(size_t)slot];
                     child = chainChild.data() + (size_t)slot * kRibbonStride * 4;
                 } else {
-                    const ppgpu_wrapper_edge we = wrapperEdge(p, cov);
+                    const ppgpu_wrapper_edge we = wrapperEdge(p, 0, cov);
                     ownChild.assign((size_t)kRibbonStride * 4, 0.0);
                     check(ppgpu_cost_wrapper_edges_host(h, 1, &we, &r, ownChild.data(), kRibbonStride), "ppgpu_cost_wrapper_edges_host");
                     child = ownChild.data();
@@ -1363,10 +1350,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
                 break;
             }
             const double brown0 = HostProfile::now();
-            ppgpu_vertex v = makeVertex(m_Nodes[startV]);
-            std::vector<double> rib;
-            ribbonsToArray(m_Nodes[startV].ribbons, rib);
-            check(ppgpu_set_vertices(h, 1, &v, v.ribbon_count, rib.empty() ? nullptr : rib.data()), "ppgpu_set_vertices");
+            setOpenVertex(m_Nodes[startV]);
             std::vector<State> t;
             std::vector<unsigned> c;
             std::vector<long> si;
