@@ -415,6 +415,70 @@ int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrappe
  * over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
 int ppgpu_last_trace_timing(ppgpu_ctx* ctx, double* ms_trace);
 
+/* -------------------------------------------------------------- coverage traces */
+
+/* What every step of an edge did to the ribbons: the coverage state machine of Edge::computeTrueCost (Edge.cpp:153-171) executed
+ * literally by pp_k_trace_cover, one record per executed step — record k of an edge belongs to ppgpu_step_record k of the same
+ * edge (same step count, same poses) — and one summary per edge that includes the last cover (Edge.cpp:181-191).  The costing
+ * launch's cover sweep visits event steps only and takes stretches of them as runs; this walk skips nothing. */
+#define PPGPU_C_EVENT   0x1u  /* the else-branch of Edge.cpp:153-158 ran: minDistanceFrom was evaluated (:158)             */
+#define PPGPU_C_COVER   0x2u  /* cover() was called at this step (:159-161)                                                */
+#define PPGPU_C_CHANGED 0x4u  /* ... and the ribbon list is not, value for value, what it was before the step              */
+#define PPGPU_C_DONE    0x8u  /* RibbonManager::done() after the step (:162; RibbonManager.cpp:24-26)                      */
+typedef struct ppgpu_cover_record {   /* 32 bytes */
+    double to_cover;          /* toCoverDistance after the step's branch (Edge.cpp:153-158).  While the list is empty
+                               * minDistanceFrom is 0 (RibbonManager.cpp:143): every step is then an event and this is 0   */
+    double remaining;         /* sum of the end-to-end lengths (start to end point) of the ribbons left after the step     */
+    uint32_t flags, step;     /* PPGPU_C_*; the step's index k.  A blocked step (Edge.cpp:144-146) breaks before the
+                               * coverage branch: its record repeats the state before it, with PPGPU_C_DONE at most        */
+    uint32_t ribbons;         /* list length after the step                                                                */
+    uint32_t reserved;        /* 0 */
+} ppgpu_cover_record;
+
+/* Bits of ppgpu_cover_summary.flags */
+#define PPGPU_CS_LAST_COVER   0x01u /* the last cover ran (Edge.cpp:182-184: coverageAllowed, or the heading did not change)  */
+#define PPGPU_CS_LAST_CHANGED 0x02u /* ... and changed the list                                                               */
+#define PPGPU_CS_DONE         0x04u /* child->done() after it (:185) = PPGPU_F_DONE of the edge's record                      */
+#define PPGPU_CS_REFUSED      0x08u /* the list is, or would have grown, beyond the device's 64 ribbons per vertex (the edge's
+                                     * record carries PPGPU_F_RIBBON_LOST): count 0, nothing else in the summary is meaningful */
+#define PPGPU_CS_THROWS       0x10u /* PPGPU_F_THROWS or a malformed descriptor: the reference throws before the last cover
+                                     * (Edge.cpp:178), there is no child; count 0                                             */
+typedef struct ppgpu_cover_summary {  /* 32 bytes, per edge */
+    int32_t events, changes;          /* steps with PPGPU_C_EVENT / PPGPU_C_CHANGED (the last cover is not a step)            */
+    int32_t ribbons_final;            /* list length after the last cover (Edge.cpp:181-191) = bits 8-15 of the record's info */
+    uint32_t flags;                   /* PPGPU_CS_*                                                                           */
+    double coverage_completed_time;   /* the child's RibbonManager::coverageCompletedTime() (:164-166,187-189), -1 unset      */
+    double remaining_final;           /* `remaining` after the last cover                                                     */
+} ppgpu_cover_summary;
+
+/* Edge::computeTrueCost's coverage branch (Edge.cpp:153-171,181-191) step by step for a list of n packed descriptors: first the
+ * costing launch of ppgpu_cost_edges_list on the same list (d_results receives exactly its records), then the walk.  d_counts[i]
+ * receives the edge's step count (what ppgpu_trace_edges_list reports; 0 with PPGPU_CS_REFUSED / PPGPU_CS_THROWS), d_cover[i *
+ * step_stride + k] the record of its step k for k < min(count, step_stride): a stride below an edge's count cuts the records,
+ * never the count, the summary or the final list; records beyond an edge's count are left untouched.  d_summaries[i] receives the
+ * edge's summary; d_child_ribbons (may be NULL) the list after the last cover, ribbon_stride * 4 doubles per edge, its first
+ * min(ribbons_final, ribbon_stride) entries written (the costing convention).  d_cover must be 16-byte aligned.  Asynchronous on
+ * the handle's stream. */
+int ppgpu_trace_cover_list(ppgpu_ctx* ctx, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results,
+                           int32_t step_stride, int32_t* d_counts, ppgpu_cover_record* d_cover,
+                           ppgpu_cover_summary* d_summaries, double* d_child_ribbons, int32_t ribbon_stride);
+/* The same with host descriptors in and host arrays out, synchronous.  h_results and h_child_ribbons may be NULL; entries of
+ * h_child_ribbons beyond an edge's final list are zeroed.  The records pass through buffers of the handle that grow like its other
+ * buffers (ppgpu_growth_stats counts them); a walk that would exceed the handle's workspace budget runs as consecutive slices of
+ * the list, like a costing launch. */
+int ppgpu_trace_cover_host(ppgpu_ctx* ctx, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results,
+                           int32_t step_stride, int32_t* h_counts, ppgpu_cover_record* h_cover,
+                           ppgpu_cover_summary* h_summaries, double* h_child_ribbons, int32_t ribbon_stride);
+/* ... for edges whose curve is given (Vertex::connect(start, DubinsWrapper, coverageAllowed), Vertex.cpp:28-36, as
+ * ppgpu_trace_wrapper_edges_host traces them).  A curve that starts after the vertex's first step has no steps (Edge.cpp:126-133):
+ * its summary is that of the last cover alone, at the vertex's own pose. */
+int ppgpu_trace_cover_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper_edge* h_wedges, ppgpu_edge_result* h_results,
+                                         int32_t step_stride, int32_t* h_counts, ppgpu_cover_record* h_cover,
+                                         ppgpu_cover_summary* h_summaries, double* h_child_ribbons, int32_t ribbon_stride);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_trace_cover took in the last coverage-trace call,
+ * summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
+int ppgpu_last_cover_trace_timing(ppgpu_ctx* ctx, double* ms_cover_trace);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

@@ -76,6 +76,10 @@ def _load():
         "ppgpu_trace_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
         "ppgpu_trace_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
         "ppgpu_last_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_trace_cover_list": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]),
+        "ppgpu_trace_cover_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]),
+        "ppgpu_trace_cover_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]),
+        "ppgpu_last_cover_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -364,6 +368,41 @@ class Context:
     def last_trace_timing(self):
         ms = C.c_double()
         self._ck(LIB.ppgpu_last_trace_timing(self._h, C.byref(ms)), "ppgpu_last_trace_timing")
+        return ms.value
+
+    def trace_cover_list(self, n, d_edges, d_results, step_stride, d_counts, d_cover, d_summaries, d_child=None, ribbon_stride=0):
+        self._ck(LIB.ppgpu_trace_cover_list(self._h, n, _ptr(d_edges), _ptr(d_results), step_stride, _ptr(d_counts), _ptr(d_cover),
+                                            _ptr(d_summaries), _ptr(d_child), ribbon_stride), "ppgpu_trace_cover_list")
+
+    def _trace_cover_host(self, fn, name, e, step_stride, cover, ribbon_stride):
+        from .types import COVER_DTYPE, COVER_SUMMARY_DTYPE
+        n = e.shape[0]
+        res = np.zeros(n, dtype=RESULT_DTYPE)
+        counts = np.zeros(n, dtype=np.int32)
+        summaries = np.zeros(n, dtype=COVER_SUMMARY_DTYPE)
+        child = np.zeros((n, ribbon_stride, 4), dtype=np.float64) if ribbon_stride > 0 else None
+        if cover is None:
+            cover = np.zeros((n, step_stride), dtype=COVER_DTYPE)
+        assert cover.dtype == COVER_DTYPE and cover.shape == (n, step_stride) and cover.flags["C_CONTIGUOUS"]
+        self._ck(fn(self._h, n, _ptr(e), _ptr(res), step_stride, _ptr(counts), _ptr(cover), _ptr(summaries), _ptr(child), ribbon_stride), name)
+        return res, counts, cover, summaries, child
+
+    def trace_cover(self, edges, step_stride, cover=None, ribbon_stride=0):
+        """The coverage branch of Edge::computeTrueCost step by step: (records as cost_edges_host returns them, step counts,
+        cover[n, step_stride], summaries, final lists [n, ribbon_stride, 4] or None).  `cover`: an array to write into (entries
+        beyond an edge's count are left as they are); a zeroed one by default."""
+        e = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._trace_cover_host(LIB.ppgpu_trace_cover_host, "ppgpu_trace_cover_host", e, step_stride, cover, ribbon_stride)
+
+    def trace_cover_wrapper_edges(self, wedges, step_stride, cover=None, ribbon_stride=0):
+        from .types import WRAPPER_EDGE_DTYPE
+        e = np.ascontiguousarray(wedges, dtype=WRAPPER_EDGE_DTYPE)
+        return self._trace_cover_host(LIB.ppgpu_trace_cover_wrapper_edges_host, "ppgpu_trace_cover_wrapper_edges_host", e, step_stride,
+                                      cover, ribbon_stride)
+
+    def last_cover_trace_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_cover_trace_timing(self._h, C.byref(ms)), "ppgpu_last_cover_trace_timing")
         return ms.value
 
     @staticmethod

@@ -7,6 +7,7 @@
 #include "pp_k_sweep.h"        // pp_k_plan_skips, pp_k_pose_sweep
 #include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep, pp_k_cover_finish
 #include "pp_k_trace.h"        // pp_k_trace_steps
+#include "pp_k_cover_trace.h"  // pp_k_trace_cover
 #include "pp_k_chain.h"        // pp_k_chain_advance
 #include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
 #include "pp_k_expand.h"       // pp_k_dubins_lengths, pp_k_select_nearest, the push-order pipeline, the round trip's pack / unpack

@@ -87,6 +87,12 @@ struct DevBuf {
 };
 
 #define PP_TIMING_RING 8
+// The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing).
+struct TraceTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms_earlier = 0;              // ... of the slices before the last one
+    bool timed = false;
+};
 // The events of one timed costing launch, in stream order except EV_APPROACHED (recorded between EV_POSED and the cover sweep).
 // A sliced launch records EV_BEGIN .. EV_COVERED and EV_APPROACHED once per slice, EV_END once.
 enum { EV_BEGIN, EV_SOLVED, EV_POSED, EV_COVERED, EV_END, EV_APPROACHED, EV_COUNT };
@@ -135,10 +141,11 @@ struct ppgpu_ctx {
     DevBuf<ppgpu_edge_result> tmp_results;
     DevBuf<double> tmp_child, tmp_lengths, tmp_len_out, int_child;
     DevBuf<ppgpu_step_record> tmp_steps;   // device end of the host forms of ppgpu_trace_*: the step records of one trace slice
+    DevBuf<ppgpu_cover_record> tmp_cover;  // ... and of ppgpu_trace_cover_*: the cover records of one slice,
+    DevBuf<ppgpu_cover_summary> tmp_summaries;   // the summaries and final lists of the whole list
+    DevBuf<double> tmp_cover_child;
     DevBuf<int> tmp_counts;
-    hipEvent_t ev_trace[2] = {nullptr, nullptr};   // around pp_k_trace_steps (ppgpu_last_trace_timing)
-    double ms_trace_earlier = 0;        // ... of the slices before the last one
-    bool trace_timed = false;
+    TraceTimer t_steps, t_cover;        // around pp_k_trace_steps / pp_k_trace_cover
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
@@ -188,7 +195,7 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_trace[0], ev_trace[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -304,11 +311,13 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
         for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < EV_COUNT; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
-    if (on && !c->ev_trace[0])
-        for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&c->ev_trace[i]));
+    for (TraceTimer* tm : {&c->t_steps, &c->t_cover}) {
+        if (on && !tm->ev[0])
+            for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm->ev[i]));
+        tm->timed = false;
+    }
     c->timing = on != 0;
     c->ev_launches = 0;
-    c->trace_timed = false;
     return PPGPU_OK;
 }
 
@@ -1142,25 +1151,28 @@ int ppgpu_cost_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgp
 }
 
 // ------------------------------------------------------------------------------ edge traces
-// The trace of the list the launch L just costed.  The trace kernel reads the PPEdgeSetup records of the costing launch: they are
+// A per-step trace of the list the launch L just costed: `launch(q, dst, rec_base)` starts the trace kernel on one slice q, its
+// records going to dst[(edge - rec_base) * stride + k].  A trace kernel reads the PPEdgeSetup records of the costing launch: they are
 // all still in the workspace when that launch ran as one slice; a launch that ran as several has only its last slice's left, and
-// pp_k_solve_edges writes them again, slice by slice (a fraction of the time the records take to write).  Host form (h_steps !=
-// NULL): the records of one pass go through c->tmp_steps, at most the handle's slice budget at a time; what the caller's array
+// pp_k_solve_edges writes them again, slice by slice (a fraction of the time the records take to write).  Host form (h_recs !=
+// NULL): the records of one pass go through `tmp`, at most the handle's slice budget at a time; what the caller's array
 // holds beyond an edge's count stays as it is (the pass starts from the caller's bytes).
-static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
+extern "C++" {
+template <typename Rec, typename Launch>
+static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, int stride, DevBuf<Rec>& tmp, TraceTimer& tm, Rec* d_recs, Rec* h_recs, Launch launch) {
     const PPParams& p = L.p;
     const long long total = p.n_edges;            // (> 0: an empty list never gets as far as a launch)
     const bool reuse = L.slice >= total;
     long long pass = reuse ? total : L.slice;
-    if (h_steps) {
-        long long cap = (long long)(c->slice_bytes / ((size_t)stride * sizeof(ppgpu_step_record)));
+    if (h_recs) {
+        long long cap = (long long)(c->slice_bytes / ((size_t)stride * sizeof(Rec)));
         if (cap < 1) cap = 1;
         if (pass > cap) pass = cap;
-        int rc = c->tmp_steps.reserve((size_t)pass * stride, false, c->stream);
+        int rc = tmp.reserve((size_t)pass * stride, false, c->stream);
         if (rc) return rc;
     }
-    c->ms_trace_earlier = 0;
-    c->trace_timed = false;
+    tm.ms_earlier = 0;
+    tm.timed = false;
     for (long long e0 = 0; e0 < total; e0 += pass) {
         PPParams q = p;
         q.e_base = e0; q.n_edges = (total - e0 < pass) ? (total - e0) : pass;
@@ -1169,38 +1181,61 @@ static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_co
             q.live_count = nullptr; q.defer_count = nullptr; q.hw_count = nullptr;     // (counters of the costing launch: ppgpu_last_cover_edges still reads them)
             hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
         }
-        ppgpu_step_record* dst = h_steps ? c->tmp_steps.p : d_steps;
-        const size_t bytes = (size_t)q.n_edges * stride * sizeof(ppgpu_step_record);
-        if (h_steps) HIP_TRY(hipMemcpyAsync(dst, h_steps + (size_t)e0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
-        if (c->timing && c->trace_timed) {              // a further slice re-uses the events: bank the one before
+        Rec* dst = h_recs ? tmp.p : d_recs;
+        const size_t bytes = (size_t)q.n_edges * stride * sizeof(Rec);
+        if (h_recs) HIP_TRY(hipMemcpyAsync(dst, h_recs + (size_t)e0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
+        if (c->timing && tm.timed) {                    // a further slice re-uses the events: bank the one before
             float ms = 0;
-            HIP_TRY(hipEventSynchronize(c->ev_trace[1]));
-            HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[0], c->ev_trace[1]));
-            c->ms_trace_earlier += ms;
+            HIP_TRY(hipEventSynchronize(tm.ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms, tm.ev[0], tm.ev[1]));
+            tm.ms_earlier += ms;
         }
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
-        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
-                           dim3(PP_TRACE_WPB * 64), 0, c->stream, q, dst, h_steps ? e0 : 0ll, stride, d_counts);
-        if (c->timing) { HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream)); c->trace_timed = true; }
+        if (c->timing) HIP_TRY(hipEventRecord(tm.ev[0], c->stream));
+        launch(q, dst, h_recs ? e0 : 0ll);
+        if (c->timing) { HIP_TRY(hipEventRecord(tm.ev[1], c->stream)); tm.timed = true; }
         HIP_TRY(hipGetLastError());
-        if (h_steps) {
-            HIP_TRY(hipMemcpyAsync(h_steps + (size_t)e0 * stride, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (h_recs) {
+            HIP_TRY(hipMemcpyAsync(h_recs + (size_t)e0 * stride, dst, bytes, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));   // the next pass writes the same buffer
         }
     }
     return PPGPU_OK;
 }
+}  // extern "C++"
 
-int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) {
-    if (!c || !ms_trace) return fail(PPGPU_EINVAL, "null argument");
-    if (!c->timing || !c->trace_timed) return fail(PPGPU_ESTATE, "no timed trace launch (ppgpu_enable_timing, then trace edges)");
+static int trace_timing(ppgpu_ctx* c, TraceTimer& tm, double* ms_out) {
+    if (!c || !ms_out) return fail(PPGPU_EINVAL, "null argument");
+    if (!c->timing || !tm.timed) return fail(PPGPU_ESTATE, "no timed trace launch (ppgpu_enable_timing, then trace edges)");
     HIP_TRY(hipSetDevice(c->device));
     float ms = 0;
-    HIP_TRY(hipEventSynchronize(c->ev_trace[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[0], c->ev_trace[1]));
-    *ms_trace = ms + c->ms_trace_earlier;
+    HIP_TRY(hipEventSynchronize(tm.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, tm.ev[0], tm.ev[1]));
+    *ms_out = ms + tm.ms_earlier;
     return PPGPU_OK;
 }
+
+// pp_k_trace_steps over the list of L
+static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
+    return trace_passes(c, L, stride, c->tmp_steps, c->t_steps, d_steps, h_steps, [&](const PPParams& q, ppgpu_step_record* dst, long long rec_base) {
+        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
+                           dim3(PP_TRACE_WPB * 64), 0, c->stream, q, dst, rec_base, stride, d_counts);
+    });
+}
+
+// What a coverage trace gives per edge beside its records (device arrays over the whole list; child may be NULL).
+struct CoverOut { ppgpu_cover_summary* summaries; double* child; int32_t ribbon_stride; };
+
+// pp_k_trace_cover over the list of L
+static int launch_cover_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_cover_record* d_cover, ppgpu_cover_record* h_cover,
+                              const CoverOut& o) {
+    return trace_passes(c, L, stride, c->tmp_cover, c->t_cover, d_cover, h_cover, [&](const PPParams& q, ppgpu_cover_record* dst, long long rec_base) {
+        hipLaunchKernelGGL(pp_k_trace_cover, dim3((unsigned)((q.n_edges + PP_CTRACE_WPB - 1) / PP_CTRACE_WPB)), dim3(PP_CTRACE_WPB * 64), 0, c->stream,
+                           q, dst, rec_base, stride, d_counts, o.summaries, o.child, o.child ? o.ribbon_stride : 0);
+    });
+}
+
+int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) { return c ? trace_timing(c, c->t_steps, ms_trace) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_cover, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
                            int32_t* d_counts, ppgpu_step_record* d_steps) {
@@ -1216,20 +1251,42 @@ int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppg
     return launch_trace(c, L, stride, d_counts, d_steps, nullptr);
 }
 
+int ppgpu_trace_cover_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride, int32_t* d_counts,
+                           ppgpu_cover_record* d_cover, ppgpu_cover_summary* d_summaries, double* d_child, int32_t ribbon_stride) {
+    int rc = require_world(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = trace_args("trace_cover_list", n, d_edges, stride, d_counts, d_cover))) return rc;
+    if (n > 0 && (!d_results || !d_summaries)) return fail(PPGPU_EINVAL, "trace_cover_list: null results or summaries");
+    if (d_child && ribbon_stride <= 0) return fail(PPGPU_EINVAL, "trace_cover_list: ribbon_stride must be positive");
+    if (((unsigned long long)d_cover & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_cover_list: d_cover must be 16-byte aligned");
+    if (n == 0) return PPGPU_OK;
+    CostLaunch L;
+    if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
+    return launch_cover_trace(c, L, stride, d_counts, d_cover, nullptr, CoverOut{d_summaries, d_child, ribbon_stride});
+}
+
 // ------------------------------------------------------------------------------ host lists
 // The host arrays of a trace form: step records at `stride` per edge, and how many steps each edge has.
 struct TraceOut { int32_t stride; int32_t* counts; ppgpu_step_record* steps; };
+// ... of a coverage-trace form: cover records at `stride` per edge, counts, summaries, and (may be NULL) the final lists.
+struct CoverTraceOut { int32_t stride; int32_t* counts; ppgpu_cover_record* cover; ppgpu_cover_summary* summaries; double* child; int32_t ribbon_stride; };
 
 // A host list in, host records out: `who`'s n packed descriptors, or wrapper edges (`wrapper`), go up to tmp_edges / tmp_wedges,
 // are costed into tmp_results (child ribbons into a zeroed tmp_child when the caller wants them) and, for the trace forms, traced;
-// records, child ribbons and counts come home; one synchronise at the end.  h_results may be NULL for a trace.
+// records, child ribbons and counts come home; one synchronise at the end.  h_results may be NULL for a trace.  A coverage trace
+// (`cover`) walks the list instead and brings its summaries and final lists home as well.
 static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n, const void* h_list, ppgpu_edge_result* h_results,
-                          double* h_child, int32_t stride, const TraceOut* trace = nullptr) {
+                          double* h_child, int32_t stride, const TraceOut* trace = nullptr, const CoverTraceOut* cover = nullptr) {
     int rc = wrapper ? require_vertices(c) : require_world(c);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (trace) {
         if ((rc = trace_args(who, n, h_list, trace->stride, trace->counts, trace->steps))) return rc;
+    } else if (cover) {
+        if ((rc = trace_args(who, n, h_list, cover->stride, cover->counts, cover->cover))) return rc;
+        if (n > 0 && !cover->summaries) return fail(PPGPU_EINVAL, std::string(who) + ": null summaries");
+        if (cover->child && cover->ribbon_stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
     } else if (n < 0 || (n > 0 && (!h_list || !h_results))) {
         return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
     }
@@ -1240,7 +1297,11 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
     const size_t child_bytes = h_child ? (size_t)n * stride * 4 * sizeof(double) : 0;
     if ((rc = wrapper ? c->tmp_wedges.reserve((size_t)n, false, st) : c->tmp_edges.reserve((size_t)n, false, st)) ||
         (rc = c->tmp_results.reserve((size_t)n, false, st)) || (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, st))) ||
-        (trace && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        ((trace || cover) && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        return rc;
+    const size_t final_bytes = (cover && cover->child) ? (size_t)n * cover->ribbon_stride * 4 * sizeof(double) : 0;
+    if (cover && ((rc = c->tmp_summaries.reserve((size_t)n, false, st)) ||
+                  (final_bytes && (rc = c->tmp_cover_child.reserve(final_bytes / sizeof(double), false, st)))))
         return rc;
     if (wrapper) HIP_TRY(hipMemcpyAsync(c->tmp_wedges.p, h_list, (size_t)n * sizeof(ppgpu_wrapper_edge), hipMemcpyHostToDevice, st));
     else HIP_TRY(hipMemcpyAsync(c->tmp_edges.p, h_list, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -1254,6 +1315,15 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
     if (trace) {
         if ((rc = launch_trace(c, L, trace->stride, c->tmp_counts.p, nullptr, trace->steps))) return rc;
         HIP_TRY(hipMemcpyAsync(trace->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (cover) {
+        if (final_bytes) HIP_TRY(hipMemsetAsync(c->tmp_cover_child.p, 0, final_bytes, st));
+        if ((rc = launch_cover_trace(c, L, cover->stride, c->tmp_counts.p, nullptr, cover->cover,
+                                     CoverOut{c->tmp_summaries.p, final_bytes ? c->tmp_cover_child.p : nullptr, cover->ribbon_stride})))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(cover->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cover->summaries, c->tmp_summaries.p, (size_t)n * sizeof(ppgpu_cover_summary), hipMemcpyDeviceToHost, st));
+        if (final_bytes) HIP_TRY(hipMemcpyAsync(cover->child, c->tmp_cover_child.p, final_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return PPGPU_OK;
@@ -1279,6 +1349,19 @@ int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_
                                    int32_t stride, int32_t* h_counts, ppgpu_step_record* h_steps) {
     const TraceOut trace{stride, h_counts, h_steps};
     return cost_host_list(c, "trace_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
+}
+
+int ppgpu_trace_cover_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t stride, int32_t* h_counts,
+                           ppgpu_cover_record* h_cover, ppgpu_cover_summary* h_summaries, double* h_child, int32_t ribbon_stride) {
+    const CoverTraceOut cover{stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride};
+    return cost_host_list(c, "trace_cover_host", false, n, h_edges, h_results, nullptr, 0, nullptr, &cover);
+}
+
+int ppgpu_trace_cover_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results, int32_t stride,
+                                         int32_t* h_counts, ppgpu_cover_record* h_cover, ppgpu_cover_summary* h_summaries, double* h_child,
+                                         int32_t ribbon_stride) {
+    const CoverTraceOut cover{stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride};
+    return cost_host_list(c, "trace_cover_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, nullptr, &cover);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own

@@ -45,6 +45,12 @@ public:
         // them (ppgpu_trace_wrapper_edges_host from the segment's parent vertex; the layout is ppgpu_step_record's).
         struct TraceStep { double x, y, heading, time, collision, penaltyBefore; uint32_t flags, step; double reserved; };
         std::vector<std::vector<TraceStep>> Trace;
+        // With PlannerConfig::setPlanCoverage: Coverage[s][k] = what step k of Plan's segment s did to the ribbons (the coverage
+        // branch of Edge::computeTrueCost executed step by step on the device, ppgpu_trace_cover_wrapper_edges_host: the fields of
+        // ppgpu_cover_record, and the step's time, Edge.cpp:114-120,173), parallel to Trace[s][k].  Segment s starts from the
+        // vertex segment s - 1 left.
+        struct CoverStep { double time, toCover, remaining; uint32_t flags, step, ribbons; };
+        std::vector<std::vector<CoverStep>> Coverage;
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -304,7 +310,7 @@ private:
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
     void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);
-    void tracePlanSteps(int v);            // Stats::Trace for the plan that ends at node v
+    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage for the plan that ends at node v
     void visualizePlan(const DubinsPlan& plan);
     void visualizeSamples();
     int costStateEdges(int source, const std::vector<State>& targets, const std::vector<unsigned>& cfgBits,

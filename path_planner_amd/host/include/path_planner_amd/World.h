@@ -231,6 +231,10 @@ public:
     // The returned plan step by step (Planner::Stats::Trace): where it was sampled, what it hit, the penalty as it accrued.
     bool planTrace() const { return m_PlanTrace; }
     void setPlanTrace(bool on) { m_PlanTrace = on; }
+    // What every step of the returned plan did to the ribbons (Planner::Stats::Coverage): how much survey line was left after it,
+    // where coverage events fell, when coverage completed.  Off by default; with it off nothing changes.
+    bool planCoverage() const { return m_PlanCoverage; }
+    void setPlanCoverage(bool on) { m_PlanCoverage = on; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -248,7 +252,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_ChainedPreviousPlan = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_ChainedPreviousPlan = false;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;
     Map::SharedPtr m_Map;

@@ -1043,11 +1043,12 @@ DubinsPlan GpuAStarPlanner::tracePlan(int v, bool addToStats) {   // Planner.cpp
     return plan;
 }
 
-// PlannerConfig::planTrace: the returned plan's segments swept once more, step by step, in one device call — segment s from its
-// parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
+// PlannerConfig::planTrace / planCoverage: the returned plan's segments swept once more, step by step, in one device call each —
+// segment s from its parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
 static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
 void GpuAStarPlanner::tracePlanSteps(int v) {
     m_Stats.Trace.clear();
+    m_Stats.Coverage.clear();
     std::vector<int> branch;
     for (int cur = v; cur >= 0 && m_Nodes[cur].parent >= 0; cur = m_Nodes[cur].parent) branch.push_back(cur);
     std::reverse(branch.begin(), branch.end());
@@ -1069,15 +1070,37 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
     ppgpu_ctx* h = m_Ctx->handle();
     check(ppgpu_set_vertices(h, (int32_t)n, verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
     std::vector<int32_t> counts(n, 0);
-    std::vector<Stats::TraceStep> steps(n * (size_t)most);
-    check(ppgpu_trace_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), reinterpret_cast<ppgpu_step_record*>(steps.data())),
-          "ppgpu_trace_wrapper_edges_host");
-    m_Stats.Trace.resize(n);
-    for (size_t s = 0; s < n; s++) {
-        if (counts[s] != m_Nodes[branch[s]].steps)
-            throw std::runtime_error("plan trace: segment " + std::to_string(s) + " traced " + std::to_string(counts[s]) + " steps, its edge executed " +
-                                     std::to_string(m_Nodes[branch[s]].steps));
-        m_Stats.Trace[s].assign(steps.begin() + (long)(s * (size_t)most), steps.begin() + (long)(s * (size_t)most) + counts[s]);
+    const auto sameCounts = [&](const char* what) {
+        for (size_t s = 0; s < n; s++)
+            if (counts[s] != m_Nodes[branch[s]].steps)
+                throw std::runtime_error(std::string(what) + ": segment " + std::to_string(s) + " traced " + std::to_string(counts[s]) + " steps, its edge executed " +
+                                         std::to_string(m_Nodes[branch[s]].steps));
+    };
+    if (m_Config.planTrace()) {
+        std::vector<Stats::TraceStep> steps(n * (size_t)most);
+        check(ppgpu_trace_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), reinterpret_cast<ppgpu_step_record*>(steps.data())),
+              "ppgpu_trace_wrapper_edges_host");
+        sameCounts("plan trace");
+        m_Stats.Trace.resize(n);
+        for (size_t s = 0; s < n; s++)
+            m_Stats.Trace[s].assign(steps.begin() + (long)(s * (size_t)most), steps.begin() + (long)(s * (size_t)most) + counts[s]);
+    }
+    if (m_Config.planCoverage()) {
+        std::vector<ppgpu_cover_record> cover(n * (size_t)most);
+        std::vector<ppgpu_cover_summary> summaries(n);
+        check(ppgpu_trace_cover_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), cover.data(), summaries.data(), nullptr, 0),
+              "ppgpu_trace_cover_wrapper_edges_host");
+        sameCounts("plan coverage");
+        m_Stats.Coverage.resize(n);
+        const double timeIncrement = m_Config.collisionCheckingIncrement() / m_Config.maxSpeed();
+        for (size_t s = 0; s < n; s++) {
+            double t = verts[s].time;
+            t += std::fmod(t - m_StartStateTime, timeIncrement);                                  // Edge.cpp:116-120
+            for (int k = 0; k < counts[s]; k++, t += timeIncrement) {                              // :173
+                const ppgpu_cover_record& c = cover[s * (size_t)most + (size_t)k];
+                m_Stats.Coverage[s].push_back(Stats::CoverStep{t, c.to_cover, c.remaining, c.flags, c.step, c.ribbons});
+            }
+        }
     }
 }
 
@@ -1398,7 +1421,7 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
         m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
         m_Stats.PlanHValue = m_Nodes[m_Best].h;
         m_Stats.Plan = tracePlan(m_Best);
-        if (m_Config.planTrace()) tracePlanSteps(m_Best);
+        if (m_Config.planTrace() || m_Config.planCoverage()) tracePlanSteps(m_Best);
     }
     for (const auto& ctx : m_Ctxs) m_Stats.OrderFallbacks += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
     m_Stats.OrderFallbacks -= orderFallbacksBefore;

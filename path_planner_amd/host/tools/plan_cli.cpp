@@ -5,6 +5,7 @@
 // Scenario lines:  cfg <key> <value> | start x y heading speed time | ribbon x1 y1 x2 y2 | heuristic H K radius |
 //                  ribbon_width w | obstacle x y heading speed time width length | gaussian x y heading speed time [c00 c01 c10 c11] | map_file path | clock t0 dt |
 //                  plan_trace_file path (with cfg plan_trace 1: one line per step of the returned plan) |
+//                  plan_coverage_file path (with cfg plan_coverage 1: one line per step, what it did to the ribbons) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -49,7 +50,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planLogPath;
     bool chainNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -72,6 +73,7 @@ int main(int argc, char** argv) {
             else if (name == "use_brown_paths") config.setUseBrownPaths(v != 0);
             else if (name == "speculation") config.setSpeculation((int)v);
             else if (name == "plan_trace") config.setPlanTrace(v != 0);
+            else if (name == "plan_coverage") config.setPlanCoverage(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else { std::fprintf(stderr, "unknown cfg %s\n", name.c_str()); return 2; }
@@ -100,6 +102,7 @@ int main(int argc, char** argv) {
         } else if (k == "fail_shard") { s >> failShard;      // tests: this shard of a sharded_batch throws before its work
         } else if (k == "cycle_log") { s >> cycleLogPath;    // replan: one JSON line per cycle (Stats::Budget and what the cycle reached)
         } else if (k == "plan_trace_file") { s >> planTracePath;   // segment step x y heading time collision penalty_before flags
+        } else if (k == "plan_coverage_file") { s >> planCoveragePath;   // segment step time to_cover remaining ribbons flags
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -341,6 +344,21 @@ int main(int argc, char** argv) {
                 tail += buf;
             }
             tail += "]";
+        }
+        if (config.planCoverage()) {              // (only with the switch on: without it the line is what it always was)
+            size_t nSteps = 0;
+            for (const auto& seg : st.Coverage) nSteps += seg.size();
+            char buf[64];
+            std::snprintf(buf, sizeof buf, ", \"plan_coverage_steps\": %zu", nSteps);
+            tail += buf;
+            if (!planCoveragePath.empty()) {
+                FILE* f = std::fopen(planCoveragePath.c_str(), "w");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", planCoveragePath.c_str()); return 2; }
+                for (size_t sg = 0; sg < st.Coverage.size(); sg++)
+                    for (const auto& c : st.Coverage[sg])
+                        std::fprintf(f, "%zu %u %.17g %.17g %.17g %u %u\n", sg, c.step, c.time, c.toCover, c.remaining, c.ribbons, c.flags);
+                std::fclose(f);
+            }
         }
         if (config.planTrace()) {
             size_t nSteps = 0;

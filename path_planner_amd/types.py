@@ -72,6 +72,22 @@ STEP_DTYPE = np.dtype([
 ])
 assert STEP_DTYPE.itemsize == 64
 
+# struct ppgpu_cover_record, 32 bytes: what one executed step did to the ribbons (ppgpu_trace_cover_*); record k of an edge belongs
+# to its STEP_DTYPE record k
+C_EVENT, C_COVER, C_CHANGED, C_DONE = 0x1, 0x2, 0x4, 0x8
+COVER_DTYPE = np.dtype([
+    ("to_cover", "<f8"), ("remaining", "<f8"), ("flags", "<u4"), ("step", "<u4"), ("ribbons", "<u4"), ("reserved", "<u4"),
+])
+assert COVER_DTYPE.itemsize == 32
+
+# struct ppgpu_cover_summary, 32 bytes, per edge: the last cover (Edge.cpp:181-191) included
+CS_LAST_COVER, CS_LAST_CHANGED, CS_DONE, CS_REFUSED, CS_THROWS = 0x01, 0x02, 0x04, 0x08, 0x10
+COVER_SUMMARY_DTYPE = np.dtype([
+    ("events", "<i4"), ("changes", "<i4"), ("ribbons_final", "<i4"), ("flags", "<u4"), ("coverage_completed_time", "<f8"),
+    ("remaining_final", "<f8"),
+])
+assert COVER_SUMMARY_DTYPE.itemsize == 32
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
