@@ -25,6 +25,7 @@
 struct ppgpu_ctx;
 
 struct ppgpu_edge_result;   // include/ppgpu.h
+struct ppgpu_vertex;
 
 namespace ppamd {
 
@@ -274,7 +275,6 @@ private:
     };
     std::unordered_map<int, Costed> m_Speculated;
 
-    void uploadWorld(const State& start);
     void pushVertexQueue(int v);
     int popVertexQueue();
     bool goalCondition(const Node& v) const;
@@ -287,14 +287,16 @@ private:
     void harvestFinished();
     void submitBatch(std::shared_ptr<Batch> b, GpuContext& ctx);
     void harvestBatch(Batch* b, bool keep);
-    void dropBatch(Batch* b);
+    std::shared_ptr<Batch> dropBatch(Batch* b);
     void drainInFlight();
     GpuContext& freeContext();
     void pickBatch(int source, std::vector<int>& batch);
+    std::shared_ptr<Batch> pickedBatch(int source);        // a new Batch: pickBatch + the guard's allowance for its longest ribbon list
     double m_EndTime = 0;                  // the deadline of this plan() call, on the injected clock
     int costEdgeList(const std::vector<uint64_t>& edges, int maxParentRibbons, std::vector<::ppgpu_edge_result>& res, std::vector<double>& child);
-    Node makeChild(int source, unsigned cfgBits, const ::ppgpu_edge_result& r, const double* childRibbons, int stride);
-    void fillChild(Node& c, int source, unsigned cfgBits, const ::ppgpu_edge_result& r, const double* childRibbons) const;
+    // record -> Node, the one path: makeChild judges (throws, counts the host heuristic), fillChild only fills.  `given`: a previous plan's leg
+    Node makeChild(int source, unsigned cfgBits, const ::ppgpu_edge_result& r, const double* childRibbons, int stride, const DubinsWrapper* given = nullptr);
+    void fillChild(Node& c, int source, unsigned cfgBits, const ::ppgpu_edge_result& r, const double* childRibbons, const DubinsWrapper* given = nullptr) const;
     void prebuildWhileWaiting(GpuContext& busy);
     void addNode(Node&& n);                // m_Nodes.push_back that counts and times reallocations (Stats::Budget)
     void noteOperation(int kind, double startedAt, double predicted, double actual);
@@ -303,9 +305,22 @@ private:
     int m_StrideFloor = 0;                 // child-ribbon stride a round trip of this plan() had to be repeated with: later ones start there
     int aStar(double endTime);
     void addSamples(long n);
-    int depth(int v) const;
+    std::vector<int> branch(int v) const;  // root's child .. v
+    void packVertices(const std::vector<int>& nodes, std::vector<::ppgpu_vertex>& verts, std::vector<double>& pool) const;
+    // plan() step by step (planner.cpp, in this order)
+    void resetSearch();
+    struct DeviceCounters;
+    DeviceCounters deviceCounters() const;
+    Node beginCall(const RibbonManager& ribbonManager, const State& start);      // shared with evaluatePlans
+    void initSampler(const State& start, unsigned long seed);
+    struct WalkedLegs;                     // the previous-plan leg filter
+    size_t costGivenLegs(const WalkedLegs& walked, std::vector<::ppgpu_edge_result>& res, std::vector<double>& child);
+    void reSolveLeg(int source, const DubinsWrapper& p);
+    int walkPreviousPlan(const DubinsPlan& previousPlan, std::vector<int>& made);
+    bool costBrownPathSeeds(const std::vector<State>& seeds, double tPoll, double endTime);
+    void anytimeLoop(double endTime, int lastPlanEnd, const std::vector<int>& previousPlanNodes, const std::vector<State>& brownPathSamples);
+    void reportPlan();
     DubinsPlan tracePlan(int v, bool addToStats = true);
-    void check(int rc, const char* what) const;
     void setOpenVertex(const Node& n);     // ppgpu_set_vertices on the planner's own device: this node alone
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);

@@ -40,17 +40,79 @@ struct HostProfile {
     }
 };
 HostProfile g_prof;
+
+// One reading of a costed edge's record (ppgpu_edge_result): `info` packs the Dubins word, the child's ribbon count and the sweep's
+// executed steps; `flags` says what the planner may do with it.  Every judgement of a record in this file is one of these.
+inline int recWord(const ppgpu_edge_result& r) { return (int)(r.info & 0xff); }
+inline int recChildRibbons(const ppgpu_edge_result& r) { return (int)((r.info >> 8) & 0xff); }
+inline int recSteps(const ppgpu_edge_result& r) { return (int)(r.info >> 16); }
+inline bool recInfeasible(const ppgpu_edge_result& r) { return (r.flags & PPGPU_F_INFEASIBLE) != 0; }
+inline bool recThrows(const ppgpu_edge_result& r) { return (r.flags & PPGPU_F_THROWS) != 0; }      // the reference throws out of computeTrueCost
+// the child's list is longer than the `stride` slots it came back in
+inline bool recTruncated(const ppgpu_edge_result& r, int stride) { return (r.flags & PPGPU_F_RIBBON_OVF) && recChildRibbons(r) > stride; }
+// PPGPU_F_RIBBON_OVF on a list that came back whole means only that the device's TSP enumeration stops at 8 (12) ribbons: the
+// reference enumerates any length (RibbonManager.cpp:53-140), so h is computed on the host, with the same arithmetic as the root's
+inline bool recHostHeuristic(const ppgpu_edge_result& r, int stride) {
+    return (r.flags & PPGPU_F_RIBBON_OVF) && !(r.flags & PPGPU_F_RIBBON_LOST) && recChildRibbons(r) <= stride;
+}
+// (PPGPU_F_RIBBON_LOST: the sweep itself ran out of its 64 ribbons per vertex and dropped pieces — that record is not the
+// reference's and is refused, whatever the count says)
+inline bool recRefused(const ppgpu_edge_result& r, int stride) {
+    return (r.flags & (PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)) || ((r.flags & PPGPU_F_RIBBON_OVF) && !recHostHeuristic(r, stride));
+}
+// Three readings of "nothing wrong with it" that differ on purpose.  expand() makes no child of an infeasible record unless making it
+// would throw (the throw must still happen) or its list is cut short; a whole list over the enumeration limit does not matter to it.
+inline bool recPlainlyInfeasible(const ppgpu_edge_result& r, int stride) {
+    return (r.flags & PPGPU_F_INFEASIBLE) && !(r.flags & (PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)) && !recTruncated(r, stride);
+}
+// prebuildWhileWaiting builds only what needs no judgement at all: any overflow bit is left to expand() (the host heuristic counts in
+// the statistics).  evaluatePlans asks whether the leg's end vertex can be searched on: an overflow bit alone does not spoil that.
+inline bool recNeedsNoJudgement(const ppgpu_edge_result& r) {
+    return !(r.flags & (PPGPU_F_INFEASIBLE | PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST | PPGPU_F_RIBBON_OVF));
+}
+inline bool recLegFeasible(const ppgpu_edge_result& r) { return !(r.flags & (PPGPU_F_INFEASIBLE | PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)); }
+// the longest child list among the records that overflowed (0: none did), for the two stride-retry loops
+inline int recLargestOverflow(const ppgpu_edge_result* res, size_t n) {
+    int need = 0;
+    for (size_t i = 0; i < n; i++)
+        if (res[i].flags & PPGPU_F_RIBBON_OVF) need = std::max(need, recChildRibbons(res[i]));
+    return need;
+}
+inline void check(int rc, const char* what) { if (rc != PPGPU_OK) throw std::runtime_error(std::string(what) + ": " + ppgpu_last_error()); }
+
+// The open list is a binary min-heap on f: walked best-first from its root (a small heap of heap positions) its entries come out in
+// non-decreasing f, so a walk touches about as many entries as it uses.  visit(f, position) -> false ends the walk.
+template <class Queue, class Visit>
+void walkBestFirst(const Queue& queue, Visit visit) {
+    typedef std::pair<double, size_t> Entry;                  // (f, position in the heap array)
+    auto worse = [](const Entry& a, const Entry& b) { return a.first > b.first; };
+    std::vector<Entry> frontier;
+    if (!queue.empty()) frontier.emplace_back(queue[0].f, 0);
+    while (!frontier.empty()) {
+        std::pop_heap(frontier.begin(), frontier.end(), worse);
+        const Entry e = frontier.back();
+        frontier.pop_back();
+        if (!visit(e.first, e.second)) return;
+        for (size_t c = 2 * e.second + 1; c <= 2 * e.second + 2 && c < queue.size(); c++) {
+            frontier.emplace_back(queue[c].f, c);
+            std::push_heap(frontier.begin(), frontier.end(), worse);
+        }
+    }
+}
+
 // PPAMD_DUMP_EDGES=<file>: every costed edge the search consumes, in consumption order, 16 doubles per line in the layout of the
 // oracle's edge dump (source state, Dubins parameters and type, radius, coverage flag, infeasible, true cost, g, h, end time)
 struct EdgeDump {
     FILE* f = nullptr;
     EdgeDump() { if (const char* p = std::getenv("PPAMD_DUMP_EDGES")) f = std::fopen(p, "w"); }
     ~EdgeDump() { if (f) std::fclose(f); }
-    void write(const State& src, const ppgpu_edge_result& r, double rho, bool cov) {
+    void write(const State& src, const ppgpu_edge_result& r, unsigned cfgBits, const PlannerConfig& config) {
         if (!f) return;
+        const bool cov = (cfgBits & PPGPU_EDGE_COVERAGE) != 0;
+        const double rho = cov ? config.coverageTurningRadius() : config.turningRadius();
         std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %d %.17g %d %d %.17g %.17g %.17g %.17g\n", src.x(), src.y(), src.heading(),
-                     src.speed(), src.time(), r.param[0], r.param[1], r.param[2], (int)(r.info & 0xff), rho, cov ? 1 : 0,
-                     (r.flags & PPGPU_F_INFEASIBLE) ? 1 : 0, r.true_cost, r.g, r.h, r.end_time);
+                     src.speed(), src.time(), r.param[0], r.param[1], r.param[2], recWord(r), rho, cov ? 1 : 0,
+                     recInfeasible(r) ? 1 : 0, r.true_cost, r.g, r.h, r.end_time);
     }
 };
 EdgeDump g_dump;
@@ -235,10 +297,6 @@ GpuAStarPlanner::~GpuAStarPlanner() {
     if (m_Ctx && m_Nodes.capacity() > m_Ctx->nodeArena.capacity()) m_Nodes.swap(m_Ctx->nodeArena);
 }
 
-void GpuAStarPlanner::check(int rc, const char* what) const {
-    if (rc != PPGPU_OK) throw std::runtime_error(std::string(what) + ": " + ppgpu_last_error());
-}
-
 static void ribbonsToArray(const RibbonManager& rm, std::vector<double>& out) {
     out.assign(rm.rows(), rm.rows() + 4 * (size_t)rm.count());   // the manager keeps its list in the device's row layout
 }
@@ -273,10 +331,24 @@ static ppgpu_wrapper_edge wrapperEdge(const DubinsWrapper& p, int32_t vertex, bo
     return we;
 }
 
-int GpuAStarPlanner::depth(int v) const {
-    int d = 0;
-    for (int p = m_Nodes[v].parent; p >= 0; p = m_Nodes[p].parent) d++;
-    return d;
+// These nodes as a device open-vertex array: one ppgpu_vertex each, their ribbon lists one after the other in `pool`.
+void GpuAStarPlanner::packVertices(const std::vector<int>& nodes, std::vector<ppgpu_vertex>& verts, std::vector<double>& pool) const {
+    verts.resize(nodes.size());
+    pool.clear();
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const Node& n = m_Nodes[nodes[i]];
+        verts[i] = makeVertex(n);
+        verts[i].ribbon_offset = (int32_t)(pool.size() / 4);
+        pool.insert(pool.end(), n.ribbons.rows(), n.ribbons.rows() + 4 * (size_t)n.ribbons.count());
+    }
+}
+
+// the vertices from the root's child down to v (the root itself is not among them; none for v < 0)
+std::vector<int> GpuAStarPlanner::branch(int v) const {
+    std::vector<int> b;
+    for (int cur = v; cur >= 0 && m_Nodes[cur].parent >= 0; cur = m_Nodes[cur].parent) b.push_back(cur);
+    std::reverse(b.begin(), b.end());
+    return b;
 }
 
 // ------------------------------------------------------------------------------------------------ world upload
@@ -315,7 +387,6 @@ static bool uploadSnapshot(const std::vector<std::shared_ptr<GpuContext>>& ctxs,
     std::vector<double> orows;
     const DynamicObstaclesManager& om = config.obstaclesManager();
     om.deviceRows(orows);
-    auto check = [](int rc, const char* what) { if (rc != PPGPU_OK) throw std::runtime_error(std::string(what) + ": " + ppgpu_last_error()); };
     for (const auto& ctx : ctxs) {
         ppgpu_ctx* h = ctx->handle();
         check(ppgpu_set_config(h, &c), "ppgpu_set_config");
@@ -331,8 +402,6 @@ static bool uploadSnapshot(const std::vector<std::shared_ptr<GpuContext>>& ctxs,
     }
     return needGrid;
 }
-
-void GpuAStarPlanner::uploadWorld(const State& start) { m_Stats.Budget.GridUploaded = uploadSnapshot(m_Ctxs, m_Config, m_RibbonManager, start.time()); }
 
 // ------------------------------------------------------------------------------------------------ budget bookkeeping
 void GpuAStarPlanner::addNode(Node&& n) {
@@ -376,12 +445,11 @@ void GpuAStarPlanner::pushVertexQueue(int vi) {   // SamplingBasedPlanner.cpp:7-
 void GpuAStarPlanner::visualizeVertex(int vi, const char* tag, bool expanded) {
     if (!m_Config.visualizations()) return;
     const Node& v = m_Nodes[vi];
-    std::vector<int> chain;
-    for (int cur = vi; cur >= 0; cur = m_Nodes[cur].parent) chain.push_back(cur);
     std::ostream& o = m_Config.visualizationStream();
     o << (expanded ? "Expanded " : "Generated ") << "State: (" << v.state.toStringRad() << "), f: " << v.g + v.h << ", g: " << v.g
       << ", h: " << v.h << " " << tag << " ";
-    for (auto it = chain.rbegin(); it != chain.rend(); ++it) o << (*it + 1) << " ";
+    o << 1 << " ";                                       // (the root, then the branch down to the vertex)
+    for (int n : branch(vi)) o << (n + 1) << " ";
     o << std::endl;
 }
 
@@ -503,21 +571,20 @@ void GpuAStarPlanner::addSamples(long n) {   // SamplingBasedPlanner::addSamples
 }
 
 // ------------------------------------------------------------------------------------------------ edges
-// The child Node of one costed edge (what Vertex::connect + Edge::computeTrueCost + Vertex::computeApproxToGo leave behind)
-GpuAStarPlanner::Node GpuAStarPlanner::makeChild(int source, unsigned cfgBits, const ppgpu_edge_result& r, const double* childRibbons, int stride) {
-    if (r.flags & PPGPU_F_THROWS) throw std::runtime_error("Edge cost evaluation failed: invalid time in sample for Dubins path");
-    const int nChild = (int)((r.info >> 8) & 0xff);
-    // PPGPU_F_RIBBON_OVF on a list that came back whole means only that the device's TSP enumeration stops at 8 (12) ribbons: the
-    // reference enumerates any length (RibbonManager.cpp:53-140), so h is computed here, with the same arithmetic as the root's
-    // (PPGPU_F_RIBBON_LOST: the sweep itself ran out of its 64 ribbons per vertex and dropped pieces — that record is not the
-    // reference's and is refused, whatever the count says)
-    const bool hostHeuristic = (r.flags & PPGPU_F_RIBBON_OVF) && !(r.flags & PPGPU_F_RIBBON_LOST) && nChild <= stride;
-    if ((r.flags & (PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)) || ((r.flags & PPGPU_F_RIBBON_OVF) && !hostHeuristic))
-        throw std::runtime_error("Edge cost evaluation exceeded a device capacity (flags " + std::to_string(r.flags) + ", child ribbons " +
-                                 std::to_string(nChild) + ", parent ribbons " + std::to_string(m_Nodes[source].ribbons.count()) + ")");
+// The child Node of one costed edge (what Vertex::connect + Edge::computeTrueCost + Vertex::computeApproxToGo leave behind): the one
+// path from a record to a vertex.  `given`: the edge is a previous plan's leg (Vertex::connect(start, DubinsWrapper, coverageAllowed)) —
+// the child keeps that curve, and what is thrown says so in the words plan()'s prologue has always used.
+GpuAStarPlanner::Node GpuAStarPlanner::makeChild(int source, unsigned cfgBits, const ppgpu_edge_result& r, const double* childRibbons, int stride,
+                                                 const DubinsWrapper* given) {
+    if (recThrows(r))
+        throw std::runtime_error(given ? "Invalid time in sample for Dubins path (previous plan)" : "Edge cost evaluation failed: invalid time in sample for Dubins path");
+    if (recRefused(r, stride))
+        throw std::runtime_error("Edge cost evaluation exceeded a device capacity" +
+                                 (given ? std::string() : " (flags " + std::to_string(r.flags) + ", child ribbons " + std::to_string(recChildRibbons(r)) +
+                                                              ", parent ribbons " + std::to_string(m_Nodes[source].ribbons.count()) + ")"));
     Node c;
-    fillChild(c, source, cfgBits, r, childRibbons);
-    if (hostHeuristic) {       // Vertex::computeApproxToGo (Vertex.cpp:49-64): the child's heading goes where the callee says yaw
+    fillChild(c, source, cfgBits, r, childRibbons, given);
+    if (recHostHeuristic(r, stride)) {       // Vertex::computeApproxToGo (Vertex.cpp:49-64): the child's heading goes where the callee says yaw
         c.h = c.ribbons.approximateDistanceUntilDone(c.state.x(), c.state.y(), c.state.heading()) / m_Config.maxSpeed() * kTimePenaltyFactor;
         m_Stats.HostHeuristics++;
     }
@@ -525,25 +592,28 @@ GpuAStarPlanner::Node GpuAStarPlanner::makeChild(int source, unsigned cfgBits, c
 }
 
 // the child vertex of one costed edge, from its record (nothing here throws or counts: prebuildWhileWaiting uses it too)
-void GpuAStarPlanner::fillChild(Node& c, int source, unsigned cfgBits, const ppgpu_edge_result& r, const double* childRibbons) const {
+void GpuAStarPlanner::fillChild(Node& c, int source, unsigned cfgBits, const ppgpu_edge_result& r, const double* childRibbons, const DubinsWrapper* given) const {
     const Node& src = m_Nodes[source];
-    const int nChild = (int)((r.info >> 8) & 0xff);
     c.parent = source;
     c.state = State(r.end_x, r.end_y, r.end_heading, r.end_speed, r.end_time);
     c.coverageAllowed = (cfgBits & PPGPU_EDGE_COVERAGE) != 0;
-    c.infeasible = (r.flags & PPGPU_F_INFEASIBLE) != 0;
+    c.infeasible = recInfeasible(r);
     c.collisionPenalty = r.collision_penalty;
-    c.steps = (int)(r.info >> 16);
+    c.steps = recSteps(r);
     c.g = r.g;
     c.h = r.h;
     c.ribbons = RibbonManager(src.ribbons.heuristic(), src.ribbons.turningRadius(), src.ribbons.k());   // the parent's settings; its list is replaced below
-    c.ribbons.assign(childRibbons, nChild, r.coverage_completed_time);
-    DubinsPath p;
-    p.qi[0] = src.state.x(); p.qi[1] = src.state.y(); p.qi[2] = src.state.yaw();
-    p.param[0] = r.param[0]; p.param[1] = r.param[1]; p.param[2] = r.param[2];
-    p.rho = c.coverageAllowed ? m_Config.coverageTurningRadius() : m_Config.turningRadius();
-    p.type = (DubinsPathType)(r.info & 0xff);
-    c.wrapper.fill(p, r.end_speed, src.state.time());
+    c.ribbons.assign(childRibbons, recChildRibbons(r), r.coverage_completed_time);
+    if (given) {
+        c.wrapper = *given;
+    } else {
+        DubinsPath p;
+        p.qi[0] = src.state.x(); p.qi[1] = src.state.y(); p.qi[2] = src.state.yaw();
+        p.param[0] = r.param[0]; p.param[1] = r.param[1]; p.param[2] = r.param[2];
+        p.rho = c.coverageAllowed ? m_Config.coverageTurningRadius() : m_Config.turningRadius();
+        p.type = (DubinsPathType)recWord(r);
+        c.wrapper.fill(p, r.end_speed, src.state.time());
+    }
     if (!c.infeasible && r.end_time < c.wrapper.getEndTime()) c.wrapper.updateEndTime(r.end_time);   // Edge.cpp:179
 }
 
@@ -554,25 +624,13 @@ void GpuAStarPlanner::fillChild(Node& c, int source, unsigned cfgBits, const ppg
 void GpuAStarPlanner::prebuildWhileWaiting(GpuContext& busy) {
     static const bool off = std::getenv("PPAMD_NO_PREBUILD") != nullptr;      // (A/B switch)
     if (off || m_Config.visualizations() || m_Queue.empty()) return;
-    // the open vertices with costed children, in pop order: the same best-first walk of the heap array as pickBatch
-    typedef std::pair<double, size_t> Entry;
-    auto worse = [](const Entry& a, const Entry& b) { return a.first > b.first; };
-    std::vector<Entry> frontier;
-    frontier.emplace_back(m_Queue[0].f, 0);
     size_t visited = 0;
-    while (!frontier.empty() && visited < 256) {
-        if (busy.idle()) return;
-        std::pop_heap(frontier.begin(), frontier.end(), worse);
-        const Entry e = frontier.back();
-        frontier.pop_back();
+    walkBestFirst(m_Queue, [&](double, size_t at) {         // the open vertices with costed children, in pop order
+        if (visited >= 256 || busy.idle()) return false;
         visited++;
-        for (size_t c = 2 * e.second + 1; c <= 2 * e.second + 2 && c < m_Queue.size(); c++) {
-            frontier.emplace_back(m_Queue[c].f, c);
-            std::push_heap(frontier.begin(), frontier.end(), worse);
-        }
-        const int v = m_Queue[e.second].v;
+        const int v = m_Queue[at].v;
         auto it = m_Speculated.find(v);
-        if (it == m_Speculated.end() || !it->second.ready.empty() || it->second.count == 0) continue;
+        if (it == m_Speculated.end() || !it->second.ready.empty() || it->second.count == 0) return true;
         Costed& cs = it->second;
         const TripBlock& blk = *cs.block;
         const ppgpu_edge_result* records = reinterpret_cast<const ppgpu_edge_result*>(blk.records.get());
@@ -580,13 +638,13 @@ void GpuAStarPlanner::prebuildWhileWaiting(GpuContext& busy) {
         cs.ready.assign(cs.count, 0);
         for (size_t i = 0; i < cs.count; i++) {
             const size_t eidx = cs.first + i;
-            const ppgpu_edge_result& r = records[eidx];
             // left to expand(): a record that is never pushed, one the planner throws on, one whose heuristic it computes itself
-            if (r.flags & (PPGPU_F_INFEASIBLE | PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST | PPGPU_F_RIBBON_OVF)) continue;
-            fillChild(cs.kids[i], v, (unsigned)(blk.edges[eidx] >> 56), r, blk.child.get() + eidx * (size_t)blk.stride * 4);
+            if (!recNeedsNoJudgement(records[eidx])) continue;
+            fillChild(cs.kids[i], v, (unsigned)(blk.edges[eidx] >> 56), records[eidx], blk.child.get() + eidx * (size_t)blk.stride * 4);
             cs.ready[i] = 1;
         }
-    }
+        return true;
+    });
 }
 
 // ppgpu_cost_edges_host with a child-ribbon stride sized for the parents at hand: children rarely carry more than a few
@@ -601,11 +659,7 @@ int GpuAStarPlanner::costEdgeList(const std::vector<uint64_t>& edges, int maxPar
         child.assign(n * (size_t)stride * 4, 0.0);
         check(ppgpu_cost_edges_host(m_Ctx->handle(), (int64_t)n, edges.data(), res.data(), child.data(), stride), "ppgpu_cost_edges_host");
         m_Stats.EdgesCosted += n;
-        bool retry = false;
-        if (stride < kRibbonStride)
-            for (size_t i = 0; i < n && !retry; i++)
-                retry = (res[i].flags & PPGPU_F_RIBBON_OVF) && (int)((res[i].info >> 8) & 0xff) > stride;
-        if (!retry) return stride;
+        if (stride == kRibbonStride || recLargestOverflow(res.data(), n) <= stride) return stride;
         stride = kRibbonStride;
     }
 }
@@ -636,10 +690,7 @@ int GpuAStarPlanner::costStateEdges(int source, const std::vector<State>& target
     std::vector<double> child;
     const int stride = costEdgeList(edges, (int)m_Nodes[source].ribbons.count(), res, child);
     for (size_t i = 0; i < n; i++) {
-        {
-            const bool cov = (cfgBits[i] & PPGPU_EDGE_COVERAGE) != 0;
-            g_dump.write(m_Nodes[source].state, res[i], cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius(), cov);
-        }
+        g_dump.write(m_Nodes[source].state, res[i], cfgBits[i], m_Config);
         addNode(makeChild(source, cfgBits[i], res[i], child.data() + i * (size_t)stride * 4, stride));
         visualizeTrajectory(m_Nodes.back());
         pushVertexQueue((int)m_Nodes.size() - 1);
@@ -662,7 +713,7 @@ struct GpuAStarPlanner::Batch {
     std::vector<int> sources;
     std::vector<ppgpu_vertex> verts;
     std::vector<double> pool, nearest;
-    int maxParent = 0;
+    int maxParent = 0;                     // the longest ribbon list among the sources (sizes the child stride and `heavy`)
     double heavy = 0;                      // heavyListAllowance of the batch (part of `predicted`)
     int strideFloor = 0, strideUsed = 0, retries = 0;      // (the child stride earlier round trips of this plan() needed; what this one ended with)
     GpuContext* ctx = nullptr;
@@ -680,16 +731,7 @@ struct GpuAStarPlanner::Batch {
 void GpuAStarPlanner::packBatch(Batch& b) const {
     Lap lap(1);
     const int M = (int)b.sources.size();
-    b.verts.resize((size_t)M);
-    b.pool.clear();
-    b.maxParent = 0;
-    for (int i = 0; i < M; i++) {                     // these vertices become the device's open-vertex array
-        const Node& n = m_Nodes[b.sources[i]];
-        b.verts[i] = makeVertex(n);
-        b.verts[i].ribbon_offset = (int32_t)(b.pool.size() / 4);
-        b.pool.insert(b.pool.end(), n.ribbons.rows(), n.ribbons.rows() + 4 * (size_t)n.ribbons.count());
-        b.maxParent = std::max(b.maxParent, (int)b.verts[i].ribbon_count);
-    }
+    packVertices(b.sources, b.verts, b.pool);         // these vertices become the device's open-vertex array
     // nearest point to cover (:64-81): one explicit target per vertex that has one (computed on the host, as in the reference)
     b.nearest.assign((size_t)M * 3, std::nan(""));
     for (int i = 0; i < M; i++) {
@@ -722,10 +764,7 @@ void GpuAStarPlanner::runBatch(Batch& b, int k) {
         // some child does not fit: again with room for the longest list the records report (round 4: the second pass used to go straight
         // to the device's per-vertex capacity of 64 — 5 MB of child slots to download for 2 500 edges — and such a trip took 5-9 ms where
         // its neighbours took 0.6: the largest under-predictions of the deadline guard)
-        int need = 0;
-        if (stride < kRibbonStride)
-            for (int64_t i = 0; i < b.n; i++)
-                if (res[i].flags & PPGPU_F_RIBBON_OVF) need = std::max(need, (int)((res[i].info >> 8) & 0xff));
+        const int need = stride < kRibbonStride ? recLargestOverflow(res, (size_t)b.n) : 0;
         if (need <= stride) break;
         stride = std::min(kRibbonStride, need + 2);
         b.retries++;
@@ -738,7 +777,7 @@ void GpuAStarPlanner::runBatch(Batch& b, int k) {
         TripBlock& blk = *b.block;
         const ppgpu_edge_result* res = reinterpret_cast<const ppgpu_edge_result*>(blk.records.get());
         int most = 1;
-        for (int64_t i = 0; i < b.n; i++) most = std::max(most, (int)(res[i].info >> 16));
+        for (int64_t i = 0; i < b.n; i++) most = std::max(most, recSteps(res[i]));
         blk.traceCounts.assign((size_t)b.n, 0);
         std::vector<Stats::TraceStep> all((size_t)b.n * (size_t)most);
         if (ppgpu_trace_edges_host(h, b.n, blk.edges.get(), nullptr, most, blk.traceCounts.data(),
@@ -783,11 +822,8 @@ void GpuAStarPlanner::submitBatch(std::shared_ptr<Batch> bp, GpuContext& ctx) {
 
 // the batch is over (wait for its thread if it has one): its children go to m_Speculated, its figures to the statistics
 void GpuAStarPlanner::harvestBatch(Batch* bp, bool keep) {
-    std::shared_ptr<Batch> own;
-    for (auto it = m_InFlight.begin(); it != m_InFlight.end(); ++it)
-        if (it->get() == bp) { own = std::move(*it); m_InFlight.erase(it); break; }
+    const std::shared_ptr<Batch> own = dropBatch(bp);
     Batch& b = *own;
-    for (int v : b.sources) m_InFlightOf.erase(v);
     if (b.threaded) {
         Lap lap(2);
         if (keep) prebuildWhileWaiting(*b.ctx);
@@ -826,10 +862,13 @@ void GpuAStarPlanner::harvestFinished() {
     }
 }
 
-void GpuAStarPlanner::dropBatch(Batch* bp) {
+// no longer in flight (-> the batch, for harvestBatch to finish with)
+std::shared_ptr<GpuAStarPlanner::Batch> GpuAStarPlanner::dropBatch(Batch* bp) {
+    std::shared_ptr<Batch> own;
     for (int v : bp->sources) m_InFlightOf.erase(v);
     for (auto it = m_InFlight.begin(); it != m_InFlight.end(); ++it)
-        if (it->get() == bp) { m_InFlight.erase(it); break; }
+        if (it->get() == bp) { own = std::move(*it); m_InFlight.erase(it); break; }
+    return own;
 }
 
 // every round trip still running is waited for and thrown away (the sample set changes, or plan() is about to return: nothing of
@@ -860,9 +899,8 @@ GpuContext& GpuAStarPlanner::freeContext() {
 // is pushed, and in which order, is exactly what expanding one vertex at a time would push: speculation only changes when
 // the arithmetic happens.  Nothing survives a change of the sample set (m_Speculated is cleared by addSamples).
 // The open vertices a round trip costs besides `source`: the up to speculation() - 1 entries of smallest f among those whose
-// children are not costed yet and that are not goals.  The open list is a binary min-heap on f: walked best-first from its root
-// (a small heap of heap positions) the entries come out in non-decreasing f, so the walk touches about as many entries as it
-// returns — round 3 scanned and partially sorted the whole list (100 000+ entries late in a cycle: up to 40 of a cycle's 100 ms).
+// children are not costed yet and that are not goals, found by walkBestFirst — round 3 scanned and partially sorted the whole
+// list (100 000+ entries late in a cycle: up to 40 of a cycle's 100 ms).
 // Ties in f are taken smallest node index first, as before: the walk goes on through every entry that ties with the last one taken.
 // Two cuts bound the walk (round 4: one cycle in a few hundred spent 76 ms of its 100 in a single walk — late in a search tens of
 // thousands of goals sit in the list at exactly f = horizon, few open vertices are better, and the walk went through the whole
@@ -870,6 +908,7 @@ GpuContext& GpuAStarPlanner::freeContext() {
 // (aStar returns when that goal is popped), so the walk ends there; and it visits at most 16 x the batch + 1 024 entries.  Either way
 // the batch is smaller, which changes when arithmetic happens, never what is pushed.
 void GpuAStarPlanner::pickBatch(int source, std::vector<int>& batch) {
+    Lap lap(0);
     const double pick0 = HostProfile::now();
     struct PickTimer {
         Stats::BudgetTrace& b; double t0;
@@ -879,31 +918,30 @@ void GpuAStarPlanner::pickBatch(int source, std::vector<int>& batch) {
     if (source >= 0) batch.push_back(source);          // -1: a prefetch batch, nobody is waiting for any of it
     const size_t want = (size_t)std::max(0, m_Config.speculation() - (source >= 0 ? 1 : 0));
     if (want == 0 || m_Queue.empty()) return;
-    typedef std::pair<double, size_t> Entry;                  // (f, position in m_Queue)
-    auto worse = [](const Entry& a, const Entry& b) { return a.first > b.first; };
-    std::vector<Entry> frontier;
-    frontier.emplace_back(m_Queue[0].f, 0);
     std::vector<std::pair<double, int>> cand;                 // (f, node)
     double lastF = 0, goalF = INFINITY;
     size_t visited = 0;
     const size_t maxVisited = 16 * want + 1024;
-    while (!frontier.empty()) {
-        std::pop_heap(frontier.begin(), frontier.end(), worse);
-        const Entry e = frontier.back();
-        frontier.pop_back();
-        if (cand.size() >= want && e.first > lastF) break;    // everything left is worse than what is already taken
-        if (e.first > goalF || ++visited > maxVisited) break; // ... or than a goal already in the list; or the walk has gone far enough
-        const int v = m_Queue[e.second].v;
+    walkBestFirst(m_Queue, [&](double f, size_t at) {
+        if (cand.size() >= want && f > lastF) return false;    // everything left is worse than what is already taken
+        if (f > goalF || ++visited > maxVisited) return false; // ... or than a goal already in the list; or the walk has gone far enough
+        const int v = m_Queue[at].v;
         const bool goal = goalCondition(m_Nodes[v]);
-        if (goal) goalF = std::min(goalF, e.first);
-        if (!goal && !m_Speculated.count(v) && !m_InFlightOf.count(v)) { cand.emplace_back(e.first, v); lastF = std::max(lastF, e.first); }
-        for (size_t c = 2 * e.second + 1; c <= 2 * e.second + 2 && c < m_Queue.size(); c++) {
-            frontier.emplace_back(m_Queue[c].f, c);
-            std::push_heap(frontier.begin(), frontier.end(), worse);
-        }
-    }
+        if (goal) goalF = std::min(goalF, f);
+        if (!goal && !m_Speculated.count(v) && !m_InFlightOf.count(v)) { cand.emplace_back(f, v); lastF = std::max(lastF, f); }
+        return true;
+    });
     std::sort(cand.begin(), cand.end());                      // (f, node index): the order the whole-list scan used to produce
     for (size_t i = 0; i < cand.size() && i < want; i++) batch.push_back(cand[i].second);
+}
+
+// a round trip in the making: `source` (-1: a prefetch) and the next-best open vertices, with the guard's allowance for their longest list
+std::shared_ptr<GpuAStarPlanner::Batch> GpuAStarPlanner::pickedBatch(int source) {
+    std::shared_ptr<Batch> b(new Batch());
+    pickBatch(source, b->sources);
+    for (int v : b->sources) b->maxParent = std::max(b->maxParent, m_Nodes[v].ribbons.count());
+    b->heavy = heavyListAllowance(b->maxParent);
+    return b;
 }
 
 bool GpuAStarPlanner::expand(int source) {
@@ -917,34 +955,16 @@ bool GpuAStarPlanner::expand(int source) {
         } else if (flying == m_InFlightOf.end()) {
             GpuContext& ctx = freeContext();           // (may harvest a batch: the source can be among its vertices now)
             if (!m_Speculated.count(source)) {
-                std::shared_ptr<Batch> b(new Batch());
-                {
-                    Lap lap(0);
-                    pickBatch(source, b->sources);
-                }
+                std::shared_ptr<Batch> b = pickedBatch(source);
                 // the deadline guard once more, with the clock as it stands now that the batch is chosen (only when the guard is on: a
                 // counting clock must see the reference's call sequence)
-                {
-                    int mp = 0;
-                    for (int v : b->sources) mp = std::max(mp, m_Nodes[v].ribbons.count());
-                    b->heavy = heavyListAllowance(mp);
-                }
                 if (m_Config.deadlineGuard() && now() + ctx.predictTrip((double)m_NumSamples) + b->heavy >= m_EndTime - m_Ctx->guardMargin()) return false;
                 Batch* mine = b.get();
                 submitBatch(std::move(b), ctx);
                 // while that one runs: the other contexts take the next-best open vertices (prefetch)
                 while (m_InFlight.size() < m_Ctxs.size()) {
-                    std::shared_ptr<Batch> p(new Batch());
-                    {
-                        Lap lap(0);
-                        pickBatch(-1, p->sources);
-                    }
+                    std::shared_ptr<Batch> p = pickedBatch(-1);
                     if (p->sources.empty()) break;
-                    {
-                        int mp = 0;
-                        for (int v : p->sources) mp = std::max(mp, m_Nodes[v].ribbons.count());
-                        p->heavy = heavyListAllowance(mp);
-                    }
                     GpuContext& pc = freeContext();
                     // (a prefetch shares the device with the round trips already in flight: at worst it ends after all of them, one
                     // predicted round trip each — with eight contexts and no such allowance a cycle's last prefetches queued up behind one
@@ -972,13 +992,8 @@ bool GpuAStarPlanner::expand(int source) {
         const unsigned cfgBits = (unsigned)(blk.edges[e] >> 56);
         // an infeasible edge is never pushed (SamplingBasedPlanner.cpp:8): no vertex is made for it, unless the search is being
         // watched (its sweep is streamed all the same) or the record carries an error (makeChild throws what the reference throws)
-        {
-            const bool cov = (cfgBits & PPGPU_EDGE_COVERAGE) != 0;
-            g_dump.write(m_Nodes[source].state, r, cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius(), cov);
-        }
-        const bool truncated = (r.flags & PPGPU_F_RIBBON_OVF) && (int)((r.info >> 8) & 0xff) > blk.stride;
-        const bool plainInfeasible = (r.flags & PPGPU_F_INFEASIBLE) && !(r.flags & (PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)) && !truncated;
-        if (plainInfeasible && !watch) continue;
+        g_dump.write(m_Nodes[source].state, r, cfgBits, m_Config);
+        if (recPlainlyInfeasible(r, blk.stride) && !watch) continue;
         const size_t ki = e - costed.first;
         if (ki < costed.ready.size() && costed.ready[ki]) addNode(std::move(costed.kids[ki]));      // built while the planner waited
         else addNode(makeChild(source, cfgBits, r, blk.child.get() + e * (size_t)blk.stride * 4, blk.stride));
@@ -1029,17 +1044,16 @@ int GpuAStarPlanner::aStar(double endTime) {   // AStarPlanner.cpp:134-148
 DubinsPlan GpuAStarPlanner::tracePlan(int v, bool addToStats) {   // Planner.cpp:12-32
     DubinsPlan plan;
     if (v < 0) return plan;
-    std::vector<int> branch;
+    const std::vector<int> nodes = branch(v);
     bool dangerous = false;
-    for (int cur = v; m_Nodes[cur].parent >= 0; cur = m_Nodes[cur].parent) {
-        branch.push_back(cur);
-        if (m_Nodes[cur].collisionPenalty > 0) {
+    for (auto it = nodes.rbegin(); it != nodes.rend(); it++) {      // (leaf first: the order the penalties have always been summed in)
+        if (m_Nodes[*it].collisionPenalty > 0) {
             dangerous = true;
-            if (addToStats) m_Stats.PlanCollisionPenalty += m_Nodes[cur].collisionPenalty;
+            if (addToStats) m_Stats.PlanCollisionPenalty += m_Nodes[*it].collisionPenalty;
         }
     }
     plan.setDangerous(dangerous);
-    for (auto it = branch.rbegin(); it != branch.rend(); it++) plan.append(m_Nodes[*it].wrapper);
+    for (int n : nodes) plan.append(m_Nodes[n].wrapper);
     return plan;
 }
 
@@ -1049,32 +1063,29 @@ static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "S
 void GpuAStarPlanner::tracePlanSteps(int v) {
     m_Stats.Trace.clear();
     m_Stats.Coverage.clear();
-    std::vector<int> branch;
-    for (int cur = v; cur >= 0 && m_Nodes[cur].parent >= 0; cur = m_Nodes[cur].parent) branch.push_back(cur);
-    std::reverse(branch.begin(), branch.end());
-    const size_t n = branch.size();
+    const std::vector<int> nodes = branch(v);
+    const size_t n = nodes.size();
     if (n == 0) return;
-    std::vector<ppgpu_vertex> verts(n);
-    std::vector<double> pool;
+    std::vector<int> parents(n);
     std::vector<ppgpu_wrapper_edge> wedges(n);
     int most = 1;
     for (size_t s = 0; s < n; s++) {
-        const Node& c = m_Nodes[branch[s]];
-        const Node& src = m_Nodes[c.parent];
-        verts[s] = makeVertex(src);
-        verts[s].ribbon_offset = (int32_t)(pool.size() / 4);
-        pool.insert(pool.end(), src.ribbons.rows(), src.ribbons.rows() + 4 * (size_t)src.ribbons.count());
+        const Node& c = m_Nodes[nodes[s]];
+        parents[s] = c.parent;
         wedges[s] = wrapperEdge(c.wrapper, (int32_t)s, c.coverageAllowed);
         most = std::max(most, c.steps);
     }
+    std::vector<ppgpu_vertex> verts;
+    std::vector<double> pool;
+    packVertices(parents, verts, pool);
     ppgpu_ctx* h = m_Ctx->handle();
     check(ppgpu_set_vertices(h, (int32_t)n, verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
     std::vector<int32_t> counts(n, 0);
     const auto sameCounts = [&](const char* what) {
         for (size_t s = 0; s < n; s++)
-            if (counts[s] != m_Nodes[branch[s]].steps)
+            if (counts[s] != m_Nodes[nodes[s]].steps)
                 throw std::runtime_error(std::string(what) + ": segment " + std::to_string(s) + " traced " + std::to_string(counts[s]) + " steps, its edge executed " +
-                                         std::to_string(m_Nodes[branch[s]].steps));
+                                         std::to_string(m_Nodes[nodes[s]].steps));
     };
     if (m_Config.planTrace()) {
         std::vector<Stats::TraceStep> steps(n * (size_t)most);
@@ -1104,35 +1115,58 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the start of a call
+// What evaluatePlans() and plan() begin with once m_Config is the call's (AStarPlanner.cpp:14-26, :35-37): start time, the call's own
+// RibbonManager, the world on every device.  -> the root vertex (h left unset: only plan() needs it)
+GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonManager, const State& start) {
+    m_Config.setStartStateTime(start.time());
+    m_RibbonManager = ribbonManager;
+    m_RibbonManager.changeHeuristicIfTooManyRibbons();
+    if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
+    m_StartStateTime = start.time();
+    m_Stats.Budget.GridUploaded = uploadSnapshot(m_Ctxs, m_Config, m_RibbonManager, start.time());
+    Node root;
+    root.state = start;
+    root.state.speed() = m_Config.maxSpeed();
+    root.g = 0;
+    root.ribbons = m_RibbonManager;
+    return root;
+}
+
+// A previous plan as AStarPlanner::plan walks it from the start time (:46-59): the legs that have not ended and take time (:49-50), each
+// with the coverage flag its radius stands for.  A leg at a radius the configuration no longer has is `foreign`: not a given curve any
+// more, Edge.cpp:78-80 solves a new one to its end state.  The `given` legs before the first foreign one are what one chain call can cost.
+struct GpuAStarPlanner::WalkedLegs {
+    struct Leg { const DubinsWrapper* curve; bool coverage, foreign; };
+    std::vector<Leg> legs;
+    size_t given = 0;
+    WalkedLegs(const DubinsPlan& plan, double startTime, const PlannerConfig& config) {
+        for (const DubinsWrapper& p : plan.get()) {
+            if (p.getEndTime() <= startTime || p.getNetTime() == 0) continue;
+            const bool cov = p.getRho() == config.coverageTurningRadius();
+            const bool foreign = p.getRho() != (cov ? config.coverageTurningRadius() : config.turningRadius());
+            if (!foreign && given == legs.size()) given++;
+            legs.push_back(Leg{&p, cov, foreign});
+        }
+    }
+    void appendGiven(std::vector<ppgpu_wrapper_edge>& out) const {      // ... as edges from open vertex 0
+        for (size_t k = 0; k < given; k++) out.push_back(wrapperEdge(*legs[k].curve, 0, legs[k].coverage));
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ evaluatePlans()
 // "What does this whole plan cost in the current world, and how far along is it still feasible": the walk plan() makes over its
 // previous plan (AStarPlanner.cpp:46-59), for any number of candidate plans from one start, all in ONE ppgpu_cost_plans_host call.
 std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
                                                                             const std::vector<DubinsPlan>& plans) {
     m_Config = std::move(config);
-    m_Config.setStartStateTime(start.time());
-    m_RibbonManager = ribbonManager;
-    m_RibbonManager.changeHeuristicIfTooManyRibbons();
-    if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
-    m_StartStateTime = start.time();
     drainInFlight();
-    uploadWorld(start);
-    ppgpu_ctx* h = m_Ctx->handle();
-    Node root;                                       // plan()'s root (:35-37)
-    root.state = start;
-    root.state.speed() = m_Config.maxSpeed();
-    root.g = 0;
-    root.ribbons = m_RibbonManager;
+    const Node root = beginCall(ribbonManager, start);
     setOpenVertex(root);
     std::vector<int32_t> offsets{0};
     std::vector<ppgpu_wrapper_edge> legs;
     for (const DubinsPlan& plan : plans) {
-        for (const auto& p : plan.get()) {
-            if (p.getEndTime() <= start.time() || p.getNetTime() == 0) continue;       // :49-50
-            const bool cov = p.getRho() == m_Config.coverageTurningRadius();
-            if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;   // Edge.cpp:78-80 would re-solve it
-            legs.push_back(wrapperEdge(p, 0, cov));
-        }
+        WalkedLegs(plan, start.time(), m_Config).appendGiven(legs);
         offsets.push_back((int32_t)legs.size());
     }
     const size_t n = plans.size();
@@ -1140,7 +1174,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
     std::vector<double> child(legs.size() * (size_t)kRibbonStride * 4, 0.0);
     std::vector<int32_t> costed(n, 0);
     std::vector<uint32_t> why(n, 0);
-    check(ppgpu_cost_plans_host(h, (int32_t)n, offsets.data(), legs.data(), res.data(), child.data(), kRibbonStride, costed.data(), why.data()),
+    check(ppgpu_cost_plans_host(m_Ctx->handle(), (int32_t)n, offsets.data(), legs.data(), res.data(), child.data(), kRibbonStride, costed.data(), why.data()),
           "ppgpu_cost_plans_host");
     std::vector<PlanEvaluation> out(n);
     for (size_t i = 0; i < n; i++) {
@@ -1155,32 +1189,23 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
             const size_t at = (size_t)offsets[i] + (size_t)k;
             const ppgpu_edge_result& r = res[at];
             PlanEvaluation::Leg& leg = e.legs[(size_t)k];
-            leg.feasible = !(r.flags & (PPGPU_F_INFEASIBLE | PPGPU_F_THROWS | PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST));
+            leg.feasible = recLegFeasible(r);
             leg.g = r.g;
             leg.collisionPenalty = r.collision_penalty;
             if (!leg.feasible) continue;             // (only ever the last costed leg)
             e.g = r.g;
             e.collisionPenalty += r.collision_penalty;
             e.coverageCompletedTime = r.coverage_completed_time;
-            e.ribbons.assign(child.data() + at * (size_t)kRibbonStride * 4, std::min((int)((r.info >> 8) & 0xff), kRibbonStride), r.coverage_completed_time);
+            e.ribbons.assign(child.data() + at * (size_t)kRibbonStride * 4, std::min(recChildRibbons(r), kRibbonStride), r.coverage_completed_time);
         }
     }
     return out;
 }
 
-// ------------------------------------------------------------------------------------------------ plan()
-Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
-                                     const DubinsPlan& previousPlan, double timeRemaining) {   // AStarPlanner.cpp:12-132
-    m_PlanEntry = HostProfile::now();
-    m_Config = std::move(config);
-    double endTime = timeRemaining + now();
-    m_EndTime = endTime;
-    m_Config.setStartStateTime(start.time());
-    m_RibbonManager = ribbonManager;
-    m_RibbonManager.changeHeuristicIfTooManyRibbons();
-    if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
+// ------------------------------------------------------------------------------------------------ plan(), step by step
+// nothing of an earlier call is left: statistics, tree, open list, children costed ahead, round trips
+void GpuAStarPlanner::resetSearch() {
     m_Stats = Stats();
-    m_StartStateTime = start.time();
     m_Nodes.clear();
     // the node array the context keeps between cycles (capacity and pages survive; a regrowth that happens all the same — the
     // first cycles of a process — is counted in Stats::Budget)
@@ -1192,157 +1217,131 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
     m_NumSamples = 0;
     m_StrideFloor = 0;
     m_DeadlineStop = false;
-    ppgpu_ctx* h = m_Ctx->handle();
-    uint64_t growthsBefore = 0;
-    double growthSecondsBefore = 0;
-    (void)ppgpu_growth_stats(h, &growthsBefore, &growthSecondsBefore);
-    unsigned long orderFallbacksBefore = 0;
-    for (const auto& ctx : m_Ctxs) orderFallbacksBefore += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
-    uploadWorld(start);
-
-    double minSpeed = m_Config.maxSpeed(), maxSpeed = m_Config.maxSpeed();
-    double magnitude = m_Config.maxSpeed() * m_Config.timeHorizon();
-    const double* mapExtremes = m_Config.map() ? m_Config.map()->extremes() : Map().extremes();
-    double bounds[6];
-    bounds[0] = std::fmax(start.x() - magnitude, mapExtremes[0]);
-    bounds[1] = std::fmin(start.x() + magnitude, mapExtremes[1]);
-    bounds[2] = std::fmax(start.y() - magnitude, mapExtremes[2]);
-    bounds[3] = std::fmin(start.y() + magnitude, mapExtremes[3]);
-    bounds[4] = minSpeed; bounds[5] = maxSpeed;
-    unsigned long seed = (unsigned long)endTime;   // :33
-    {
-        std::vector<double> rib;
-        ribbonsToArray(m_RibbonManager, rib);
-        for (const auto& ctx : m_Ctxs)
-            check(ppgpu_sampler_init(ctx->handle(), bounds, seed, (int32_t)(rib.size() / 4), rib.empty() ? nullptr : rib.data()), "ppgpu_sampler_init");
-    }
-    // root (:35-37)
-    Node root;
-    root.state = start;
-    root.state.speed() = m_Config.maxSpeed();
-    root.g = 0;
-    root.ribbons = m_RibbonManager;
-    root.h = root.ribbons.approximateDistanceUntilDone(root.state.x(), root.state.y(), root.state.heading()) / m_Config.maxSpeed() *
-             kTimePenaltyFactor;   // Vertex::computeApproxToGo (Vertex.cpp:49-64), once per plan, on the host
-    m_Nodes.push_back(root);
-    const int startV = 0;
     m_Best = -1;
-    std::vector<State> brownPathSamples;
-    if (m_Config.useBrownPaths()) brownPathSamples = m_RibbonManager.findNearStatesOnRibbons(start, m_Config.coverageTurningRadius());
+}
 
-    // collision check old plan (:46-59)
+// the devices' running counts that Stats reports per call (read before and after)
+struct GpuAStarPlanner::DeviceCounters { bool haveGrowths = false; uint64_t growths = 0; double growthSeconds = 0; unsigned long orderFallbacks = 0; };
+GpuAStarPlanner::DeviceCounters GpuAStarPlanner::deviceCounters() const {
+    DeviceCounters c;
+    c.haveGrowths = ppgpu_growth_stats(m_Ctx->handle(), &c.growths, &c.growthSeconds) == PPGPU_OK;
+    for (const auto& ctx : m_Ctxs) c.orderFallbacks += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
+    return c;
+}
+
+// the sampling box around the start (AStarPlanner.cpp:27-32): what the vehicle can reach within the horizon, inside the map, at full speed
+static void samplingBox(const PlannerConfig& config, const State& start, double bounds[6]) {
+    const double magnitude = config.maxSpeed() * config.timeHorizon();
+    const double* ext = config.map() ? config.map()->extremes() : Map().extremes();
+    bounds[0] = std::fmax(start.x() - magnitude, ext[0]); bounds[1] = std::fmin(start.x() + magnitude, ext[1]);
+    bounds[2] = std::fmax(start.y() - magnitude, ext[2]); bounds[3] = std::fmin(start.y() + magnitude, ext[3]);
+    bounds[4] = bounds[5] = config.maxSpeed();
+}
+
+// ... and the generator's seed (:33), on every device
+void GpuAStarPlanner::initSampler(const State& start, unsigned long seed) {
+    double bounds[6];
+    samplingBox(m_Config, start, bounds);
+    std::vector<double> rib;
+    ribbonsToArray(m_RibbonManager, rib);
+    for (const auto& ctx : m_Ctxs)
+        check(ppgpu_sampler_init(ctx->handle(), bounds, seed, (int32_t)(rib.size() / 4), rib.empty() ? nullptr : rib.data()), "ppgpu_sampler_init");
+}
+
+// PlannerConfig::chainedPreviousPlan: the given legs of the previous plan are costed by ONE call, every leg from the vertex the leg
+// before left on the device.  The walk then finds their records here instead of making a round trip per leg; it builds the same nodes.
+// -> how many legs the call costed (the one it stopped at included)
+size_t GpuAStarPlanner::costGivenLegs(const WalkedLegs& walked, std::vector<ppgpu_edge_result>& res, std::vector<double>& child) {
+    std::vector<ppgpu_wrapper_edge> legs;
+    walked.appendGiven(legs);
+    if (legs.empty()) return 0;
+    setOpenVertex(m_Nodes[0]);
+    const int32_t offsets[2] = {0, (int32_t)legs.size()};
+    int32_t costed = 0; uint32_t why = 0;
+    res.resize(legs.size());
+    child.assign(legs.size() * (size_t)kRibbonStride * 4, 0.0);
+    check(ppgpu_cost_plans_host(m_Ctx->handle(), 1, offsets, legs.data(), res.data(), child.data(), kRibbonStride, &costed, &why), "ppgpu_cost_plans_host");
+    m_Stats.Budget.PrologueTrips++;
+    return (size_t)costed;
+}
+
+// Edge.cpp:78-80: a curve at a radius the configuration no longer has is re-solved to the wrapper's end state
+void GpuAStarPlanner::reSolveLeg(int source, const DubinsWrapper& p) {
+    State s;
+    s.time() = p.getEndTime();
+    p.sample(s);
+    const size_t q = m_Queue.size();
+    const unsigned long gen = m_Stats.Generated;
+    costStateEdges(source, {s}, {s.speed() == m_Config.maxSpeed() ? 0u : PPGPU_EDGE_SLOW}, {-1});
+    m_Queue.resize(q);   // connect + computeTrueCost only: the reference does not push here
+    std::make_heap(m_Queue.begin(), m_Queue.end(), [](const QEntry& a, const QEntry& b) { return a.f > b.f; });
+    m_Stats.Generated = gen;
+}
+
+// collision check old plan (:46-59): a vertex per walked leg, each from the one before.  -> lastPlanEnd (the root when the plan is
+// empty or its walk met an infeasible leg); `made`: the vertices made from it, for the search dump
+int GpuAStarPlanner::walkPreviousPlan(const DubinsPlan& previousPlan, std::vector<int>& made) {
+    const int startV = 0;
     int lastPlanEnd = startV;
-    std::vector<int> previousPlanNodes;   // the vertices made from it, for the search dump
-    if (!previousPlan.empty()) {
-        const std::vector<DubinsWrapper>& prevLegs = previousPlan.get();
-        auto skipped = [&](const DubinsWrapper& p) { return p.getEndTime() <= start.time() || p.getNetTime() == 0; };   // :49-50
-        // PlannerConfig::chainedPreviousPlan: the legs up to the first one at a radius the configuration no longer has (Edge.cpp:78-80
-        // re-solves that one: not a given curve any more) are costed by ONE call, every leg from the vertex the leg before left on the
-        // device.  The walk below then finds their records here instead of making a round trip per leg; it builds the same nodes.
-        std::vector<long> chainSlot(prevLegs.size(), -1);
-        std::vector<ppgpu_edge_result> chainRes;
-        std::vector<double> chainChild;
-        if (m_Config.chainedPreviousPlan()) {
-            std::vector<ppgpu_wrapper_edge> legs;
-            std::vector<size_t> legOf;
-            for (size_t i = 0; i < prevLegs.size(); i++) {
-                const DubinsWrapper& p = prevLegs[i];
-                if (skipped(p)) continue;
-                const bool cov = p.getRho() == m_Config.coverageTurningRadius();
-                if (p.getRho() != (cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius())) break;
-                legs.push_back(wrapperEdge(p, 0, cov));
-                legOf.push_back(i);
-            }
-            if (!legs.empty()) {
-                setOpenVertex(m_Nodes[startV]);
-                const int32_t offsets[2] = {0, (int32_t)legs.size()};
-                int32_t costed = 0;
-                uint32_t why = 0;
-                chainRes.resize(legs.size());
-                chainChild.assign(legs.size() * (size_t)kRibbonStride * 4, 0.0);
-                check(ppgpu_cost_plans_host(h, 1, offsets, legs.data(), chainRes.data(), chainChild.data(), kRibbonStride, &costed, &why), "ppgpu_cost_plans_host");
-                m_Stats.Budget.PrologueTrips++;
-                for (int k = 0; k < costed; k++) chainSlot[legOf[(size_t)k]] = k;
-            }
+    const WalkedLegs walked(previousPlan, m_StartStateTime, m_Config);
+    std::vector<ppgpu_edge_result> chainRes;
+    std::vector<double> chainChild, ownChild;
+    const size_t chained = m_Config.chainedPreviousPlan() ? costGivenLegs(walked, chainRes, chainChild) : 0;
+    for (size_t k = 0; k < walked.legs.size(); k++) {
+        const WalkedLegs::Leg& leg = walked.legs[k];
+        if (k >= chained) {
+            setOpenVertex(m_Nodes[lastPlanEnd]);
+            m_Stats.Budget.PrologueTrips++;
         }
-        for (size_t legIndex = 0; legIndex < prevLegs.size(); legIndex++) {
-            const DubinsWrapper& p = prevLegs[legIndex];
-            if (skipped(p)) continue;
-            const bool cov = p.getRho() == m_Config.coverageTurningRadius();
-            const double expectRho = cov ? m_Config.coverageTurningRadius() : m_Config.turningRadius();
-            const long slot = chainSlot[legIndex];
-            if (slot < 0) {
-                setOpenVertex(m_Nodes[lastPlanEnd]);
-                m_Stats.Budget.PrologueTrips++;
+        const size_t before = m_Nodes.size();
+        if (leg.foreign) {
+            reSolveLeg(lastPlanEnd, *leg.curve);
+        } else {
+            const unsigned cfgBits = leg.coverage ? PPGPU_EDGE_COVERAGE : 0u;
+            ppgpu_edge_result own;
+            if (k >= chained) {
+                const ppgpu_wrapper_edge we = wrapperEdge(*leg.curve, 0, leg.coverage);
+                ownChild.assign((size_t)kRibbonStride * 4, 0.0);
+                check(ppgpu_cost_wrapper_edges_host(m_Ctx->handle(), 1, &we, &own, ownChild.data(), kRibbonStride), "ppgpu_cost_wrapper_edges_host");
             }
-            const size_t before = m_Nodes.size();
-            if (p.getRho() != expectRho) {
-                // Edge.cpp:78-80: a curve at a radius the configuration no longer has is re-solved to the wrapper's end state
-                State s;
-                s.time() = p.getEndTime();
-                p.sample(s);
-                std::vector<State> t{s};
-                std::vector<unsigned> c{(s.speed() == m_Config.maxSpeed() ? 0u : PPGPU_EDGE_SLOW)};
-                std::vector<long> si{-1};
-                const size_t q = m_Queue.size();
-                const unsigned long gen = m_Stats.Generated;
-                costStateEdges(lastPlanEnd, t, c, si);
-                m_Queue.resize(q);   // connect + computeTrueCost only: the reference does not push here
-                std::make_heap(m_Queue.begin(), m_Queue.end(), [](const QEntry& a, const QEntry& b) { return a.f > b.f; });
-                m_Stats.Generated = gen;
-            } else {
-                const DubinsPath& dp = p.unwrap();
-                ppgpu_edge_result r;
-                std::vector<double> ownChild;
-                const double* child;
-                if (slot >= 0) {
-                    r = chainRes[(size_t)slot];
-                    child = chainChild.data() + (size_t)slot * kRibbonStride * 4;
-                } else {
-                    const ppgpu_wrapper_edge we = wrapperEdge(p, 0, cov);
-                    ownChild.assign((size_t)kRibbonStride * 4, 0.0);
-                    check(ppgpu_cost_wrapper_edges_host(h, 1, &we, &r, ownChild.data(), kRibbonStride), "ppgpu_cost_wrapper_edges_host");
-                    child = ownChild.data();
-                }
-                m_Stats.EdgesCosted++;
-                g_dump.write(m_Nodes[lastPlanEnd].state, r, dp.rho, cov);
-                if (r.flags & PPGPU_F_THROWS) throw std::runtime_error("Invalid time in sample for Dubins path (previous plan)");
-                const int nChild = (int)((r.info >> 8) & 0xff);
-                const bool hostHeuristic = (r.flags & PPGPU_F_RIBBON_OVF) && !(r.flags & PPGPU_F_RIBBON_LOST) && nChild <= kRibbonStride;
-                if ((r.flags & (PPGPU_F_DUBINS_ERR | PPGPU_F_RIBBON_LOST)) || ((r.flags & PPGPU_F_RIBBON_OVF) && !hostHeuristic))
-                    throw std::runtime_error("Edge cost evaluation exceeded a device capacity");
-                Node c;
-                c.parent = lastPlanEnd;
-                c.state = State(r.end_x, r.end_y, r.end_heading, r.end_speed, r.end_time);
-                c.coverageAllowed = cov;
-                c.infeasible = (r.flags & PPGPU_F_INFEASIBLE) != 0;
-                c.collisionPenalty = r.collision_penalty;
-                c.steps = (int)(r.info >> 16);
-                c.g = r.g; c.h = r.h;
-                c.ribbons = m_Nodes[lastPlanEnd].ribbons;
-                c.ribbons.assign(child, nChild, r.coverage_completed_time);
-                if (hostHeuristic) {
-                    c.h = c.ribbons.approximateDistanceUntilDone(c.state.x(), c.state.y(), c.state.heading()) / m_Config.maxSpeed() * kTimePenaltyFactor;
-                    m_Stats.HostHeuristics++;
-                }
-                c.wrapper = p;
-                if (!c.infeasible && r.end_time < c.wrapper.getEndTime()) c.wrapper.updateEndTime(r.end_time);
-                addNode(std::move(c));
-            }
-            if (m_Nodes.size() == before) break;
-            lastPlanEnd = (int)m_Nodes.size() - 1;
-            previousPlanNodes.push_back(lastPlanEnd);
-            m_Stats.PreviousPlanLegs.push_back({m_Nodes[lastPlanEnd].g, m_Nodes[lastPlanEnd].collisionPenalty, m_Nodes[lastPlanEnd].infeasible});
-            if (m_Nodes[lastPlanEnd].infeasible) {
-                lastPlanEnd = startV;
-                break;
-            }
-            if (goalCondition(m_Nodes[lastPlanEnd])) break;
+            const ppgpu_edge_result& r = k < chained ? chainRes[k] : own;
+            m_Stats.EdgesCosted++;
+            g_dump.write(m_Nodes[lastPlanEnd].state, r, cfgBits, m_Config);      // (a given leg's radius is the configuration's)
+            addNode(makeChild(lastPlanEnd, cfgBits, r, k < chained ? chainChild.data() + k * (size_t)kRibbonStride * 4 : ownChild.data(), kRibbonStride, leg.curve));
         }
+        if (m_Nodes.size() == before) break;
+        lastPlanEnd = (int)m_Nodes.size() - 1;
+        made.push_back(lastPlanEnd);
+        m_Stats.PreviousPlanLegs.push_back({m_Nodes[lastPlanEnd].g, m_Nodes[lastPlanEnd].collisionPenalty, m_Nodes[lastPlanEnd].infeasible});
+        if (m_Nodes[lastPlanEnd].infeasible) return startV;
+        if (goalCondition(m_Nodes[lastPlanEnd])) break;
     }
+    return lastPlanEnd;
+}
 
-    // big loop (:61-119)
-    m_Stats.Budget.PrologueMs = 1e3 * (HostProfile::now() - m_PlanEntry);
+// expandToCoverSpecificSamples(startV, brownPathSamples, ..., true) (:150-162): the seeds on nearby ribbons connected from the root at
+// the coverage radius and both speeds.  -> false: the deadline guard did not start it (a device round trip like any other: after the
+// first pass it is not started when it cannot end in time)
+bool GpuAStarPlanner::costBrownPathSeeds(const std::vector<State>& seeds, double tPoll, double endTime) {
+    if (seeds.empty() || !(m_Config.coverageTurningRadius() > 0)) return true;
+    const double predicted = m_Ctx->predictTrip((double)m_NumSamples);
+    if (m_Config.deadlineGuard() && m_Stats.Iterations > 0 && tPoll + predicted >= endTime - m_Ctx->guardMargin()) return false;
+    const double t0 = HostProfile::now();
+    setOpenVertex(m_Nodes[0]);
+    std::vector<State> t;
+    std::vector<unsigned> c;
+    for (const State& s : seeds) {
+        t.push_back(s); c.push_back(PPGPU_EDGE_COVERAGE);
+        t.push_back(s); c.push_back(PPGPU_EDGE_COVERAGE | PPGPU_EDGE_SLOW);
+    }
+    costStateEdges(0, t, c, std::vector<long>(t.size(), -1));
+    noteOperation(3, t0, m_Stats.Iterations > 0 ? predicted : 0.0, HostProfile::now() - t0);
+    return true;
+}
+
+// big loop (:61-119): the anytime search, an A* pass over a sample set that doubles every iteration, until the clock says stop
+void GpuAStarPlanner::anytimeLoop(double endTime, int lastPlanEnd, const std::vector<int>& previousPlanNodes, const std::vector<State>& brownPathSamples) {
+    const int startV = 0;
     const bool guard = m_Config.deadlineGuard();
     double tPoll;
     while ((tPoll = now()) < (guard ? endTime - kHostMargin : endTime)) {
@@ -1364,25 +1363,9 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
         }
         pushVertexQueue(startV);
         if (lastPlanEnd != startV) pushVertexQueue(lastPlanEnd);
-        // expandToCoverSpecificSamples(startV, brownPathSamples, ..., true) (:150-162)
-        if (!brownPathSamples.empty() && m_Config.coverageTurningRadius() > 0) {
-            // (a device round trip like any other: after the first pass it is not started when it cannot end in time)
-            const double brownPredicted = m_Ctx->predictTrip((double)m_NumSamples);
-            if (guard && m_Stats.Iterations > 0 && tPoll + brownPredicted >= endTime - m_Ctx->guardMargin()) {
-                m_Stats.DeadlineStops++;
-                break;
-            }
-            const double brown0 = HostProfile::now();
-            setOpenVertex(m_Nodes[startV]);
-            std::vector<State> t;
-            std::vector<unsigned> c;
-            std::vector<long> si;
-            for (const State& s : brownPathSamples) {
-                t.push_back(s); c.push_back(PPGPU_EDGE_COVERAGE); si.push_back(-1);
-                t.push_back(s); c.push_back(PPGPU_EDGE_COVERAGE | PPGPU_EDGE_SLOW); si.push_back(-1);
-            }
-            costStateEdges(startV, t, c, si);
-            noteOperation(3, brown0, m_Stats.Iterations > 0 ? brownPredicted : 0.0, HostProfile::now() - brown0);
+        if (!costBrownPathSeeds(brownPathSamples, tPoll, endTime)) {
+            m_Stats.DeadlineStops++;
+            break;
         }
         // first iteration: initialSamples; afterwards double them (:101-102)
         const long moreSamples = m_NumSamples < m_Config.initialSamples() ? m_Config.initialSamples() : m_NumSamples;
@@ -1410,29 +1393,52 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
         if (m_DeadlineStop) break;
     }
     drainInFlight();                           // nothing of this planner runs on a context once plan() has returned
-    m_Stats.Budget.LoopEndMs = 1e3 * (HostProfile::now() - m_PlanEntry);
-    m_Stats.Budget.MarginMs = guard ? 1e3 * m_Ctx->guardMargin() : 0.0;
+}
+
+// the incumbent as Stats reports it (:121-131), with its step traces when the configuration asks for them
+void GpuAStarPlanner::reportPlan() {
     m_Stats.Samples = (unsigned long)m_NumSamples;
     if (m_Best < 0) {
         *m_Config.output() << "Failed to find a plan" << std::endl;
-    } else {
-        m_Stats.PlanFValue = m_Nodes[m_Best].f();
-        m_Stats.PlanDepth = (unsigned long)depth(m_Best);
-        m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
-        m_Stats.PlanHValue = m_Nodes[m_Best].h;
-        m_Stats.Plan = tracePlan(m_Best);
-        if (m_Config.planTrace() || m_Config.planCoverage()) tracePlanSteps(m_Best);
+        return;
     }
-    for (const auto& ctx : m_Ctxs) m_Stats.OrderFallbacks += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
-    m_Stats.OrderFallbacks -= orderFallbacksBefore;
+    m_Stats.PlanFValue = m_Nodes[m_Best].f();
+    m_Stats.PlanDepth = (unsigned long)branch(m_Best).size();
+    m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
+    m_Stats.PlanHValue = m_Nodes[m_Best].h;
+    m_Stats.Plan = tracePlan(m_Best);
+    if (m_Config.planTrace() || m_Config.planCoverage()) tracePlanSteps(m_Best);
+}
+
+Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,
+                                     const DubinsPlan& previousPlan, double timeRemaining) {   // AStarPlanner.cpp:12-132
+    m_PlanEntry = HostProfile::now();
+    m_Config = std::move(config);
+    const double endTime = timeRemaining + now();
+    m_EndTime = endTime;
+    resetSearch();
+    const DeviceCounters before = deviceCounters();
+    // begin: the root (:35-37), its h from Vertex::computeApproxToGo (Vertex.cpp:49-64), once per plan, on the host
+    Node root = beginCall(ribbonManager, start);
+    root.h = root.ribbons.approximateDistanceUntilDone(root.state.x(), root.state.y(), root.state.heading()) / m_Config.maxSpeed() * kTimePenaltyFactor;
+    m_Nodes.push_back(std::move(root));
+    initSampler(start, (unsigned long)endTime);   // :27-33
+    std::vector<State> brownPathSamples;
+    if (m_Config.useBrownPaths()) brownPathSamples = m_RibbonManager.findNearStatesOnRibbons(start, m_Config.coverageTurningRadius());
+    std::vector<int> previousPlanNodes;
+    const int lastPlanEnd = walkPreviousPlan(previousPlan, previousPlanNodes);
+    m_Stats.Budget.PrologueMs = 1e3 * (HostProfile::now() - m_PlanEntry);
+    anytimeLoop(endTime, lastPlanEnd, previousPlanNodes, brownPathSamples);
+    m_Stats.Budget.LoopEndMs = 1e3 * (HostProfile::now() - m_PlanEntry);
+    m_Stats.Budget.MarginMs = m_Config.deadlineGuard() ? 1e3 * m_Ctx->guardMargin() : 0.0;
+    reportPlan();
+    // statistics: what the devices counted during this call
+    const DeviceCounters after = deviceCounters();
+    m_Stats.OrderFallbacks = after.orderFallbacks - before.orderFallbacks;
     g_prof.report("plan()");
-    {
-        uint64_t growths = 0;
-        double growthSeconds = 0;
-        if (ppgpu_growth_stats(h, &growths, &growthSeconds) == PPGPU_OK) {
-            m_Stats.Budget.DeviceGrowths = (unsigned long)(growths - growthsBefore);
-            m_Stats.Budget.DeviceGrowthMs = 1e3 * (growthSeconds - growthSecondsBefore);
-        }
+    if (after.haveGrowths) {
+        m_Stats.Budget.DeviceGrowths = (unsigned long)(after.growths - before.growths);
+        m_Stats.Budget.DeviceGrowthMs = 1e3 * (after.growthSeconds - before.growthSeconds);
     }
     m_Stats.Budget.TotalMs = 1e3 * (HostProfile::now() - m_PlanEntry);
     return m_Stats;
@@ -1490,11 +1496,10 @@ ShardedIteration::Result ShardedIteration::run(const RibbonManager& ribbonManage
     rm.changeHeuristicIfTooManyRibbons();                                  // AStarPlanner.cpp:18
     uploadSnapshot(m_Ctxs, config, rm, start.time());
     // the sampling box and the root vertex of AStarPlanner::plan (:27-37)
-    const double magnitude = config.maxSpeed() * config.timeHorizon();
-    const double* ext = config.map() ? config.map()->extremes() : Map().extremes();
-    const double bounds[6] = {std::fmax(start.x() - magnitude, ext[0]), std::fmin(start.x() + magnitude, ext[1]), std::fmax(start.y() - magnitude, ext[2]),
-                              std::fmin(start.y() + magnitude, ext[3]), config.maxSpeed(), config.maxSpeed()};
-    std::vector<double> rib(rm.rows(), rm.rows() + 4 * (size_t)rm.count());
+    double bounds[6];
+    samplingBox(config, start, bounds);
+    std::vector<double> rib;
+    ribbonsToArray(rm, rib);
     ppgpu_vertex root{};
     root.x = start.x(); root.y = start.y(); root.heading = start.heading(); root.speed = config.maxSpeed(); root.time = start.time();
     root.g = 0; root.coverage_completed_time = rm.done() ? start.time() : rm.coverageCompletedTime();
@@ -1505,7 +1510,6 @@ ShardedIteration::Result ShardedIteration::run(const RibbonManager& ribbonManage
     Result out;
     out.kept.assign(D, 0);
     std::vector<uint64_t> keys(2 * D, ~0ull);
-    auto check = [](int rc, const char* what) { if (rc != PPGPU_OK) throw std::runtime_error(std::string(what) + ": " + ppgpu_last_error()); };
     // Phase 1, per shard, no collective in it: skip, draw, cost, reduce to the shard's best key (left on the device).
     auto local = [&](size_t d) {
         ppgpu_ctx* h = m_Ctxs[d]->handle();

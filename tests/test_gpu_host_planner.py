@@ -167,6 +167,69 @@ def test_host_planner_matches_oracle_plan(name, init, calls, prepass_route):
             _compare(host2, st2, plan2)
 
 
+@pytest.mark.parametrize("name,init,calls,radius,old_leg_first", [("cfg1", 64, 60, 6.0, True), ("cfg2", 256, 40, 7.0, False)])
+def test_previous_plan_leg_at_an_old_radius_is_re_solved(name, init, calls, radius, old_leg_first):
+    """The replan cycle of test_host_planner_matches_oracle_plan after PlannerConfig::turningRadius changed (the coverage radius did
+    not): a previous-plan leg at the old turning radius is not a given curve any more, Edge.cpp:78-80 solves a new one at the new
+    radius to the leg's end state.  cfg1's plan is (turning, coverage): the walk's first leg is the re-solved one and the chained
+    call has nothing before it to cost.  cfg2's is (coverage, turning): the chained call costs the first leg and the walk re-solves
+    the second in the same prologue.  With PlannerConfig::chainedPreviousPlan off and on: the same plan, counters, previous-plan
+    vertices and search dump (the assertions of test_chained_prologue_changes_nothing_but_the_round_trips), and the oracle's
+    replan under the same configuration.  Radii chosen with the oracle alone: its replan returns a plan at each."""
+    import math
+    import oracle as orc
+    from path_planner_amd import workloads
+    w = workloads.by_name(name)
+    orc.O.ppo_set_ribbon_width(w.cfg.ribbon_width)
+    world = orc.World(w.cfg, w.grid, w.res, w.obst)
+    t0, dt = 1000.0, 1e-3
+    with tempfile.TemporaryDirectory() as d:
+        mp = os.path.join(d, "grid.map")
+        _write_map(w.grid, w.res, mp)
+        sc = os.path.join(d, "s.txt")
+        _scenario(w, sc, mp, t0, dt, calls, init)
+        host = _run_cli(sc)
+        rc, st, plan, _, _ = world.plan(w.ribbons4, w.start5, calls * dt, t0, dt, initial_samples=init)
+        assert rc == 0
+        _compare(host, st, plan)
+        old = w.cfg.turning_radius
+        assert radius != old and w.cfg.coverage_turning_radius != old
+        seg = plan[0]
+        e, q = orc.dubins_sample(seg[:8], min(1.0 * seg[8], (seg[10] - seg[9]) * seg[8]))
+        assert e == 0
+        hdg = math.pi / 2 - q[2]
+        if hdg < 0:
+            hdg += 2 * math.pi
+        start2 = np.array([q[0], q[1], hdg, seg[8], seg[9] + 1.0])
+        walked = [p for p in plan if p[10] > start2[4] and p[10] > p[9]]
+        assert any(p[6] == old for p in walked)                       # a leg at the old turning radius is still ahead
+        assert (walked[0][6] == old) == old_leg_first                 # ... first (cfg1) or behind a coverage leg (cfg2)
+        w.cfg.turning_radius = radius                                 # scenario file and oracle alike
+        w.cfg.start_state_time = float(start2[4])
+        world.set_config(w.cfg)
+        runs = {}
+        for on in (0, 1):
+            sc2 = os.path.join(d, "replan%d.txt" % on)
+            dump = os.path.join(d, "dump%d.txt" % on)
+            _scenario(w, sc2, mp, t0 + 1.0, dt, calls, init, prev=plan, start=start2)
+            with open(sc2, "a") as f:
+                f.write("cfg chained_previous_plan %d\nvisualization_file %s\n" % (on, dump))
+            runs[on] = (_run_cli(sc2), open(dump, "rb").read())
+        (off, dump_off), (on, dump_on) = runs[0], runs[1]
+        print(name, {k: off[k] for k in off if k != "plan"}, "| on:", on["round_trips"], on["prologue_trips"])
+        assert "exception" not in off and "exception" not in on
+        assert on["plan"] == off["plan"] and len(on["plan"]) >= 1
+        for k in ("samples", "expanded", "generated", "iterations", "edges_costed", "first_goal_iteration", "plan_depth", "plan_f", "plan_h",
+                  "plan_collision_penalty", "plan_time_penalty", "host_heuristics", "previous_plan_legs"):
+            assert on[k] == off[k], k
+        assert dump_on == dump_off and len(dump_off) > 0
+        assert len(off["previous_plan_legs"]) >= 1
+        rc2, st2, plan2, _, _ = world.plan(w.ribbons4, start2, calls * dt, t0 + 1.0, dt, initial_samples=init, prev11=plan)
+        assert rc2 == 0 and len(plan2) >= 1
+        _compare(on, st2, plan2)
+        _compare(off, st2, plan2)
+
+
 def test_host_planner_with_gaussian_obstacles():
     """The same plan() through GaussianDynamicObstaclesManager (unordered_map of mmsi -> obstacle on the host, uploaded with
     ppgpu_set_gaussian_obstacles): collision penalties are sums of densities, so a plan that passes near an obstacle
