@@ -471,6 +471,28 @@ __device__ __forceinline__ bool pp_is_blocked(const PPGrid& g, double x, double 
     uint32_t w = g.bits[(size_t)r * g.wpr + (c >> 5)];
     return (w >> (c & 31)) & 1u;
 }
+// pp_is_blocked in two halves, for a caller that wants the words of several chunks on their way before it looks at any of them:
+// the same arithmetic up to the cell, then the load alone (a lane outside the grid reads word 0, which it does not use), then the test.
+struct PPCellRef { size_t word; unsigned col; bool outside; };
+__device__ __forceinline__ PPCellRef pp_blocked_cell(const PPGrid& g, double x, double y) {
+    const double cx = x * g.inv_res, cy = y * g.inv_res;
+    const unsigned cxl = (unsigned)(cx * (1.0 - 4e-9)), cxh = (unsigned)(cx * (1.0 + 4e-9));
+    const unsigned cyl = (unsigned)(cy * (1.0 - 4e-9)), cyh = (unsigned)(cy * (1.0 + 4e-9));
+    unsigned r = cyl, c = cxl;
+    bool outside = (x < 0) | (cxl >= (unsigned)g.cols) | (y < 0) | (cyl >= (unsigned)g.rows);
+    if (__ballot((cxl != cxh) | (cyl != cyh)) != 0ull) {
+        const double qx = x / g.res, qy = y / g.res;                  // GridWorldMap.cpp:85-88, literally
+        outside = (x < 0) | (qx >= (double)g.cols) | (y < 0) | (qy >= (double)g.rows);
+        r = (unsigned)qy;
+        c = (unsigned)qx;
+    }
+    PPCellRef ref;
+    ref.word = outside ? (size_t)0 : (size_t)r * g.wpr + (c >> 5);
+    ref.col = c;
+    ref.outside = outside;
+    return ref;
+}
+__device__ __forceinline__ bool pp_blocked_test(const PPCellRef& ref, uint32_t w) { return ref.outside | (((w >> (ref.col & 31)) & 1u) != 0u); }
 // (BASELINE's north_star asks for the occupancy grid "tiled into LDS".  Built and measured in round 3 — the wave copies the words under
 // its 64 cells into an LDS tile, every lane reads its word there, commit c47d58f — parity green, pose sweep 496 -> 606 us: the whole
 // 2048 x 2048 bit grid is 512 KiB and lives in every XCD's 4 MiB L2, so the direct lookup above stays.  DESIGN.md Appendix B.)
@@ -486,6 +508,15 @@ struct PPObst { double X, Y, cosYaw, sinYaw, Speed, Time, halfL, halfW, reach, p
 // the pdf is below 1e-13.  Same size and leading fields as PPObst so the culling code is shared.
 struct PPGauss { double X, Y, cosYaw, sinYaw, Speed, Time, i00, i01, reach, i10, i11, norm; };
 
+// Row j (wave-uniform) of the obstacle table, which the host wrote before the launch, through scalar loads whatever the kernel stores
+// elsewhere: what pp_obstacle_hit reads of it.
+__device__ __forceinline__ PPObst pp_obst_load_uniform(const PPObst* o) {
+    const PP_AS4 double* d = pp_const_f64(o);
+    PPObst r;
+    r.X = d[0]; r.Y = d[1]; r.cosYaw = d[2]; r.sinYaw = d[3]; r.Speed = d[4]; r.Time = d[5]; r.halfL = d[6]; r.halfW = d[7]; r.reach = d[8];
+    r.pad[0] = r.pad[1] = r.pad[2] = 0.0;
+    return r;
+}
 // One obstacle's contribution to BinaryDynamicObstaclesManager::collisionExists(x, y, t, strict=true)
 // (.cpp:4-22): project to t, translate, rotate by +Yaw, strict box test.
 __device__ __forceinline__ int pp_obstacle_hit(const PPObst& o, double x, double y, double t) {

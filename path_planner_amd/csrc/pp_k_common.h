@@ -70,9 +70,11 @@ struct PPEdgeSetupBody {
     unsigned long long omask;              // bit j: obstacle j can come near this edge at all (all ones with more than 64 obstacles)
     int type;                              // DubinsPathType, -1 = no path
     unsigned vi, cbits, sflags;
+    double srcH;                           // the source vertex's heading (`lastHeading` starts there, Edge.cpp:96): the sweep and the skip
+                                           // planner take it from here instead of waiting for vi and then for verts[vi]
 };
 struct __attribute__((aligned(128))) PPEdgeSetup : PPEdgeSetupBody {};
-static_assert(sizeof(PPEdgeSetup) == 256 && sizeof(PPEdgeSetupBody) == 248, "PPEdgeSetup is sized for two 128-byte lines");
+static_assert(sizeof(PPEdgeSetup) == 256 && sizeof(PPEdgeSetupBody) == 256, "PPEdgeSetup is sized for two 128-byte lines");
 // this lane's pose on segment i of a record (dubins_path_sample on that segment, un-normalised yaw): the lane-per-edge kernels
 // (p0, p1, word: the record's own, which a caller that samples several poses keeps in registers — per pose only the 40-byte base
 // is then read, and the three bases share the record's first 128-byte line)
@@ -87,11 +89,11 @@ __device__ __forceinline__ void pp_setup_seg_pose(const PPEdgeSetupBody* S, int 
 }
 // The lane-per-edge prepasses read a record per LANE.  Straight from memory that is one 64-line gather per field; they stage the
 // records of their workgroup in LDS instead (contiguous, coalesced 8-byte-per-lane loads) and read the fields from there.  The
-// LDS copy holds the 31 doubles that carry data, at a stride of 31: odd in 8-byte units, so lanes reading one field of
+// LDS copy holds the record's 32 doubles at a stride of 33: odd in 8-byte units, so lanes reading one field of
 // consecutive records fall on different banks.
 #define PP_SETUP_GLOBAL_WORDS 32
-#define PP_SETUP_WORDS 31
-#define PP_SETUP_LDS_STRIDE 31
+#define PP_SETUP_WORDS 32
+#define PP_SETUP_LDS_STRIDE 33
 static_assert(sizeof(PPEdgeSetup) == 8 * PP_SETUP_GLOBAL_WORDS && sizeof(PPEdgeSetupBody) == 8 * PP_SETUP_WORDS, "the LDS staging of the skip planner copies whole records");
 
 // ------------------------------------------------------------------------------------------

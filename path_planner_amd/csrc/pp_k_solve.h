@@ -42,6 +42,7 @@ __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPPa
     bool valid = false;
     unsigned sflags = 0;
     double srcT = 0, wSpeed = 1, wStart = 0, wEnd = 0;        // (w*: of a given curve)
+    double srcHeading = 0;
     PPDubins dub;
     dub.p0 = dub.p1 = dub.p2 = 0; dub.type = -1;
     if (vi >= (unsigned)p.nverts || (!p.wedges && (long long)target >= p.n_samples)) {
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPPa
         const ppgpu_vertex* V = p.verts + vi;
         const double srcX = V->x, srcY = V->y, srcH = V->heading;
         srcT = V->time;
+        srcHeading = srcH;
         valid = true;
         double rho = (cbits & PPGPU_EDGE_COVERAGE) ? p.rho_cov : p.rho;             // Edge.cpp:73-76
         if (p.wedges) {
@@ -98,6 +100,7 @@ __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPPa
         O->p0 = cv.p0; O->p1 = cv.p1; O->p2 = cv.p2; O->hi1 = cv.p0 + cv.p1;
         O->approx = S.approx; O->wStart = S.wStart; O->wEnd = S.wEnd; O->speed = S.speed;
         O->type = S.type; O->vi = S.vi; O->cbits = S.cbits; O->sflags = S.sflags;
+        O->srcH = srcHeading;                                           // the record's spare word: the sweep's first `lastHeading`
         // Which obstacles can come near this edge at all?  Every sampled pose lies within `travel` (arc length) of the curve's first
         // point and an obstacle moves at most |Speed| * duration during the sweep.  pp_k_plan_skips only looks at these, and
         // the pose sweep leaves the obstacles alone on an edge that has none.  Bit j = obstacle j, all ones when there are more than 64.

@@ -139,7 +139,7 @@ __device__ __forceinline__ bool pp_chunk_clear_of(const PPObst& o, double x, dou
 #define PP_SKIP_GRID 2    // sampled, but no pose of it can lie on a blocked cell
 #define PP_SKIP_OBST 4    // sampled, but no pose of it can lie inside an obstacle
 #define PP_SKIP_HITS 8    // with PP_SKIP_ALL: every pose of the chunk lies inside some obstacle box (the chunk's hit count is not zero)
-#define PP_PLAN_EDGES_MAX 32          // edges a workgroup of the skip planner stages at most (12.3 KB of LDS)
+#define PP_PLAN_EDGES_MAX 32          // edges a workgroup of the skip planner stages at most (14 KB of LDS)
 template <bool GAUSSIAN, bool OBST_LDS>
 __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPEdgeSetupBody* S, const PPObst* OB, const long long e, const int chunk) {
     {
@@ -186,7 +186,7 @@ __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPE
             const int gtype = pp_word_seg_type(S->type, segF);
             const double tt = (tpF - pp_seg_o1(segF, S->p0)) - pp_seg_o2(segF, S->p1);
             const double uth0 = (gtype == 1) ? (0.0 + g->bth) : ((gtype == 0) ? (tt + g->bth) : (-tt + g->bth));
-            const bool same0 = pp_heading_from_yaw(pp_mod2pi(uth0)) == p.verts[S->vi].heading;
+            const bool same0 = pp_heading_from_yaw(pp_mod2pi(uth0)) == S->srcH;
             eqWord = (eqWord & ~1ull) | (same0 ? 1ull : 0ull);
         }
     }
@@ -323,23 +323,60 @@ __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p,
 
 // e = the edge's slot in the workspace.  GAUSSIAN: the dynamic obstacles are GaussianDynamicObstaclesManager's (its own
 // instantiation: exp() and the density bookkeeping would otherwise cost the common kernel registers).
-template <bool GAUSSIAN>
+//
+// The wave is short (some 760 VALU instructions) and spent seven eighths of its life waiting on a chain of dependent loads: record,
+// then vertex and time row, then the obstacle row of the lane, then per sampled chunk the times, the grid words, the obstacle rows
+// and the branch on `stop`.  So the loads are issued in as few rounds as the data dependences allow:
+//   * at wave start everything whose address follows from the work item alone: the record, the skip bytes, the lane's obstacle row
+//     (the source heading travels in the record: pp_k_solve_edges);
+//   * the loop steps through the set bits of "not skipped" instead of 64 trips with `continue`, G chunks at a time: their times (and
+//     `carry` words) together, their poses, then their grid words together;
+//   * the chunks of a batch are then resolved one after the other with exactly the sequential code: a chunk that stops the sweep
+//     discards the later ones of its batch, which have stored nothing and changed nothing the sweep keeps (dubErr is per chunk).
+// G = 1 is the same walk with one chunk at a time, and what pp_k_pose_sweep is built with: at config 3 a second chunk in flight
+// measured slower.  pp_k_pose_sweep_single is always G = 1 (PPGPU_POSE_CHUNKS=1: a test demands the same bytes
+// from both, whatever PP_POSE_CHUNKS the library was built with).
+template <bool GAUSSIAN, int G>
 __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long long e) {
     const int lane = pp_lane();
     const PPEdgeSetup* S = p.setup + e;
     PPTrackSummary* sum = p.track_summary + e;
+    // ---- the loads that need nothing but the work item, before the first wait
+    // Chunks of 64 steps that provably touch neither a blocked cell nor an obstacle are not sampled at all (pp_k_plan_skips decided
+    // which, one thread per chunk); the others go through the per-step code below, one step per lane.
+    const unsigned char* skipb = p.track_skip ? p.track_skip + (size_t)e * p.nch : nullptr;
+    unsigned sbits = (skipb && lane < p.nch) ? (unsigned)skipb[lane] : 0u;     // the skip bytes of the first 64 chunks
+    // Up to 64 obstacles: lane i answers for obstacle i's motion during the whole sweep (position at the first step's time, velocity,
+    // squared culling radius), so the per-chunk culling below is a dozen instructions and no trip to memory.  The bound is the one
+    // pp_obstacle_hits_chunk uses (reach + chunk span + |Speed| * chunk time + slack); it only has to be conservative.
+    const bool laneCull = p.n_obst <= PP_WAVE;
+    PPObst ol;
+    if (laneCull && p.ng > 0 && p.n_obst > 0) {
+        // (every lane loads a row, the lanes past the table its last one: no lane masking around the loads)
+        const PPObst* o = p.obst + (lane < p.n_obst ? lane : p.n_obst - 1);
+        ol.X = o->X; ol.Y = o->Y; ol.cosYaw = o->cosYaw; ol.sinYaw = o->sinYaw; ol.Speed = o->Speed; ol.Time = o->Time; ol.reach = o->reach;
+    }
+    // the whole record in one round: the fields are asked for together and pinned here, ahead of the test of its flags, or the
+    // compiler moves each load down to the branch that first needs it and the wave makes four trips to the record's four lines
     const unsigned sflags = (unsigned)PP_SI32(sflags);
     const int dubType = PP_SI32(type);
+    const unsigned vi = (unsigned)PP_SI32(vi);
+    const unsigned cbitsW = (unsigned)PP_SI32(cbits);
+    const double srcH = PP_SF64(srcH);
+    const PPCurveHot hot = pp_curve_hot(S);
+    const double wEnd = PP_SF64(wEnd), wStart = hot.wStart, speed = hot.speed;
+    const unsigned long long omask = pp_const_u64(&S->omask)[0];
+    // the segment of the curve the sweep is on: its constants live in scalar registers, the other two stay in memory
+    int cur = 0;
+    PPSeg cs = pp_seg_load_uniform(&S->seg[0], 0, PP_SF64(p0), PP_SF64(p1), PP_SF64(hi1), dubType);
+    asm volatile("" :: "s"(sflags), "s"(dubType), "s"(vi), "s"(cbitsW), "s"(srcH), "s"(hot.wStart), "s"(hot.speed), "s"(hot.length), "s"(hot.rho),
+                 "s"(hot.rho_inv), "s"(hot.qx), "s"(hot.qy), "s"(wEnd), "s"(omask), "s"(cs.bx), "s"(cs.by), "s"(cs.bth), "s"(cs.sb), "s"(cs.cb),
+                 "s"(cs.hi));
+    const bool cov = (cbitsW & PPGPU_EDGE_COVERAGE) != 0;
     if ((sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || dubType < 0) {
         if (lane == 0) { sum->limit = 0; sum->blocked = 0; sum->dub_err = 0; sum->pad = 0; }
         return;
     }
-    const unsigned vi = (unsigned)PP_SI32(vi);
-    const bool cov = (((unsigned)PP_SI32(cbits)) & PPGPU_EDGE_COVERAGE) != 0;
-    const ppgpu_vertex* V = p.verts + vi;
-    const double srcH = pp_sgpr(V->heading);
-    const PPCurveHot hot = pp_curve_hot(S);
-    const double wEnd = PP_SF64(wEnd), wStart = hot.wStart, speed = hot.speed;
     const double endTime = fmin(p.horizon + 1e-12 + p.sst, wEnd);    // Edge.cpp:90 (the cover sweep may end the edge earlier)
     const double* tg = p.tgrid + (size_t)vi * p.ng;
     if (p.wedges && p.ng > 0) {
@@ -351,10 +388,6 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
             return;
         }
     }
-    // the segment of the curve the sweep is on: its constants live in scalar registers, the other two stay in memory
-    int cur = 0;
-    PPSeg cs = pp_seg_load_uniform(&S->seg[0], 0, PP_SF64(p0), PP_SF64(p1), PP_SF64(hi1), PP_SI32(type));
-
     unsigned short* thits = p.track_hits + (size_t)e * p.ngp;
     unsigned long long* teq = p.track_eq + (size_t)e * p.nch;
     unsigned* tch = p.track_chunk_hits + (size_t)e * p.nch;
@@ -363,102 +396,150 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
     const double chunkTime = 64.0 * (p.inc_d / p.max_speed);
     const double chunkSpan = 64.0 * (p.inc_d / p.max_speed) * speed;
     double carryHeading = srcH;                                       // `lastHeading`, Edge.cpp:96
-    bool dubErr = false;
+    int anyErr = 0;
     int limit = 0, blocked = 0;
     // Can any obstacle come near this edge at all?  Every sampled pose lies within `travel` (arc length from the start of
     // the curve) of the curve's first point, and an obstacle moves at most |Speed| * duration during the sweep: the same
     // kind of exact bound as the per-chunk culling, applied once — by pp_k_solve_edges, which left the obstacles that pass it in the
     // record's omask (all ones with more than 64 obstacles: then the per-chunk culling alone decides, which is as exact).
-    bool anyObstacle = false;
-    // Up to 64 obstacles: lane i keeps obstacle i's motion for the whole sweep (position at the first step's time, velocity,
-    // squared culling radius), so the per-chunk culling below is a dozen instructions and no loads.  The bound is the one
-    // pp_obstacle_hits_chunk uses (reach + chunk span + |Speed| * chunk time + slack); it only has to be conservative.
-    const bool laneCull = p.n_obst <= PP_WAVE;
-    double oX0 = 0, oY0 = 0, oVx = 0, oVy = 0, oR2 = -1.0, cullT0 = 0;
-    if (p.n_obst > 0 && p.ng > 0) anyObstacle = pp_const_u64(&S->omask)[0] != 0ull;
+    const bool anyObstacle = (p.n_obst > 0 && p.ng > 0) ? (omask != 0ull) : false;
+    const double* carry = reinterpret_cast<const double*>(p.track_eq + (size_t)e * p.nch);   // (a chunk's word before the sweep gets to it)
+    // the group of 64 chunks the walk is in: which are skipped, which are left to sample (todo), the planner's partial answers
+    int g0 = -PP_WAVE;
+    unsigned long long skips = 0ull, todo = 0ull, gclear = 0ull, oclear = 0ull;
+    bool lastSkipped = false;                                         // the last chunk of the group before was skipped
+    // the next G chunks to sample: their times and, after a skipped chunk, the planner's `lastHeading`
+    int ci[G];
+    double t[G], carryW[G];
+    bool have[G], after[G];
+    auto next_batch = [&]() {
+        while (todo == 0ull) {
+            lastSkipped = (g0 >= 0) && ((skips >> 63) & 1ull) != 0ull;
+            g0 += PP_WAVE;
+            if (g0 > 0) sbits = (skipb && g0 + lane < p.nch) ? (unsigned)skipb[g0 + lane] : 0u;   // (edges of more than 64 chunks; the first group's bytes came with the record)
+            skips = __ballot((sbits & PP_SKIP_ALL) != 0u);
+            gclear = __ballot((sbits & PP_SKIP_GRID) != 0u);
+            oclear = anyObstacle ? __ballot((sbits & PP_SKIP_OBST) != 0u) : ~0ull;   // (no obstacle near the edge: as good as none near any chunk)
+            todo = ~skips;                                            // (chunks past the row's end count as sampled: the walk ends at the first of them)
+        }
+#pragma unroll
+        for (int i = 0; i < G; i++) {
+            have[i] = i == 0 || todo != 0ull;                         // (the first always exists: the walk above ended on a group with chunks to sample)
+            ci[i] = have[i] ? (__ffsll((long long)todo) - 1) : 0;
+            if (have[i]) todo &= todo - 1ull;
+            after[i] = have[i] && (ci[i] > 0 ? (((skips >> (ci[i] - 1)) & 1ull) != 0ull) : lastSkipped);
+            const int k = (g0 + ci[i]) * PP_WAVE + lane;
+            t[i] = (have[i] && k < p.ng) ? tg[k] : INFINITY;
+            carryW[i] = 0.0;
+            if (!cov && after[i] && g0 + ci[i] < p.nch) carryW[i] = pp_const_f64(carry + (g0 + ci[i]))[0];
+        }
+    };
+    next_batch();                                                     // (the first batch's times travel while the obstacle lanes are set up)
+    // The five doubles a lane keeps about its obstacle are read once per sampled chunk, by the culling alone: they wait in LDS, not
+    // in ten registers the pose arithmetic in between needs (at 6 waves per SIMD the kernel has 80; kept in registers, one of the
+    // five went to scratch and came back from memory in every chunk).  A wave reads only what it wrote itself.
+    __shared__ double s_cull[PP_WPB * 5 * PP_WAVE];
+    double* cullL = s_cull + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (5 * PP_WAVE) + lane;
+    double cullT0 = 0;                                                // (wave-uniform: the row's first time)
     if (anyObstacle && laneCull) {
         const double t0 = pp_const_f64(tg)[0];
+        cullT0 = t0;
+        double oX0 = 0, oY0 = 0, oVx = 0, oVy = 0, oR2 = -1.0;
         if (lane < p.n_obst) {
-            cullT0 = t0;
-            const PPObst o = p.obst[lane];
+            const PPObst& o = ol;
             const double dt = t0 - o.Time;
             oX0 = o.X + o.Speed * dt * o.cosYaw; oY0 = o.Y + o.Speed * dt * o.sinYaw;
             oVx = o.Speed * o.cosYaw; oVy = o.Speed * o.sinYaw;
             const double Rc = o.reach + chunkSpan + fabs(o.Speed) * chunkTime + 2e-3;
             oR2 = Rc * Rc;
         }
+        cullL[0 * PP_WAVE] = oX0; cullL[1 * PP_WAVE] = oY0; cullL[2 * PP_WAVE] = oVx; cullL[3 * PP_WAVE] = oVy; cullL[4 * PP_WAVE] = oR2;
+        pp_wave_lds_fence();
     }
-
-    // Chunks of 64 steps that provably touch neither a blocked cell nor an obstacle are not sampled at all (pp_k_plan_skips decided
-    // which, one thread per chunk); the others go through the per-step code below, one step per lane.
-    const unsigned char* skipb = p.track_skip ? p.track_skip + (size_t)e * p.nch : nullptr;
-    const double* carry = reinterpret_cast<const double*>(p.track_eq + (size_t)e * p.nch);   // (a chunk's word before the sweep gets to it)
-    bool afterSkip = false, stop = false;
-    for (int g0 = 0; !stop; g0 += PP_WAVE) {
-        const unsigned sbits = (skipb && g0 + lane < p.nch) ? (unsigned)skipb[g0 + lane] : 0u;
-        const unsigned long long skips = __ballot((sbits & PP_SKIP_ALL) != 0u);
-        const unsigned long long gclear = __ballot((sbits & PP_SKIP_GRID) != 0u), oclear = anyObstacle ? __ballot((sbits & PP_SKIP_OBST) != 0u) : ~0ull;   // (no obstacle near the edge: as good as none near any chunk)
-        int ci = 0;
-        for (; ci < PP_WAVE; ci++) {
-            const int base = (g0 + ci) * PP_WAVE;
-#ifdef PP_DBG_TRACE
-            if (pp_edge_position(p, p.e_base + (e - p.ws_base)) == (long long)(PP_DBG_TRACE) && lane == 0 && base < 400)
-                printf("[pose] chunk at %d: skip %d (eq word %llx)\n", base, (int)((skips >> ci) & 1ull), (unsigned long long)teq[base >> 6]);
-#endif
-            if ((skips >> ci) & 1ull) { limit = base + PP_WAVE; afterSkip = true; continue; }
-            const bool gridClear = ((gclear >> ci) & 1ull) != 0ull, obstClear = ((oclear >> ci) & 1ull) != 0ull;
-            const int k = base + lane;
-            const double t = (k < p.ng) ? tg[k] : INFINITY;
-            const double tFirst = pp_readlane(t, 0);
-            if (!(tFirst < endTime)) { limit = base; stop = true; break; }   // `while (intermediate.time() < endTime)`
-            // `lastHeading` (Edge.cpp:96,174) of the step before this chunk: the chunks in between were skipped, pp_k_plan_skips left it
-            if (!cov && afterSkip) carryHeading = pp_const_f64(carry + (base >> 6))[0];
-            afterSkip = false;
-            const bool valid = t < endTime;
-            double x, y, heading;
-            bool blk = false;
-            int hits = 0;
-            {
+    bool stop = false;
+    for (;;) {
+        // ---- their poses; the grid words set off together
+        double tFirst[G], x[G], y[G], heading[G];
+        bool live[G], dubErr[G];
+        PPCellRef cell[G];
+        uint32_t word[G];
+        unsigned long long near[G];
+#pragma unroll
+        for (int i = 0; i < G; i++) {
+            tFirst[i] = pp_readlane(t[i], 0);
+            live[i] = have[i] && (tFirst[i] < endTime);               // `while (intermediate.time() < endTime)`
+            dubErr[i] = false;
+            near[i] = 0ull;
+            if (live[i]) {
+                const bool gridClear = ((gclear >> ci[i]) & 1ull) != 0ull, obstClear = ((oclear >> ci[i]) & 1ull) != 0ull;
+                const bool valid = t[i] < endTime;
                 double uth;
-                pp_window_pose(S, hot, cur, cs, t, tFirst, valid, x, y, uth, dubErr);
+                pp_window_pose(S, hot, cur, cs, t[i], tFirst[i], valid, x[i], y[i], uth, dubErr[i]);
                 // the heading itself (:47) only matters for "unchanged since the last step" (Edge.cpp:159), which only matters
                 // on edges that may not cover while turning
-                heading = cov ? 0.0 : pp_heading_from_yaw(pp_mod2pi(uth));
-                if (!gridClear) blk = valid & pp_is_blocked(p.grid, x, y);   // Edge.cpp:144 (pp_k_plan_skips may have ruled it out for the whole chunk)
+                heading[i] = cov ? 0.0 : pp_heading_from_yaw(pp_mod2pi(uth));
+                if (!gridClear && p.grid.rows != 0) {                 // Edge.cpp:144 (pp_k_plan_skips may have ruled it out for the whole chunk)
+                    cell[i] = pp_blocked_cell(p.grid, x[i], y[i]);
+                    word[i] = p.grid.bits[cell[i].word];
+                }
+                if (!obstClear && laneCull) {                         // :150-151
+                    // which obstacles can come near this chunk: lane j answers for obstacle j from its registers
+                    const double dtc = tFirst[i] - cullT0;
+                    const double oX0 = cullL[0 * PP_WAVE], oY0 = cullL[1 * PP_WAVE], oVx = cullL[2 * PP_WAVE], oVy = cullL[3 * PP_WAVE], oR2 = cullL[4 * PP_WAVE];
+                    const double ddx = pp_readlane(x[i], 0) - (oX0 + oVx * dtc), ddy = pp_readlane(y[i], 0) - (oY0 + oVy * dtc);
+                    near[i] = __ballot(!(ddx * ddx + ddy * ddy > oR2));      // oR2 = -1 in lanes without an obstacle
+                }
             }
+        }
+        // ---- resolved in order, with the sequential semantics: the first chunk that ends the sweep discards the rest of the batch
+#pragma unroll
+        for (int i = 0; i < G; i++) {
+            if (!have[i]) break;
+            const int base = (g0 + ci[i]) * PP_WAVE;
+            const int k = base + lane;
+#ifdef PP_DBG_TRACE
+            if (pp_edge_position(p, p.e_base + (e - p.ws_base)) == (long long)(PP_DBG_TRACE) && lane == 0 && base < 400)
+                printf("[pose] chunk at %d: sampled after skip %d (eq word %llx)\n", base, (int)after[i], (unsigned long long)teq[base >> 6]);
+#endif
+            if (!live[i]) { limit = base; stop = true; break; }
+            // `lastHeading` (Edge.cpp:96,174) of the step before this chunk: the chunks in between were skipped, pp_k_plan_skips left it
+            if (!cov && after[i]) carryHeading = carryW[i];
+            const bool obstClear = ((oclear >> ci[i]) & 1ull) != 0ull;
+            const bool valid = t[i] < endTime;
+            const bool gridTested = !(((gclear >> ci[i]) & 1ull) != 0ull) && p.grid.rows != 0;
+            const bool blk = gridTested ? (valid & pp_blocked_test(cell[i], word[i])) : false;
+            int hits = 0;
             double dens = 0;
             if (obstClear) {
                 // pp_k_plan_skips: no obstacle can hold a pose of this chunk
-            } else if (laneCull) {                                        // :150-151
-                // which obstacles can come near this chunk: lane i answers for obstacle i from its registers
-                const double dtc = tFirst - cullT0;
-                const double ddx = pp_readlane(x, 0) - (oX0 + oVx * dtc), ddy = pp_readlane(y, 0) - (oY0 + oVy * dtc);
-                unsigned long long m = __ballot(!(ddx * ddx + ddy * ddy > oR2));      // oR2 = -1 in lanes without an obstacle
+            } else if (laneCull) {
+                unsigned long long m = near[i];
                 while (m) {
                     const int j = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    if (!gaussian) { if (valid) hits += pp_obstacle_hit(p.obst[j], x, y, t); }
-                    else dens += pp_obstacle_pdf(reinterpret_cast<const PPGauss*>(p.obst)[j], x, y, t);
+                    if (!gaussian) { if (valid) hits += pp_obstacle_hit(pp_obst_load_uniform(p.obst + j), x[i], y[i], t[i]); }
+                    else dens += pp_obstacle_pdf(reinterpret_cast<const PPGauss*>(p.obst)[j], x[i], y[i], t[i]);
                 }
                 if (gaussian) { if (dens < 1e-5) dens = 0; if (!valid) dens = 0; }   // GaussianDynamicObstaclesManager.cpp:11
             } else {
                 if (!gaussian)
-                    hits = pp_obstacle_hits_chunk(p.obst, p.n_obst, x, y, t, valid, pp_readlane(x, 0), pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
+                    hits = pp_obstacle_hits_chunk(p.obst, p.n_obst, x[i], y[i], t[i], valid, pp_readlane(x[i], 0), pp_readlane(y[i], 0), tFirst[i], chunkSpan, chunkTime);
                 else
-                    dens = pp_obstacle_density_chunk(reinterpret_cast<const PPGauss*>(p.obst), p.n_obst, x, y, t, valid, pp_readlane(x, 0),
-                                                     pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
+                    dens = pp_obstacle_density_chunk(reinterpret_cast<const PPGauss*>(p.obst), p.n_obst, x[i], y[i], t[i], valid, pp_readlane(x[i], 0),
+                                                     pp_readlane(y[i], 0), tFirst[i], chunkSpan, chunkTime);
             }
             unsigned long long eqMask = ~0ull;
             if (!cov) {
-                double prevHeading = __shfl_up(heading, 1, PP_WAVE);
+                double prevHeading = __shfl_up(heading[i], 1, PP_WAVE);
                 if (lane == 0) prevHeading = carryHeading;
-                eqMask = __ballot(prevHeading == heading);
+                eqMask = __ballot(prevHeading == heading[i]);
 #ifdef PP_DBG_TRACE
                 if (pp_edge_position(p, p.e_base + (e - p.ws_base)) == (long long)(PP_DBG_TRACE) && lane == 0 && base < 400)
-                    printf("[pose] chunk at %d sampled: carry %.17g heading0 %.17g heading1 %.17g eq %llx\n", base, prevHeading, heading, pp_readlane(heading, 1), (unsigned long long)eqMask);
+                    printf("[pose] chunk at %d sampled: carry %.17g heading0 %.17g heading1 %.17g eq %llx\n", base, prevHeading, heading[i], pp_readlane(heading[i], 1), (unsigned long long)eqMask);
 #endif
-                carryHeading = pp_readlane(heading, 63);
+                carryHeading = pp_readlane(heading[i], 63);           // (the next chunk's, when that one is adjacent)
             }
+            if (__ballot(dubErr[i]) != 0ull) anyErr = 1;
 
             const unsigned long long bm = __ballot(blk);
             const int fb = bm ? (__ffsll((long long)bm) - 1) : PP_WAVE;
@@ -488,24 +569,33 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
             if (nvalid < PP_WAVE) { limit = base + nvalid; stop = true; break; }
             limit = base + PP_WAVE;
         }
-        // skipped chunks the sweep passed whose every pose lies inside some box: the planner's count, 64 per box (rare; kept out of
-        // the per-chunk path above, which runs 3.5 million times per launch)
+        if (stop) break;
+        next_batch();
     }
-    const int anyErr = (__ballot(dubErr) != 0ull) ? 1 : 0;
     if (lane == 0) { sum->limit = limit; sum->blocked = blocked; sum->dub_err = anyErr; sum->pad = 0; }
 }
 
 #ifndef PP_POSE_MIN_WAVES
 #define PP_POSE_MIN_WAVES 6
 #endif
+#ifndef PP_POSE_CHUNKS
+#define PP_POSE_CHUNKS 1     // sampled chunks a wave of pp_k_pose_sweep has in flight.  1 / 2 / 3 measured (profiles/pose_chain_ab.txt): a second
+                             // chunk costs registers the kernel does not have at 6 waves per SIMD and poses that a blocked first chunk throws away
+#endif
 // n_edges = slice size (ppgpu.hip: launch_cost)
 __global__ __launch_bounds__(PP_WPB * 64, PP_POSE_MIN_WAVES) void pp_k_pose_sweep(PPParams p) {
     PPQueue qs = pp_queue_init();
     for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
-        pp_pose_sweep_edge<false>(p, p.ws_base + idx);
+        pp_pose_sweep_edge<false, PP_POSE_CHUNKS>(p, p.ws_base + idx);
+}
+// one chunk at a time (handle switch PPGPU_POSE_CHUNKS=1)
+__global__ __launch_bounds__(PP_WPB * 64, 6) void pp_k_pose_sweep_single(PPParams p) {
+    PPQueue qs = pp_queue_init();
+    for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
+        pp_pose_sweep_edge<false, 1>(p, p.ws_base + idx);
 }
 __global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian(PPParams p) {
     PPQueue qs = pp_queue_init();
     for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
-        pp_pose_sweep_edge<true>(p, p.ws_base + idx);
+        pp_pose_sweep_edge<true, 1>(p, p.ws_base + idx);
 }

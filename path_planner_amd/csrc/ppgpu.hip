@@ -149,6 +149,7 @@ struct ppgpu_ctx {
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
+    int pose_chunks = 0;                // env PPGPU_POSE_CHUNKS=1: the pose sweep samples one chunk at a time (tests compare it with the batched default)
     bool lane_heuristic = true;         // env PPGPU_LANE_HEURISTIC=0: large launches keep the wave-per-edge enumeration too (tests compare the two)
     long long prepass_min_edges = PP_PREPASS_MIN_EDGES;   // env PPGPU_PREPASS_MIN_EDGES overrides (tests run the prepasses on small launches too)
     size_t slice_bytes = PP_SLICE_BYTES; // workspace budget of one costing slice (env PPGPU_SLICE_BYTES overrides: tests)
@@ -281,6 +282,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* qf = std::getenv("PPGPU_QUIET_FINISH")) c->quiet_finish = std::atoi(qf) != 0;
     if (const char* lf = std::getenv("PPGPU_LANE_FINISH")) c->lane_finish = std::atoi(lf) != 0;
     if (const char* ls = std::getenv("PPGPU_LANE_SPLIT")) c->lane_split = std::atoi(ls) != 0;
+    if (const char* pc = std::getenv("PPGPU_POSE_CHUNKS")) c->pose_chunks = std::atoi(pc);
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
@@ -1044,7 +1046,7 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
         void (*planner)(PPParams, int) = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : pp_k_plan_skips_gaussian) : (many ? pp_k_plan_skips_many : pp_k_plan_skips);
         hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, st, p, epw);
     }
-    void (*pose)(PPParams) = m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep;
+    void (*pose)(PPParams) = m.gaussian ? pp_k_pose_sweep_gaussian : (c->pose_chunks == 1 ? pp_k_pose_sweep_single : pp_k_pose_sweep);
     hipLaunchKernelGGL(pose, dim3(resident_grid(c, m.gaussian ? 0 : 1, pose, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_POSED], st));
     if (m.prepasses) hipLaunchKernelGGL(pp_k_approach_events, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
