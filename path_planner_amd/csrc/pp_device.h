@@ -1048,19 +1048,26 @@ __device__ __forceinline__ bool pp_lane_tsp_ok(int heuristic, int tsp_k, int n) 
     return false;
 }
 
-// RibbonManager::maxDistance (RibbonManager.cpp:234-248); pts = x,y of the query point then of every ribbon's start, end
-__device__ inline double pp_h_max_distance(const double* pts, int n, double w) {
-    const double x = pts[0], y = pts[1];
+// RibbonManager::maxDistance (RibbonManager.cpp:234-248) from (x, y) over n ribbons in list order.  rib(i, sx, sy, ex, ey) gives ribbon i:
+// from global memory, from another lane's registers or from the LDS point table, whichever the caller holds them in.
+template <class Rib>
+__device__ __forceinline__ double pp_max_distance(int n, double w, double x, double y, Rib rib) {
     double sumLength = 0, mn = PP_DBL_MAX, mx = 0;
     for (int i = 0; i < n; i++) {
-        const double sx = pts[2 * (1 + 2 * i)], sy = pts[2 * (1 + 2 * i) + 1], ex = pts[2 * (2 + 2 * i)], ey = pts[2 * (2 + 2 * i) + 1];
+        double sx, sy, ex, ey;
+        rib(i, sx, sy, ex, ey);
         sumLength += sqrt(pp_sq_len(sx, sy, ex, ey)) - 2 * w;
-        double dStart = pp_dist(sx, sy, x, y);
-        double dEnd = pp_dist(ex, ey, x, y);
+        const double dStart = pp_dist(sx, sy, x, y);
+        const double dEnd = pp_dist(ex, ey, x, y);
         mn = fmin(fmin(mn, dEnd), dStart);
         mx = fmax(fmax(mx, dEnd), dStart);
     }
     return fmax(sumLength + mn, mx);
+}
+// ... with pts = x,y of the query point then of every ribbon's start, end
+__device__ inline double pp_h_max_distance(const double* pts, int n, double w) {
+    return pp_max_distance(n, w, pts[0], pts[1], [&](int i, double& sx, double& sy, double& ex, double& ey) {
+        sx = pts[2 * (1 + 2 * i)]; sy = pts[2 * (1 + 2 * i) + 1]; ex = pts[2 * (2 + 2 * i)]; ey = pts[2 * (2 + 2 * i) + 1]; });
 }
 
 // RibbonManager::tspPointRobotNoSplitAllRibbons (:53-67) and ...KRibbons (:69-94), wave-parallel.

@@ -1,5 +1,7 @@
-// pp_k_cover.h — the coverage state machine of Edge::computeTrueCost (Edge.cpp:153-171) and the rest of the function (:177-205):
-// pp_k_approach_events (lane per edge), pp_k_cover_sweep (wave per edge), pp_k_cover_finish (lane per edge).  Included by pp_kernels.h.
+// pp_k_cover.h — the coverage state machine of Edge::computeTrueCost (Edge.cpp:153-171): pp_k_approach_events (lane per edge) walks each
+// edge's approach to the ribbons, pp_k_cover_sweep (wave per edge) visits the events that change them.  The rest of the function
+// (:177-205, "phase C") is pp_k_finish.h's: the approach lane finishes a quiet edge with it, the wave hands its edge to pp_k_cover_finish or
+// finishes it in wave form at the end of pp_cover_sweep_edge (its own stop rule, the shared flags and maxDistance).  Included by pp_kernels.h.
 #pragma once
 // How many steps pass before the next coverage event: the loop of Edge.cpp:153-154 subtracts the increment from toCoverDistance
 // once per step while it is above the increment, so after an event that measured D the next one is m + 1 steps on, m = the
@@ -30,38 +32,17 @@ __device__ __forceinline__ int pp_event_stride(double D, double inc_d, double in
 // ribbon's bounding box grown by the ribbon width: the test of pp_ribbons_event's fast path) a coverage event changes nothing
 // and only yields the index of the next one, from the distance to the nearest ribbon endpoint.  That chain is sequential per
 // edge but independent across edges; walked by the edge's own wavefront it costs a 64-lane window of poses per event to use one
-// pose (2.5 of the 3.85 one-at-a-time events per edge at config 3).  Here 64 edges walk their chains side by side — pose,
-// boxes and distance per lane with the expressions of pp_window_pose / pp_ribbons_event, so every number is the one the
-// wavefront would have computed — and each hands over {next event, last event visited} where its chain meets a ribbon, runs
-// past the sweep's limit or end time, or passes the point from which the curve stays clear of all ribbons (PPEdgeSetup::tfar).
+// pose (2.5 of the 3.85 one-at-a-time events per edge at config 3).  Here 64 edges walk their chains side by side — pose by
+// pp_lane_pose (the arithmetic of pp_window_pose), boxes and distance per lane with the expressions of pp_ribbons_event, so every number
+// is the one the wavefront would have computed — and each hands over {next event, last event visited} where its chain meets a ribbon,
+// runs past the sweep's limit or end time, or passes the point from which the curve stays clear of all ribbons (PPEdgeSetup::tfar).
 // The cover sweep starts its state machine there instead of at step 0.
 //
 // Quiet edges.  When the chain ends without meeting a ribbon (past the sweep's limit, or past PPEdgeSetup::tfar) the cover sweep's
 // event loop has nothing to do for this edge, and unless the last cover (Edge.cpp:182-191) happens within reach of a ribbon
-// the rest of computeTrueCost is scalar work: where the loop stopped, two poses, the hit sums, the cost, the record, a copy of the
-// vertex's ribbons.  The lane does that too (pp_finish_quiet_edge: phase C of pp_cover_sweep_edge, the same expressions, for the
-// case "no event changed anything") and marks the edge PP_FAR_DONE; the cover sweep's wave then drops it at once.  Nearly half
-// the edges of config 3.
-// One ribbon's part of a coverage event at (x, y), lane form (the expressions of pp_k_cover_finish / pp_ribbons_event): does the ribbon
-// contain the point (RibbonManager::minDistanceFrom then returns 0) and does it contain it strictly (cover() would split it)?
-// Only called for a ribbon whose grown bounding box holds the point; outside it neither can be.
-__device__ __forceinline__ void pp_lane_ribbon_contains(double sx, double sy, double ex, double ey, double x, double y, double w, bool& inside, bool& strict,
-                                                        double& px, double& py) {
-    const double T = PP_RIBBON_TOL;
-    const double dxr = ex - sx, dyr = ey - sy;
-    const double sqL = dxr * dxr + dyr * dyr;
-    const double dot = (x - sx) * dxr + (y - sy) * dyr;
-    px = dxr * dot / sqL + sx;                               // Ribbon::getProjection (Ribbon.cpp:72-78)
-    py = dyr * dot / sqL + sy;
-    const double a1 = px - sx, a2 = px - ex, b1 = py - sy, b2 = py - ey;
-    const bool outx = ((a1 < -T) & (a2 < -T)) | ((a1 > T) & (a2 > T));
-    const bool outy = ((b1 < -T) & (b2 < -T)) | ((b1 > T) & (b2 > T));
-    const bool cp = !(outx | outy);                          // Ribbon::containsProjection (:90-95)
-    const double num = dyr * x - dxr * y + ex * sy - ey * sx;
-    const double ld = fabs(num) / sqrt(sqL);                 // Ribbon::distance (Ribbon.h:118-121)
-    inside = cp && (ld < w);
-    strict = cp && (ld < (w / 2.0));
-}
+// the rest of computeTrueCost is scalar work.  The lane does that too (pp_finish_quiet_edge: pp_lane_phase_c from the vertex's own
+// state, the function pp_k_cover_finish runs from a wave's) and marks the edge PP_FAR_DONE; the cover sweep's wave then drops it at
+// once.  Nearly half the edges of config 3.
 #define PP_FAR_DONE (-2)
 // PPParams::track_far[e].y = (last event before the hand-over) + 1 in the low 20 bits, and, when the approach lane has already split the
 // one ribbon the vehicle entered (round 4): PP_FAR_SPLIT, which piece the corridor run that follows moves (6 bits) and which of its ends
@@ -69,134 +50,32 @@ __device__ __forceinline__ void pp_lane_ribbon_contains(double sx, double sy, do
 #define PP_FAR_SPLIT (1 << 30)
 #define PP_FAR_MOVE_END (1 << 29)
 #define PP_FAR_PIECE_SHIFT 21
-__device__ __forceinline__ void pp_lane_pose(const PPEdgeSetupBody* S, double t, double wStart, double speed, double length, double rho, double rho_inv,
-                                             double qx, double qy, double hi0, double hi1, double p1, int word, double& x, double& y, double& uth, bool& err) {
-    double dist = (t - wStart) * speed;                                     // DubinsWrapper.cpp:36
-    if (dist < 0 || dist > length) dist = dist - 1e-5;                      // EDUBPARAM retry, :39-42
-    if (dist < 0 || dist > length) { err = true; dist = fmin(fmax(dist, 0.0), length); }
-    const double tprime = (rho_inv != 0.0) ? dist * rho_inv : dist / rho;
-    double ux, uy;
-    pp_setup_seg_pose(S, pp_seg_of(tprime, hi0, hi1), tprime, hi0, p1, word, ux, uy, uth);      // (hi0 = the record's p0)
-    x = ux * rho + qx;
-    y = uy * rho + qy;
-}
-// -> true: the edge's record and child ribbons are written.  false: nothing was written, the wave does the edge.
-// `stage` = this lane's 16 doubles of LDS (stride PP_REC_STRIDE): the record goes there, and the wave then stores the records of its
+// A quiet edge's record goes to its lane's 16 doubles of LDS (stride PP_REC_STRIDE), and the wave then stores the records of its
 // lanes together, 4 records of 128 contiguous bytes per store instruction instead of 64 different lines per field.
 #define PP_REC_STRIDE 17
-__device__ __forceinline__ bool pp_finish_quiet_edge(const PPParams& p, const PPEdgeSetupBody* S, const ppgpu_vertex* V, long long e, long long eg,
-                                                     int limit, int lastEv, const double* rp, const double* tg, double* stage, bool rpUniform) {
-    const int nrib = V->ribbon_count;                                       // > 0, no piece short enough to be erased
-    const PPTrackSummary* sum = p.track_summary + e;
-    if (sum->dub_err) return false;
-    if (nrib > p.stride || nrib > PP_TSP_MAX) return false;
-    if (p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN) return false;
-    // the heuristic must not need this edge's wave either
-    const bool deferH = p.defer_h && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib);
-    if (p.fuse_h && !deferH && p.heuristic != PPGPU_H_MAX_DISTANCE) return false;
-    const double wStart = S->wStart, wEnd = S->wEnd, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv, qx = S->qx, qy = S->qy;
-    const double hi0 = S->p0, hi1 = S->hi1, segP1 = S->p1;
-    const int dubWord = S->type;
-    const double srcT = V->time;
-    const bool cov = (S->cbits & PPGPU_EDGE_COVERAGE) != 0;
-    const double endTime = fmin(p.horizon + 1e-12 + p.sst, wEnd);           // Edge.cpp:90; no event shortened it
-    bool infeasible = (srcT >= endTime);                                    // :102-110
-    const int stopKind = sum->blocked;
-    // where the loop of Edge.cpp:143-175 stopped (no event: every step below `limit` ran)
-    int steps, hexec, lastIdx;
-    double tfinal;
-    bool coverFinal = true;
-    const int nexec = limit;                                                // max(cnt, lastEv + 1), cnt = limit
-    (void)lastEv;
-    if (stopKind == 1 && tg[limit] < endTime) {                             // `break` at :146
-        infeasible = true;
-        lastIdx = limit;
-        coverFinal = cov || (((p.track_eq[(size_t)e * p.nch + (limit >> 6)] >> (limit & 63)) & 1ull) != 0ull);
-        tfinal = tg[limit];
-        steps = limit + 1;
-        hexec = limit;
-    } else {
-        if (stopKind == 2 && tg[0] < endTime) infeasible = true;
-        lastIdx = nexec - 1;
-        tfinal = (nexec < p.ng) ? tg[nexec] : INFINITY;
-        steps = nexec;
-        hexec = nexec;
+// The approach loop's two walks over the lane's ribbon list (pp_with_ribbons picks the address space).  Is some piece short enough to
+// be erased (Ribbon::covered(strict)) wherever the vehicle is?
+template <class RP>
+__device__ __forceinline__ bool pp_any_tiny_ribbon(RP r, int n, double thr) {
+    bool tiny = false;
+    for (int i = 0; i < n; i++) tiny |= pp_sq_len(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]) < thr;
+    return tiny;
+}
+// One event at (x, y): which grown boxes hold the point (any, how many, the last such ribbon) and q = the squared distance to the
+// nearest ribbon endpoint.
+struct PPBoxScan { bool inBox; int boxCount, boxIdx; double q; };
+template <class RP>
+__device__ __forceinline__ PPBoxScan pp_box_scan(RP r, int n, double x, double y, double grow) {
+    PPBoxScan s = {false, 0, 0, PP_DBL_MAX};
+    for (int i = 0; i < n; i++) {
+        const double sx = r[4 * i], sy = r[4 * i + 1], ex = r[4 * i + 2], ey = r[4 * i + 3];
+        const bool in = pp_in_grown_box(sx, sy, ex, ey, x, y, grow);
+        s.inBox |= in; s.boxCount += in ? 1 : 0; s.boxIdx = in ? i : s.boxIdx;
+        const double qS = (sx - x) * (sx - x) + (sy - y) * (sy - y);
+        const double qE = (ex - x) * (ex - x) + (ey - y) * (ey - y);
+        s.q = fmin(s.q, fmin(qE, qS));
     }
-    (void)tfinal;                                                           // only used when the ribbons run out: they do not here
-    if (!(wStart <= endTime && wEnd >= endTime)) return false;              // DubinsWrapper::containsTime: the reference throws
-    double ix = V->x, iy = V->y, uth;
-    bool perr = false, ignored = false;
-    if (lastIdx >= 0) pp_lane_pose(S, tg[lastIdx], wStart, speed, length, rho, rho_inv, qx, qy, hi0, hi1, segP1, dubWord, ix, iy, uth, ignored);
-    double endX, endY;
-    pp_lane_pose(S, endTime, wStart, speed, length, rho, rho_inv, qx, qy, hi0, hi1, segP1, dubWord, endX, endY, uth, perr);
-    if (perr) return false;
-    const double endHeading = pp_heading_from_yaw(pp_mod2pi(uth));
-    if (cov || coverFinal) {                                                // the last cover (:182-191): only if it cannot touch a ribbon
-        const double grow = p.ribw + 1e-3;
-        bool inBox = false;
-        if (rpUniform) {                                                    // one vertex for the whole wave: its ribbons through scalar loads
-            const PP_AS4 double* ru = pp_const_f64(rp);
-            for (int i = 0; i < nrib; i++) {
-                const double sx = ru[4 * i], sy = ru[4 * i + 1], ex = ru[4 * i + 2], ey = ru[4 * i + 3];
-                inBox |= (ix >= fmin(sx, ex) - grow) & (ix <= fmax(sx, ex) + grow) & (iy >= fmin(sy, ey) - grow) & (iy <= fmax(sy, ey) + grow);
-            }
-        } else
-        for (int i = 0; i < nrib; i++) {
-            const double sx = rp[4 * i], sy = rp[4 * i + 1], ex = rp[4 * i + 2], ey = rp[4 * i + 3];
-            inBox |= (ix >= fmin(sx, ex) - grow) & (ix <= fmax(sx, ex) + grow) & (iy >= fmin(sy, ey) - grow) & (iy <= fmax(sy, ey) + grow);
-        }
-        if (inBox) return false;
-    }
-    int hitsTotal = 0;
-    if (p.n_obst > 0) {
-        const unsigned* tch = p.track_chunk_hits + (size_t)e * p.nch;
-        const int cfull = hexec >> 6;
-        for (int c = 0; c < cfull; c++) hitsTotal += (int)tch[c];
-        if ((hexec & 63) != 0 && tch[cfull] != 0u) {
-            if (p.track_skip && (p.track_skip[(size_t)e * p.nch + cfull] & PP_SKIP_ALL) != 0) {
-                hitsTotal += (hexec & 63) * (int)(tch[cfull] >> 6);           // a skipped chunk: the same boxes at every step (no per-step counts)
-            } else {
-                const unsigned short* thits = p.track_hits + (size_t)e * p.ngp;
-                for (int i = cfull << 6; i < hexec; i++) hitsTotal += (int)thits[i];
-            }
-        }
-    }
-    const double penalty = (double)hitsTotal * p.cpf;
-    const double netTime = endTime - srcT;
-    const double tc = fmax(netTime - 0, 0);                                 // :197 with ribbons left
-    const double trueCost = tc * p.tpf + penalty;
-    const double g = V->g + trueCost;
-    unsigned flags = infeasible ? PPGPU_F_INFEASIBLE : 0u;
-    if (endTime >= p.sst + p.horizon) flags |= PPGPU_F_GOAL;
-    double h = 0;
-    if (deferH) h = PP_H_DEFERRED;
-    else if (p.fuse_h) {                                                    // MaxDistance (RibbonManager.cpp:234-248), as pp_h_max_distance
-        double sumLength = 0, mn = PP_DBL_MAX, mx = 0;
-        for (int i = 0; i < nrib; i++) {
-            const double sx = rp[4 * i], sy = rp[4 * i + 1], ex = rp[4 * i + 2], ey = rp[4 * i + 3];
-            sumLength += sqrt(pp_sq_len(sx, sy, ex, ey)) - 2 * p.ribw;
-            const double dStart = pp_dist(sx, sy, endX, endY);
-            const double dEnd = pp_dist(ex, ey, endX, endY);
-            mn = fmin(fmin(mn, dEnd), dStart);
-            mx = fmax(fmax(mx, dEnd), dStart);
-        }
-        h = fmax(sumLength + mn, mx) / p.max_speed * p.tpf;
-    }
-    double* r = stage;
-    const unsigned info = (unsigned)(S->type & 0xff) | ((unsigned)(nrib & 0xff) << 8) | ((unsigned)(steps & 0xffff) << 16);
-    r[0] = __hiloint2double((int)info, (int)flags);
-    r[1] = trueCost; r[2] = penalty; r[3] = S->approx;
-    r[4] = endX; r[5] = endY; r[6] = endHeading; r[7] = speed; r[8] = endTime;
-    r[9] = g; r[10] = h; r[11] = (h == PP_H_DEFERRED) ? g : g + h;
-    r[12] = V->coverage_completed_time; r[13] = S->p0; r[14] = S->p1; r[15] = S->p2;
-    double* c = p.child + (size_t)eg * p.stride * 4;
-    if (rpUniform) {
-        const PP_AS4 double* ru = pp_const_f64(rp);
-        for (int i = 0; i < 4 * nrib; i++) c[i] = ru[i];
-    } else {
-        for (int i = 0; i < 4 * nrib; i++) c[i] = rp[i];
-    }
-    return true;
+    return s;
 }
 #ifndef PP_APPROACH_MIN_WAVES
 #define PP_APPROACH_MIN_WAVES 1
@@ -235,16 +114,12 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
         if (nrib > 0 && nrib <= PP_WAVE && limit > 0) {
             const double* rp = p.ribbons + 4 * (size_t)V->ribbon_offset;
             const double* tg = p.tgrid + (size_t)S->vi * p.ng;
-            const double wStart = S->wStart, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv, qx = S->qx, qy = S->qy;
-            const double hi0 = S->p0, hi1 = S->hi1, segP1 = S->p1;
+            const PPLaneCurve cv = pp_lane_curve(S);
             const double endTime0 = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
             const double w = p.ribw, grow = w + 1e-3, minLength0 = 2 * w;
-            bool tiny = false;
-            if (oneVertex) {
-                const PP_AS4 double* ru = pp_const_f64(rpU);
-                for (int i = 0; i < nribU; i++) tiny |= pp_sq_len(ru[4 * i], ru[4 * i + 1], ru[4 * i + 2], ru[4 * i + 3]) < minLength0 * minLength0 / (2.0 * 2.0);
-            } else
-            for (int i = 0; i < nrib; i++) tiny |= pp_sq_len(rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]) < minLength0 * minLength0 / (2.0 * 2.0);
+            // (oneVertex: the list comes through scalar loads instead of twenty vector loads per event)
+            const PPLaneRibbons ribs = {rp, nrib, rpU, nribU, oneVertex};
+            const bool tiny = pp_with_ribbons(ribs, [&](auto r, int n) { return pp_any_tiny_ribbon(r, n, minLength0 * minLength0 / (2.0 * 2.0)); });
             int k = 0, lastEv = -1;
             bool handOver = tiny;               // the wave has events to visit (or an error to flag)
             // Round 3: an event within reach of ONE ribbon is no longer handed over at once.  The lane takes it exactly (does that
@@ -266,43 +141,18 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
 #ifdef PP_DBG_PHASES
                 apEvents++;
 #endif
-                double dist = (t - wStart) * speed;                                     // DubinsWrapper.cpp:36
-                if (dist < 0 || dist > length) dist = dist - 1e-5;                      // EDUBPARAM retry, :39-42
-                if (dist < 0 || dist > length) { handOver = true; break; }              // the wavefront's code flags the error
-                const double tprime = (rho_inv != 0.0) ? dist * rho_inv : dist / rho;
-                double ux, uy, uth;
-                pp_setup_seg_pose(S, pp_seg_of(tprime, hi0, hi1), tprime, hi0, segP1, dubType, ux, uy, uth);
-                const double x = ux * rho + qx, y = uy * rho + qy;
-                bool inBox = false;
-                int boxCount = 0, boxIdx = 0;
-                double q = PP_DBL_MAX;
-                if (oneVertex) {
-                    // every lane of the wave starts from the same vertex (a dense launch from one open vertex): its ribbons come through
-                    // scalar loads instead of twenty vector loads per event
-                    const PP_AS4 double* ru = pp_const_f64(rpU);
-                    for (int i = 0; i < nribU; i++) {
-                        const double sx = ru[4 * i], sy = ru[4 * i + 1], ex = ru[4 * i + 2], ey = ru[4 * i + 3];
-                        const bool in = (x >= fmin(sx, ex) - grow) & (x <= fmax(sx, ex) + grow) & (y >= fmin(sy, ey) - grow) & (y <= fmax(sy, ey) + grow);
-                        inBox |= in; boxCount += in ? 1 : 0; boxIdx = in ? i : boxIdx;
-                        const double qS = (sx - x) * (sx - x) + (sy - y) * (sy - y);
-                        const double qE = (ex - x) * (ex - x) + (ey - y) * (ey - y);
-                        q = fmin(q, fmin(qE, qS));
-                    }
-                } else
-                for (int i = 0; i < nrib; i++) {
-                    const double sx = rp[4 * i], sy = rp[4 * i + 1], ex = rp[4 * i + 2], ey = rp[4 * i + 3];
-                    const bool in = (x >= fmin(sx, ex) - grow) & (x <= fmax(sx, ex) + grow) & (y >= fmin(sy, ey) - grow) & (y <= fmax(sy, ey) + grow);
-                    inBox |= in; boxCount += in ? 1 : 0; boxIdx = in ? i : boxIdx;
-                    const double qS = (sx - x) * (sx - x) + (sy - y) * (sy - y);
-                    const double qE = (ex - x) * (ex - x) + (ey - y) * (ey - y);
-                    q = fmin(q, fmin(qE, qS));
-                }
+                double x, y, uth;
+                bool perr = false;
+                pp_lane_pose(S, cv, t, x, y, uth, perr);
+                if (perr) { handOver = true; break; }                                   // the wavefront's code flags the error
+                const PPBoxScan scan = pp_with_ribbons(ribs, [&](auto r, int n) { return pp_box_scan(r, n, x, y, grow); });
+                const int boxIdx = scan.boxIdx;
 #ifdef PP_DBG_TRACE
-                if (pp_edge_position(p, p.e_base + e) == (long long)(PP_DBG_TRACE)) printf("[lane] event %d: inBox %d q %.17g x %.17g y %.17g\n", k, (int)inBox, q, x, y);
+                if (pp_edge_position(p, p.e_base + e) == (long long)(PP_DBG_TRACE)) printf("[lane] event %d: inBox %d q %.17g x %.17g y %.17g\n", k, (int)scan.inBox, scan.q, x, y);
 #endif
-                double D = fmin(PP_DBL_MAX, sqrt(q));
-                if (inBox) {
-                    if (boxCount == 1 && nearBudget-- > 0) {
+                double D = fmin(PP_DBL_MAX, sqrt(scan.q));
+                if (scan.inBox) {
+                    if (scan.boxCount == 1 && nearBudget-- > 0) {
                         bool inside, strict;
                         double px, py;
                         const double bsx = rp[4 * boxIdx], bsy = rp[4 * boxIdx + 1], bex = rp[4 * boxIdx + 2], bey = rp[4 * boxIdx + 3];
@@ -351,7 +201,7 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
             apT2 = (long long)__builtin_readcyclecounter();
 #endif
             if (!handOver && k >= limit && p.quiet_finish &&
-                pp_finish_quiet_edge(p, S, V, p.ws_base + e, pp_edge_position(p, p.e_base + e), limit, lastEv, oneVertex ? rpU : rp, tg, s_rec + (size_t)threadIdx.x * PP_REC_STRIDE, oneVertex))
+                pp_finish_quiet_edge(p, S, cv, V, p.ws_base + e, pp_edge_position(p, p.e_base + e), limit, lastEv, ribs, tg, s_rec + (size_t)threadIdx.x * PP_REC_STRIDE))
                 out.x = PP_FAR_DONE;
         }
     }
@@ -722,7 +572,7 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
         }
         return;
     }
-    // ---- where the loop of Edge.cpp:143-175 stopped
+    // ---- where the loop of Edge.cpp:143-175 stopped: pp_loop_stop's rule (pp_k_finish.h), wave form — through wave-uniform scalar loads
     int steps = 0;
     double ix = srcX, iy = srcY;        // `intermediate` position
     double tfinal = (p.ng > 0) ? pp_const_f64(tg)[0] : INFINITY;
@@ -749,8 +599,6 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
         }
         int nexec = cnt > lastEv + 1 ? cnt : lastEv + 1;
         nexec = nexec < limit ? nexec : limit;
-        // the blocked step is reached only if every step before it ran AND its own time still passes `while (t < endTime)`
-        // (endTime may have shrunk at an event before it, Edge.cpp:169)
         if (blockedAtLimit && nexec == limit && pp_const_f64(tg + limit)[0] < endTime) {   // `break` at :146
             infeasible = true;
             lastIdx = limit;
@@ -840,13 +688,7 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
 
     if (infeasible) flags |= PPGPU_F_INFEASIBLE;
     if (throwsRef) flags |= PPGPU_F_THROWS | PPGPU_F_INFEASIBLE;
-    if (!throwsRef) {
-        if (nrib == 0) flags |= PPGPU_F_DONE;
-        // SamplingBasedPlanner::goalCondition (SamplingBasedPlanner.cpp:42-50)
-        const double coverageDoneTime = cct + p.tmin;
-        const double nonCoverageDoneTime = p.sst + p.horizon;
-        if (endTime >= nonCoverageDoneTime || (nrib == 0 && endTime >= coverageDoneTime)) flags |= PPGPU_F_GOAL;
-    }
+    if (!throwsRef) flags |= pp_done_goal_flags(p, nrib, endTime, cct);
 
     // ---- one 128-byte record, lanes 0..15 write one 8-byte slot each
     {
@@ -909,17 +751,9 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
             if (pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) leaveToBigPass = true;    // pp_k_heuristic_big fills it in
             else flags |= PPGPU_F_RIBBON_OVF;
         } else if (!tsp && nrib > 31) {
-            // MaxDistance over a long list (RibbonManager.cpp:234-248), ribbon by ribbon in list order
-            double sumLength = 0, mn = PP_DBL_MAX, mx = 0;
-            for (int i = 0; i < nrib; i++) {
-                const double sx = pp_readlane(rib.sx, i), sy = pp_readlane(rib.sy, i), ex = pp_readlane(rib.ex, i), ey = pp_readlane(rib.ey, i);
-                sumLength += sqrt(pp_sq_len(sx, sy, ex, ey)) - 2 * p.ribw;
-                const double dStart = pp_dist(sx, sy, endX, endY);
-                const double dEnd = pp_dist(ex, ey, endX, endY);
-                mn = fmin(fmin(mn, dEnd), dStart);
-                mx = fmax(fmax(mx, dEnd), dStart);
-            }
-            hdist = fmax(sumLength + mn, mx);
+            // MaxDistance over a long list, from the lanes' registers
+            hdist = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
+                sx = pp_readlane(rib.sx, i); sy = pp_readlane(rib.sy, i); ex = pp_readlane(rib.ex, i); ey = pp_readlane(rib.ey, i); });
         } else {
             pp_wave_lds_fence();                                   // the event machinery is done with this scratch
             if (lane == 0) { lds[0] = endX; lds[1] = endY; }
@@ -945,216 +779,23 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
 // just written by the same wave, there is no second launch, and the two phases' stalls fall at different times in the four
 // waves of a SIMD.  Cover sweep + heuristic 2.26 -> 2.18 ms (tools/ablate.py fuse0).
 #define PP_COVER_LDS ((PP_FUSE_HEUR) ? (PPTsp<PP_TSP_MAX>::LDS > PP_WAVE * 4 ? PPTsp<PP_TSP_MAX>::LDS : PP_WAVE * 4) : PP_WAVE * 4)
-__global__ __launch_bounds__(PP_WPB * 64, PP_MIN_WAVES) void pp_k_cover_sweep(PPParams p) {
-    __shared__ double lds_all[PP_WPB][PP_COVER_LDS];
+// lds_all = the workgroup's scratch, [PP_WPB][LDS] doubles: a row per wave
+template <bool GAUSSIAN, int LDS>
+__device__ __forceinline__ void pp_cover_sweep_waves(PPParams p, double (*lds_all)[LDS]) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     PPQueue qs = pp_queue_init();
     const long long n = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_count)[0] : p.n_edges;
     for (PP_EACH_EDGE(i, 2, PP_Q_COVER, n, PP_Q_CHUNK_COVER)) {
         const long long idx = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[0] : i;
         const long long eg = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[1] : pp_edge_position(p, p.e_base + idx);
-        pp_cover_sweep_edge<false>(p, p.ws_base + idx, eg, lds_all[wave]);
+        pp_cover_sweep_edge<GAUSSIAN>(p, p.ws_base + idx, eg, lds_all[wave]);
     }
+}
+__global__ __launch_bounds__(PP_WPB * 64, PP_MIN_WAVES) void pp_k_cover_sweep(PPParams p) {
+    __shared__ double lds_all[PP_WPB][PP_COVER_LDS];
+    pp_cover_sweep_waves<false>(p, lds_all);
 }
 __global__ __launch_bounds__(PP_WPB * 64, PP_MIN_WAVES) void pp_k_cover_sweep_gaussian(PPParams p) {
     __shared__ double lds_all[PP_WPB][PP_WAVE * 4];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    PPQueue qs = pp_queue_init();
-    const long long n = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_count)[0] : p.n_edges;
-    for (PP_EACH_EDGE(i, 2, PP_Q_COVER, n, PP_Q_CHUNK_COVER)) {
-        const long long idx = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[0] : i;
-        const long long eg = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[1] : pp_edge_position(p, p.e_base + idx);
-        pp_cover_sweep_edge<true>(p, p.ws_base + idx, eg, lds_all[wave]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Phase C of the edges the cover sweep's waves handed over (PPCoverState), one LANE per edge: Edge.cpp:177-205 with the expressions
-// of pp_cover_sweep_edge's own phase C (which stays, for the edges a wave keeps: a list longer than PP_FINISH_MAX, the Gaussian
-// model, a curve the reference throws on) — pp_lane_pose for pp_window_pose, the reference's strict cover() ribbon by ribbon in list
-// order for pp_ribbons_event (Ribbon::split / covered, Ribbon.cpp:9-25,39-58: the same projection, containsProjection and distance
-// expressions; the wave decides the distance test on squares and falls back to this very quotient when it is close).
-// Heuristic: a list the lane kernel enumerates is marked PP_H_DEFERRED as the wave would; MaxDistance is computed here; the rare
-// list of 7 or 8 ribbons under a TSP heuristic goes to pp_k_heuristic_listed (a wave per such edge).
-#ifndef PP_FINISH_THREADS
-#define PP_FINISH_THREADS 64
-#endif
-__global__ __launch_bounds__(PP_FINISH_THREADS) void pp_k_cover_finish(PPParams p) {
-    const unsigned nlive = (unsigned)pp_const_i32(p.live_count)[0];
-    const unsigned li = blockIdx.x * PP_FINISH_THREADS + threadIdx.x;
-    if (li >= nlive) return;
-    const long long e = p.ws_base + (long long)p.live_list[2 * (size_t)li];
-    const long long eg = (long long)p.live_list[2 * (size_t)li + 1];
-    const PPCoverState st = p.cover_state[e];
-    if (st.nrib < 0) return;                                   // its wave finished it
-    const PPEdgeSetupBody* S = p.setup + e;
-    const unsigned vi = S->vi;
-    const ppgpu_vertex* V = p.verts + vi;
-    const bool cov = (S->cbits & PPGPU_EDGE_COVERAGE) != 0;
-    const double wStart = S->wStart, wEnd = S->wEnd, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv, qx = S->qx, qy = S->qy;
-    const double hi0 = S->p0, hi1 = S->hi1, segP1 = S->p1;
-    const int dubWord = S->type;
-    const double srcT = V->time;
-    const double endTime0 = fmin(p.horizon + 1e-12 + p.sst, wEnd);    // Edge.cpp:90
-    const double endTime = st.endTime;
-    double cct = st.cct;
-    int nrib = st.nrib, rdt = st.rdt;
-    const int lastEv = st.lastEv;
-    unsigned flags = st.flags;
-    bool infeasible = (flags & PPGPU_F_INFEASIBLE) != 0;
-    const bool startedDone = V->ribbon_count == 0;             // Edge.cpp:93
-    const PPTrackSummary* sum = p.track_summary + e;
-    const int limit = sum->limit, stopKind = sum->blocked;
-    const double* tg = p.tgrid + (size_t)vi * p.ng;
-    const double w = p.ribw;
-
-    // ---- where the loop of Edge.cpp:143-175 stopped
-    int cnt = limit;                                           // steps k < limit with t_k < endTime (the time grid is non-decreasing)
-    if (endTime != endTime0) {
-        int lo = 0, hi = limit;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (tg[mid] < endTime) lo = mid + 1; else hi = mid;
-        }
-        cnt = lo;
-    }
-    int nexec = cnt > lastEv + 1 ? cnt : lastEv + 1;
-    nexec = nexec < limit ? nexec : limit;
-    int steps, hexec, lastIdx;
-    double tfinal;
-    bool coverFinal = true;
-    if (stopKind == 1 && nexec == limit && tg[limit] < endTime) {   // `break` at :146
-        infeasible = true;
-        lastIdx = limit;
-        coverFinal = cov || (((p.track_eq[(size_t)e * p.nch + (limit >> 6)] >> (limit & 63)) & 1ull) != 0ull);
-        tfinal = tg[limit];
-        steps = limit + 1;
-        hexec = limit;
-    } else {
-        if (stopKind == 2 && p.ng > 0 && tg[0] < endTime) infeasible = true;
-        lastIdx = nexec - 1;
-        tfinal = (nexec < p.ng) ? tg[nexec] : INFINITY;
-        steps = nexec;
-        hexec = nexec;
-    }
-    // ---- end state (:177-178) and the pose `intermediate` stopped on
-    double ix = V->x, iy = V->y, uth;
-    bool ignored = false, perr = false;
-    if (lastIdx >= 0) pp_lane_pose(S, tg[lastIdx], wStart, speed, length, rho, rho_inv, qx, qy, hi0, hi1, segP1, dubWord, ix, iy, uth, ignored);
-    double endX, endY;
-    pp_lane_pose(S, endTime, wStart, speed, length, rho, rho_inv, qx, qy, hi0, hi1, segP1, dubWord, endX, endY, uth, perr);
-    if (perr) flags |= PPGPU_F_DUBINS_ERR;
-    const double endHeading = pp_heading_from_yaw(pp_mod2pi(uth));
-    // ---- cover the last little bit (:182-191): RibbonManager::cover(x, y, strict) over the list in order
-    double* c = p.child + (size_t)eg * p.stride * 4;
-    if ((cov || coverFinal) && nrib > 0) {
-        double rsx[PP_FINISH_MAX], rsy[PP_FINISH_MAX], rex[PP_FINISH_MAX], rey[PP_FINISH_MAX];
-#pragma unroll
-        for (int i = 0; i < PP_FINISH_MAX; i++) {
-            const bool have = i < nrib;
-            rsx[i] = have ? c[4 * i] : 0.0; rsy[i] = have ? c[4 * i + 1] : 0.0; rex[i] = have ? c[4 * i + 2] : 0.0; rey[i] = have ? c[4 * i + 3] : 0.0;
-        }
-        const double minLength = 2 * w;                                  // Ribbon::minLength (Ribbon.cpp:52-58)
-        const double thr = minLength * minLength / (2.0 * 2.0);          // covered(strict): c_StrictModifier^2
-        const double T = PP_RIBBON_TOL;
-        int nout = 0;
-#pragma unroll
-        for (int i = 0; i < PP_FINISH_MAX; i++) {
-            if (i < nrib) {
-                const double sx = rsx[i], sy = rsy[i], ex = rex[i], ey = rey[i];
-                const double dxr = ex - sx, dyr = ey - sy;
-                const double sqL = dxr * dxr + dyr * dyr;
-                const double dot = (ix - sx) * dxr + (iy - sy) * dyr;
-                const double px = dxr * dot / sqL + sx;                  // Ribbon::getProjection (Ribbon.cpp:72-78)
-                const double py = dyr * dot / sqL + sy;
-                const double a1 = px - sx, a2 = px - ex, b1 = py - sy, b2 = py - ey;
-                const bool outx = ((a1 < -T) & (a2 < -T)) | ((a1 > T) & (a2 > T));
-                const bool outy = ((b1 < -T) & (b2 < -T)) | ((b1 > T) & (b2 > T));
-                const bool cp = !(outx | outy);                          // Ribbon::containsProjection (:90-95)
-                const double num = dyr * ix - dxr * iy + ex * sy - ey * sx;
-                const bool stc = cp && ((fabs(num) / sqrt(sqL)) < (w / 2.0));   // Ribbon::contains(strict): distance (Ribbon.h:118-121) < w / 2
-                const bool keepF = stc && !(pp_sq_len(sx, sy, px, py) < thr);
-                const bool keepR = stc ? !(pp_sq_len(px, py, ex, ey) < thr) : !(sqL < thr);
-                if (keepF) {
-                    if (nout < p.stride) { c[4 * nout] = sx; c[4 * nout + 1] = sy; c[4 * nout + 2] = px; c[4 * nout + 3] = py; }
-                    nout++;
-                }
-                if (keepR) {
-                    if (nout < p.stride) { c[4 * nout] = stc ? px : sx; c[4 * nout + 1] = stc ? py : sy; c[4 * nout + 2] = ex; c[4 * nout + 3] = ey; }
-                    nout++;
-                }
-            }
-        }
-        // (the slots the handed-over list filled beyond the final one go back to zero: a wave that finishes its own edge never
-        // writes them, and callers hand in zeroed buffers)
-        for (int i = nout; i < nrib; i++) { c[4 * i] = 0.0; c[4 * i + 1] = 0.0; c[4 * i + 2] = 0.0; c[4 * i + 3] = 0.0; }
-        nrib = nout;
-    }
-    if (nrib == 0) {
-        if (cct == -1) cct = tfinal;
-        rdt = (int)tfinal;
-    }
-    // ---- obstacle hits of the executed steps (:150-151 summed)
-    int hitsTotal = 0;
-    if (p.n_obst > 0) {
-        const unsigned* tch = p.track_chunk_hits + (size_t)e * p.nch;
-        const int cfull = hexec >> 6;
-        for (int ch = 0; ch < cfull; ch++) hitsTotal += (int)tch[ch];
-        if ((hexec & 63) != 0 && tch[cfull] != 0u) {
-            if (p.track_skip && (p.track_skip[(size_t)e * p.nch + cfull] & PP_SKIP_ALL) != 0) {
-                hitsTotal += (hexec & 63) * (int)(tch[cfull] >> 6);       // a skipped chunk: the same boxes at every step (no per-step counts)
-            } else {
-                const unsigned short* thits = p.track_hits + (size_t)e * p.ngp;
-                for (int i = cfull << 6; i < hexec; i++) hitsTotal += (int)thits[i];
-            }
-        }
-    }
-    const double penalty = (double)hitsTotal * p.cpf;
-    const double netTime = endTime - srcT;                                        // Edge::netTime
-    double tc = fmax(netTime - ((nrib == 0) ? (endTime - (double)rdt) : 0), 0);  // :197
-    if (startedDone) tc = 0;                                                      // :198
-    const double trueCost = tc * p.tpf + penalty;                                 // :199
-    const double g = V->g + trueCost;                                             // Vertex::setCurrentCost
-    if (infeasible) flags |= PPGPU_F_INFEASIBLE;
-    if (nrib == 0) flags |= PPGPU_F_DONE;
-    {   // SamplingBasedPlanner::goalCondition (SamplingBasedPlanner.cpp:42-50)
-        const double coverageDoneTime = cct + p.tmin;
-        const double nonCoverageDoneTime = p.sst + p.horizon;
-        if (endTime >= nonCoverageDoneTime || (nrib == 0 && endTime >= coverageDoneTime)) flags |= PPGPU_F_GOAL;
-    }
-    if (nrib > PP_TSP_MAX) atomicOr(p.need_big, 1u);
-    if (nrib > p.stride) flags |= PPGPU_F_RIBBON_OVF;
-    // ---- h: Vertex::computeApproxToGo, as the wave decides it
-    double h = 0;
-    bool listed = false;
-    if (p.defer_h && nrib <= p.stride && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib)) {
-        h = PP_H_DEFERRED;
-    } else if (p.fuse_h && nrib > 0 && nrib <= p.stride) {
-        const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
-        if (tsp && nrib > PP_TSP_MAX) {
-            if (!pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) flags |= PPGPU_F_RIBBON_OVF;      // else pp_k_heuristic_big fills it in
-        } else if (!tsp) {                                      // MaxDistance (RibbonManager.cpp:234-248), ribbon by ribbon in list order
-            double sumLength = 0, mn = PP_DBL_MAX, mx = 0;
-            for (int i = 0; i < nrib; i++) {
-                const double sx = c[4 * i], sy = c[4 * i + 1], ex = c[4 * i + 2], ey = c[4 * i + 3];
-                sumLength += sqrt(pp_sq_len(sx, sy, ex, ey)) - 2 * p.ribw;
-                const double dStart = pp_dist(sx, sy, endX, endY);
-                const double dEnd = pp_dist(ex, ey, endX, endY);
-                mn = fmin(fmin(mn, dEnd), dStart);
-                mx = fmax(fmax(mx, dEnd), dStart);
-            }
-            h = fmax(sumLength + mn, mx) / p.max_speed * p.tpf;
-        } else {
-            listed = true;                                      // a TSP enumeration the lanes do not take: a wave's work
-        }
-    }
-    ppgpu_edge_result* rec = p.out + eg;
-    double* r = reinterpret_cast<double*>(rec);
-    const unsigned info = (unsigned)(S->type & 0xff) | ((unsigned)(nrib & 0xff) << 8) | ((unsigned)(steps & 0xffff) << 16);
-    r[0] = __hiloint2double((int)info, (int)flags);
-    r[1] = trueCost; r[2] = penalty; r[3] = S->approx;
-    r[4] = endX; r[5] = endY; r[6] = endHeading; r[7] = speed; r[8] = endTime;
-    r[9] = g; r[10] = h; r[11] = (h == PP_H_DEFERRED) ? g : g + h;
-    r[12] = cct; r[13] = S->p0; r[14] = S->p1; r[15] = S->p2;
-    if (listed) p.hw_list[atomicAdd(p.hw_count, 1u)] = (unsigned)eg;
+    pp_cover_sweep_waves<true>(p, lds_all);
 }

@@ -61,16 +61,9 @@ __device__ __forceinline__ void pp_heuristic_edge(const PPParams& p, const long 
             flags |= PPGPU_F_RIBBON_OVF;
         } else if (!tsp && nrib > 31) {
             // MaxDistance over a long list: straight from global memory, no table
-            double sumLength = 0, mn = PP_DBL_MAX, mx = 0;
-            for (int i = 0; i < nrib; i++) {
+            hdist = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
                 const double* c = p.child + ((size_t)e * p.stride + i) * 4;
-                sumLength += sqrt(pp_sq_len(c[0], c[1], c[2], c[3])) - 2 * p.ribw;
-                double dStart = pp_dist(c[0], c[1], endX, endY);
-                double dEnd = pp_dist(c[2], c[3], endX, endY);
-                mn = fmin(fmin(mn, dEnd), dStart);
-                mx = fmax(fmax(mx, dEnd), dStart);
-            }
-            hdist = fmax(sumLength + mn, mx);
+                sx = c[0]; sy = c[1]; ex = c[2]; ey = c[3]; });
         } else {
             if (lane == 0) { pts[0] = endX; pts[1] = endY; }
             if (lane < nrib) {

@@ -5,7 +5,8 @@
 #include "pp_k_common.h"       // PPParams, PPEdgeSetup, clearance map, time grids, edge decoding, work queues
 #include "pp_k_solve.h"        // pp_k_solve_edges
 #include "pp_k_sweep.h"        // pp_k_plan_skips, pp_k_pose_sweep
-#include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep, pp_k_cover_finish
+#include "pp_k_finish.h"       // phase C of an edge: the pieces every route shares, pp_lane_phase_c, pp_k_cover_finish
+#include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep
 #include "pp_k_trace.h"        // pp_k_trace_steps
 #include "pp_k_cover_trace.h"  // pp_k_trace_cover
 #include "pp_k_chain.h"        // pp_k_chain_advance

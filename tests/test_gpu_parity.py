@@ -335,6 +335,91 @@ def test_lane_finish_is_the_wave_finish(torch_cuda, monkeypatch, heur):
     print(heur, "child ribbon counts (second world)", np.bincount(nr))
 
 
+@pytest.mark.parametrize("heur", ["max", "all"])
+def test_every_finish_route_writes_the_same_bytes(torch_cuda, monkeypatch, heur):
+    """Phase C of an edge (Edge.cpp:177-205) is reached by three routes: the approach lane finishes a quiet edge itself, a lane of
+    pp_k_cover_finish takes over an edge its wave visited, or the wave finishes its own edge.  PPGPU_QUIET_FINISH / PPGPU_LANE_FINISH =
+    1/1, 0/1 and 0/0 move the edges from the first route to the second to the third: the same bytes every time, records and child
+    ribbons.  Two small launches that take the prepass route (PPGPU_PREPASS_MIN_EDGES=0, the suite's setting): dense from the root —
+    every lane of a wave starts from the same vertex, its ribbons come through scalar loads, and the last workgroup of the approach
+    kernel is partial — and an explicit list over children of the root, a random vertex per edge: waves mix vertices (vector loads),
+    and the children have their own time grids, coverage_completed_time and split lists."""
+    import os
+    from path_planner_amd import api, workloads
+    from path_planner_amd.types import RESULT_DTYPE, H_MAX_DISTANCE, H_TSP_POINT_ALL, F_INFEASIBLE, F_GOAL, edge_pack
+    torch = torch_cuda
+    assert os.environ.get("PPGPU_PREPASS_MIN_EDGES") == "0"
+    w = workloads.config3(n_samples=512)
+    w.cfg.heuristic, w.cfg.tsp_k = {"max": (H_MAX_DISTANCE, 2), "all": (H_TSP_POINT_ALL, 0)}[heur]
+    stride = 10
+    verts = pool = edges = evi = None
+    outs = []
+    for quiet, lanes in (("1", "1"), ("0", "1"), ("0", "0")):
+        monkeypatch.setenv("PPGPU_QUIET_FINISH", quiet)
+        monkeypatch.setenv("PPGPU_LANE_FINISH", lanes)
+        ctx = api.Context(0)
+        ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
+        ctx.sampler_init(w.bounds6, w.seed, w.ribbons4)
+        n = ctx.sampler_add(w.n_samples)
+        a = _dense(torch, ctx, 1, n, 0xF, stride=stride)
+        if edges is None:       # the second launch's vertices and edges, once, from the first route's records
+            res, child = a
+            assert len(res) % 256 != 0, "the approach kernel's last workgroup should be partial"
+            inf, goal = (res["flags"] & F_INFEASIBLE) != 0, (res["flags"] & F_GOAL) != 0
+            rib = np.asarray(w.ribbons4, dtype=np.float64).reshape(-1, 4)
+            nr = (res["info"] >> 8) & 0xFF
+            same = (nr == len(rib)) & np.all(child[:, :len(rib)].reshape(len(res), -1) == rib.reshape(1, -1), axis=1)
+            print(heur, "dense:", len(res), "edges,", int(inf.sum()), "infeasible,", int(goal.sum()), "goal,", int((~inf & ~goal).sum()),
+                  "neither,", int(same.sum()), "keep the parent's list,", int((~same).sum()), "change it")
+            assert inf.any() and goal.any() and (~inf & ~goal).any() and same.any() and (~same).any()
+            feas = np.nonzero(~inf & ~goal)[0]
+            pick = feas[:: max(1, len(feas) // 40)][:40]
+            verts, pool = _children_as_vertices(w, res, child, pick, stride=stride)
+            rng = np.random.default_rng(11)
+            vi, ti, cb = rng.integers(0, len(verts), 1000), rng.integers(0, n, 1000), rng.integers(0, 4, 1000)
+            samples = ctx.get_samples()
+            # (the reference never builds an edge shorter than the collision-check increment: a child and the sample it was built from)
+            far = np.hypot(verts["x"][vi] - samples[ti, 0], verts["y"][vi] - samples[ti, 1]) > w.cfg.collision_checking_increment
+            edges = edge_pack(vi[far], ti[far], cb[far])
+            assert len(pick) >= 30 and len(edges) > 900 and len(np.unique(vi[far][:64])) > 8
+            vnr = verts["ribbon_count"][1:]
+            print(heur, "children: ribbon counts", np.bincount(vnr).tolist(), "the root has", len(rib))
+            assert (vnr != len(rib)).any(), "no child carries a split list"
+            evi = vi[far]
+        ne = len(edges)
+        ctx.set_vertices(verts, pool)
+        d_e = torch.from_numpy(edges.view(np.int64)).to("cuda:0")
+        d_res = torch.zeros(ne * RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+        d_child = torch.zeros(ne * stride * 4, dtype=torch.float64, device="cuda:0")
+        torch.cuda.synchronize()      # the fill ran on torch's stream, the library works on its own
+        ctx.cost_edges_list(ne, d_e.data_ptr(), d_res.data_ptr(), d_child.data_ptr(), stride)
+        ctx.synchronize()
+        outs.append((a, (d_res.cpu().numpy().view(RESULT_DTYPE), d_child.cpu().numpy().reshape(ne, stride, 4))))
+        if len(outs) == 1:      # the list launch too must hold work for every route, split lists among it
+            lres, lchild = outs[0][1]
+            lnr = ((lres["info"] >> 8) & 0xFF).astype(np.int64)
+            keeps = np.zeros(ne, dtype=bool)        # the child's list is its vertex's: only such an edge can take the quiet route
+            for i in range(ne):
+                o, c = int(verts["ribbon_offset"][evi[i]]), int(verts["ribbon_count"][evi[i]])
+                keeps[i] = lnr[i] == c and np.array_equal(lchild[i, :c], pool[o:o + c])
+            linf = (lres["flags"] & F_INFEASIBLE) != 0
+            split = verts["ribbon_count"][evi] != len(rib)
+            print(heur, "list:", ne, "edges,", int(linf.sum()), "infeasible,", int((keeps & ~linf).sum()), "feasible and keep their vertex's list (",
+                  int((keeps & ~linf & split).sum()), "of them from a split list ),", int((~keeps).sum()), "change it")
+            assert (keeps & ~linf & split).any()
+    for route in (1, 2):
+        for k, launch in enumerate(("dense", "list")):
+            for part, what in enumerate(("records", "child ribbons")):
+                x, y = outs[0][k][part], outs[route][k][part]
+                if x.tobytes() != y.tobytes():
+                    rows = np.nonzero(np.any(x.reshape(len(x), -1).view(np.uint8) != y.reshape(len(y), -1).view(np.uint8), axis=1))[0]
+                    print(heur, launch, what, "route 1/1 against", ("", "0/1", "0/0")[route], "differ at edges", rows[:10].tolist(), "of", len(rows))
+                    if part == 0:
+                        for r in rows[:3]:
+                            print("  ", [nm for nm in x.dtype.names if x[nm][r].tobytes() != y[nm][r].tobytes()], x[r], y[r])
+                assert x.tobytes() == y.tobytes(), f"{launch} launch: {what} of route 1/1 and route {('', '0/1', '0/0')[route]} differ"
+
+
 def test_lane_split_is_the_wave_split(torch_cuda, monkeypatch):
     """Large launches: the approach lane splits the one ribbon an edge enters itself and hands the wave the new list (in the edge's
     child slot) with the corridor run already guessed, in long-run mode from its first window (round 4).  PPGPU_LANE_SPLIT=0 leaves
