@@ -337,6 +337,23 @@ int ppgpu_expand_host(ppgpu_ctx* ctx, int32_t nv, const ppgpu_vertex* h_vertices
 int ppgpu_heuristic_host(ppgpu_ctx* ctx, int32_t n, const double* h_poses3, const int32_t* h_ribbon_counts, const double* h_ribbons,
                          double* h_out, uint32_t* h_flags);
 
+/* The point-robot TSP heuristics of child lists beyond the enumeration's 8 (12) ribbons, on the device: an exact table over (ribbons
+ * done, last ribbon, end entered) gives the enumeration's value bit for bit.  Off by default.  With max_ribbons in
+ * 1 .. PPGPU_TSP_TABLE_MAX every costing launch and ppgpu_heuristic_host ends with a pass over the records whose whole list
+ * (count <= ribbon_stride) has min_ribbons .. max_ribbons ribbons: h and f are filled in and PPGPU_F_RIBBON_OVF is cleared.
+ * min_ribbons = 0 takes only the records the enumeration flagged PPGPU_F_RIBBON_OVF; min_ribbons >= 1 takes every record in the
+ * range (tests hold the table to the enumeration that way).  Under PPGPU_H_TSP_POINT_K a list on which the reference's choice of K
+ * ribbons depends on an exact tie of sort keys is refused: the record stays as it was (flag, h = 0) and is counted.  The other
+ * heuristics are not touched.  max_ribbons = 0 switches the pass off and frees nothing; the workspace (at most 1 GiB) is allocated
+ * here, never inside a costing call.  PPGPU_EINVAL: min_ribbons < 0, max_ribbons < 0 or > PPGPU_TSP_TABLE_MAX, min > max > 0. */
+#define PPGPU_TSP_TABLE_MAX 16
+int ppgpu_set_tsp_table(ppgpu_ctx* ctx, int32_t min_ribbons, int32_t max_ribbons);
+/* Lists the pass answered / refused on this handle so far (device counters, one small copy; waits for the handle's stream). */
+int ppgpu_tsp_table_stats(ppgpu_ctx* ctx, uint64_t* lists, uint64_t* refused);
+/* With ppgpu_enable_timing on: device milliseconds of the last table pass (listing kernel and table kernel, from HIP events; waits
+ * for it).  PPGPU_ESTATE when no pass has been timed. */
+int ppgpu_last_tsp_table_timing(ppgpu_ctx* ctx, double* ms);
+
 /* Convenience for small batches (the host planner's <= 40 edges per expansion):
  * host descriptors in, host results out, synchronous. */
 int ppgpu_cost_edges_host(ppgpu_ctx* ctx, int64_t n, const uint64_t* h_edges,

@@ -45,6 +45,9 @@ def _load():
         "ppgpu_copy_engine_read": (C.c_int, [vp, vp, vp, u64]),
         "ppgpu_copy_engine_wait": (C.c_int, [vp]),
         "ppgpu_heuristic_host": (C.c_int, [vp, i32, vp, vp, vp, vp, vp]),
+        "ppgpu_set_tsp_table": (C.c_int, [vp, i32, i32]),
+        "ppgpu_tsp_table_stats": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64)]),
+        "ppgpu_last_tsp_table_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_expand_capacity": (C.c_int64, [i32, i32]),
         "ppgpu_expand_host": (C.c_int, [vp, i32, vp, i32, vp, vp, i32, C.POINTER(C.c_int64), vp, vp, vp, i32]),
         "ppgpu_enable_timing": (C.c_int, [vp, i32]),
@@ -286,6 +289,23 @@ class Context:
         fl = np.zeros(len(ps), dtype=np.uint32)
         self._ck(LIB.ppgpu_heuristic_host(self._h, len(ps), _ptr(ps), _ptr(counts), _ptr(flat) if len(flat) else None, _ptr(out), _ptr(fl)), "ppgpu_heuristic_host")
         return out, fl
+
+    def set_tsp_table(self, min_ribbons, max_ribbons):
+        """The exact-table pass over child lists of min_ribbons .. max_ribbons (<= 16) ribbons; min_ribbons = 0: the lists the
+        enumeration declines; max_ribbons = 0: off (the default)."""
+        self._ck(LIB.ppgpu_set_tsp_table(self._h, int(min_ribbons), int(max_ribbons)), "ppgpu_set_tsp_table")
+
+    def tsp_table_stats(self):
+        """(lists the table pass answered, lists it refused for a tie) on this handle so far."""
+        lists, refused = C.c_uint64(), C.c_uint64()
+        self._ck(LIB.ppgpu_tsp_table_stats(self._h, C.byref(lists), C.byref(refused)), "ppgpu_tsp_table_stats")
+        return int(lists.value), int(refused.value)
+
+    def last_tsp_table_timing(self):
+        """Device milliseconds of the last table pass (enable_timing first)."""
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_tsp_table_timing(self._h, C.byref(ms)), "ppgpu_last_tsp_table_timing")
+        return float(ms.value)
 
     def expand_host(self, vertices, ribbons4, nearest3, k, stride=0):
         """SamplingBasedPlanner::expand for several vertices in one round trip: (descriptors, records, child ribbons)."""

@@ -11,5 +11,6 @@
 #include "pp_k_cover_trace.h"  // pp_k_trace_cover
 #include "pp_k_chain.h"        // pp_k_chain_advance
 #include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
+#include "pp_k_tsp_table.h"    // pp_k_tsp_table_list, pp_k_tsp_table
 #include "pp_k_expand.h"       // pp_k_dubins_lengths, pp_k_select_nearest, the push-order pipeline, the round trip's pack / unpack
 #include "pp_k_incumbent.h"    // pp_k_best_stage1/2, pp_k_key_min_n

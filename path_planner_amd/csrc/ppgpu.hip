@@ -146,6 +146,7 @@ struct ppgpu_ctx {
     DevBuf<double> tmp_cover_child;
     DevBuf<int> tmp_counts;
     TraceTimer t_steps, t_cover;        // around pp_k_trace_steps / pp_k_trace_cover
+    TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
@@ -192,11 +193,17 @@ struct ppgpu_ctx {
     // ppgpu_copy_engine_read: the HSA agents of this device and of the host, the completion signal of the copy in flight
     unsigned long long hsa_gpu = 0, hsa_cpu = 0, hsa_signal = 0;
     bool copy_pending = false;
+    // the table pass over long child lists (ppgpu_set_tsp_table): 0 = off
+    int tsp_table_min = 0, tsp_table_max = 0;
+    int tsp_table_cap = 0;              // the workspace holds at least one slot for a list of this many ribbons
+    DevBuf<unsigned char> tsp_slots;
+    DevBuf<unsigned> tsp_list;
+    DevBuf<unsigned long long> tsp_words;   // [0] lists answered, [1] lists refused, [2] length of the list of the launch under way
 
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_tsp.ev[0], t_tsp.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -313,7 +320,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
         for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < EV_COUNT; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
-    for (TraceTimer* tm : {&c->t_steps, &c->t_cover}) {
+    for (TraceTimer* tm : {&c->t_steps, &c->t_cover, &c->t_tsp}) {
         if (on && !tm->ev[0])
             for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm->ev[i]));
         tm->timed = false;
@@ -391,6 +398,49 @@ int ppgpu_growth_stats(ppgpu_ctx* c, uint64_t* count, double* seconds) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     if (count) *count = g_growth_count.load(std::memory_order_relaxed);
     if (seconds) *seconds = 1e-9 * (double)g_growth_ns.load(std::memory_order_relaxed);
+    return PPGPU_OK;
+}
+
+int ppgpu_set_tsp_table(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (min_ribbons < 0 || max_ribbons < 0 || max_ribbons > PP_TSP_TABLE_MAX || (max_ribbons > 0 && min_ribbons > max_ribbons))
+        return fail(PPGPU_EINVAL, "set_tsp_table: 0 <= min_ribbons <= max_ribbons <= 16 (max_ribbons = 0: off)");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));            // no launch under way reads the fields or the slots
+    if (max_ribbons > 0) {
+        // as many slots as the budget holds, each for lists of max_ribbons (grow-only: a later, smaller range keeps the larger slots)
+        int rc = c->tsp_words.p ? PPGPU_OK : c->tsp_words.reserve(4, false, c->stream);
+        if (rc) return rc;
+        if (c->tsp_table_cap == 0) HIP_TRY(hipMemsetAsync(c->tsp_words.p, 0, 4 * sizeof(unsigned long long), c->stream));
+        const int cap = max_ribbons > c->tsp_table_cap ? max_ribbons : c->tsp_table_cap;
+        size_t slots = (size_t)PP_TSP_TABLE_BYTES / pp_tt_slot_bytes(cap);
+        if (slots > PP_TT_GRID) slots = PP_TT_GRID;
+        if (slots < 1) return fail(PPGPU_ECAPACITY, "set_tsp_table: PP_TSP_TABLE_BYTES holds no slot");
+        if (cap != c->tsp_table_cap) {
+            // (exactly what is asked for: DevBuf rounds up to a power of two of its first size, so the first size is the whole)
+            if (c->tsp_slots.p) { HIP_TRY(hipFree(c->tsp_slots.p)); c->tsp_slots.p = nullptr; c->tsp_slots.cap = 0; }
+            GrowthTimer growth;
+            HIP_TRY(hipMalloc((void**)&c->tsp_slots.p, slots * pp_tt_slot_bytes(cap)));
+            c->tsp_slots.cap = slots * pp_tt_slot_bytes(cap);
+            c->tsp_table_cap = cap;
+        }
+        // room for a million listed records per launch, allocated here and never in a costing call; what does not fit stays with the host
+        if ((rc = c->tsp_list.reserve(1u << 20, false, c->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->tsp_table_min = min_ribbons; c->tsp_table_max = max_ribbons;
+    return PPGPU_OK;
+}
+
+int ppgpu_tsp_table_stats(ppgpu_ctx* c, uint64_t* lists, uint64_t* refused) {
+    if (!c || !lists || !refused) return fail(PPGPU_EINVAL, "null argument");
+    unsigned long long w[2] = {0, 0};
+    if (c->tsp_words.p) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemcpyAsync(w, c->tsp_words.p, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    *lists = w[0]; *refused = w[1];
     return PPGPU_OK;
 }
 
@@ -1059,6 +1109,28 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
     return PPGPU_OK;
 }
 
+// The table pass over the child lists the enumeration declined (ppgpu_set_tsp_table), last of all: the records to take are listed
+// on the device, then a workgroup per listed record, striding, each with its own slot of workspace.  Nothing is launched while the
+// switch is off, for the heuristics the pass does not serve, or for a launch that keeps no child lists.
+static int tsp_table_pass(ppgpu_ctx* c, const PPParams& p) {
+    if (c->tsp_table_max <= 0 || !p.child || p.stride <= 0 || p.n_edges <= 0) return PPGPU_OK;
+    if (p.heuristic != PPGPU_H_TSP_POINT_ALL && p.heuristic != PPGPU_H_TSP_POINT_K) return PPGPU_OK;
+    hipStream_t st = c->stream;
+    PPTspTableArgs q;
+    q.out = p.out; q.child = p.child; q.stride = p.stride; q.n_edges = p.n_edges;
+    q.heuristic = p.heuristic; q.tsp_k = p.tsp_k; q.ribw = p.ribw; q.max_speed = p.max_speed; q.tpf = p.tpf;
+    q.min_ribbons = c->tsp_table_min; q.max_ribbons = c->tsp_table_max;
+    q.list = c->tsp_list.p; q.list_cap = (unsigned)c->tsp_list.cap; q.count = (unsigned*)(c->tsp_words.p + 2); q.stats = c->tsp_words.p;
+    q.slots = c->tsp_slots.p; q.bytes = c->tsp_slots.cap;
+    if (c->timing) HIP_TRY(hipEventRecord(c->t_tsp.ev[0], st));
+    HIP_TRY(hipMemsetAsync(c->tsp_words.p + 2, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(pp_k_tsp_table_list, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, q);
+    const long long grid = p.n_edges < PP_TT_GRID ? p.n_edges : PP_TT_GRID;       // (how many of them work: see the kernel)
+    hipLaunchKernelGGL(pp_k_tsp_table, dim3((unsigned)grid), dim3(PP_TT_THREADS), 0, st, q);
+    if (c->timing) { HIP_TRY(hipEventRecord(c->t_tsp.ev[1], st)); c->t_tsp.ms_earlier = 0; c->t_tsp.timed = true; }
+    return PPGPU_OK;
+}
+
 // What is left of h once every slice is swept (p: the whole list again).
 static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
     const PPParams& p = m.p;
@@ -1089,7 +1161,7 @@ static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
     if (p.heuristic == PPGPU_H_TSP_POINT_K)
         hipLaunchKernelGGL(pp_k_heuristic_big, dim3((unsigned)(total < PP_BIG_GRID ? total : PP_BIG_GRID)), dim3(PP_BIG_WPB * 64), 0, st, p);
     if (m.forked) HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-    return PPGPU_OK;
+    return tsp_table_pass(c, p);
 }
 
 // Costs the edges `asked` describes (list_params, or the dense form's own): modes, workspace, the slices one after the other, the
@@ -1238,6 +1310,7 @@ static int launch_cover_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int
 
 int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) { return c ? trace_timing(c, c->t_steps, ms_trace) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_cover, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
                            int32_t* d_counts, ppgpu_step_record* d_steps) {
@@ -1408,6 +1481,7 @@ int ppgpu_heuristic_host(ppgpu_ctx* c, int32_t n, const double* poses3, const in
     else hipLaunchKernelGGL(pp_k_heuristic, grid, block, 0, c->stream, p);
     if (p.heuristic == PPGPU_H_TSP_POINT_K)
         hipLaunchKernelGGL(pp_k_heuristic_big, dim3((unsigned)(n < PP_BIG_GRID ? n : PP_BIG_GRID)), dim3(PP_BIG_WPB * 64), 0, c->stream, p);
+    if ((rc = tsp_table_pass(c, p))) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rec.data(), c->tmp_results.p, rec.size() * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
