@@ -348,7 +348,15 @@ int ppgpu_heuristic_host(ppgpu_ctx* ctx, int32_t n, const double* h_poses3, cons
  * here, never inside a costing call.  PPGPU_EINVAL: min_ribbons < 0, max_ribbons < 0 or > PPGPU_TSP_TABLE_MAX, min > max > 0. */
 #define PPGPU_TSP_TABLE_MAX 16
 int ppgpu_set_tsp_table(ppgpu_ctx* ctx, int32_t min_ribbons, int32_t max_ribbons);
-/* Lists the pass answered / refused on this handle so far (device counters, one small copy; waits for the handle's stream). */
+/* The same pass for the Dubins-TSP heuristics (PPGPU_H_TSP_DUBINS_ALL / _K), whose enumeration stops at 8 ribbons: a switch of its
+ * own, off by default, with the arguments, the range rules and the errors of ppgpu_set_tsp_table.  Each switch serves its own two
+ * heuristics and leaves the other two alone.  The table is filled over the Dubins lengths between oriented ribbon ends that the
+ * enumeration uses, so it gives the enumeration's bits.  The reference's K variant never limits the ribbons entered:
+ * no list is refused, and with tsp_k <= 0 h is DBL_MAX / max_speed * time_penalty_factor as from the enumeration.  The workspace is
+ * the one of ppgpu_set_tsp_table, sized for the larger of the two ranges and allocated here or there, never in a costing call; the
+ * counters of ppgpu_tsp_table_stats and the time of ppgpu_last_tsp_table_timing are shared by the two switches. */
+int ppgpu_set_dubins_tsp_table(ppgpu_ctx* ctx, int32_t min_ribbons, int32_t max_ribbons);
+/* Lists the pass answered / refused on this handle so far, under either switch (device counters, one small copy; waits for the handle's stream). */
 int ppgpu_tsp_table_stats(ppgpu_ctx* ctx, uint64_t* lists, uint64_t* refused);
 /* With ppgpu_enable_timing on: device milliseconds of the last table pass (listing kernel and table kernel, from HIP events; waits
  * for it).  PPGPU_ESTATE when no pass has been timed. */

@@ -46,6 +46,7 @@ def _load():
         "ppgpu_copy_engine_wait": (C.c_int, [vp]),
         "ppgpu_heuristic_host": (C.c_int, [vp, i32, vp, vp, vp, vp, vp]),
         "ppgpu_set_tsp_table": (C.c_int, [vp, i32, i32]),
+        "ppgpu_set_dubins_tsp_table": (C.c_int, [vp, i32, i32]),
         "ppgpu_tsp_table_stats": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64)]),
         "ppgpu_last_tsp_table_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_expand_capacity": (C.c_int64, [i32, i32]),
@@ -294,6 +295,10 @@ class Context:
         """The exact-table pass over child lists of min_ribbons .. max_ribbons (<= 16) ribbons; min_ribbons = 0: the lists the
         enumeration declines; max_ribbons = 0: off (the default)."""
         self._ck(LIB.ppgpu_set_tsp_table(self._h, int(min_ribbons), int(max_ribbons)), "ppgpu_set_tsp_table")
+
+    def set_dubins_tsp_table(self, min_ribbons, max_ribbons):
+        """The same pass for the Dubins-TSP heuristics (3, 4): a switch of its own, same arguments, shared workspace and counters."""
+        self._ck(LIB.ppgpu_set_dubins_tsp_table(self._h, int(min_ribbons), int(max_ribbons)), "ppgpu_set_dubins_tsp_table")
 
     def tsp_table_stats(self):
         """(lists the table pass answered, lists it refused for a tie) on this handle so far."""

@@ -195,9 +195,11 @@ struct ppgpu_ctx {
     bool copy_pending = false;
     // the table pass over long child lists (ppgpu_set_tsp_table): 0 = off
     int tsp_table_min = 0, tsp_table_max = 0;
+    int tsp_dubins_min = 0, tsp_dubins_max = 0;   // ... over those of the Dubins-TSP heuristics (ppgpu_set_dubins_tsp_table): 0 = off
     int tsp_table_cap = 0;              // the workspace holds at least one slot for a list of this many ribbons
     DevBuf<unsigned char> tsp_slots;
     DevBuf<unsigned> tsp_list;
+    DevBuf<double> tsp_T;               // Dubins switch only: the Dubins-length tables of the listed records (PP_TT_TCAP of them)
     DevBuf<unsigned long long> tsp_words;   // [0] lists answered, [1] lists refused, [2] length of the list of the launch under way
 
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
@@ -401,7 +403,8 @@ int ppgpu_growth_stats(ppgpu_ctx* c, uint64_t* count, double* seconds) {
     return PPGPU_OK;
 }
 
-int ppgpu_set_tsp_table(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons) {
+// The two switches of the table pass: one workspace (slots sized for the larger of the two ranges, grow-only), one range each.
+static int set_table_range(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons, int& range_min, int& range_max, bool dubins) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     if (min_ribbons < 0 || max_ribbons < 0 || max_ribbons > PP_TSP_TABLE_MAX || (max_ribbons > 0 && min_ribbons > max_ribbons))
         return fail(PPGPU_EINVAL, "set_tsp_table: 0 <= min_ribbons <= max_ribbons <= 16 (max_ribbons = 0: off)");
@@ -426,10 +429,19 @@ int ppgpu_set_tsp_table(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons) 
         }
         // room for a million listed records per launch, allocated here and never in a costing call; what does not fit stays with the host
         if ((rc = c->tsp_list.reserve(1u << 20, false, c->stream))) return rc;
+        if (dubins && (rc = c->tsp_T.reserve((size_t)PP_TT_TCAP * PP_TT_TSTRIDE, false, c->stream))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->tsp_table_min = min_ribbons; c->tsp_table_max = max_ribbons;
+    range_min = min_ribbons; range_max = max_ribbons;
     return PPGPU_OK;
+}
+
+int ppgpu_set_tsp_table(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons) {
+    return c ? set_table_range(c, min_ribbons, max_ribbons, c->tsp_table_min, c->tsp_table_max, false) : fail(PPGPU_EINVAL, "null context");
+}
+
+int ppgpu_set_dubins_tsp_table(ppgpu_ctx* c, int32_t min_ribbons, int32_t max_ribbons) {
+    return c ? set_table_range(c, min_ribbons, max_ribbons, c->tsp_dubins_min, c->tsp_dubins_max, true) : fail(PPGPU_EINVAL, "null context");
 }
 
 int ppgpu_tsp_table_stats(ppgpu_ctx* c, uint64_t* lists, uint64_t* refused) {
@@ -1111,22 +1123,29 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
 
 // The table pass over the child lists the enumeration declined (ppgpu_set_tsp_table), last of all: the records to take are listed
 // on the device, then a workgroup per listed record, striding, each with its own slot of workspace.  Nothing is launched while the
-// switch is off, for the heuristics the pass does not serve, or for a launch that keeps no child lists.
+// switch of the launch's heuristic is off (the point-robot TSP heuristics have one, the Dubins-TSP heuristics another), for
+// MaxDistance, or for a launch that keeps no child lists.
 static int tsp_table_pass(ppgpu_ctx* c, const PPParams& p) {
-    if (c->tsp_table_max <= 0 || !p.child || p.stride <= 0 || p.n_edges <= 0) return PPGPU_OK;
-    if (p.heuristic != PPGPU_H_TSP_POINT_ALL && p.heuristic != PPGPU_H_TSP_POINT_K) return PPGPU_OK;
+    const bool point = p.heuristic == PPGPU_H_TSP_POINT_ALL || p.heuristic == PPGPU_H_TSP_POINT_K;
+    const bool dubins = p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K;
+    if (!point && !dubins) return PPGPU_OK;
+    const int range_min = dubins ? c->tsp_dubins_min : c->tsp_table_min, range_max = dubins ? c->tsp_dubins_max : c->tsp_table_max;
+    if (range_max <= 0 || !p.child || p.stride <= 0 || p.n_edges <= 0) return PPGPU_OK;
     hipStream_t st = c->stream;
     PPTspTableArgs q;
     q.out = p.out; q.child = p.child; q.stride = p.stride; q.n_edges = p.n_edges;
-    q.heuristic = p.heuristic; q.tsp_k = p.tsp_k; q.ribw = p.ribw; q.max_speed = p.max_speed; q.tpf = p.tpf;
-    q.min_ribbons = c->tsp_table_min; q.max_ribbons = c->tsp_table_max;
+    q.heuristic = p.heuristic; q.tsp_k = p.tsp_k; q.ribw = p.ribw; q.max_speed = p.max_speed; q.tpf = p.tpf; q.h_rho = p.h_rho;
+    q.min_ribbons = range_min; q.max_ribbons = range_max;
     q.list = c->tsp_list.p; q.list_cap = (unsigned)c->tsp_list.cap; q.count = (unsigned*)(c->tsp_words.p + 2); q.stats = c->tsp_words.p;
     q.slots = c->tsp_slots.p; q.bytes = c->tsp_slots.cap;
+    q.T = dubins ? c->tsp_T.p : nullptr;
+    if (dubins && q.list_cap > PP_TT_TCAP) q.list_cap = PP_TT_TCAP;               // a table of Dubins lengths per listed record
     if (c->timing) HIP_TRY(hipEventRecord(c->t_tsp.ev[0], st));
     HIP_TRY(hipMemsetAsync(c->tsp_words.p + 2, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(pp_k_tsp_table_list, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, q);
     const long long grid = p.n_edges < PP_TT_GRID ? p.n_edges : PP_TT_GRID;       // (how many of them work: see the kernel)
-    hipLaunchKernelGGL(pp_k_tsp_table, dim3((unsigned)grid), dim3(PP_TT_THREADS), 0, st, q);
+    if (dubins) hipLaunchKernelGGL(pp_k_tsp_table_dubins_T, dim3((unsigned)grid), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(dubins ? pp_k_tsp_table_dubins : pp_k_tsp_table, dim3((unsigned)grid), dim3(PP_TT_THREADS), 0, st, q);
     if (c->timing) { HIP_TRY(hipEventRecord(c->t_tsp.ev[1], st)); c->t_tsp.ms_earlier = 0; c->t_tsp.timed = true; }
     return PPGPU_OK;
 }

@@ -54,6 +54,8 @@ public:
     void setDeadlineGuard(bool on) { m_PlannerConfig.setDeadlineGuard(on); }
     // PlannerConfig::setChainedPreviousPlan: the previous plan is re-costed by one device call per cycle instead of one per leg
     void setChainedPreviousPlan(bool on) { m_PlannerConfig.setChainedPreviousPlan(on); }
+    // PlannerConfig::setDeviceTspTable: the heuristic of long child ribbon lists comes from the device's table pass (0 = off)
+    void setDeviceTspTable(int maxRibbons) { m_PlannerConfig.setDeviceTspTable(maxRibbons); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

@@ -59,6 +59,8 @@ public:
         long FirstGoalIteration = -1;
         unsigned long EdgesCosted = 0;
         unsigned long HostHeuristics = 0;     // children whose ribbon list exceeded the device's TSP enumeration: h computed on the host
+        unsigned long TableHeuristics = 0;    // PlannerConfig::deviceTspTable: costed records (speculated ones included) the device's table pass answered ...
+        unsigned long TableRefused = 0;       // ... and refused for a tie of sort keys (ppgpu_tsp_table_stats over this plan())
         unsigned long DeadlineStops = 0;      // round trips / sample doublings not started because they could not end before the deadline
         unsigned long OrderFallbacks = 0;     // (vertex, radius) lists whose push order the device could not replay (ppgpu_order_fallbacks)
         // Where the budget of this call went, for the time contract ("guaranteed to return before timeRemaining has elapsed",
@@ -196,6 +198,9 @@ public:
     std::vector<SearchNode> nodeArena;
     // Which occupancy map the device holds (identity + Map::version): the planner of the next cycle uploads the grid only when
     // the Executive has been given another map.  nullptr / 0: nothing cached.
+    // The range of the table pass this context's two switches were last set to by a planner (-1: never set): beginCall sets them
+    // again only when the call's PlannerConfig::deviceTspTable differs.
+    int tspTableRibbons = -1;
     const void* gridOf = nullptr;
     unsigned long gridVersion = 0;
     // round-trip result blocks not referred to by any planner any more are handed out again (used by this context's thread only)

@@ -240,6 +240,11 @@ public:
     // default.
     bool chainedPreviousPlan() const { return m_ChainedPreviousPlan; }
     void setChainedPreviousPlan(bool on) { m_ChainedPreviousPlan = on; }
+    // The TSP heuristic of children whose ribbon list exceeds the device's enumeration, by the device's exact table pass
+    // (ppgpu_set_tsp_table and ppgpu_set_dubins_tsp_table, range 0 .. maxRibbons) instead of the host search on the planning thread.
+    // 0 = off, the default; otherwise 1 .. 16 (values outside are clamped).  Lists the pass leaves flagged go to the host as before.
+    int deviceTspTable() const { return m_DeviceTspTable; }
+    void setDeviceTspTable(int maxRibbons) { m_DeviceTspTable = maxRibbons < 0 ? 0 : maxRibbons > 16 ? 16 : maxRibbons; }
 
 private:
     int m_BranchingFactor = 9;
@@ -253,6 +258,7 @@ private:
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
     bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_ChainedPreviousPlan = false;
+    int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;
     Map::SharedPtr m_Map;

@@ -134,6 +134,46 @@ static const int kRibbonStride = 64;              // child ribbon capacity per e
 static double heavyListAllowance(int maxParentRibbons) {
     return maxParentRibbons >= 11 ? 3.0e-3 : maxParentRibbons == 10 ? 1.0e-3 : maxParentRibbons == 9 ? 0.5e-3 : maxParentRibbons == 8 ? 0.25e-3 : 0.0;
 }
+// With PlannerConfig::deviceTspTable the children the enumeration declines are answered by the table pass inside the round trip.  What
+// that may take, from the measured rows of profiles/tsp_table.txt (tools/tsp_table_time.py gpu on an MI355X): milliseconds of the
+// pass for ONE list and for 2 500 lists of n ribbons, each the slowest of five runs plus their spread (max - min).  The Dubins table
+// serves both Dubins-TSP heuristics (the K variant is the All enumeration) and takes, cell by cell, the larger of the DubinsAll and the
+// DubinsK=2 row; its times include the kernel that fills the Dubins-length tables.  Lengths between two measured ones take the longer
+// one's row.
+struct TablePassTime { int ribbons; double oneMs, manyMs; };
+static const int kTablePassMany = 2500;
+static const TablePassTime kTablePassPointAll[] = {{9, 0.0934 + 0.0016, 0.9181 + 0.0058}, {12, 0.6867 + 0.0011, 7.7784 + 0.0649}, {13, 1.4777 + 0.0086, 18.9294 + 0.0518},
+                                                   {14, 3.2041 + 0.0144, 42.5274 + 0.0448}, {16, 16.3767 + 0.1111, 898.7637 + 1.7540}};
+static const TablePassTime kTablePassPointK[] = {{9, 0.0960 + 0.0005, 0.9333 + 0.0262}, {12, 0.6183 + 0.0027, 7.4828 + 0.0606}, {13, 1.2775 + 0.0052, 17.5104 + 0.0705},
+                                                 {14, 2.8462 + 0.0058, 38.3545 + 0.0607}, {16, 12.9603 + 0.0211, 739.8693 + 1.9420}};
+static const TablePassTime kTablePassDubins[] = {{9, 0.0954 + 0.0023, 0.7283 + 0.0143}, {12, 0.5674 + 0.0071, 5.5208 + 0.3579}, {13, 1.1759 + 0.0028, 12.3385 + 0.1702},
+                                                 {14, 2.4941 + 0.0112, 34.8732 + 0.0877}, {16, 12.4547 + 0.0207, 702.2817 + 1.2456}};
+// The allowance of a batch of `edges` edges whose longest parent list has maxParentRibbons ribbons under `heuristic`: today's value, and —
+// when a child list (one ribbon more than its parent's, at most tableRibbons: longer ones stay with the host) exceeds what the
+// enumeration kernels answer (8 ribbons; 12 under the point-robot K variant) — the table pass over `edges` such lists, between the
+// one-list and the 2 500-list time in proportion to the edge count (beyond 2 500 in proportion to the many-list time).
+// "One ribbon more" is today's assumption kept, a prediction and not a bound: an edge that crosses several ribbons splits each of them,
+// and the trip of such a child takes longer than predicted here.  The guard absorbs that like every other under-prediction — the excess
+// goes into its margin (GpuContext::noteExcess, up to that margin's 3 ms; a larger miss on a cycle's last trip is a late cycle, as it is
+// today when several 12-ribbon lists meet in one trip), and a trip with an allowance is kept out of the ordinary trips' model (noteTrip).  The
+// bound the option itself gives, a child of tableRibbons ribbons whatever the parent, is no use as a prediction: at 16 ribbons it is
+// 12-16 ms for one list and 80-107 ms for a batch of 256 edges, and nearly every batch of a 100 ms cycle would be refused.  Only the search loop's
+// round trips (pickedBatch) are predicted at all: the previous-plan, chained and Brown-path costing launches (costEdgeList) run the pass
+// too, with no allowance, as they run the enumeration kernels with none today.
+static double heavyListAllowance(int maxParentRibbons, RibbonManager::Heuristic heuristic, int tableRibbons, long long edges) {
+    const double today = heavyListAllowance(maxParentRibbons);
+    if (tableRibbons <= 0 || heuristic == RibbonManager::MaxDistance) return today;
+    const int enumerated = heuristic == RibbonManager::TspPointRobotNoSplitKRibbons ? 12 : 8;
+    const int child = std::min(maxParentRibbons + 1, tableRibbons);
+    if (child <= enumerated) return today;
+    const TablePassTime* rows = heuristic == RibbonManager::TspPointRobotNoSplitAllRibbons ? kTablePassPointAll
+                                : heuristic == RibbonManager::TspPointRobotNoSplitKRibbons ? kTablePassPointK : kTablePassDubins;
+    int at = 0;
+    while (at < 4 && rows[at].ribbons < child) at++;
+    const double n = (double)std::max(1ll, edges);
+    const double ms = n <= kTablePassMany ? rows[at].oneMs + (rows[at].manyMs - rows[at].oneMs) * (n - 1) / (kTablePassMany - 1) : rows[at].manyMs * n / kTablePassMany;
+    return today + 1e-3 * ms;
+}
 static const size_t kNodeArenaMin = 1u << 20;     // nodes the search tree has room for before its first node arrives (250 MB of address space, touched as used;
                                                   // a 100 ms cycle of config 5 makes 250 000 - 300 000 of them)
 
@@ -940,7 +980,8 @@ std::shared_ptr<GpuAStarPlanner::Batch> GpuAStarPlanner::pickedBatch(int source)
     std::shared_ptr<Batch> b(new Batch());
     pickBatch(source, b->sources);
     for (int v : b->sources) b->maxParent = std::max(b->maxParent, m_Nodes[v].ribbons.count());
-    b->heavy = heavyListAllowance(b->maxParent);
+    b->heavy = heavyListAllowance(b->maxParent, m_RibbonManager.heuristic(), m_Config.deviceTspTable(),
+                                  (long long)ppgpu_expand_capacity((int32_t)b->sources.size(), m_Config.branchingFactor()));
     return b;
 }
 
@@ -1125,6 +1166,14 @@ GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonMana
     if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
     m_StartStateTime = start.time();
     m_Stats.Budget.GridUploaded = uploadSnapshot(m_Ctxs, m_Config, m_RibbonManager, start.time());
+    // PlannerConfig::deviceTspTable on every context, on or off: contexts outlive planners, and the last call's range must not serve this one
+    for (const auto& ctx : m_Ctxs) {
+        const int ribbons = m_Config.deviceTspTable();
+        if (ctx->tspTableRibbons == ribbons) continue;
+        check(ppgpu_set_tsp_table(ctx->handle(), 0, ribbons), "ppgpu_set_tsp_table");
+        check(ppgpu_set_dubins_tsp_table(ctx->handle(), 0, ribbons), "ppgpu_set_dubins_tsp_table");
+        ctx->tspTableRibbons = ribbons;
+    }
     Node root;
     root.state = start;
     root.state.speed() = m_Config.maxSpeed();
@@ -1220,12 +1269,23 @@ void GpuAStarPlanner::resetSearch() {
     m_Best = -1;
 }
 
-// the devices' running counts that Stats reports per call (read before and after)
-struct GpuAStarPlanner::DeviceCounters { bool haveGrowths = false; uint64_t growths = 0; double growthSeconds = 0; unsigned long orderFallbacks = 0; };
+// the devices' running counts that Stats reports per plan() (read before and after; evaluatePlans() has no Stats and reads none).  The
+// table counters live on the device: with PlannerConfig::deviceTspTable on, each reading is a 16-byte copy and a stream synchronisation
+// on every context (ppgpu_tsp_table_stats), twice per plan(), inside the call's budget; with it off nothing is read.
+struct GpuAStarPlanner::DeviceCounters {
+    bool haveGrowths = false; uint64_t growths = 0; double growthSeconds = 0; unsigned long orderFallbacks = 0;
+    uint64_t tableLists = 0, tableRefused = 0;        // ppgpu_tsp_table_stats, summed over the contexts (PlannerConfig::deviceTspTable only)
+};
 GpuAStarPlanner::DeviceCounters GpuAStarPlanner::deviceCounters() const {
     DeviceCounters c;
     c.haveGrowths = ppgpu_growth_stats(m_Ctx->handle(), &c.growths, &c.growthSeconds) == PPGPU_OK;
     for (const auto& ctx : m_Ctxs) c.orderFallbacks += (unsigned long)ppgpu_order_fallbacks(ctx->handle());
+    if (m_Config.deviceTspTable() > 0)
+        for (const auto& ctx : m_Ctxs) {
+            uint64_t lists = 0, refused = 0;
+            check(ppgpu_tsp_table_stats(ctx->handle(), &lists, &refused), "ppgpu_tsp_table_stats");
+            c.tableLists += lists; c.tableRefused += refused;
+        }
     return c;
 }
 
@@ -1435,6 +1495,8 @@ Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const S
     // statistics: what the devices counted during this call
     const DeviceCounters after = deviceCounters();
     m_Stats.OrderFallbacks = after.orderFallbacks - before.orderFallbacks;
+    m_Stats.TableHeuristics = (unsigned long)(after.tableLists - before.tableLists);
+    m_Stats.TableRefused = (unsigned long)(after.tableRefused - before.tableRefused);
     g_prof.report("plan()");
     if (after.haveGrowths) {
         m_Stats.Budget.DeviceGrowths = (unsigned long)(after.growths - before.growths);

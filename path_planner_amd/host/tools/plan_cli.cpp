@@ -11,6 +11,7 @@
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
 //                  prologue_ms and previous_plan_legs to the JSON) | evaluate (instead of plan(): GpuAStarPlanner::evaluatePlans on the `prev`
 //                  plan, or on every prev_begin ... prev_end block of prev lines; one JSON line of PlanEvaluations) |
+//                  cfg device_tsp_table N (PlannerConfig::setDeviceTspTable; naming it at all adds table_heuristics and table_refused to the JSON) |
 //                  replan_clock_calls n (replan under a counting clock: every cycle gets n polls of dt) | plan_log path (replan: one JSON
 //                  line per cycle with the plan and the search counters)
 #include <algorithm>
@@ -51,7 +52,7 @@ int main(int argc, char** argv) {
     unsigned long shardedSeed = 7;
     int failShard = -1;
     std::string cycleLogPath, planTracePath, planCoveragePath, planLogPath;
-    bool chainNamed = false, evaluate = false, inBlock = false;
+    bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
     std::string line;
@@ -76,6 +77,7 @@ int main(int argc, char** argv) {
             else if (name == "plan_coverage") config.setPlanCoverage(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
+            else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
             else { std::fprintf(stderr, "unknown cfg %s\n", name.c_str()); return 2; }
         } else if (k == "start") {
             double x, y, h, v, t; s >> x >> y >> h >> v >> t; start = State(x, y, h, v, t);
@@ -344,6 +346,11 @@ int main(int argc, char** argv) {
                 tail += buf;
             }
             tail += "]";
+        }
+        if (tableNamed) {
+            char buf[96];
+            std::snprintf(buf, sizeof buf, ", \"table_heuristics\": %lu, \"table_refused\": %lu", st.TableHeuristics, st.TableRefused);
+            tail += buf;
         }
         if (config.planCoverage()) {              // (only with the switch on: without it the line is what it always was)
             size_t nSteps = 0;
