@@ -220,6 +220,11 @@ int ppgpu_set_config(ppgpu_ctx* ctx, const ppgpu_config* cfg);
  * (GridWorldMap.cpp:84-93).  rows == 0 selects the base Map: nothing is ever
  * blocked and the extremes are +-DBL_MAX (Map.cpp:4-6, Map.h:34). */
 int ppgpu_set_grid(ppgpu_ctx* ctx, const uint8_t* h_cells, int32_t rows, int32_t cols, double resolution);
+/* For tests and tools: the clearance map the device built from the grid (rows*cols bytes, cell (r, c) at r*cols + c: the
+ * chessboard distance in cells to the nearest cell that is blocked or outside the grid, 0 on a blocked cell, capped at 64),
+ * which decides which chunks of steps the pose sweep never samples.  Copied on the handle's stream; the call waits for it.
+ * PPGPU_EINVAL without a grid (rows == 0) or when capacity < rows*cols.  No planner path calls this. */
+int ppgpu_get_grid_clearance(ppgpu_ctx* ctx, uint8_t* h_out, int64_t capacity);
 
 /* BinaryDynamicObstaclesManager contents: n rows of
  * {x, y, heading, speed, time, width, length} exactly as passed to update()

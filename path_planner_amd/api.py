@@ -57,6 +57,7 @@ def _load():
         "ppgpu_last_cover_edges": (C.c_int, [vp, C.POINTER(i64)]),
         "ppgpu_set_config": (C.c_int, [vp, C.POINTER(PpgpuConfig)]),
         "ppgpu_set_grid": (C.c_int, [vp, vp, i32, i32, dbl]),
+        "ppgpu_get_grid_clearance": (C.c_int, [vp, vp, i64]),
         "ppgpu_set_obstacles": (C.c_int, [vp, i32, i32, vp]),
         "ppgpu_set_gaussian_obstacles": (C.c_int, [vp, i32, vp, i32]),
         "ppgpu_set_vertices": (C.c_int, [vp, i32, vp, i32, vp]),
@@ -179,6 +180,12 @@ class Context:
             return
         cells = np.ascontiguousarray(cells, dtype=np.uint8)
         self._ck(LIB.ppgpu_set_grid(self._h, _ptr(cells), cells.shape[0], cells.shape[1], float(resolution)), "ppgpu_set_grid")
+
+    def get_grid_clearance(self, rows, cols):
+        """The device's clearance map of the grid last set (rows x cols bytes); for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint8)
+        self._ck(LIB.ppgpu_get_grid_clearance(self._h, _ptr(out), out.size), "ppgpu_get_grid_clearance")
+        return out
 
     def set_obstacles(self, obst7, model=1):
         if obst7 is None or len(obst7) == 0:

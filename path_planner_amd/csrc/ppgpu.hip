@@ -533,6 +533,17 @@ int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t col
     return PPGPU_OK;
 }
 
+int ppgpu_get_grid_clearance(ppgpu_ctx* c, uint8_t* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, "grid clearance: null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, "grid clearance: no grid is set");
+    const int64_t ncell = (int64_t)c->rows * c->cols;
+    if (capacity < ncell) return fail(PPGPU_EINVAL, "grid clearance: capacity below rows * cols");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(h_out, c->grid_clear.p, (size_t)ncell, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
 int ppgpu_set_obstacles(ppgpu_ctx* c, int32_t model, int32_t n, const double* o7) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));

@@ -1,0 +1,529 @@
+"""Directed worlds for the static map on the device (ppgpu_set_grid's packing into words, pp_is_blocked / pp_blocked_cell, the clearance
+map of pp_k_grid_row_clear / pp_k_grid_clear and its lookup in pp_plan_skips_chunk, the sampler's map filter): grids that
+workloads.config1/2/3, sweep_worlds.py and tools/fuzz_parity.py never draw.  Non-square maps whose width is no multiple of 32 (padding
+bits in every row, r * cols != c * rows), single blocked cells that an edge touches with one sample, one-cell walls with a gap, an
+empty map whose centre reaches the clearance cap, maps of one row and of one column, resolutions whose reciprocal is not exact
+(1/3, 0.3, 0.07) with poses on cell boundaries, and edges that leave the map through each of its four sides.
+
+A plain module: no fixtures, no device.  tests/test_grid_worlds.py asserts on the oracle alone that every world is what it claims to
+be; tests/test_gpu_grid_inputs.py puts the same worlds on the device.  oracle_records() costs a world once per process and hands
+out read-only arrays."""
+import functools
+import math
+
+import numpy as np
+
+from path_planner_amd import workloads
+from path_planner_amd.types import make_config, edge_pack, H_MAX_DISTANCE, F_INFEASIBLE
+from sweep_worlds import SweepWorld, RIBBON_STRIDE, MASK, T0
+
+CLEAR_CAP = 64            # PP_CLEAR_CAP of pp_device.h
+
+
+class GridWorld(SweepWorld):
+    """A SweepWorld without dynamic obstacles that may carry several vertices (all at T0, all with the whole ribbon list) and an
+    explicit edge list; with one vertex and no list, every (sample, configuration) edge of mask 0xF as SweepWorld has them."""
+
+    def __init__(self, name, cfg, grid, res, ribbons4, roots5, sx, sy, sh, edges=None):
+        roots5 = np.asarray(roots5, dtype=np.float64).reshape(-1, 5)
+        super().__init__(name, cfg, np.ascontiguousarray(grid, dtype=np.uint8), res, ribbons4, roots5[0], sx, sy, sh)
+        self.verts = np.concatenate([workloads.root_vertex(r[0], r[1], r[2], r[3], r[4], self.rib) for r in roots5])
+        if edges is not None:
+            self.edges = np.ascontiguousarray(edges, dtype=np.uint64)
+
+    @property
+    def rows(self):
+        return self.grid.shape[0]
+
+    @property
+    def cols(self):
+        return self.grid.shape[1]
+
+    def with_grid(self, grid, name=None):
+        w = GridWorld(name or self.name, self.cfg, grid, self.res, self.rib, [[0, 0, 0, 0, 0]], self.sx, self.sy, self.sh, edges=self.edges)
+        w.verts = self.verts
+        return w
+
+    def cleared(self):
+        """The same world with every cell free: what is infeasible there left the map."""
+        return self.with_grid(np.zeros_like(self.grid), self.name + "-cleared")
+
+    def context(self):
+        from path_planner_amd import api
+        ctx = api.Context(0)
+        ctx.set_config(self.cfg); ctx.set_grid(self.grid, self.res)
+        ctx.set_obstacles(None)
+        ctx.set_vertices(self.verts, self.rib)
+        ctx.set_samples(self.sx, self.sy, self.sh)
+        return ctx
+
+    def oracle_world(self):
+        import oracle as orc
+        return orc.World(self.cfg, self.grid, self.res)
+
+    # what an edge descriptor says
+    def edge_vertex(self):
+        return ((self.edges >> np.uint64(32)) & np.uint64(0xFFFFFF)).astype(np.int64)
+
+    def edge_target(self):
+        return (self.edges & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+    def edge_config(self):
+        return (self.edges >> np.uint64(56)).astype(np.int64)
+
+    def step_times(self, n):
+        """The first n step times of a vertex at T0 = start_state_time: a running sum (Edge.cpp:114-120, 173), no nudge."""
+        inc = self.cfg.collision_checking_increment / self.cfg.max_speed
+        return np.add.accumulate(np.concatenate([[T0], np.full(max(n - 1, 0), inc)]))
+
+    def stop_poses(self, records, pick):
+        """(x, y) of the last pose the oracle sampled on each picked edge (the blocked one of an infeasible edge): the edge's own
+        DubinsWrapper sampled at its last step time."""
+        import oracle as orc
+        steps = (records["info"][pick] >> 16).astype(np.int64)
+        times = self.step_times(int(steps.max()) if len(steps) else 1)
+        vi, ti, ci = self.edge_vertex()[pick], self.edge_target()[pick], self.edge_config()[pick]
+        out = np.full((len(pick), 2), np.nan)
+        o5 = np.zeros(5)
+        for k in range(len(pick)):
+            if steps[k] == 0:
+                continue
+            v = self.verts[vi[k]]
+            speed = self.cfg.slow_speed if (ci[k] & 2) else self.cfg.max_speed
+            rho = self.cfg.coverage_turning_radius if (ci[k] & 1) else self.cfg.turning_radius
+            s1 = np.array([v["x"], v["y"], v["heading"], v["speed"], v["time"]], dtype=np.float64)
+            s2 = np.array([self.sx[ti[k]], self.sy[ti[k]], self.sh[ti[k]], speed, 0.0])
+            rc = orc.O.ppo_wrapper_sample(s1.ctypes.data, s2.ctypes.data, rho, speed, float(times[steps[k] - 1]), o5.ctypes.data, None)
+            if rc == 0:
+                out[k] = o5[:2]
+        return out
+
+
+def cell_of(v, res):
+    """size_t(v / res) of GridWorldMap::isBlocked for v >= 0: the IEEE quotient, truncated."""
+    return np.floor(np.asarray(v, dtype=np.float64) / res).astype(np.int64)
+
+
+def side_of(w, x, y):
+    """Which side a pose left the map through, in GridWorldMap::isBlocked's own order of tests: 'W', 'E', 'S', 'N' or '' (inside)."""
+    if x < 0:
+        return "W"
+    if x / w.res >= w.cols:
+        return "E"
+    if y < 0:
+        return "S"
+    if y / w.res >= w.rows:
+        return "N"
+    return ""
+
+
+# ------------------------------------------------------------------------------------------------------------ clearance
+def clearance_numpy(grid):
+    """PPGrid::clearance as pp_device.h defines it: the chessboard distance in cells to the nearest cell that is blocked or outside
+    the grid, 0 on a blocked cell, capped at 64.  The two separable passes: r(x, y') along each row, then
+    d(x, y) = min over dy of max(|dy|, r(x, y + dy)) with r = 0 on the rows outside."""
+    g = np.asarray(grid) != 0
+    rows, cols = g.shape
+    c = np.arange(cols)[None, :]
+    left = np.maximum.accumulate(np.where(g, c, -1), axis=1)                           # nearest blocked column at or before c (-1: outside)
+    right = np.minimum.accumulate(np.where(g, c, cols)[:, ::-1], axis=1)[:, ::-1]      # ... at or after c (cols: outside)
+    row = np.minimum(np.minimum(c - left, right - c), CLEAR_CAP)
+    pad = np.zeros((rows + 2 * CLEAR_CAP, cols), dtype=np.int64)                       # the rows outside: r = 0
+    pad[CLEAR_CAP:CLEAR_CAP + rows] = row
+    best = row.copy()
+    for dy in range(1, CLEAR_CAP):
+        up, dn = pad[CLEAR_CAP + dy:CLEAR_CAP + dy + rows], pad[CLEAR_CAP - dy:CLEAR_CAP - dy + rows]
+        best = np.minimum(best, np.maximum(dy, np.minimum(up, dn)))
+    return best.astype(np.uint8)
+
+
+def clearance_brute(grid):
+    """The definition itself, cell by cell against every blocked cell and the four sides."""
+    g = np.asarray(grid) != 0
+    rows, cols = g.shape
+    br, bc = np.nonzero(g)
+    out = np.zeros((rows, cols), dtype=np.uint8)
+    for r in range(rows):
+        for c in range(cols):
+            d = min(r + 1, rows - r, c + 1, cols - c, CLEAR_CAP)
+            if len(br):
+                d = min(d, int(np.maximum(np.abs(br - r), np.abs(bc - c)).min()))
+            out[r, c] = d
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ pillar maps
+def _pillars(rows, cols, frac, rng, keep_rc, keep=3):
+    """Single blocked cells, none touching another (not even at a corner), none within `keep` cells of keep_rc."""
+    g = np.zeros((rows, cols), dtype=np.uint8)
+    n = int(round(frac * rows * cols))
+    r0, c0 = keep_rc
+    for r, c in zip(rng.integers(0, rows, n), rng.integers(0, cols, n)):
+        if max(abs(r - r0), abs(c - c0)) > keep and not g[max(r - 1, 0):r + 2, max(c - 1, 0):c + 2].any():
+            g[r, c] = 1
+    return g
+
+
+def _grown_samples(rng, n, width, height, grow=0.1):
+    return (rng.uniform(-grow * width, (1 + grow) * width, n), rng.uniform(-grow * height, (1 + grow) * height, n),
+            rng.uniform(0, 2 * np.pi, n))
+
+
+def _pillar_world(name, rows, cols, res, frac, seed, n_samples, increment=0.05, grid=None, heading=0.0, root_rc=None):
+    cfg = make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE, collision_checking_increment=increment)
+    rng = np.random.default_rng(seed)
+    width, height = cols * res, rows * res
+    r0, c0 = root_rc or (rows // 2, cols // 2)
+    rx, ry = (c0 + 0.37) * res, (r0 + 0.61) * res
+    if grid is None:
+        grid = _pillars(rows, cols, frac, rng, (r0, c0))
+    sx, sy, sh = _grown_samples(rng, n_samples, width, height)
+    rib = [[0.3 * width, 0.62 * height, 0.7 * width, 0.62 * height], [0.3 * width, 0.3 * height, 0.7 * width, 0.34 * height]]
+    return GridWorld(name, cfg, grid, res, rib, [[rx, ry, heading, 2.5, T0]], sx, sy, sh)
+
+
+def wide():
+    """37 x 83 @ 1.0: cols % 32 = 19, rows < 64 < cols; need = 2 .. 3 cells at full speed, so the planner culls right up to the pillars."""
+    return _pillar_world("wide", 37, 83, 1.0, 0.004, 101, 256)
+
+
+def tall():
+    """201 x 45 @ 0.5: 22.5 m wide, so only a U-turn at the tighter radius from near the west side stays inside on its way south."""
+    return _pillar_world("tall", 201, 45, 0.5, 0.004, 102, 512, root_rc=(80, 7))
+
+
+def third():
+    """1 / res = 3.0000000000000004: the product x * (1 / res) and the quotient x / res are different numbers."""
+    return _pillar_world("third", 240, 100, 1.0 / 3.0, 0.004, 103, 256)
+
+
+def fine():
+    """Pillars of 0.07 m under steps of 0.25 m: an edge can step over one, and the oracle says which do."""
+    return _pillar_world("fine", 300, 700, 0.07, 0.002, 104, 512, increment=0.25)
+
+
+def open_():
+    """Empty, 60 m x 42 m: the centre is more than 64 cells from anything (the cap), need < 64 cells: whole chunks are skipped far
+    from the border and none near it."""
+    return _pillar_world("open", 300, 210, 0.2, 0.0, 105, 256, grid=np.zeros((300, 210), dtype=np.uint8))
+
+
+# ------------------------------------------------------------------------------------------------------------ walls
+WALLS_SHAPE = (150, 210)         # rows x cols @ 0.25 m: 37.5 m x 52.5 m, cols % 32 = 18
+
+
+def walls_grid():
+    rows, cols = WALLS_SHAPE
+    g = np.zeros((rows, cols), dtype=np.uint8)
+    g[110, 20:190] = 1; g[110, 97] = 0                 # horizontal, north of the root, a gap of one cell
+    g[15:100, 160] = 1; g[60, 160] = 0                 # vertical, east of the root
+    for i in range(70):                                # a diagonal staircase south-west of the root: 8-connected, so a curve can pass
+        g[20 + i, 25 + i] = 1                          # between two of its cells
+    g[20 + 35, 25 + 35] = 0
+    return g
+
+
+def walls():
+    rows, cols = WALLS_SHAPE
+    return _pillar_world("walls", rows, cols, 0.25, 0.0, 106, 384, grid=walls_grid())
+
+
+# ------------------------------------------------------------------------------------------------------------ words
+WORDS_COLS = (31, 32, 33, 63, 64, 65, 96)
+WORDS_ROWS = 40
+WORDS_HAND = (0, 30, 31, 32, 33, 62, 63, 64)           # hand-blocked columns of the one pattern (and cols - 1 of each prefix)
+WORDS_RES = 0.5
+
+
+def _words_lane(col):
+    """The row whose straight eastbound edge meets the hand-blocked cell of this column first."""
+    return 4 + 3 * WORDS_HAND.index(col) if col in WORDS_HAND else 31
+
+
+def words_pattern():
+    """40 x 96: pillars, one hand-blocked cell per listed column, each in a row of its own that is otherwise free, rows 0 and 39
+    blocked in places."""
+    rng = np.random.default_rng(107)
+    g = _pillars(WORDS_ROWS, 96, 0.004, rng, (20, 10))
+    for col in WORDS_HAND:
+        g[_words_lane(col), :] = 0
+        g[_words_lane(col), col] = 1
+    g[31, :] = 0                                       # the lane that reaches column cols - 1 of every prefix
+    g[0, 5:96:7] = 1
+    g[WORDS_ROWS - 1, 3:96:5] = 1
+    return g
+
+
+def words(cols):
+    """The first `cols` columns of the one pattern, with (31, cols - 1) blocked.  Vertex 0 is the root of the random edges; one more
+    vertex per lane heads exactly east from column 2 at a target in the last column (column 0's lane: from column 1, heading exactly
+    west, at a target in column 0): feasible with every cell cleared."""
+    assert cols in WORDS_COLS
+    g = np.ascontiguousarray(words_pattern()[:, :cols])
+    g[31, cols - 1] = 1
+    cfg = make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE)
+    rng = np.random.default_rng(108)
+    n = 160
+    # random targets over the 96-column map grown by 10 %: the same for every prefix
+    sx, sy, sh = _grown_samples(rng, n, 96 * WORDS_RES, WORDS_ROWS * WORDS_RES)
+    sx[::2] = rng.uniform(-1.0, 28 * WORDS_RES, (n + 1) // 2)          # every second one in the part that all prefixes share
+    roots = [[10.37 * WORDS_RES, 20.61 * WORDS_RES, math.pi / 2, 2.5, T0]]
+    ev, et, ec = [np.zeros(n * 4, dtype=np.int64)], [np.repeat(np.arange(n), 4)], [np.tile(np.arange(4), n)]
+    lanes = [c for c in WORDS_HAND if c < cols - 1] + [cols - 1]
+    ax, ay, ah = [], [], []
+    for col in lanes:
+        y = (_words_lane(col if col in WORDS_HAND and col < cols - 1 else -1) + 0.5) * WORDS_RES
+        if col == 0:
+            roots.append([1.5 * WORDS_RES, y, 3 * math.pi / 2, 2.5, T0]); ax.append(0.25 * WORDS_RES)
+            ah.append(3 * math.pi / 2)
+        else:
+            roots.append([2.25 * WORDS_RES, y, math.pi / 2, 2.5, T0]); ax.append((cols - 0.5) * WORDS_RES)
+            ah.append(math.pi / 2)
+        ay.append(y)
+        for c in (0, 1):                               # both radii at full speed: the same straight line
+            ev.append([len(roots) - 1]); et.append([n + len(ax) - 1]); ec.append([c])
+    sx, sy, sh = np.concatenate([sx, ax]), np.concatenate([sy, ay]), np.concatenate([sh, ah])
+    edges = edge_pack(np.concatenate(ev), np.concatenate(et), np.concatenate(ec))
+    rib = [[4.0, 13.0, 14.0, 13.0], [4.0, 6.0, 14.0, 7.0]]
+    w = GridWorld("words%d" % cols, cfg, g, WORDS_RES, rib, roots, sx, sy, sh, edges=edges)
+    w.n_random, w.lanes = n * 4, lanes
+    return w
+
+
+# ------------------------------------------------------------------------------------------------------------ tiny
+def tiny(shape):
+    cfg = make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE)
+    rng = np.random.default_rng(109)
+    n = 64
+    if shape == "5x7":
+        g = np.zeros((5, 7), dtype=np.uint8)
+        g[2, 5] = g[3, 1] = 1
+        res, root = 4.0, [13.0, 10.5, math.pi / 2, 2.5, T0]
+        n = 128
+        sx, sy, sh = _grown_samples(rng, n, 28.0, 20.0)
+        rib = [[6.0, 9.0, 20.0, 9.0]]
+    elif shape == "1x40":
+        g, res, root = np.zeros((1, 40), dtype=np.uint8), 1.0, [4.5, 0.5, math.pi / 2, 2.5, T0]
+        sx, sy, sh = rng.uniform(-4, 44, n), rng.uniform(-0.5, 1.5, n), rng.uniform(0, 2 * np.pi, n)
+        sx[:16], sy[:16], sh[:16] = np.linspace(8.0, 43.0, 16), 0.5, math.pi / 2          # straight ahead, the last two beyond the border
+        rib = [[10.0, 0.5, 30.0, 0.5]]
+    else:
+        assert shape == "40x1"
+        g, res, root = np.zeros((40, 1), dtype=np.uint8), 1.0, [0.5, 4.5, 0.0, 2.5, T0]
+        sx, sy, sh = rng.uniform(-0.5, 1.5, n), rng.uniform(-4, 44, n), rng.uniform(0, 2 * np.pi, n)
+        sx[:16], sy[:16], sh[:16] = 0.5, np.linspace(8.0, 43.0, 16), 0.0
+        rib = [[0.5, 10.0, 0.5, 30.0]]
+    return GridWorld("tiny" + shape, cfg, g, res, rib, [root], sx, sy, sh)
+
+
+TINY = ("5x7", "1x40", "40x1")
+
+
+# ------------------------------------------------------------------------------------------------------------ boundary
+BOUNDARY_RES = {"0.1": 0.1, "0.3": 0.3, "third": 1.0 / 3.0, "0.07": 0.07}
+B_ROWS, B_COLS = 75, 90           # vertices in rows / columns 3 .. 69; the walls beyond
+B_CU, B_CL, B_CB = 76, 80, 84     # eastbound lane k: cell (k, 76) blocked, cell (k - 1, 80) blocked, column 84 blocked throughout
+B_RU, B_RL, B_RB = 71, 72, 73     # northbound lane k: cell (71, k) blocked, cell (72, k - 1) blocked, row 73 blocked throughout
+
+
+def rounds_down(res, lo=3, hi=70):
+    """The k in [lo, hi) whose coordinate k * res lies in cell k - 1: size_t(k * res / res) == k - 1."""
+    k = np.arange(lo, hi)
+    return [int(v) for v in k[cell_of(k * res, res) == k - 1]]
+
+
+def boundary_lanes(res):
+    """Lane coordinates k (the vertex sits on the line k * res), at least two apart so that the cells of two lanes do not meet:
+    every k that rounds down, then others up to 12 lanes."""
+    lanes = []
+    for k in rounds_down(res) + list(range(5, 70, 4)):
+        if all(abs(k - j) >= 2 for j in lanes) and len(lanes) < 12:
+            lanes.append(k)
+    return sorted(lanes)
+
+
+def boundary(key):
+    """Straight edges along cell boundaries.  Eastbound lane k: the vertex at (8 res, k res) heading pi/2 at a target beyond the
+    east border, steps of res / 2; its poses lie on the row boundary y = k res, so GridWorldMap::isBlocked reads row
+    size_t(k res / res), k or k - 1, and every second pose lies on a column boundary.  Cell (k, 76) is blocked and cell (k - 1, 80)
+    is: the edge stops at column 76 when the quotient says row k, at column 80 when it says k - 1.  Northbound lanes likewise with
+    rows and columns exchanged, against rows 71 / 72.  A few random targets besides."""
+    res = BOUNDARY_RES[key]
+    cfg = make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE, collision_checking_increment=res / 2)
+    g = np.zeros((B_ROWS, B_COLS), dtype=np.uint8)
+    g[:, B_CB] = 1
+    g[B_RB, :] = 1
+    lanes = boundary_lanes(res)
+    roots, sx, sy, sh, ev, et, ec = [], [], [], [], [], [], []
+    for k in lanes:                                    # eastbound
+        g[k, B_CU] = 1; g[k - 1, B_CL] = 1
+        roots.append([8 * res, k * res, math.pi / 2, 2.5, T0])
+        sx.append((B_COLS + 20) * res); sy.append(k * res); sh.append(math.pi / 2)
+    for k in lanes:                                    # northbound
+        g[B_RU, k] = 1; g[B_RL, k - 1] = 1
+        roots.append([k * res, 8 * res, 0.0, 2.5, T0])
+        sx.append(k * res); sy.append((B_ROWS + 20) * res); sh.append(0.0)
+    for i in range(len(roots)):
+        for c in (0, 1):                               # both radii at full speed (steps of res / 2): the same straight line
+            ev.append(i); et.append(i); ec.append(c)
+    n_straight = len(ev)
+    rng = np.random.default_rng(110)
+    rx, ry, rh = _grown_samples(rng, 48, B_COLS * res, B_ROWS * res)
+    roots.append([40.37 * res, 35.61 * res, 0.7, 2.5, T0])
+    for i in range(48):
+        for c in range(4):
+            ev.append(len(roots) - 1); et.append(len(sx) + i); ec.append(c)
+    sx, sy, sh = np.concatenate([sx, rx]), np.concatenate([sy, ry]), np.concatenate([sh, rh])
+    rib = [[-50.0, -50.0, -40.0, -50.0]]               # out of every lane's way: no edge completes the coverage
+    w = GridWorld("boundary" + key, cfg, g, res, rib, roots, sx, sy, sh, edges=edge_pack(ev, et, ec))
+    w.lanes, w.n_straight = lanes, n_straight
+    return w
+
+
+# ------------------------------------------------------------------------------------------------------------ apex
+APEX_BLOB = 5        # cells: 0.35 m, wider than a step of 0.25 m
+
+
+def apex():
+    """Where the `dev` term of the skip planner's bound decides.  300 x 400 @ 0.07 m, steps of 0.25 m: a full-speed chunk is 15.75 m
+    of arc, and at the tighter radius (8 m) a chunk that lies wholly on a turn bulges 3.6 m from its chord, so the apex of the arc
+    is 4.9 m (70 cells) from both quarter points of the chord while a quarter of the chord is 3.9 m (56 cells).  Two vertices head
+    north and make a U-turn (right from x = 6, left from x = 26) to targets that face south; a blob of
+    5 x 5 cells sits on the apex of each first chunk, more than 64 cells from anything else.  A bound without `dev` (56 + 2 cells)
+    skips the chunk that holds the blocked pose; the bound as it is exceeds the cap there and skips nothing."""
+    res, inc, rho = 0.07, 0.25, 8.0
+    cfg = make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE, collision_checking_increment=inc)
+    g = np.zeros((300, 400), dtype=np.uint8)
+    half = 63 * inc / rho / 2                          # half the angle of a full-speed chunk at the tighter radius
+    roots, sx, sy, sh, ev, et, ec = [], [], [], [], [], [], []
+    rng = np.random.default_rng(113)
+    for i, (x0, turn) in enumerate(((6.0, 1.0), (26.0, -1.0))):
+        ax, ay = x0 + turn * (rho - rho * math.cos(half)), 5.0 + rho * math.sin(half)
+        r, c = int(ay / res) - APEX_BLOB // 2, int(ax / res) - APEX_BLOB // 2
+        g[r:r + APEX_BLOB, c:c + APEX_BLOB] = 1
+        roots.append([x0, 5.0, 0.0, 2.5, T0])
+        for j in range(12):
+            sx.append(x0 + turn * 2 * rho + rng.uniform(-0.3, 0.3)); sy.append(rng.uniform(0.5, 4.5)); sh.append(math.pi + rng.uniform(-0.1, 0.1))
+            for cb in range(4):
+                ev.append(i); et.append(len(sx) - 1); ec.append(cb)
+    rx, ry, rh = _grown_samples(rng, 40, 400 * res, 300 * res)
+    for j in range(40):
+        for cb in range(4):
+            ev.append(j % 2); et.append(len(sx) + j); ec.append(cb)
+    sx, sy, sh = np.concatenate([sx, rx]), np.concatenate([sy, ry]), np.concatenate([sh, rh])
+    return GridWorld("apex", cfg, g, res, [[10.0, 16.0, 18.0, 16.0]], roots, sx, sy, sh, edges=edge_pack(ev, et, ec))
+
+
+# ------------------------------------------------------------------------------------------------------------ the sampler's map
+def dense30():
+    """37 x 83 @ 1.0 with 30 % of the cells blocked at random: (grid, res, bounds6, ribbons4, seed) for sampler_init / sampler_add."""
+    rng = np.random.default_rng(111)
+    g = (rng.uniform(size=(37, 83)) < 0.30).astype(np.uint8)
+    w = workloads.Workload("dense30", g, 1.0, None, [[20.0, 22.0, 60.0, 22.0], [20.0, 12.0, 60.0, 14.0]], [41.37, 18.61, 0.0, 2.5, T0], 2000, 11,
+                           make_config(start_state_time=T0, heuristic=H_MAX_DISTANCE))
+    return w
+
+
+def wide_plan():
+    """A whole plan() on `wide`'s grid: (workload, initial samples, clock polls).  Two ribbons north of the start; sizes at which the
+    oracle's planner finds a goal and expands at least three vertices (tests/test_grid_worlds.py)."""
+    from path_planner_amd.types import H_TSP_POINT_K
+    g = wide().grid
+    cfg = make_config(start_state_time=T0, heuristic=H_TSP_POINT_K, tsp_k=2)
+    w = workloads.Workload("wide_plan", g, 1.0, None, [[30.0, 24.0, 55.0, 24.0], [30.0, 30.0, 55.0, 30.0]], [41.37, 18.61, 0.0, 2.5, T0], 128, 7, cfg)
+    return w, 128, 40
+
+
+PILLARS = ["wide", "tall", "third", "fine", "walls"]
+WORLDS = {"wide": wide, "tall": tall, "third": third, "fine": fine, "walls": walls, "open": open_, "apex": apex}
+WORLDS.update({"words%d" % c: functools.partial(words, c) for c in WORDS_COLS})
+WORLDS.update({"tiny" + s: functools.partial(tiny, s) for s in TINY})
+WORLDS.update({"boundary" + k: functools.partial(boundary, k) for k in BOUNDARY_RES})
+
+_CACHE = {}
+_CLEARED = {}
+
+
+def oracle_records(name):
+    """(world, records, child ribbons) of a named world, costed by the oracle once per process; the arrays are read-only."""
+    if name not in _CACHE:
+        w = WORLDS[name]()
+        cpu, cchild = w.oracle_cost()
+        cpu.setflags(write=False); cchild.setflags(write=False)
+        _CACHE[name] = (w, cpu, cchild)
+    return _CACHE[name]
+
+
+def cleared_records(name):
+    """The oracle's records of the same world with every cell free."""
+    if name not in _CLEARED:
+        w, _, _ = oracle_records(name)
+        rec, _ = w.cleared().oracle_cost()
+        rec.setflags(write=False)
+        _CLEARED[name] = rec
+    return _CLEARED[name]
+
+
+def edge_classes(name):
+    """(cell-blocked edges, {side: edges that leave through it}): cell-blocked = infeasible here, feasible with every cell cleared;
+    a side's edges = infeasible on the cleared world with the oracle's last pose beyond that side."""
+    w, cpu, _ = oracle_records(name)
+    clr = cleared_records(name)
+    inf, inf0 = (cpu["flags"] & F_INFEASIBLE) != 0, (clr["flags"] & F_INFEASIBLE) != 0
+    cell = np.nonzero(inf & ~inf0)[0]
+    out = np.nonzero(inf0 & ((clr["info"] >> 16) > 0))[0]
+    poses = w.stop_poses(clr, out)
+    sides = {s: [] for s in "WESN"}
+    for e, (x, y) in zip(out, poses):
+        if not np.isnan(x):
+            s = side_of(w, x, y)
+            if s:
+                sides[s].append(int(e))
+    return cell, {s: np.asarray(v, dtype=np.int64) for s, v in sides.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------ the skip planner's bound
+def need_cells(w, Lc, rho, plus=2, with_dev=True):
+    """pp_plan_skips_chunk's `need`: the clearance (in cells) around both quarter points of a chunk's chord above which the chunk
+    is not sampled.  plus / with_dev: the same bound with a term left out, to ask which edges hinge on that term."""
+    dev = Lc * Lc / (8.0 * rho) * (1.0 + 1e-9) + 1e-3 if with_dev else 0.0
+    return int((0.25 * Lc + dev) * (1.0 / w.res)) + plus
+
+
+def blocking_chunk_skippable(name, plus=2, with_dev=True):
+    """Of the edges of a named world that a cell blocks: those whose blocking pose lies in a whole chunk of 64 steps that a skip
+    planner with this bound would decline to sample (both quarter points of the chord between the chunk's first and last pose
+    inside the map with clearance above the bound, the bound below the cap).  With the bound as it is this must be none."""
+    import oracle as orc
+    w, cpu, _ = oracle_records(name)
+    cell, _ = edge_classes(name)
+    clear = clearance_numpy(w.grid)
+    steps = (cpu["info"] >> 16).astype(np.int64)
+    times = w.step_times(w.ng)
+    vi, ti, ci = w.edge_vertex(), w.edge_target(), w.edge_config()
+    out, o5, end = [], np.zeros(5), np.zeros(1)
+    for e in cell:
+        k0 = (int(steps[e]) - 1) // 64 * 64
+        if k0 + 63 >= w.ng:
+            continue
+        v = w.verts[vi[e]]
+        speed = w.cfg.slow_speed if (ci[e] & 2) else w.cfg.max_speed
+        rho = w.cfg.coverage_turning_radius if (ci[e] & 1) else w.cfg.turning_radius
+        s1 = np.array([v["x"], v["y"], v["heading"], v["speed"], v["time"]], dtype=np.float64)
+        s2 = np.array([w.sx[ti[e]], w.sy[ti[e]], w.sh[ti[e]], speed, 0.0])
+        ends = []
+        for k in (k0, k0 + 63):
+            if orc.O.ppo_wrapper_sample(s1.ctypes.data, s2.ctypes.data, rho, speed, float(times[k]), o5.ctypes.data, end.ctypes.data) != 0 or not times[k] < end[0]:
+                break
+            ends.append((o5[0], o5[1]))
+        if len(ends) < 2:
+            continue                                   # the chunk runs past the end of the curve: always sampled
+        (xF, yF), (xL, yL) = ends
+        need = need_cells(w, (times[k0 + 63] - times[k0]) * speed, rho, plus, with_dev)
+        ok = need < CLEAR_CAP
+        for f in (0.25, 0.75):
+            x, y = xF + f * (xL - xF), yF + f * (yL - yF)
+            ok = ok and x >= 0 and y >= 0 and x / w.res < w.cols and y / w.res < w.rows and clear[int(y / w.res), int(x / w.res)] > need
+        if ok:
+            out.append(int(e))
+    return out

@@ -167,6 +167,30 @@ def test_host_planner_matches_oracle_plan(name, init, calls, prepass_route):
             _compare(host2, st2, plan2)
 
 
+def test_host_planner_on_a_ragged_map(prepass_route):
+    """One whole plan() on a map that is neither square nor a multiple of 32 cells wide (tests/grid_worlds.py `wide`: 37 x 83 @ 1.0,
+    single blocked cells, two ribbons): the map goes through the host GridWorldMap loader and the planner's own ppgpu_set_grid.
+    tests/test_grid_worlds.py shows on the oracle alone that the sizes give a goal after at least three expansions."""
+    import oracle as orc
+    import grid_worlds as gw
+    w, init, calls = gw.wide_plan()
+    assert w.grid.shape[0] != w.grid.shape[1] and w.grid.shape[1] % 32 != 0
+    orc.O.ppo_set_ribbon_width(w.cfg.ribbon_width)
+    world = orc.World(w.cfg, w.grid, w.res, w.obst)
+    t0, dt = 1000.0, 1e-3
+    with tempfile.TemporaryDirectory() as d:
+        mp = os.path.join(d, "grid.map")
+        _write_map(w.grid, w.res, mp)
+        sc = os.path.join(d, "s.txt")
+        _scenario(w, sc, mp, t0, dt, calls, init)
+        host = _run_cli(sc)
+        rc, st, plan, itf, _ = world.plan(w.ribbons4, w.start5, calls * dt, t0, dt, initial_samples=init)
+        assert rc == 0
+        print("wide_plan", {k: host[k] for k in host if k != "plan"})
+        assert st.first_goal_iteration >= 0 and st.expanded >= 3
+        _compare(host, st, plan)
+
+
 @pytest.mark.parametrize("name,init,calls,radius,old_leg_first", [("cfg1", 64, 60, 6.0, True), ("cfg2", 256, 40, 7.0, False)])
 def test_previous_plan_leg_at_an_old_radius_is_re_solved(name, init, calls, radius, old_leg_first):
     """The replan cycle of test_host_planner_matches_oracle_plan after PlannerConfig::turningRadius changed (the coverage radius did

@@ -1,0 +1,310 @@
+"""The worlds of tests/grid_worlds.py are what they claim to be, on the oracle alone (no device): a device test over a map on which
+no edge meets a single cell after its first chunk, no edge leaves through the south side or no pose lies on a cell boundary would
+prove nothing.  Conditions, not measurements; if a map misses a bar after a seed changes, the map changes, not the bar.  Also here:
+the oracle's isBlocked against the reference's GridWorldMap on these grids (where the reference build is present), and
+clearance_numpy, the restatement the device's clearance map is held to, against the definition cell by cell."""
+import os
+import tempfile
+
+import numpy as np
+import pytest
+
+import grid_worlds as gw
+import oracle as orc
+from path_planner_amd.types import F_INFEASIBLE
+
+
+def _shape(name):
+    w, cpu, cchild = gw.oracle_records(name)
+    return w, cpu, (cpu["flags"] & F_INFEASIBLE) == 0, (cpu["info"] >> 16).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------- pillar maps and walls
+@pytest.mark.parametrize("name", gw.PILLARS)
+def test_cells_block_edges_late_and_every_side_is_left(name):
+    w, cpu, feas, steps = _shape(name)
+    assert w.rows != w.cols and w.cols % 32 != 0 and len(w.edges) <= 2048
+    cell, sides = gw.edge_classes(name)
+    late = cell[steps[cell] > 64]
+    long_ = int((feas & (steps > 128)).sum())
+    print(name, "edges", len(cpu), "feasible", int(feas.sum()), "cell-blocked", len(cell), "after step 64", len(late), "feasible beyond 128 steps", long_,
+          "left through", {s: len(v) for s, v in sides.items()})
+    assert len(cell) >= 30 and len(late) >= 15
+    assert long_ >= (20 if name == "fine" else 100)
+    for s in "WESN":
+        assert len(sides[s]) >= 20, s
+    # the oracle's last pose of a cell-blocked edge is inside the map, on a blocked cell
+    xy = w.stop_poses(cpu, cell)
+    assert not np.isnan(xy).any()
+    cx, cy = gw.cell_of(xy[:, 0], w.res), gw.cell_of(xy[:, 1], w.res)
+    assert np.all((cx >= 0) & (cx < w.cols) & (cy >= 0) & (cy < w.rows)) and np.all(w.grid[cy, cx] == 1)
+    if name != "walls":
+        # single cells: the 3 x 3 block around a blocked cell holds that cell alone
+        g = np.pad(w.grid.astype(np.int64), 1)
+        around = sum(g[1 + dr:1 + dr + w.rows, 1 + dc:1 + dc + w.cols] for dr in (-1, 0, 1) for dc in (-1, 0, 1))
+        assert np.all(around[w.grid == 1] == 1)
+        want = 0.002 if name == "fine" else 0.004
+        assert 0.8 * want <= w.grid.mean() <= want
+
+
+@pytest.mark.parametrize("name", gw.PILLARS + ["apex"])
+def test_blocking_chunks_hinge_on_the_terms_of_the_skip_planners_bound(name):
+    """pp_plan_skips_chunk skips a chunk when the clearance at both quarter points of its chord exceeds
+    need = int((Lc / 4 + dev) / res) + 2.  Restated on the oracle's poses (gw.blocking_chunk_skippable): with the bound as it is no
+    chunk that holds a blocking pose is skippable; with `+ 2` dropped several are (the device test then loses those edges); with
+    `dev` dropped the chunks of `apex` are, and only those: elsewhere int() swallows it.  `+ 1` in place of `+ 2`, which is what
+    `clear >= need` in place of `clear > need` amounts to, skips none either: a pose within R of a point of cell c lies in a cell at
+    most int(R) + 1 from c, so clearance >= int(R) + 2 is enough and the comparison as written keeps one cell to spare."""
+    as_is = gw.blocking_chunk_skippable(name)
+    no_plus = gw.blocking_chunk_skippable(name, plus=0)
+    one = gw.blocking_chunk_skippable(name, plus=1)
+    no_dev = gw.blocking_chunk_skippable(name, with_dev=False)
+    print(name, "blocking chunks skippable: as is", len(as_is), "without + 2:", len(no_plus), "with + 1:", len(one), "without dev:", len(no_dev))
+    assert as_is == [] and one == []
+    if name == "apex":
+        w, cpu, _ = gw.oracle_records(name)
+        assert len(no_dev) >= 10 and np.all(w.edge_config()[no_dev] == 0)          # full speed, the tighter radius
+        assert gw.need_cells(w, 15.75, 8.0) >= gw.CLEAR_CAP > gw.need_cells(w, 15.75, 8.0, with_dev=False)
+    elif name != "fine":
+        assert len(no_plus) >= 3
+    else:
+        w, _, _ = gw.oracle_records(name)
+        assert gw.need_cells(w, 15.75, 16.0) >= gw.CLEAR_CAP                           # full speed: nothing is skipped, the lookup alone
+
+
+def test_fine_edges_step_over_pillars():
+    """Steps of 0.25 m over cells of 0.07 m: some feasible edge's chord between two consecutive poses crosses a blocked cell."""
+    w, cpu, feas, steps = _shape("fine")
+    assert w.cfg.collision_checking_increment > 3 * w.res
+    cell, _ = gw.edge_classes("fine")
+    # an edge blocked by a cell at full speed whose slow twin (same target and radius, steps five times shorter) ... or the reverse:
+    # the slow twin samples five times as many poses of the same curve, so it is blocked wherever the fast one is, unless time ran out
+    cfgs = w.edge_config()
+    fast_free_slow_blocked = 0
+    for e in cell:
+        if cfgs[e] & 2 and feas[e - 2] and steps[e - 2] > steps[e] // 5 + 1:
+            fast_free_slow_blocked += 1
+    print("fine: slow edges blocked by a cell that the fast edge of the same curve stepped over:", fast_free_slow_blocked)
+    assert fast_free_slow_blocked >= 3
+
+
+def test_walls_have_gaps_and_a_staircase():
+    g = gw.walls_grid()
+    assert g[110, 20:190].sum() == 169 and g[15:100, 160].sum() == 84
+    d = np.array([g[20 + i, 25 + i] for i in range(70)])
+    assert d.sum() == 69 and g[20, 26] == 0 and g[21, 25] == 0           # diagonal neighbours only
+    assert np.all(g.sum(axis=0)[[c for c in range(20, 190) if c not in range(25, 95) and c != 160 and c != 97]] == 1)    # one cell wide
+
+
+def test_open_reaches_the_cap_and_chunks_are_skippable_far_from_the_border_only():
+    w, cpu, feas, steps = _shape("open")
+    assert w.grid.sum() == 0
+    cl = gw.clearance_numpy(w.grid)
+    assert cl.max() == gw.CLEAR_CAP and (cl == gw.CLEAR_CAP).sum() > 1000 and cl.min() == 1
+    # need = int((0.25 Lc + dev) / res) + 2 of pp_plan_skips_chunk for a full-speed chunk at the tighter radius
+    Lc = 63 * w.cfg.collision_checking_increment
+    need = int((0.25 * Lc + Lc * Lc / (8 * w.cfg.turning_radius) + 1e-3) / w.res) + 2
+    assert need < gw.CLEAR_CAP and (cl > need).sum() > 0.5 * cl.size and (cl <= need).sum() >= 5000
+    assert int((feas & (steps > 128)).sum()) >= 100
+    _, sides = gw.edge_classes("open")
+    assert all(len(sides[s]) >= 10 for s in "WESN")
+
+
+# ---------------------------------------------------------------------------------------------- words
+@pytest.mark.parametrize("cols", gw.WORDS_COLS)
+def test_words_every_hand_blocked_column_blocks_an_edge(cols):
+    w, cpu, feas, steps = _shape("words%d" % cols)
+    assert np.array_equal(w.grid[:, :cols - 1], gw.words_pattern()[:, :cols - 1]) and w.grid.shape == (gw.WORDS_ROWS, cols)
+    assert w.grid[0].sum() >= 2 and w.grid[-1].sum() >= 2
+    cell, sides = gw.edge_classes("words%d" % cols)
+    xy = w.stop_poses(cpu, cell)
+    hit_cols = gw.cell_of(xy[:, 0], w.res)
+    want = [c for c in gw.WORDS_HAND if c < cols] + [cols - 1]
+    print("words", cols, "cell-blocked", len(cell), "columns", sorted(set(hit_cols.tolist())), "left east", len(sides["E"]))
+    for c in want:
+        assert (hit_cols == c).sum() >= 1, c
+    assert len(sides["E"]) >= 10
+
+
+def test_words_prefixes_agree_west_of_column_30():
+    """The random edges (the same targets for every prefix) that stay west of column 30 — the largest x of the curve sampled every
+    eighth step of the 96-column world, plus those eight steps, below 30 cells — have the same records on every prefix."""
+    w96, cpu96, _, steps96 = _shape("words96")
+    nr = w96.n_random
+    stay = []
+    times = w96.step_times(int(steps96[:nr].max()))
+    o5 = np.zeros(5)
+    v = w96.verts[0]
+    s1 = np.array([v["x"], v["y"], v["heading"], v["speed"], v["time"]])
+    ti, ci = w96.edge_target(), w96.edge_config()
+    for e in range(nr):
+        speed = w96.cfg.slow_speed if ci[e] & 2 else w96.cfg.max_speed
+        rho = w96.cfg.coverage_turning_radius if ci[e] & 1 else w96.cfg.turning_radius
+        s2 = np.array([w96.sx[ti[e]], w96.sy[ti[e]], w96.sh[ti[e]], speed, 0.0])
+        xmax = s1[0]
+        for k in list(range(0, int(steps96[e]), 8)) + [int(steps96[e]) - 1]:
+            if k >= 0 and orc.O.ppo_wrapper_sample(s1.ctypes.data, s2.ctypes.data, rho, speed, float(times[k]), o5.ctypes.data, None) == 0:
+                xmax = max(xmax, o5[0])
+        if steps96[e] > 0 and xmax + 8 * w96.cfg.collision_checking_increment < 30 * w96.res:
+            stay.append(e)
+    stay = np.asarray(stay)
+    print("words: random edges that stay west of column 30:", len(stay), "of", nr, "feasible", int(((cpu96["flags"][stay] & F_INFEASIBLE) == 0).sum()))
+    assert len(stay) >= 60
+    for cols in gw.WORDS_COLS[:-1]:
+        w, cpu, _, _ = _shape("words%d" % cols)
+        assert w.n_random == nr and np.array_equal(w.edges[:nr], w96.edges[:nr])
+        assert np.array_equal(cpu[stay].view(np.uint8), cpu96[stay].view(np.uint8)), cols
+
+
+# ---------------------------------------------------------------------------------------------- tiny
+@pytest.mark.parametrize("shape", gw.TINY)
+def test_tiny_maps(shape):
+    w, cpu, feas, steps = _shape("tiny" + shape)
+    cl = gw.clearance_numpy(w.grid)
+    print("tiny", shape, "feasible", int(feas.sum()), "of", len(cpu))
+    if shape == "5x7":
+        assert w.grid.shape == (5, 7) and w.grid.sum() == 2 and w.res == 4.0
+        cell, _ = gw.edge_classes("tiny5x7")
+        assert len(cell) >= 3
+    else:
+        assert 1 in w.grid.shape and cl.max() == 1              # every cell touches the outside
+    assert int(feas.sum()) >= 5 and int((~feas).sum()) >= 20
+
+
+# ---------------------------------------------------------------------------------------------- boundary
+@pytest.mark.parametrize("key", list(gw.BOUNDARY_RES))
+def test_boundary_poses_lie_on_cell_boundaries(key):
+    w, cpu, feas, steps = _shape("boundary" + key)
+    res = w.res
+    assert w.rows != w.cols and w.cols % 32 != 0
+    ns = w.n_straight
+    lanes = w.lanes
+    assert len(lanes) >= 8 and np.all((cpu["flags"][:ns] & F_INFEASIBLE) != 0)
+    xy = w.stop_poses(cpu, np.arange(ns))
+    vi = w.edge_vertex()[:ns]
+    on_line, trunc_differs, walls = 0, 0, {"near": 0, "far": 0, "through": 0}
+    for e in range(ns):
+        east = vi[e] < len(lanes)
+        k = lanes[vi[e] % len(lanes)]
+        along, across = (xy[e, 0], xy[e, 1]) if east else (xy[e, 1], xy[e, 0])
+        # a straight edge keeps its line to a few ulps (the solver's angles are 1e-16 off zero), so which of the rows k and k - 1 the
+        # quotient names is decided pose by pose; the lane's near wall stands in row k, the far one in row k - 1, the last in both
+        assert abs(across - k * res) <= 1e-12 * k * res
+        row = int(gw.cell_of(across, res))
+        assert row in (k - 1, k)
+        near, far, last = (gw.B_CU, gw.B_CL, gw.B_CB) if east else (gw.B_RU, gw.B_RL, gw.B_RB)
+        wall = int(gw.cell_of(along, res))
+        assert wall in (near, far, last) and (wall != near or row == k) and (wall != far or row == k - 1)
+        walls["near" if wall == near else "far" if wall == far else "through"] += 1
+        # steps of res / 2 from cell 8: pose s (1-based) is at cell 8 + (s - 1) / 2, so the wall's near face is pose 2 (wall - 8) + 1;
+        # that pose is on the face to within an ulp and the quotient may still say the cell before: then the next pose stops the edge
+        first = 2 * (wall - 8) + 1
+        assert steps[e] in (first, first + 1), (e, k, steps[e], first)
+        want = wall * res if steps[e] == first else (wall + 0.5) * res
+        assert abs(along - want) <= 1e-9 * want
+        for v in (along, across):
+            q = v / res
+            if abs(q - round(q)) <= 1e-9 * abs(q):
+                on_line += 1
+                trunc_differs += int(np.floor(q)) != round(q)
+    down = gw.rounds_down(res)
+    print("boundary", key, "lanes", lanes, "k that round down", down, "stopping coordinates on a cell boundary", on_line, "of which the quotient truncates below", trunc_differs, "stopped by", walls)
+    assert on_line >= 8
+    if key in ("third", "0.3"):
+        assert len(down) >= 1 and set(down) & set(lanes) and trunc_differs >= 1
+
+
+# ---------------------------------------------------------------------------------------------- the sampler's map
+def test_dense30_keeps_most_candidates():
+    w = gw.dense30()
+    assert w.grid.shape == (37, 83) and 0.27 <= w.grid.mean() <= 0.33
+    b = w.bounds6
+    assert b[0] == 0.0 and b[1] == 83.0 and b[2] == 0.0 and b[3] == 37.0            # the non-square extents, not the reach of the vehicle
+    kept = orc.World(w.cfg, w.grid, w.res).add_samples(b, w.seed, w.ribbons4, 0, 2000)
+    print("dense30: kept", len(kept), "of 2000")
+    assert 0.60 * 2000 <= len(kept) <= 0.80 * 2000
+
+
+def test_wide_plan_finds_a_goal_after_three_expansions():
+    w, init, calls = gw.wide_plan()
+    assert len(w.ribbons4) == 2 and w.grid.shape == (37, 83)
+    orc.O.ppo_set_ribbon_width(w.cfg.ribbon_width)
+    world = orc.World(w.cfg, w.grid, w.res, w.obst)
+    rc, st, plan, _, _ = world.plan(w.ribbons4, w.start5, calls * 1e-3, 1000.0, 1e-3, initial_samples=init)
+    print("wide plan: samples", st.samples, "expanded", st.expanded, "first goal at iteration", st.first_goal_iteration, "legs", len(plan))
+    assert rc == 0 and st.first_goal_iteration >= 0 and st.expanded >= 3 and len(plan) >= 1
+
+
+# ---------------------------------------------------------------------------------------------- the oracle against the reference's map
+def _grids():
+    out = [(n, gw.WORLDS[n]().grid, gw.WORLDS[n]().res) for n in ("wide", "tall", "third", "fine", "walls", "apex", "words33", "words64", "tiny5x7", "tiny1x40", "tiny40x1")]
+    out += [("boundary" + k, gw.boundary(k).grid, gw.BOUNDARY_RES[k]) for k in gw.BOUNDARY_RES]
+    d = gw.dense30()
+    return out + [("dense30", d.grid, d.res)]
+
+
+def _points(rows, cols, res):
+    """Cell centres, every cell corner, the k * res lines against the half-cell lines, and points just outside each side."""
+    cx, cy = np.arange(cols + 1) * res, np.arange(rows + 1) * res
+    X, Y = np.meshgrid(cx, cy)
+    pts = [np.stack([X.ravel(), Y.ravel()], 1), np.stack([X.ravel() + 0.5 * res, Y.ravel() + 0.5 * res], 1),
+           np.stack([X.ravel(), Y.ravel() + 0.5 * res], 1), np.stack([X.ravel() + 0.5 * res, Y.ravel()], 1)]
+    w, h = cols * res, rows * res
+    eps = [np.nextafter(0.0, -1.0), -1e-12, -res]
+    for e in eps:
+        pts.append(np.stack([np.full(rows + 1, e), cy], 1)); pts.append(np.stack([cx, np.full(cols + 1, e)], 1))
+    for f in (np.nextafter(w, np.inf), w, np.nextafter(w, 0.0), w + res):
+        pts.append(np.stack([np.full(rows + 1, f), cy], 1))
+    for f in (np.nextafter(h, np.inf), h, np.nextafter(h, 0.0), h + res):
+        pts.append(np.stack([cx, np.full(cols + 1, f)], 1))
+    p = np.concatenate(pts)
+    return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+
+
+def test_oracle_is_blocked_matches_reference_grid_world_map():
+    REF = orc.REF
+    if REF is None:
+        pytest.skip("oracle/_ref/libpp_ref.so is not built")
+    with tempfile.TemporaryDirectory() as d:
+        for name, grid, res in _grids():
+            path = os.path.join(d, name + ".map")
+            with open(path, "w") as f:
+                f.write(repr(float(res)) + "\n")
+                for row in grid[::-1]:          # the last text line is y = 0 (GridWorldMap.cpp:25)
+                    f.write("".join("#" if c else "." for c in row) + "\n")
+            g = REF.ref_grid_load(path.encode())
+            try:
+                assert REF.ref_grid_resolution(g) == res
+                x, y = _points(grid.shape[0], grid.shape[1], res)
+                theirs = np.zeros(len(x), dtype=np.uint8)
+                REF.ref_grid_is_blocked_many(g, len(x), x.ctypes.data, y.ctypes.data, theirs.ctypes.data)
+            finally:
+                REF.ref_grid_free(g)
+            ours = orc.World(orc.PpgpuConfig(), grid, res).is_blocked(x, y)
+            bad = np.nonzero(ours != theirs)[0]
+            assert bad.size == 0, (name, x[bad[:5]].tolist(), y[bad[:5]].tolist())
+            # and the numpy restatement the device tests apply to the device's own poses
+            inside = (x >= 0) & (y >= 0) & (x / res < grid.shape[1]) & (y / res < grid.shape[0])
+            mine = np.ones(len(x), dtype=np.uint8)
+            mine[inside] = grid[gw.cell_of(y[inside], res), gw.cell_of(x[inside], res)]
+            assert np.array_equal(mine, theirs), name
+
+
+# ---------------------------------------------------------------------------------------------- the clearance map's restatement
+@pytest.mark.parametrize("which", ["tiny5x7", "tiny1x40", "tiny40x1", "words33", "random70x45"])
+def test_clearance_numpy_is_the_definition(which):
+    if which == "random70x45":
+        rng = np.random.default_rng(112)
+        grid = (rng.uniform(size=(70, 45)) < 0.01).astype(np.uint8)
+    else:
+        grid = gw.WORLDS[which]().grid
+    a, b = gw.clearance_numpy(grid), gw.clearance_brute(grid)
+    assert a.dtype == np.uint8 and a.shape == grid.shape
+    assert np.array_equal(a, b)
+    assert np.array_equal(a == 0, grid != 0) and a.max() <= gw.CLEAR_CAP
+
+
+def test_clearance_numpy_caps_at_64():
+    a = gw.clearance_numpy(np.zeros((200, 131), dtype=np.uint8))
+    assert a.max() == 64 and a[100, 65] == 64 and a[100, 63] == 64 and a[100, 62] == 63 and a[62, 65] == 63 and a[199, 130] == 1
+    assert np.array_equal(a, gw.clearance_brute(np.zeros((200, 131), dtype=np.uint8)))
