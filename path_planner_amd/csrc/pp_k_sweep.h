@@ -315,11 +315,255 @@ __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw)
 #ifndef PP_PLAN_MIN_WAVES
 #define PP_PLAN_MIN_WAVES 8   // 62 VGPRs, no spills; 0.28 -> 0.27 ms against the compiler's own choice (6 waves)
 #endif
-// the obstacle table in LDS (up to 64 obstacles) / read from memory (more)
-__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips(PPParams p, int epw) { pp_plan_skips_thread<false, true>(p, epw); }
+// the obstacle table in LDS (up to 64 obstacles; PPGPU_PLAN_SPANS=0: the tests compare the span planner below with these, and A/B runs
+// take both from one library) / read from memory (more)
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<false, true>(p, epw); }
 __global__ __launch_bounds__(256) void pp_k_plan_skips_many(PPParams p, int epw) { pp_plan_skips_thread<false, false>(p, epw); }
-__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian(PPParams p, int epw) { pp_plan_skips_thread<true, true>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<true, true>(p, epw); }
 __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p, int epw) { pp_plan_skips_thread<true, false>(p, epw); }
+
+// The same decisions with two pieces of work taken out of the thread (up to 64 obstacles, the table in LDS).  The workgroup goes
+// through three phases, and every thread stays to the last barrier (what were early returns above are predicates here):
+//
+//   boundary poses   The chord of chunk c runs from its first step 64c to step 64c + 64, the first step of chunk c + 1, where that
+//                    step exists, lies before the edge's end time and on the curve proper, and belongs to a thread of this
+//                    workgroup: each thread samples ONE pose, its first step's, leaves it in LDS, and takes the far end from its
+//                    neighbour.  Otherwise it samples its own last step 64c + 63 as above.  Everything the chord argument uses is
+//                    stated for the steps [64c, E] the chord spans, E = 64c + 64 or 64c + 63: L = d_E - d_F (so dev, the grid's two
+//                    balls and the circle around the chord's midpoint), ht = the farthest of t_F and t_E from the middle step's time
+//                    (the time row rises with the step, as every bound above already takes for granted).  The steps of the chunk
+//                    are among those of the chord, so "no pose inside" and "every pose inside" (both ends inside the shrunk convex
+//                    box) hold for them as before.  (`hs` above is a leftover of the ball test and bounds nothing any more.)
+//   span masks       A span is PP_PLAN_SPAN consecutive chunks of an edge, and its PP_PLAN_SPAN threads share out the edge's omask
+//                    (obstacle j goes to thread j mod PP_PLAN_SPAN; a short last span deals the residues round) to test each obstacle
+//                    ONCE for the whole span.  With A the pose at the span's first step (time tA, arc length dA):
+//                      two ends   B = the pose at the next span's first step, from LDS (tB, dB).  Every step the span's chords cover
+//                                 lies between the two, so its pose P has |PA| + |PB| <= Ls = dB - dA (arc lengths bound chords) and
+//                                 |P - (A+B)/2| = |(P-A) + (P-B)| / 2 <= Ls/2; its time is within (tB - tA)/2 of (tA + tB)/2, and an
+//                                 obstacle's centre moves at |Speed|.
+//                      one end    no such B (the edge ends in the span, or the tile does): a chord is only used by a chunk whose steps
+//                                 all lie before the end time on the curve proper, so every covered step has t <= tE = min(time of
+//                                 the step after the span's last, or of the row's last entry; end time) and d <= dE = min((tE - wStart) speed, length), and
+//                                 |PA| <= dE - dA; the obstacle's centre is within |Speed| (tE - tA) of where it is at tA.
+//                    An obstacle farther from that centre than reach + the pose radius + the obstacle's drift + 1e-3 (the slack of the
+//                    bounds above; the pose radius carries 1e-9 relative and 1e-3 besides) cannot hold a pose any chord of the span
+//                    covers: against() above would answer "out" or not run its box test, and leaving the obstacle out answers the
+//                    same.  (It can answer "out" where the box test's four faces could not decide: the span planner may skip a chunk
+//                    the chunkwise one samples, never the other way round for these obstacles.)  A span whose first pose is not
+//                    there keeps the whole omask.
+//   chunks           as above, over the span's mask.
+#ifndef PP_PLAN_SPAN
+#define PP_PLAN_SPAN 4        // 2 / 4 / 8: profiles/plan_spans_ab.txt
+#endif
+static_assert(PP_PLAN_SPAN >= 2 && PP_PLAN_SPAN <= 32 && 256 % PP_PLAN_SPAN == 0, "a span may not straddle a 256-chunk tile of a long edge (and 256 threads clear the span words)");
+#define PP_PLAN_SPANS_MAX (256 / PP_PLAN_SPAN + PP_PLAN_EDGES_MAX)   // epw ceil(nch / SPAN) <= (epw nch + epw (SPAN - 1)) / SPAN < 256 / SPAN + 32
+template <bool GAUSSIAN>
+__device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) {
+    constexpr int LOG = __builtin_ctz(PP_PLAN_SPAN);
+    __shared__ double s_setup[PP_PLAN_EDGES_MAX * PP_SETUP_LDS_STRIDE];
+    __shared__ PPObst s_obst[PP_WAVE];
+    __shared__ double s_bx[256], s_by[256];                    // the pose at each thread's first step; x = NaN: none
+    __shared__ unsigned long long s_span[PP_PLAN_SPANS_MAX];
+    const int tid = (int)threadIdx.x;
+    const long long el0 = (long long)blockIdx.x * epw;
+    const int ne = (int)((p.n_edges - el0 < (long long)epw) ? (p.n_edges - el0) : (long long)epw);
+    {
+        const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
+        for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
+            const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
+            if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
+        }
+        const double* os = reinterpret_cast<const double*>(p.obst);
+        double* od = reinterpret_cast<double*>(s_obst);
+        for (int i = tid; i < p.n_obst * (int)(sizeof(PPObst) / sizeof(double)); i += 256) od[i] = os[i];
+        if (tid < PP_PLAN_SPANS_MAX) s_span[tid] = 0ull;
+    }
+    __syncthreads();
+    // (blockIdx.y: further tiles of 256 chunks when one edge alone has more than 256 of them)
+    const int t = (int)blockIdx.y * 256 + tid;
+    const bool live = t < ne * p.nch;                          // (the others work on edge 0's chunk 0 and store nothing)
+    const int el = live ? (int)((unsigned)t / (unsigned)p.nch) : 0;
+    const int chunk = live ? t - el * p.nch : 0;
+    const PPEdgeSetupBody* S = reinterpret_cast<const PPEdgeSetupBody*>(&s_setup[el * PP_SETUP_LDS_STRIDE]);
+    const long long e = p.ws_base + el0 + el;
+    const int k0 = chunk * PP_WAVE;
+    const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
+    const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
+    const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
+    const double tF = (live && sane && k0 < p.ng) ? tg[k0] : INFINITY;
+    const bool reached = tF < endTime;                         // the sweep reaches this chunk
+    const double wStart = S->wStart, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv;
+    const double hi0 = S->p0, hi1 = S->hi1;
+    const double dF = (tF - wStart) * speed;
+    // ---- boundary poses
+    {
+        double x = NAN, y = 0.0;
+        if (reached && dF >= 0.0 && dF <= length) {
+            const double tpF = (rho_inv != 0.0) ? dF * rho_inv : dF / rho;
+            double ux, uy, uth;
+            pp_setup_seg_pose(S, pp_seg_of(tpF, hi0, hi1), tpF, ux, uy, uth);
+            x = ux * rho + S->qx; y = uy * rho + S->qy;
+        }
+        s_bx[tid] = x; s_by[tid] = y;
+    }
+    __syncthreads();
+    // ---- span masks
+    const int sp = live ? el * ((p.nch + PP_PLAN_SPAN - 1) >> LOG) + ((chunk - (int)blockIdx.y * 256) >> LOG) : 0;
+    {
+        const int r = chunk & (PP_PLAN_SPAN - 1), cA = chunk - r, tidA = tid - r;
+        const int nT = (p.nch - cA < PP_PLAN_SPAN) ? p.nch - cA : PP_PLAN_SPAN;       // threads of this span
+        unsigned long long mine = 0ull;
+        for (int q = r; q < PP_PLAN_SPAN; q += nT) mine |= (~0ull / ((1ull << PP_PLAN_SPAN) - 1ull)) << q;   // bits q, q + SPAN, q + 2 SPAN ...
+        unsigned long long m = live ? (S->omask & mine) : 0ull;
+        unsigned long long keep = m;
+        const double xA = s_bx[tidA], yA = s_by[tidA];
+        if (m != 0ull && xA == xA) {
+            const double tA = tg[cA * PP_WAVE], dA = (tA - wStart) * speed;
+            const int cB = cA + PP_PLAN_SPAN, tidB = tidA + PP_PLAN_SPAN;
+            const bool inTile = cB < p.nch && tidB < 256;
+            const double xB = inTile ? s_bx[tidB] : NAN, yB = inTile ? s_by[tidB] : 0.0;
+            double cx, cy, rad, tc, th;
+            if (xB == xB) {
+                const double tB = tg[cB * PP_WAVE], dB = (tB - wStart) * speed;
+                cx = 0.5 * (xA + xB); cy = 0.5 * (yA + yB); rad = 0.5 * (dB - dA); tc = 0.5 * (tA + tB); th = 0.5 * (tB - tA);
+            } else {
+                const int kE = (cB * PP_WAVE < p.ng) ? cB * PP_WAVE : p.ng - 1;
+                const double tE = fmin(tg[kE], endTime), dE = fmin((tE - wStart) * speed, length);
+                cx = xA; cy = yA; rad = dE - dA; tc = tA; th = tE - tA;
+            }
+            if (rad >= 0.0 && th >= 0.0) {
+                rad = rad * (1.0 + 1e-9) + 1e-3; th = th * (1.0 + 1e-9);
+                while (m) {
+                    const int j = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const PPObst& o = s_obst[j];
+                    const double dt = tc - o.Time;
+                    const double ddx = cx - (o.X + o.Speed * dt * o.cosYaw), ddy = cy - (o.Y + o.Speed * dt * o.sinYaw);
+                    const double R = o.reach + rad + fabs(o.Speed) * th + 1e-3;
+                    if (ddx * ddx + ddy * ddy > R * R) keep &= ~(1ull << j);
+                }
+            }
+        }
+        if (keep != 0ull) atomicOr(&s_span[sp], keep);
+    }
+    __syncthreads();
+    // ---- the chunk (no barrier from here on)
+    if (!live) return;
+    unsigned char* skipb = p.track_skip + (size_t)e * p.nch + chunk;
+    if (!reached) { *skipb = 0; return; }                      // the sweep never reaches this chunk: most threads of a short edge
+    const bool whole = k0 + PP_WAVE - 1 < p.ng;                // only whole chunks can be skipped (a cut one: see above)
+    const bool cov = (S->cbits & PPGPU_EDGE_COVERAGE) != 0;
+    const double tM = whole ? tg[k0 + PP_WAVE / 2] : tF, tL = whole ? tg[k0 + PP_WAVE - 1] : tF;
+    const double tP = (k0 > 0) ? tg[k0 - 1] : 0.0;
+    const double dP = (tP - wStart) * speed, dL = (tL - wStart) * speed;
+    const bool okGeom = whole && tL < endTime && (dF >= 0.0) && (dL <= length);   // 64 steps, all before the end time, on the curve proper
+    unsigned long long eqWord = ~0ull;
+    double tpP = 0.0;
+    int segP = 0;
+    bool okHead = true;                                        // the heading-unchanged bits of the chunk are known without sampling
+    if (!cov) {
+        // (the heading logic of pp_plan_skips_chunk, over the chunk's own 64 steps)
+        tpP = (rho_inv != 0.0) ? dP * rho_inv : dP / rho;
+        const double tpL = (rho_inv != 0.0) ? dL * rho_inv : dL / rho;
+        segP = pp_seg_of(tpP, hi0, hi1);
+        const int segL = pp_seg_of(tpL, hi0, hi1);
+        const bool straight = pp_word_seg_type(S->type, segL) == 1;
+        eqWord = straight ? ~0ull : 0ull;
+        if (k0 > 0) {
+            okHead = (dP >= 0.0) && (segP == segL) && (straight || (tpL - tpP) > 65.0 * 1e-9);
+        } else {
+            const double tpF = (rho_inv != 0.0) ? dF * rho_inv : dF / rho;
+            const int segF = pp_seg_of(tpF, hi0, hi1);
+            okHead = (dF >= 0.0) && (segF == segL) && (straight || (tpL - tpF) > 64.0 * 1e-9);
+            const PPSegBase* g = &S->seg[segF];
+            const int gtype = pp_word_seg_type(S->type, segF);
+            const double tt = (tpF - pp_seg_o1(segF, S->p0)) - pp_seg_o2(segF, S->p1);
+            const double uth0 = (gtype == 1) ? (0.0 + g->bth) : ((gtype == 0) ? (tt + g->bth) : (-tt + g->bth));
+            const bool same0 = pp_heading_from_yaw(pp_mod2pi(uth0)) == S->srcH;
+            eqWord = (eqWord & ~1ull) | (same0 ? 1ull : 0ull);
+        }
+    }
+    bool gridClear = false, obstClear = false;
+    int nInside = 0;                                           // obstacles that hold EVERY pose of the chunk (binary model)
+    bool decided = false;                                      // every obstacle either holds all poses or none
+    if (okGeom) {
+        const double xF = s_bx[tid], yF = s_by[tid];           // (okGeom: 0 <= dF <= dL <= length, so this thread left its pose there)
+        // the far end E of the chord: the neighbour's first step, or this chunk's last
+        double xE = NAN, yE = 0.0, tE = tL, dE = dL;
+        if (tid + 1 < 256 && chunk + 1 < p.nch) { xE = s_bx[tid + 1]; yE = s_by[tid + 1]; }
+        if (xE == xE) {
+            tE = tg[k0 + PP_WAVE]; dE = (tE - wStart) * speed;
+        } else {
+            const double tpL2 = (rho_inv != 0.0) ? dL * rho_inv : dL / rho;
+            double uxL, uyL, uthU;
+            pp_setup_seg_pose(S, pp_seg_of(tpL2, hi0, hi1), tpL2, uxL, uyL, uthU);
+            xE = uxL * rho + S->qx; yE = uyL * rho + S->qy;
+        }
+        const double ht = fmax(tE - tM, tM - tF);
+        const double Lc = dE - dF;
+        // (rho a power of two: the product is the quotient, to the bit, without the division's thirty instructions)
+        const double dev = ((rho_inv != 0.0) ? Lc * Lc * (0.125 * rho_inv) : Lc * Lc / (8.0 * rho)) * (1.0 + 1e-9) + 1e-3;
+        gridClear = true;
+        if (p.grid.rows != 0) {
+            // two balls around the quarter points of the chord: every chord point is within L/4 of one of them, every pose within dev
+            // of the chord
+            const int need = (int)((0.25 * Lc + dev) * p.grid.inv_res) + 2;
+            for (int h = 0; h < 2; h++) {
+                const double f = h ? 0.75 : 0.25;
+                const double x = xF + f * (xE - xF), y = yF + f * (yE - yF);
+                const double cx = x * p.grid.inv_res, cy = y * p.grid.inv_res;
+                const bool inside = (x >= 0.0) & (y >= 0.0) & (cx < (double)p.grid.cols) & (cy < (double)p.grid.rows);
+                int clear = 0;
+                if (inside) clear = (int)p.grid.clearance[(size_t)(unsigned)cy * p.grid.cols + (unsigned)cx];
+                gridClear = gridClear && inside && (need < PP_CLEAR_CAP) && (clear > need);
+            }
+        }
+        decided = true;
+        unsigned long long m = s_span[sp];                     // the obstacles that can come near this span of the edge
+        while (decided && m) {
+            const int j = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const PPObst& o = s_obst[j];
+            if (GAUSSIAN) {
+                // the 1e-13 radius around the chord's midpoint (no "inside": the density varies)
+                if (!pp_chunk_clear_of<true>(o, 0.5 * (xF + xE), 0.5 * (yF + yE), tM, 0.5 * Lc + dev, ht)) decided = false;
+                continue;
+            }
+            {
+                // every pose lies within Lc/2 + dev of the chord's midpoint, the box within its own reach of its centre, which moves
+                // at most |Speed| ht around where it is at the middle step
+                const double dtM = tM - o.Time;
+                const double ddx = 0.5 * (xF + xE) - (o.X + o.Speed * dtM * o.cosYaw), ddy = 0.5 * (yF + yE) - (o.Y + o.Speed * dtM * o.sinYaw);
+                const double R = o.reach + 0.5 * Lc + dev + fabs(o.Speed) * ht + 1e-3;
+                if (ddx * ddx + ddy * ddy > R * R) continue;
+            }
+            const double dtF = tF - o.Time, dtE = tE - o.Time;
+            const double txF = xF - (o.X + o.Speed * dtF * o.cosYaw), tyF = yF - (o.Y + o.Speed * dtF * o.sinYaw);
+            const double txE = xE - (o.X + o.Speed * dtE * o.cosYaw), tyE = yE - (o.Y + o.Speed * dtE * o.sinYaw);
+            const double rxF = txF * o.cosYaw - tyF * o.sinYaw, ryF = txF * o.sinYaw + tyF * o.cosYaw;
+            const double rxE = txE * o.cosYaw - tyE * o.sinYaw, ryE = txE * o.sinYaw + tyE * o.cosYaw;
+            const bool out = (fmin(rxF, rxE) > o.halfL + dev) | (fmax(rxF, rxE) < -o.halfL - dev) | (fmin(ryF, ryE) > o.halfW + dev) | (fmax(ryF, ryE) < -o.halfW - dev);
+            const bool in = (fmax(fabs(rxF), fabs(rxE)) < o.halfL - dev) & (fmax(fabs(ryF), fabs(ryE)) < o.halfW - dev);
+            if (in) nInside++;
+            else if (!out) decided = false;
+        }
+        obstClear = decided && nInside == 0;
+    }
+    const bool ok = okGeom && okHead && gridClear && decided;
+    *skipb = ok ? (unsigned char)(PP_SKIP_ALL | (nInside > 0 ? PP_SKIP_HITS : 0)) : (unsigned char)((gridClear ? PP_SKIP_GRID : 0) | (obstClear ? PP_SKIP_OBST : 0));
+    if (ok) {
+        p.track_chunk_hits[(size_t)e * p.nch + chunk] = (unsigned)(PP_WAVE * nInside);
+        if (!cov) p.track_eq[(size_t)e * p.nch + chunk] = eqWord;
+        if (GAUSSIAN) p.track_chunk_pen[(size_t)e * p.nch + chunk] = 0.0;
+    } else if (!cov && k0 > 0 && dP >= 0.0 && dP <= length) {
+        // not skipped: if the chunk before this one is, the sweep takes `lastHeading` from here
+        double ux, uy, uth;
+        pp_setup_seg_pose(S, segP, tpP, ux, uy, uth);
+        p.track_eq[(size_t)e * p.nch + chunk] = (unsigned long long)__double_as_longlong(pp_heading_from_yaw(pp_mod2pi(uth)));   // (the sweep replaces it by the chunk's bits)
+    }
+}
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips(PPParams p, int epw) { pp_plan_skips_spans<false>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussian(PPParams p, int epw) { pp_plan_skips_spans<true>(p, epw); }
 
 // e = the edge's slot in the workspace.  GAUSSIAN: the dynamic obstacles are GaussianDynamicObstaclesManager's (its own
 // instantiation: exp() and the density bookkeeping would otherwise cost the common kernel registers).

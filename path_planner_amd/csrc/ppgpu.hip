@@ -150,6 +150,7 @@ struct ppgpu_ctx {
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
+    bool plan_spans = true;             // env PPGPU_PLAN_SPANS=0: the skip planner tests every obstacle of an edge's list per chunk (the tests compare the two)
     int pose_chunks = 0;                // env PPGPU_POSE_CHUNKS=1: the pose sweep samples one chunk at a time (tests compare it with the batched default)
     bool lane_heuristic = true;         // env PPGPU_LANE_HEURISTIC=0: large launches keep the wave-per-edge enumeration too (tests compare the two)
     long long prepass_min_edges = PP_PREPASS_MIN_EDGES;   // env PPGPU_PREPASS_MIN_EDGES overrides (tests run the prepasses on small launches too)
@@ -292,6 +293,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* lf = std::getenv("PPGPU_LANE_FINISH")) c->lane_finish = std::atoi(lf) != 0;
     if (const char* ls = std::getenv("PPGPU_LANE_SPLIT")) c->lane_split = std::atoi(ls) != 0;
     if (const char* pc = std::getenv("PPGPU_POSE_CHUNKS")) c->pose_chunks = std::atoi(pc);
+    if (const char* ps = std::getenv("PPGPU_PLAN_SPANS")) c->plan_spans = std::atoi(ps) != 0;
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
@@ -1116,7 +1118,8 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
         if (epw > PP_PLAN_EDGES_MAX) epw = PP_PLAN_EDGES_MAX;
         const unsigned blocks = (unsigned)((p.n_edges + epw - 1) / epw);
         const bool many = p.n_obst > PP_WAVE;
-        void (*planner)(PPParams, int) = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : pp_k_plan_skips_gaussian) : (many ? pp_k_plan_skips_many : pp_k_plan_skips);
+        void (*planner)(PPParams, int) = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : (c->plan_spans ? pp_k_plan_skips_gaussian : pp_k_plan_skips_gaussian_chunkwise))
+                                                    : (many ? pp_k_plan_skips_many : (c->plan_spans ? pp_k_plan_skips : pp_k_plan_skips_chunkwise));
         hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, st, p, epw);
     }
     void (*pose)(PPParams) = m.gaussian ? pp_k_pose_sweep_gaussian : (c->pose_chunks == 1 ? pp_k_pose_sweep_single : pp_k_pose_sweep);
