@@ -509,6 +509,53 @@ int ppgpu_trace_cover_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_
  * summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
 int ppgpu_last_cover_trace_timing(ppgpu_ctx* ctx, double* ms_cover_trace);
 
+/* --------------------------------------------------------------- contact traces */
+
+/* Which contact an edge pays for: one record per (edge i, obstacle row j) at contacts[i * n_obst + j], rows in the order of
+ * ppgpu_set_obstacles / ppgpu_set_gaussian_obstacles (ppgpu_obstacle_count gives n_obst).  pp_k_trace_contacts walks the executed
+ * steps of the edge's sweep — the steps of ppgpu_step_record, same count, same poses and times — and evaluates every contact on its
+ * own at every one of them with the arithmetic of collisionExists (Edge.cpp:150-151): the contact's centre projected to the step's
+ * time, then the strict box test (BinaryDynamicObstaclesManager.cpp:4-22) or the pdf (GaussianDynamicObstaclesManager.h:31-43).
+ *   hit step, binary model     a step that is not blocked (a blocked step breaks before :150) and whose pose the contact's strict box
+ *                              holds.  For every edge sum_j hit_steps * collision_penalty_factor is the record's collision_penalty,
+ *                              exactly.
+ *   hit step, Gaussian model   a COUNTED step — not blocked, and collisionExists, the floored sum over all contacts, is not 0 — at
+ *                              which this contact's own pdf is >= 1e-5 (the manager's floor applied to the contact alone).  exposure
+ *                              sums the contact's pdf over all counted steps: sum_j exposure * collision_penalty_factor agrees with
+ *                              collision_penalty to rounding and to what the costing launch's 1e-13 cull leaves out (this walk
+ *                              culls nothing). */
+typedef struct ppgpu_contact_record {       /* 64 bytes */
+    double cpa_distance;      /* min over EVERY executed step (the blocked one included) of the distance from the pose to the
+                               * contact's centre projected to the step's time = sqrt(min d2); -1 without steps */
+    double cpa_time;          /* that step's time (the earliest step on equal d2); -1 without steps */
+    double first_hit_time, last_hit_time;   /* -1 without a hit step */
+    double exposure;          /* binary: (double)hit_steps.  Gaussian: sum of this contact's pdf over the counted steps */
+    int32_t cpa_step, hit_steps, first_hit_step, last_hit_step;   /* -1 / 0 / -1 / -1 when empty */
+    double peak;              /* Gaussian: max of this contact's pdf over every executed step; binary: 0 */
+} ppgpu_contact_record;
+
+/* Rows and model (PPGPU_OBST_*) of the handle's obstacle table: what sizes a contacts array.  Either output may be NULL. */
+int ppgpu_obstacle_count(ppgpu_ctx* ctx, int32_t* n, int32_t* model);
+/* The per-contact reports of a list of n packed descriptors: first the costing launch of ppgpu_cost_edges_list on the same list
+ * (d_results receives exactly its records), then the walk.  d_counts[i] receives the edge's step count (what
+ * ppgpu_trace_edges_list reports), d_contacts[i * n_obst + j] the record of edge i and row j; an edge without steps gets the
+ * empty record for every row.  With no obstacles set the call still writes results and counts, and touches nothing of d_contacts
+ * (which may then be NULL).  d_contacts must be 16-byte aligned.  Asynchronous on the handle's stream. */
+int ppgpu_trace_contacts_list(ppgpu_ctx* ctx, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
+                              ppgpu_contact_record* d_contacts);
+/* The same with host descriptors in and host arrays out, synchronous.  h_results may be NULL.  The records pass through a buffer of
+ * the handle that grows like its other buffers (ppgpu_growth_stats counts it); a walk that would exceed the handle's workspace
+ * budget runs as consecutive slices of the list, like a costing launch. */
+int ppgpu_trace_contacts_host(ppgpu_ctx* ctx, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t* h_counts,
+                              ppgpu_contact_record* h_contacts);
+/* ... for edges whose curve is given (as ppgpu_trace_wrapper_edges_host traces them): the contacts of a plan's segments.  A curve
+ * that starts after the vertex's first step has no steps (Edge.cpp:126-133): empty records. */
+int ppgpu_trace_contacts_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper_edge* h_wedges, ppgpu_edge_result* h_results,
+                                            int32_t* h_counts, ppgpu_contact_record* h_contacts);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_trace_contacts took in the last contact-trace call,
+ * summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
+int ppgpu_last_contact_trace_timing(ppgpu_ctx* ctx, double* ms_contact_trace);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

@@ -85,6 +85,11 @@ def _load():
         "ppgpu_trace_cover_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]),
         "ppgpu_trace_cover_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]),
         "ppgpu_last_cover_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_obstacle_count": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "ppgpu_trace_contacts_list": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+        "ppgpu_trace_contacts_host": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+        "ppgpu_trace_contacts_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+        "ppgpu_last_contact_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -435,6 +440,44 @@ class Context:
     def last_cover_trace_timing(self):
         ms = C.c_double()
         self._ck(LIB.ppgpu_last_cover_trace_timing(self._h, C.byref(ms)), "ppgpu_last_cover_trace_timing")
+        return ms.value
+
+    def obstacle_count(self):
+        """(rows, model) of the handle's obstacle table: what sizes a contacts array."""
+        n, model = C.c_int32(), C.c_int32()
+        self._ck(LIB.ppgpu_obstacle_count(self._h, C.byref(n), C.byref(model)), "ppgpu_obstacle_count")
+        return n.value, model.value
+
+    def trace_contacts_list(self, n, d_edges, d_results, d_counts, d_contacts):
+        self._ck(LIB.ppgpu_trace_contacts_list(self._h, n, _ptr(d_edges), _ptr(d_results), _ptr(d_counts), _ptr(d_contacts)),
+                 "ppgpu_trace_contacts_list")
+
+    def _trace_contacts_host(self, fn, name, e, contacts):
+        from .types import CONTACT_DTYPE
+        n = e.shape[0]
+        n_obst = self.obstacle_count()[0]
+        res = np.zeros(n, dtype=RESULT_DTYPE)
+        counts = np.zeros(n, dtype=np.int32)
+        if contacts is None:
+            contacts = np.zeros((n, n_obst), dtype=CONTACT_DTYPE)
+        assert contacts.dtype == CONTACT_DTYPE and contacts.shape == (n, n_obst) and contacts.flags["C_CONTIGUOUS"]
+        self._ck(fn(self._h, n, _ptr(e), _ptr(res), _ptr(counts), _ptr(contacts) if contacts.size else None), name)
+        return res, counts, contacts
+
+    def trace_contacts(self, edges, contacts=None):
+        """Edge::computeTrueCost contact by contact: (records as cost_edges_host returns them, step counts, contacts[n, n_obst]).
+        `contacts`: an array to write into; a zeroed one by default."""
+        e = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._trace_contacts_host(LIB.ppgpu_trace_contacts_host, "ppgpu_trace_contacts_host", e, contacts)
+
+    def trace_contacts_wrapper_edges(self, wedges, contacts=None):
+        from .types import WRAPPER_EDGE_DTYPE
+        e = np.ascontiguousarray(wedges, dtype=WRAPPER_EDGE_DTYPE)
+        return self._trace_contacts_host(LIB.ppgpu_trace_contacts_wrapper_edges_host, "ppgpu_trace_contacts_wrapper_edges_host", e, contacts)
+
+    def last_contact_trace_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_contact_trace_timing(self._h, C.byref(ms)), "ppgpu_last_contact_trace_timing")
         return ms.value
 
     @staticmethod

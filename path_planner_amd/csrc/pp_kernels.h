@@ -9,6 +9,7 @@
 #include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep
 #include "pp_k_trace.h"        // pp_k_trace_steps
 #include "pp_k_cover_trace.h"  // pp_k_trace_cover
+#include "pp_k_contact_trace.h"  // pp_k_trace_contacts
 #include "pp_k_chain.h"        // pp_k_chain_advance
 #include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
 #include "pp_k_tsp_table.h"    // pp_k_tsp_table_list, pp_k_tsp_table

@@ -87,7 +87,7 @@ struct DevBuf {
 };
 
 #define PP_TIMING_RING 8
-// The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing).
+// The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing, ppgpu_last_contact_trace_timing).
 struct TraceTimer {
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_earlier = 0;              // ... of the slices before the last one
@@ -144,8 +144,9 @@ struct ppgpu_ctx {
     DevBuf<ppgpu_cover_record> tmp_cover;  // ... and of ppgpu_trace_cover_*: the cover records of one slice,
     DevBuf<ppgpu_cover_summary> tmp_summaries;   // the summaries and final lists of the whole list
     DevBuf<double> tmp_cover_child;
+    DevBuf<ppgpu_contact_record> tmp_contacts;   // ... of ppgpu_trace_contacts_*: the contact records of one slice
     DevBuf<int> tmp_counts;
-    TraceTimer t_steps, t_cover;        // around pp_k_trace_steps / pp_k_trace_cover
+    TraceTimer t_steps, t_cover, t_contacts;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
@@ -206,7 +207,7 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_tsp.ev[0], t_tsp.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_tsp.ev[0], t_tsp.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -324,7 +325,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
         for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < EV_COUNT; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
-    for (TraceTimer* tm : {&c->t_steps, &c->t_cover, &c->t_tsp}) {
+    for (TraceTimer* tm : {&c->t_steps, &c->t_cover, &c->t_contacts, &c->t_tsp}) {
         if (on && !tm->ev[0])
             for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm->ev[i]));
         tm->timed = false;
@@ -1341,8 +1342,20 @@ static int launch_cover_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int
     });
 }
 
+// pp_k_trace_contacts over the list of L: n_obst records per edge (the stride of the passes).  Without obstacles the kernel still runs,
+// for the counts, and is handed no records.
+static int launch_contact_trace(ppgpu_ctx* c, const CostLaunch& L, int* d_counts, ppgpu_contact_record* d_contacts, ppgpu_contact_record* h_contacts) {
+    const bool none = L.p.n_obst <= 0;
+    return trace_passes(c, L, none ? 1 : L.p.n_obst, c->tmp_contacts, c->t_contacts, none ? nullptr : d_contacts, none ? nullptr : h_contacts,
+                        [&](const PPParams& q, ppgpu_contact_record* dst, long long rec_base) {
+        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_contacts_gaussian : pp_k_trace_contacts, dim3((unsigned)((q.n_edges + PP_KTRACE_WPB - 1) / PP_KTRACE_WPB)),
+                           dim3(PP_KTRACE_WPB * 64), 0, c->stream, q, dst, rec_base, d_counts);
+    });
+}
+
 int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) { return c ? trace_timing(c, c->t_steps, ms_trace) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_cover, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_contact_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_contacts, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
@@ -1374,18 +1387,49 @@ int ppgpu_trace_cover_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppg
     return launch_cover_trace(c, L, stride, d_counts, d_cover, nullptr, CoverOut{d_summaries, d_child, ribbon_stride});
 }
 
+int ppgpu_obstacle_count(ppgpu_ctx* c, int32_t* n, int32_t* model) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n) *n = c->n_obst;
+    if (model) *model = c->n_obst > 0 ? c->obst_model : PPGPU_OBST_NONE;
+    return PPGPU_OK;
+}
+
+// what a contact-trace entry was handed: the records may be missing only when there is no obstacle to report on
+static int contact_args(const ppgpu_ctx* c, const char* who, int64_t n, const void* edges, const void* counts, const void* contacts) {
+    if (n < 0 || (n > 0 && (!edges || !counts || (c->n_obst > 0 && !contacts)))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
+    return PPGPU_OK;
+}
+
+int ppgpu_trace_contacts_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
+                              ppgpu_contact_record* d_contacts) {
+    int rc = require_world(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = contact_args(c, "trace_contacts_list", n, d_edges, d_counts, d_contacts))) return rc;
+    if (n > 0 && !d_results) return fail(PPGPU_EINVAL, "trace_contacts_list: null results");
+    if (((unsigned long long)d_contacts & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_contacts_list: d_contacts must be 16-byte aligned");
+    if (n == 0) return PPGPU_OK;
+    CostLaunch L;
+    if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
+    return launch_contact_trace(c, L, d_counts, d_contacts, nullptr);
+}
+
 // ------------------------------------------------------------------------------ host lists
 // The host arrays of a trace form: step records at `stride` per edge, and how many steps each edge has.
 struct TraceOut { int32_t stride; int32_t* counts; ppgpu_step_record* steps; };
 // ... of a coverage-trace form: cover records at `stride` per edge, counts, summaries, and (may be NULL) the final lists.
 struct CoverTraceOut { int32_t stride; int32_t* counts; ppgpu_cover_record* cover; ppgpu_cover_summary* summaries; double* child; int32_t ribbon_stride; };
+// ... of a contact-trace form: counts, and one record per edge and obstacle row.
+struct ContactTraceOut { int32_t* counts; ppgpu_contact_record* contacts; };
 
 // A host list in, host records out: `who`'s n packed descriptors, or wrapper edges (`wrapper`), go up to tmp_edges / tmp_wedges,
 // are costed into tmp_results (child ribbons into a zeroed tmp_child when the caller wants them) and, for the trace forms, traced;
 // records, child ribbons and counts come home; one synchronise at the end.  h_results may be NULL for a trace.  A coverage trace
-// (`cover`) walks the list instead and brings its summaries and final lists home as well.
+// (`cover`) walks the list instead and brings its summaries and final lists home as well; a contact trace (`contact`) brings
+// its records and counts.
 static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n, const void* h_list, ppgpu_edge_result* h_results,
-                          double* h_child, int32_t stride, const TraceOut* trace = nullptr, const CoverTraceOut* cover = nullptr) {
+                          double* h_child, int32_t stride, const TraceOut* trace = nullptr, const CoverTraceOut* cover = nullptr,
+                          const ContactTraceOut* contact = nullptr) {
     int rc = wrapper ? require_vertices(c) : require_world(c);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -1395,6 +1439,8 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
         if ((rc = trace_args(who, n, h_list, cover->stride, cover->counts, cover->cover))) return rc;
         if (n > 0 && !cover->summaries) return fail(PPGPU_EINVAL, std::string(who) + ": null summaries");
         if (cover->child && cover->ribbon_stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
+    } else if (contact) {
+        if ((rc = contact_args(c, who, n, h_list, contact->counts, contact->contacts))) return rc;
     } else if (n < 0 || (n > 0 && (!h_list || !h_results))) {
         return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
     }
@@ -1405,7 +1451,7 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
     const size_t child_bytes = h_child ? (size_t)n * stride * 4 * sizeof(double) : 0;
     if ((rc = wrapper ? c->tmp_wedges.reserve((size_t)n, false, st) : c->tmp_edges.reserve((size_t)n, false, st)) ||
         (rc = c->tmp_results.reserve((size_t)n, false, st)) || (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, st))) ||
-        ((trace || cover) && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        ((trace || cover || contact) && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
         return rc;
     const size_t final_bytes = (cover && cover->child) ? (size_t)n * cover->ribbon_stride * 4 * sizeof(double) : 0;
     if (cover && ((rc = c->tmp_summaries.reserve((size_t)n, false, st)) ||
@@ -1432,6 +1478,10 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
         HIP_TRY(hipMemcpyAsync(cover->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(cover->summaries, c->tmp_summaries.p, (size_t)n * sizeof(ppgpu_cover_summary), hipMemcpyDeviceToHost, st));
         if (final_bytes) HIP_TRY(hipMemcpyAsync(cover->child, c->tmp_cover_child.p, final_bytes, hipMemcpyDeviceToHost, st));
+    }
+    if (contact) {
+        if ((rc = launch_contact_trace(c, L, c->tmp_counts.p, nullptr, contact->contacts))) return rc;
+        HIP_TRY(hipMemcpyAsync(contact->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return PPGPU_OK;
@@ -1470,6 +1520,18 @@ int ppgpu_trace_cover_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wr
                                          int32_t ribbon_stride) {
     const CoverTraceOut cover{stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride};
     return cost_host_list(c, "trace_cover_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, nullptr, &cover);
+}
+
+int ppgpu_trace_contacts_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t* h_counts,
+                              ppgpu_contact_record* h_contacts) {
+    const ContactTraceOut contact{h_counts, h_contacts};
+    return cost_host_list(c, "trace_contacts_host", false, n, h_edges, h_results, nullptr, 0, nullptr, nullptr, &contact);
+}
+
+int ppgpu_trace_contacts_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
+                                            int32_t* h_counts, ppgpu_contact_record* h_contacts) {
+    const ContactTraceOut contact{h_counts, h_contacts};
+    return cost_host_list(c, "trace_contacts_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, nullptr, nullptr, &contact);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own

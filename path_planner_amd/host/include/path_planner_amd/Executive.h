@@ -56,6 +56,8 @@ public:
     void setChainedPreviousPlan(bool on) { m_PlannerConfig.setChainedPreviousPlan(on); }
     // PlannerConfig::setDeviceTspTable: the heuristic of long child ribbon lists comes from the device's table pass (0 = off)
     void setDeviceTspTable(int maxRibbons) { m_PlannerConfig.setDeviceTspTable(maxRibbons); }
+    // PlannerConfig::setPlanContacts: every cycle's Stats carry the per-contact reports of the plan it returns
+    void setPlanContacts(bool on) { m_PlannerConfig.setPlanContacts(on); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

@@ -26,6 +26,7 @@ struct ppgpu_ctx;
 
 struct ppgpu_edge_result;   // include/ppgpu.h
 struct ppgpu_vertex;
+struct ppgpu_wrapper_edge;
 
 namespace ppamd {
 
@@ -52,6 +53,44 @@ public:
         // vertex segment s - 1 left.
         struct CoverStep { double time, toCover, remaining; uint32_t flags, step, ribbons; };
         std::vector<std::vector<CoverStep>> Coverage;
+        // With PlannerConfig::setPlanContacts: Contacts[s][j] = what Plan's segment s has to do with contact j (the rows of the
+        // obstacle manager's deviceRows, named by deviceIds): the fields of ppgpu_contact_record from one
+        // ppgpu_trace_contacts_wrapper_edges_host call over the segments — on how many steps the contact is hit, from when to
+        // when, what it adds to the penalty, the closest approach.  PlanContacts[j] = the segments merged (mergeContacts).
+        struct Contact {
+            uint32_t mmsi = 0;
+            double cpaDistance = -1, cpaTime = -1, firstHitTime = -1, lastHitTime = -1, exposure = 0, peak = 0;
+            int32_t cpaStep = -1, hitSteps = 0, firstHitStep = -1, lastHitStep = -1;     // steps count within their segment
+        };
+        std::vector<std::vector<Contact>> Contacts;
+        std::vector<Contact> PlanContacts;
+        // hitSteps and exposure summed, first and last hit the earliest and latest, the closest approach the smallest (the
+        // earlier segment on ties), peak the largest.  Step indices belong to a segment: the merged record keeps those of the
+        // segment its times come from.
+        static std::vector<Contact> mergeContacts(const std::vector<std::vector<Contact>>& segments) {
+            std::vector<Contact> out;
+            for (const std::vector<Contact>& seg : segments) {
+                if (out.empty()) {
+                    out.resize(seg.size());
+                    for (size_t j = 0; j < seg.size(); j++) out[j].mmsi = seg[j].mmsi;
+                }
+                for (size_t j = 0; j < seg.size() && j < out.size(); j++) {
+                    const Contact& c = seg[j];
+                    Contact& o = out[j];
+                    if (c.hitSteps > 0) {
+                        if (o.hitSteps == 0 || c.firstHitTime < o.firstHitTime) { o.firstHitTime = c.firstHitTime; o.firstHitStep = c.firstHitStep; }
+                        if (o.hitSteps == 0 || c.lastHitTime > o.lastHitTime) { o.lastHitTime = c.lastHitTime; o.lastHitStep = c.lastHitStep; }
+                    }
+                    o.hitSteps += c.hitSteps;
+                    o.exposure += c.exposure;
+                    if (c.peak > o.peak) o.peak = c.peak;
+                    if (c.cpaStep >= 0 && (o.cpaStep < 0 || c.cpaDistance < o.cpaDistance)) {
+                        o.cpaDistance = c.cpaDistance; o.cpaTime = c.cpaTime; o.cpaStep = c.cpaStep;
+                    }
+                }
+            }
+            return out;
+        }
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -248,6 +287,7 @@ public:
         double coverageCompletedTime = -1;    // of that vertex's RibbonManager
         bool goalReached = false;
         RibbonManager ribbons;                // ... and what it has left to cover
+        std::vector<Planner::Stats::Contact> contacts;   // PlannerConfig::setPlanContacts: the costed legs merged, per contact (Stats::mergeContacts)
     };
     // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
     // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
@@ -330,7 +370,10 @@ private:
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
     void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);
-    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage for the plan that ends at node v
+    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage / Stats::Contacts for the plan that ends at node v
+    void evaluationContacts(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+                            const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
+                            std::vector<PlanEvaluation>& out);
     void visualizePlan(const DubinsPlan& plan);
     void visualizeSamples();
     int costStateEdges(int source, const std::vector<State>& targets, const std::vector<unsigned>& cfgBits,

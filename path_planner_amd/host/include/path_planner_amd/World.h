@@ -81,6 +81,9 @@ public:
     // {x, y, heading, speed, time, c00, c01, c10, c11} (Gaussian)
     virtual int deviceModel() const { return 0; }
     virtual void deviceRows(std::vector<double>& rows) const { rows.clear(); }
+    // the MMSIs of deviceRows' rows, in the same order and with the same rows left out: whose record row j of a device contact
+    // report (ppgpu_contact_record) is
+    virtual void deviceIds(std::vector<uint32_t>& ids) const { ids.clear(); }
 };
 
 // Obstacle tracks keyed by MMSI, kept as a dense array in the order the contacts were first reported (the row order the device
@@ -108,6 +111,7 @@ public:
         m_Slot.erase(it);
     }
     const std::vector<Track>& tracks() const { return m_Tracks; }
+    const std::vector<uint32_t>& ids() const { return m_Mmsi; }       // parallel to tracks()
     void mute(uint32_t mmsi) { m_Muted.insert(mmsi); }
     void unmute(uint32_t mmsi) { m_Muted.erase(mmsi); }
     bool muted(uint32_t mmsi) const { return m_Muted.count(mmsi) != 0; }
@@ -135,6 +139,7 @@ public:
     size_t size() const { return m_Table.tracks().size(); }
     int deviceModel() const override { return 1; }
     void deviceRows(std::vector<double>& rows7) const override;
+    void deviceIds(std::vector<uint32_t>& ids) const override { ids = m_Table.ids(); }
 
 private:
     TrackTable<Track> m_Table;
@@ -156,6 +161,7 @@ public:
     size_t size() const { return m_Table.tracks().size(); }
     int deviceModel() const override { return 2; }
     void deviceRows(std::vector<double>& rows9) const override;
+    void deviceIds(std::vector<uint32_t>& ids) const override { ids = m_Table.ids(); }
 
 private:
     TrackTable<Track> m_Table;
@@ -235,6 +241,10 @@ public:
     // where coverage events fell, when coverage completed.  Off by default; with it off nothing changes.
     bool planCoverage() const { return m_PlanCoverage; }
     void setPlanCoverage(bool on) { m_PlanCoverage = on; }
+    // Per-contact reports of the returned plan (Planner::Stats::Contacts / PlanContacts) and of evaluated plans
+    // (GpuAStarPlanner::PlanEvaluation::contacts): one more device call over the plan's segments.  Off by default.
+    bool planContacts() const { return m_PlanContacts; }
+    void setPlanContacts(bool on) { m_PlanContacts = on; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -257,7 +267,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_ChainedPreviousPlan = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_ChainedPreviousPlan = false;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;

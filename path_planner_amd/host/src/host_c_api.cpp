@@ -159,6 +159,17 @@ void pph_obst_forget(void* h, unsigned mmsi) {
 double pph_obst_collision_exists(void* h, double x, double y, double t, int strict) {
     return (*static_cast<std::shared_ptr<DynamicObstaclesManager>*>(h))->collisionExists(x, y, t, strict != 0);
 }
+void pph_obst_add_ignore(void* h, unsigned mmsi) {
+    auto& m = *static_cast<std::shared_ptr<DynamicObstaclesManager>*>(h);
+    if (auto* b = dynamic_cast<BinaryDynamicObstaclesManager*>(m.get())) b->addIgnore(mmsi);
+    else if (auto* g = dynamic_cast<GaussianDynamicObstaclesManager*>(m.get())) g->addIgnore(mmsi);
+}
+int pph_obst_device_ids(void* h, unsigned* out, int cap) {
+    std::vector<uint32_t> ids;
+    (*static_cast<std::shared_ptr<DynamicObstaclesManager>*>(h))->deviceIds(ids);
+    for (size_t i = 0; i < ids.size() && (int)i < cap; i++) out[i] = ids[i];
+    return (int)ids.size();
+}
 int pph_obst_device_rows(void* h, double* out, int cap_doubles) {
     std::vector<double> rows;
     (*static_cast<std::shared_ptr<DynamicObstaclesManager>*>(h))->deviceRows(rows);

@@ -1098,12 +1098,24 @@ DubinsPlan GpuAStarPlanner::tracePlan(int v, bool addToStats) {   // Planner.cpp
     return plan;
 }
 
-// PlannerConfig::planTrace / planCoverage: the returned plan's segments swept once more, step by step, in one device call each —
+// A device contact record under its MMSI.
+static Planner::Stats::Contact contactOf(uint32_t mmsi, const ppgpu_contact_record& r) {
+    Planner::Stats::Contact c;
+    c.mmsi = mmsi;
+    c.cpaDistance = r.cpa_distance; c.cpaTime = r.cpa_time; c.firstHitTime = r.first_hit_time; c.lastHitTime = r.last_hit_time;
+    c.exposure = r.exposure; c.peak = r.peak;
+    c.cpaStep = r.cpa_step; c.hitSteps = r.hit_steps; c.firstHitStep = r.first_hit_step; c.lastHitStep = r.last_hit_step;
+    return c;
+}
+
+// PlannerConfig::planTrace / planCoverage / planContacts: the returned plan's segments swept once more, step by step, in one device call each —
 // segment s from its parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
 static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
 void GpuAStarPlanner::tracePlanSteps(int v) {
     m_Stats.Trace.clear();
     m_Stats.Coverage.clear();
+    m_Stats.Contacts.clear();
+    m_Stats.PlanContacts.clear();
     const std::vector<int> nodes = branch(v);
     const size_t n = nodes.size();
     if (n == 0) return;
@@ -1153,6 +1165,21 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
                 m_Stats.Coverage[s].push_back(Stats::CoverStep{t, c.to_cover, c.remaining, c.flags, c.step, c.ribbons});
             }
         }
+    }
+    if (m_Config.planContacts()) {
+        std::vector<uint32_t> ids;
+        m_Config.obstaclesManager().deviceIds(ids);                                               // row j of the snapshot uploadSnapshot made
+        int32_t rows = 0;
+        check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
+        if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
+        std::vector<ppgpu_contact_record> recs(n * ids.size());
+        check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
+              "ppgpu_trace_contacts_wrapper_edges_host");
+        sameCounts("plan contacts");
+        m_Stats.Contacts.resize(n);
+        for (size_t s = 0; s < n; s++)
+            for (size_t j = 0; j < ids.size(); j++) m_Stats.Contacts[s].push_back(contactOf(ids[j], recs[s * ids.size() + j]));
+        m_Stats.PlanContacts = Stats::mergeContacts(m_Stats.Contacts);
     }
 }
 
@@ -1248,7 +1275,71 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
             e.ribbons.assign(child.data() + at * (size_t)kRibbonStride * 4, std::min(recChildRibbons(r), kRibbonStride), r.coverage_completed_time);
         }
     }
+    if (m_Config.planContacts()) evaluationContacts(root, offsets, legs, res, child, costed, out);
     return out;
+}
+
+// PlanEvaluation::contacts: every costed leg of every plan swept once more from the vertex the leg before it left (the root for a
+// plan's first leg; state, g, ribbons and coverageCompletedTime from that leg's record and child list), all in one contact-trace call.
+void GpuAStarPlanner::evaluationContacts(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+                                         const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
+                                         std::vector<PlanEvaluation>& out) {
+    std::vector<uint32_t> ids;
+    m_Config.obstaclesManager().deviceIds(ids);
+    ppgpu_ctx* h = m_Ctx->handle();
+    int32_t rows = 0;
+    check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
+    if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
+    std::vector<ppgpu_vertex> verts{makeVertex(root)};
+    std::vector<double> pool;
+    ribbonsToArray(root.ribbons, pool);
+    std::vector<ppgpu_wrapper_edge> wedges;
+    std::vector<int> steps;
+    for (size_t i = 0; i < out.size(); i++) {
+        for (int k = 0; k < costed[i]; k++) {
+            const size_t at = (size_t)offsets[i] + (size_t)k;
+            ppgpu_wrapper_edge we = legs[at];
+            we.vertex = 0;
+            if (k > 0) {
+                const ppgpu_edge_result& r = res[at - 1];
+                ppgpu_vertex v;
+                v.x = r.end_x; v.y = r.end_y; v.heading = r.end_heading; v.speed = r.end_speed; v.time = r.end_time;
+                v.g = r.g;
+                v.coverage_completed_time = r.coverage_completed_time;
+                v.ribbon_offset = (int32_t)(pool.size() / 4);
+                v.ribbon_count = std::min(recChildRibbons(r), kRibbonStride);
+                const double* rows4 = child.data() + (at - 1) * (size_t)kRibbonStride * 4;
+                pool.insert(pool.end(), rows4, rows4 + 4 * (size_t)v.ribbon_count);
+                we.vertex = (int32_t)verts.size();
+                verts.push_back(v);
+            }
+            wedges.push_back(we);
+            steps.push_back(recThrows(res[at]) ? 0 : recSteps(res[at]));
+        }
+    }
+    const size_t n = wedges.size();
+    if (n == 0) {
+        for (PlanEvaluation& e : out) { e.contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) e.contacts[j].mmsi = ids[j]; }
+        return;
+    }
+    check(ppgpu_set_vertices(h, (int32_t)verts.size(), verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
+    std::vector<int32_t> counts(n, 0);
+    std::vector<ppgpu_contact_record> recs(n * ids.size());
+    check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
+          "ppgpu_trace_contacts_wrapper_edges_host");
+    size_t w = 0;
+    for (size_t i = 0; i < out.size(); i++) {
+        std::vector<std::vector<Stats::Contact>> segs((size_t)costed[i]);
+        for (int k = 0; k < costed[i]; k++, w++) {
+            if (counts[w] != steps[w])
+                throw std::runtime_error("plan contacts: leg " + std::to_string(k) + " of plan " + std::to_string(i) + " traced " + std::to_string(counts[w]) +
+                                         " steps, its edge executed " + std::to_string(steps[w]));
+            for (size_t j = 0; j < ids.size(); j++) segs[(size_t)k].push_back(contactOf(ids[j], recs[w * ids.size() + j]));
+        }
+        out[i].contacts = Stats::mergeContacts(segs);
+        if (out[i].contacts.empty()) { out[i].contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) out[i].contacts[j].mmsi = ids[j]; }
+    }
+    setOpenVertex(root);      // (the handle's open vertices are the call's again)
 }
 
 // ------------------------------------------------------------------------------------------------ plan(), step by step
@@ -1467,7 +1558,7 @@ void GpuAStarPlanner::reportPlan() {
     m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
     m_Stats.PlanHValue = m_Nodes[m_Best].h;
     m_Stats.Plan = tracePlan(m_Best);
-    if (m_Config.planTrace() || m_Config.planCoverage()) tracePlanSteps(m_Best);
+    if (m_Config.planTrace() || m_Config.planCoverage() || m_Config.planContacts()) tracePlanSteps(m_Best);
 }
 
 Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,

@@ -6,6 +6,8 @@
 //                  ribbon_width w | obstacle x y heading speed time width length | gaussian x y heading speed time [c00 c01 c10 c11] | map_file path | clock t0 dt |
 //                  plan_trace_file path (with cfg plan_trace 1: one line per step of the returned plan) |
 //                  plan_coverage_file path (with cfg plan_coverage 1: one line per step, what it did to the ribbons) |
+//                  plan_contacts_file path (with cfg plan_contacts 1: one line per segment and contact, what the segment has to do with it;
+//                  the MMSIs are those the obstacle / gaussian lines were given, 1, 2, ... in file order) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -26,6 +28,21 @@
 #include "path_planner_amd/Planner.h"
 
 using namespace ppamd;
+
+// ", plan_contacts_hit ..., nearest_contact_mmsi ..., nearest_contact_cpa ..." of a plan's merged contact records (-1 / -1 without a
+// contact that has a closest approach)
+static std::string contactKeys(const std::vector<Planner::Stats::Contact>& contacts) {
+    int hit = 0;
+    long nearest = -1;
+    double cpa = -1;
+    for (const Planner::Stats::Contact& c : contacts) {
+        if (c.hitSteps > 0) hit++;
+        if (c.cpaStep >= 0 && (nearest < 0 || c.cpaDistance < cpa)) { nearest = (long)c.mmsi; cpa = c.cpaDistance; }
+    }
+    char buf[160];
+    std::snprintf(buf, sizeof buf, ", \"plan_contacts_hit\": %d, \"nearest_contact_mmsi\": %ld, \"nearest_contact_cpa\": %.17g", hit, nearest, cpa);
+    return buf;
+}
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: plan_cli scenario.txt\n"); return 2; }
@@ -51,7 +68,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planCoveragePath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planLogPath;
     bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -75,6 +92,7 @@ int main(int argc, char** argv) {
             else if (name == "speculation") config.setSpeculation((int)v);
             else if (name == "plan_trace") config.setPlanTrace(v != 0);
             else if (name == "plan_coverage") config.setPlanCoverage(v != 0);
+            else if (name == "plan_contacts") config.setPlanContacts(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -105,6 +123,7 @@ int main(int argc, char** argv) {
         } else if (k == "cycle_log") { s >> cycleLogPath;    // replan: one JSON line per cycle (Stats::Budget and what the cycle reached)
         } else if (k == "plan_trace_file") { s >> planTracePath;   // segment step x y heading time collision penalty_before flags
         } else if (k == "plan_coverage_file") { s >> planCoveragePath;   // segment step time to_cover remaining ribbons flags
+        } else if (k == "plan_contacts_file") { s >> planContactsPath;   // segment mmsi hit_steps first_hit_time last_hit_time cpa_distance cpa_time exposure peak
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -175,7 +194,7 @@ int main(int argc, char** argv) {
                 for (size_t k = 0; k < e.legs.size(); k++)
                     std::printf("%s{\"feasible\": %s, \"g\": %.17g, \"collision_penalty\": %.17g}", k ? ", " : "", e.legs[k].feasible ? "true" : "false", e.legs[k].g,
                                 e.legs[k].collisionPenalty);
-                std::printf("]}");
+                std::printf("]%s}", config.planContacts() ? contactKeys(e.contacts).c_str() : "");
             }
             std::printf("]}\n");
             return 0;
@@ -364,6 +383,18 @@ int main(int argc, char** argv) {
                 for (size_t sg = 0; sg < st.Coverage.size(); sg++)
                     for (const auto& c : st.Coverage[sg])
                         std::fprintf(f, "%zu %u %.17g %.17g %.17g %u %u\n", sg, c.step, c.time, c.toCover, c.remaining, c.ribbons, c.flags);
+                std::fclose(f);
+            }
+        }
+        if (config.planContacts()) {              // (only with the switch on: without it the line is what it always was)
+            tail += contactKeys(st.PlanContacts);
+            if (!planContactsPath.empty()) {
+                FILE* f = std::fopen(planContactsPath.c_str(), "w");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", planContactsPath.c_str()); return 2; }
+                for (size_t sg = 0; sg < st.Contacts.size(); sg++)
+                    for (const auto& c : st.Contacts[sg])
+                        std::fprintf(f, "%zu %u %d %.17g %.17g %.17g %.17g %.17g %.17g\n", sg, c.mmsi, c.hitSteps, c.firstHitTime, c.lastHitTime, c.cpaDistance, c.cpaTime,
+                                     c.exposure, c.peak);
                 std::fclose(f);
             }
         }

@@ -88,6 +88,13 @@ COVER_SUMMARY_DTYPE = np.dtype([
 ])
 assert COVER_SUMMARY_DTYPE.itemsize == 32
 
+# struct ppgpu_contact_record, 64 bytes, per (edge, obstacle row): hits, exposure and closest approach (ppgpu_trace_contacts_*)
+CONTACT_DTYPE = np.dtype([
+    ("cpa_distance", "<f8"), ("cpa_time", "<f8"), ("first_hit_time", "<f8"), ("last_hit_time", "<f8"), ("exposure", "<f8"),
+    ("cpa_step", "<i4"), ("hit_steps", "<i4"), ("first_hit_step", "<i4"), ("last_hit_step", "<i4"), ("peak", "<f8"),
+])
+assert CONTACT_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
