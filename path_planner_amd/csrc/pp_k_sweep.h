@@ -105,28 +105,28 @@ __device__ __forceinline__ void pp_window_pose(const PPEdgeSetup* S, const PPCur
         pp_window_pose<PP_COVER_SINCOS_TAB>(_S, _hot, _cur, _cs, t, t0, valid, x, y, _u, _e);              \
     } while (0)
 // Which 64-step chunks of an edge's sweep can be skipped?  One THREAD per (edge, chunk), in a kernel of its own ahead of the pose
-// sweep (inside the sweep the test's registers pushed the per-step loop into spills).  A chunk is skipped when it provably changes
-// nothing the sweep records:
+// sweep (inside the sweep the test's registers pushed the per-step loop into spills).  The decision is pp_plan_chunk below, the one
+// body of all six planner kernels; its two callers differ in where the ends of the chunk's chord come from and which obstacles it
+// is shown (pp_plan_skips_chunk: sampled by the thread, the edge's omask or the whole table; pp_plan_skips_spans: shared between
+// neighbouring threads, the obstacles that can come near the chunk's span).  A chunk is skipped when it provably changes nothing the
+// sweep records:
 //   * all 64 steps exist and lie before the edge's end time, on the curve proper (no retry at the ends);
-//   * every pose of the chunk lies within `hs` (arc length from the chunk's middle step, so also Euclidean distance) of the middle
-//     pose, and the clearance map says every cell within that distance of the middle pose's cell is free and inside the grid
-//     (+2 cells for the pose's place inside its cell and the rounding of the cell index): no step can be blocked;
-//   * no obstacle can hold any pose of the chunk: seen from the middle step, the pose stays outside the obstacle's box grown by
-//     the distance pose and obstacle can drift apart within the chunk (Gaussian model: outside the 1e-13 radius grown likewise);
+//   * no pose of the chunk can lie on a blocked cell or off the grid, and every obstacle either holds every pose of the chunk or
+//     none (Gaussian model: none comes within its 1e-13 radius): the bounds are stated at pp_plan_chunk;
 //   * on edges that may not cover while turning (Edge.cpp:159) the heading-unchanged bits are known without sampling: the step
 //     before the chunk and its last step lie on the same segment of the curve — a straight (the heading is the same expression
 //     at every step: all bits set) or an arc whose steps are more than 1e-9 rad apart (no two headings equal: all bits clear).
-// A skipped chunk's outputs are stored here (no hits; the heading bits); for a chunk that is NOT skipped on such an edge the
+// A skipped chunk's outputs are stored here (its hits; the heading bits); for a chunk that is NOT skipped on such an edge the
 // heading of the step before it is stored (`lastHeading`, Edge.cpp:96,174: the sweep needs it when the chunk before was skipped).
 // Everything is the arithmetic the sweep itself would do (pp_window_pose's expressions, one lane's worth).
-// Can obstacle o hold any pose of a chunk whose middle pose is (x, y) at time tM, when no pose is farther than hs and no time
-// farther than ht from the middle step?  The box test of pp_obstacle_hit with both half-extents grown by the distance pose and
-// obstacle can drift apart (Gaussian model: the 1e-13 radius grown likewise).  true = certainly not.
+// Can obstacle o hold a pose that lies within `rad` of (x, y), the midpoint of a chunk's chord, at a time within ht of tM?  The
+// box test of pp_obstacle_hit with both half-extents grown by the distance pose and obstacle can drift apart (Gaussian model: the
+// 1e-13 radius grown likewise).  true = certainly not.
 template <bool GAUSSIAN>
-__device__ __forceinline__ bool pp_chunk_clear_of(const PPObst& o, double x, double y, double tM, double hs, double ht) {
+__device__ __forceinline__ bool pp_chunk_clear_of(const PPObst& o, double x, double y, double tM, double rad, double ht) {
     const double dt = tM - o.Time;
     const double X = o.X + o.Speed * dt * o.cosYaw, Y = o.Y + o.Speed * dt * o.sinYaw;
-    const double slack = hs + fabs(o.Speed) * ht + 1e-3;
+    const double slack = rad + fabs(o.Speed) * ht + 1e-3;
     const double dx = x - X, dy = y - Y;
     if (GAUSSIAN) {
         const double R = o.reach + slack;
@@ -140,27 +140,61 @@ __device__ __forceinline__ bool pp_chunk_clear_of(const PPObst& o, double x, dou
 #define PP_SKIP_OBST 4    // sampled, but no pose of it can lie inside an obstacle
 #define PP_SKIP_HITS 8    // with PP_SKIP_ALL: every pose of the chunk lies inside some obstacle box (the chunk's hit count is not zero)
 #define PP_PLAN_EDGES_MAX 32          // edges a workgroup of the skip planner stages at most (14 KB of LDS)
-template <bool GAUSSIAN, bool OBST_LDS>
-__device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPEdgeSetupBody* S, const PPObst* OB, const long long e, const int chunk) {
-    {
+// The pose at arc length d of the edge's curve (0 <= d <= length), as the sweep computes it, in two steps: on the unit curve, then
+// scaled and placed.
+__device__ __forceinline__ void pp_plan_unit_pose(const PPEdgeSetupBody* S, double d, double& ux, double& uy) {
+    const double rho = S->rho, rho_inv = S->rho_inv;
+    const double tp = (rho_inv != 0.0) ? d * rho_inv : d / rho;
+    double uth;
+    pp_setup_seg_pose(S, pp_seg_of(tp, S->p0, S->hi1), tp, ux, uy, uth);
+}
+__device__ __forceinline__ void pp_plan_place(const PPEdgeSetupBody* S, double ux, double uy, double& x, double& y) {
+    x = ux * S->rho + S->qx; y = uy * S->rho + S->qy;
+}
+__device__ __forceinline__ void pp_plan_pose(const PPEdgeSetupBody* S, double d, double& x, double& y) {
+    double ux, uy;
+    pp_plan_unit_pose(S, d, ux, uy);
+    pp_plan_place(S, ux, uy, x, y);
+}
+// The decision for one (edge, chunk), and its stores.  S: the edge's setup record (in LDS); tg: its time row; tF: the time of the
+// chunk's first step (INFINITY: there is none).  ends(dF, dL, xF, yF, xE, yE, tE, dE) gives the chord, from
+// the pose F at the first step to the pose E at step 64c + 63 or 64c + 64, with E's time and arc length.  tE and dE arrive as the
+// last step's; dF and dL are the arc lengths of the first and the last step.  It is only called for a chunk of 64 steps that all
+// lie before the end time on the curve proper.  (Six references and not a struct of them: handed to the lambda, the struct costs
+// pp_k_plan_skips six more spilled registers, profiles/plan_skips_shared.txt.)
+// each(against, decided) shows against() the obstacles that can matter, while `decided` holds.
+//
+// The bounds.  The vehicle moves at constant speed on a curve of curvature <= 1/rho and an obstacle at constant velocity, both
+// linear in the step time: relative to an obstacle's box the pose at time t is within dev = L^2 / (8 rho) of the point of the
+// chord at the same time fraction (a function that vanishes at both ends with second derivative bounded by 1/rho), L = dE - dF
+// the arc length the chord spans.  The steps of the chunk are among those the chord spans, the time row rises with the step.
+// At config 3 dev is 0.08 .. 0.16 m where a ball around the middle pose needed 3.5 m.
+//   grid    two balls around the quarter points of the chord: every chord point is within L/4 of one of them, every pose within dev
+//           of the chord, so within L/4 + dev of one of the two.  The clearance map must say every cell that near (+2 cells for
+//           the pose's place inside its cell and the rounding of the cell index) is free and inside the grid.
+//   box     a box is convex, so both ends inside it shrunk by dev => every pose inside (64 hits per step, known without
+//           sampling); both ends beyond one face grown by dev => no pose inside.  In front of that a circle: every pose lies
+//           within L/2 + dev of the chord's midpoint, the box within its own reach of its centre, which moves at most |Speed| ht
+//           around where it is at the middle step's time, ht = the farthest of tF and tE from it.
+//   Gaussian  the same circle with the 1e-13 radius for the reach (no "inside": the density varies).
+// Two separate answers come out: no pose of the chunk can be on a blocked cell; no pose can be inside an obstacle.  Both, with
+// the heading bits known, skip the chunk; one alone still spares the sweep that half of its per-step work (PP_SKIP_* bits).
+template <bool GAUSSIAN, typename Ends, typename Each>
+__device__ __forceinline__ void pp_plan_chunk(const PPParams& p, const PPEdgeSetupBody* S, const long long e, const int chunk, const double* tg,
+                                              const double endTime, const double tF, Ends ends, Each each) {
     const int k0 = chunk * PP_WAVE;
     unsigned char* skipb = p.track_skip + (size_t)e * p.nch + chunk;
-    const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
-    const bool whole = k0 + PP_WAVE - 1 < p.ng;                // only whole chunks can be skipped ...
-    const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
-    const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
-    // ... but a chunk cut by the end of the time grid is still sampled, and if the chunk before it is skipped the sweep takes
-    // `lastHeading` from here like for any other chunk (tools/fuzz_parity.py seed 17 round 3: an edge of 291 steps on a 300-step grid)
-    const double tF = (sane && k0 < p.ng) ? tg[k0] : INFINITY;
     if (!(tF < endTime)) { *skipb = 0; return; }               // the sweep never reaches this chunk: most threads of a short edge
+    // only whole chunks can be skipped, but a chunk cut by the end of the time grid is still sampled, and if the chunk before it is
+    // skipped the sweep takes `lastHeading` from here like for any other chunk (tools/fuzz_parity.py seed 17 round 3: an edge of 291
+    // steps on a 300-step grid)
+    const bool whole = k0 + PP_WAVE - 1 < p.ng;
     const bool cov = (S->cbits & PPGPU_EDGE_COVERAGE) != 0;
     const double wStart = S->wStart, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv;
     const double tM = whole ? tg[k0 + PP_WAVE / 2] : tF, tL = whole ? tg[k0 + PP_WAVE - 1] : tF;
     const double tP = (k0 > 0) ? tg[k0 - 1] : 0.0;
-    const double dP = (tP - wStart) * speed, dF = (tF - wStart) * speed, dM = (tM - wStart) * speed, dL = (tL - wStart) * speed;
+    const double dP = (tP - wStart) * speed, dF = (tF - wStart) * speed, dL = (tL - wStart) * speed;
     const bool okGeom = whole && tL < endTime && (dF >= 0.0) && (dL <= length);   // 64 steps, all before the end time, on the curve proper
-    const double hs = fmax(dL - dM, dM - dF) * (1.0 + 1e-12) + 1e-9;      // how far (arc length) a step of the chunk is from the middle step
-    const double ht = fmax(tL - tM, tM - tF);
     const double hi0 = S->p0, hi1 = S->hi1;
     unsigned long long eqWord = ~0ull;
     double tpP = 0.0;
@@ -190,33 +224,23 @@ __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPE
             eqWord = (eqWord & ~1ull) | (same0 ? 1ull : 0ull);
         }
     }
-    // Two separate answers: no pose of the chunk can be on a blocked cell; no pose can be inside an obstacle.  Both, with the
-    // heading bits known, skip the chunk; one alone still spares the sweep that half of its per-step work (PP_SKIP_* bits).
     bool gridClear = false, obstClear = false;
     int nInside = 0;                                           // obstacles that hold EVERY pose of the chunk (binary model)
     bool decided = false;                                      // every obstacle either holds all poses or none
     if (okGeom) {
-        // The chunk's poses against the chord between its first and its last pose.  The vehicle moves at constant speed on a curve
-        // of curvature <= 1/rho and an obstacle at constant velocity, both linear in the step time: relative to an obstacle's box
-        // the pose at time t is within dev = L^2 / (8 rho) of the point of the chord at the same time fraction (a function that
-        // vanishes at both ends with second derivative bounded by 1/rho), L = the chunk's arc length.  A box is convex, so
-        // both ends inside it shrunk by dev => every pose inside (64 hits per step, known without sampling); both ends beyond one
-        // face grown by dev => no pose inside.  At config 3 dev is 0.08 .. 0.16 m where the ball around the middle pose needed 3.5 m.
-        const double tpF2 = (rho_inv != 0.0) ? dF * rho_inv : dF / rho, tpL2 = (rho_inv != 0.0) ? dL * rho_inv : dL / rho;
-        double uxF, uyF, uxL, uyL, uthU;
-        pp_setup_seg_pose(S, pp_seg_of(tpF2, hi0, hi1), tpF2, uxF, uyF, uthU);
-        pp_setup_seg_pose(S, pp_seg_of(tpL2, hi0, hi1), tpL2, uxL, uyL, uthU);
-        const double xF = uxF * rho + S->qx, yF = uyF * rho + S->qy, xL = uxL * rho + S->qx, yL = uyL * rho + S->qy;
-        const double Lc = dL - dF;
-        const double dev = Lc * Lc / (8.0 * rho) * (1.0 + 1e-9) + 1e-3;
+        double xF, yF, xE, yE, tE = tL, dE = dL;
+        ends(dF, dL, xF, yF, xE, yE, tE, dE);
+        const double ht = fmax(tE - tM, tM - tF);
+        const double Lc = dE - dF;
+        // rho_inv is not zero only where rho is a power of two: there 8 rho and 0.125 rho_inv are exact and the product is the
+        // quotient, to the bit, without the division's thirty instructions
+        const double dev = ((rho_inv != 0.0) ? Lc * Lc * (0.125 * rho_inv) : Lc * Lc / (8.0 * rho)) * (1.0 + 1e-9) + 1e-3;
         gridClear = true;
         if (p.grid.rows != 0) {
-            // two balls around the quarter points of the chord: every chord point is within L/4 of one of them, every pose within dev
-            // of the chord
             const int need = (int)((0.25 * Lc + dev) * p.grid.inv_res) + 2;
             for (int h = 0; h < 2; h++) {
                 const double f = h ? 0.75 : 0.25;
-                const double x = xF + f * (xL - xF), y = yF + f * (yL - yF);
+                const double x = xF + f * (xE - xF), y = yF + f * (yE - yF);
                 const double cx = x * p.grid.inv_res, cy = y * p.grid.inv_res;
                 const bool inside = (x >= 0.0) & (y >= 0.0) & (cx < (double)p.grid.cols) & (cy < (double)p.grid.rows);
                 int clear = 0;
@@ -227,38 +251,27 @@ __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPE
         decided = true;
         auto against = [&](const PPObst& o) {
             if (GAUSSIAN) {
-                // the 1e-13 radius around the chord's midpoint (no "inside": the density varies)
-                if (!pp_chunk_clear_of<true>(o, 0.5 * (xF + xL), 0.5 * (yF + yL), tM, 0.5 * Lc + dev, ht)) decided = false;
+                if (!pp_chunk_clear_of<true>(o, 0.5 * (xF + xE), 0.5 * (yF + yE), tM, 0.5 * Lc + dev, ht)) decided = false;
                 return;
             }
             {
-                // most boxes on an edge's list are nowhere near this chunk: every pose lies within Lc/2 + dev of the chord's midpoint,
-                // the box within its own reach of its centre, which moves at most |Speed| ht around where it is at the middle step
+                // most boxes on an edge's list are nowhere near this chunk (this sum is not pp_chunk_clear_of's, to the bit)
                 const double dtM = tM - o.Time;
-                const double ddx = 0.5 * (xF + xL) - (o.X + o.Speed * dtM * o.cosYaw), ddy = 0.5 * (yF + yL) - (o.Y + o.Speed * dtM * o.sinYaw);
+                const double ddx = 0.5 * (xF + xE) - (o.X + o.Speed * dtM * o.cosYaw), ddy = 0.5 * (yF + yE) - (o.Y + o.Speed * dtM * o.sinYaw);
                 const double R = o.reach + 0.5 * Lc + dev + fabs(o.Speed) * ht + 1e-3;
                 if (ddx * ddx + ddy * ddy > R * R) return;
             }
-            const double dtF = tF - o.Time, dtL = tL - o.Time;
+            const double dtF = tF - o.Time, dtE = tE - o.Time;
             const double txF = xF - (o.X + o.Speed * dtF * o.cosYaw), tyF = yF - (o.Y + o.Speed * dtF * o.sinYaw);
-            const double txL = xL - (o.X + o.Speed * dtL * o.cosYaw), tyL = yL - (o.Y + o.Speed * dtL * o.sinYaw);
+            const double txE = xE - (o.X + o.Speed * dtE * o.cosYaw), tyE = yE - (o.Y + o.Speed * dtE * o.sinYaw);
             const double rxF = txF * o.cosYaw - tyF * o.sinYaw, ryF = txF * o.sinYaw + tyF * o.cosYaw;
-            const double rxL = txL * o.cosYaw - tyL * o.sinYaw, ryL = txL * o.sinYaw + tyL * o.cosYaw;
-            const bool out = (fmin(rxF, rxL) > o.halfL + dev) | (fmax(rxF, rxL) < -o.halfL - dev) | (fmin(ryF, ryL) > o.halfW + dev) | (fmax(ryF, ryL) < -o.halfW - dev);
-            const bool in = (fmax(fabs(rxF), fabs(rxL)) < o.halfL - dev) & (fmax(fabs(ryF), fabs(ryL)) < o.halfW - dev);
+            const double rxE = txE * o.cosYaw - tyE * o.sinYaw, ryE = txE * o.sinYaw + tyE * o.cosYaw;
+            const bool out = (fmin(rxF, rxE) > o.halfL + dev) | (fmax(rxF, rxE) < -o.halfL - dev) | (fmin(ryF, ryE) > o.halfW + dev) | (fmax(ryF, ryE) < -o.halfW - dev);
+            const bool in = (fmax(fabs(rxF), fabs(rxE)) < o.halfL - dev) & (fmax(fabs(ryF), fabs(ryE)) < o.halfW - dev);
             if (in) nInside++;
             else if (!out) decided = false;
         };
-        // only the obstacles that can come near this edge at all (pp_k_solve_edges left the list in the setup record)
-        unsigned long long m = S->omask;
-        if (p.n_obst > PP_WAVE) m = 0ull;
-        while (decided && m) {
-            const int j = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            against(OB[j]);
-        }
-        if (p.n_obst > PP_WAVE)
-            for (int j = 0; j < p.n_obst && decided; j++) against(OB[j]);
+        each(against, decided);
         obstClear = decided && nInside == 0;
     }
     const bool ok = okGeom && okHead && gridClear && decided;
@@ -276,14 +289,58 @@ __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPE
         pp_setup_seg_pose(S, segP, tpP, ux, uy, uth);
         p.track_eq[(size_t)e * p.nch + chunk] = (unsigned long long)__double_as_longlong(pp_heading_from_yaw(pp_mod2pi(uth)));   // (the sweep replaces it by the chunk's bits)
     }
+}
+// The chunkwise caller: the thread samples both ends of its chunk's own 64 steps and goes through the obstacles that can come near
+// the edge at all (pp_k_solve_edges left the list in the setup record), or through the whole table when it holds more than 64.
+template <bool GAUSSIAN>
+__device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPEdgeSetupBody* S, const PPObst* OB, const long long e, const int chunk) {
+    const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
+    const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
+    const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
+    const double tF = (sane && chunk * PP_WAVE < p.ng) ? tg[chunk * PP_WAVE] : INFINITY;
+    pp_plan_chunk<GAUSSIAN>(p, S, e, chunk, tg, endTime, tF,
+        [&](double dF, double dL, double& xF, double& yF, double& xE, double& yE, double&, double&) {
+            // Keep this order, both ends evaluated on the unit curve before either is placed: pp_plan_pose twice costs
+            // pp_k_plan_skips_chunkwise six more spilled registers and the Gaussian kernels a wave (profiles/plan_skips_shared.txt)
+            double uxF, uyF, uxE, uyE;
+            pp_plan_unit_pose(S, dF, uxF, uyF);
+            pp_plan_unit_pose(S, dL, uxE, uyE);
+            pp_plan_place(S, uxF, uyF, xF, yF);
+            pp_plan_place(S, uxE, uyE, xE, yE);
+        },
+        [&](auto& against, const bool& decided) {
+            unsigned long long m = S->omask;
+            if (p.n_obst > PP_WAVE) m = 0ull;
+            while (decided && m) {
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                against(OB[j]);
+            }
+            if (p.n_obst > PP_WAVE)
+                for (int j = 0; j < p.n_obst && decided; j++) against(OB[j]);
+        });
+}
+// The workgroup's `ne` setup records (contiguous in the workspace from edge el0 on) into s_setup and, OBST_LDS, the obstacle table
+// into s_obst; the caller's barrier follows.  A thread reads some 40 fields of its record and ten doubles per obstacle it tests;
+// from memory every one of those was a vector load whose lanes hit two or three different lines, ≈ 200 per thread, and the kernel
+// ran at the rate the L1 serves such loads, not at the VALU's (round 3).
+template <bool OBST_LDS>
+__device__ __forceinline__ void pp_plan_stage(const PPParams& p, const long long el0, const int ne, double* s_setup, PPObst* s_obst) {
+    const int tid = (int)threadIdx.x;
+    const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
+    for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
+        const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
+        if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
+    }
+    if (OBST_LDS) {
+        const double* os = reinterpret_cast<const double*>(p.obst);
+        double* od = reinterpret_cast<double*>(s_obst);
+        for (int i = tid; i < p.n_obst * (int)(sizeof(PPObst) / sizeof(double)); i += 256) od[i] = os[i];
     }
 }
 // One workgroup per `epw` consecutive edges (host: as many as give it 256 (edge, chunk) pairs, at most PP_PLAN_EDGES_MAX), one
 // THREAD per (edge, chunk) — measured against one lane per edge walking its chunks (0.29 ms at config 3: 24 dependent iterations
-// on 3 700 wavefronts) this mapping took 0.21 ms, most threads of a short edge leaving after two loads.  Round 3: the workgroup
-// first copies its edges' setup records (contiguous in the workspace) and the obstacle table into LDS.  A thread reads some 40
-// fields of its record and ten doubles per obstacle it tests; from memory every one of those was a vector load whose lanes hit
-// two or three different lines, ≈ 200 per thread, and the kernel ran at the rate the L1 serves such loads, not at the VALU's.
+// on 3 700 wavefronts) this mapping took 0.21 ms, most threads of a short edge leaving after two loads.
 template <bool GAUSSIAN, bool OBST_LDS>
 __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw) {
     __shared__ double s_setup[PP_PLAN_EDGES_MAX * PP_SETUP_LDS_STRIDE];
@@ -291,18 +348,7 @@ __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw)
     const int tid = (int)threadIdx.x;
     const long long el0 = (long long)blockIdx.x * epw;
     const int ne = (int)((p.n_edges - el0 < (long long)epw) ? (p.n_edges - el0) : (long long)epw);
-    {
-        const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
-        for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
-            const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
-            if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
-        }
-        if (OBST_LDS) {
-            const double* os = reinterpret_cast<const double*>(p.obst);
-            double* od = reinterpret_cast<double*>(s_obst);
-            for (int i = tid; i < p.n_obst * (int)(sizeof(PPObst) / sizeof(double)); i += 256) od[i] = os[i];
-        }
-    }
+    pp_plan_stage<OBST_LDS>(p, el0, ne, s_setup, s_obst);
     __syncthreads();
     // (blockIdx.y: further tiles of 256 chunks when one edge alone has more than 256 of them)
     const int t = (int)blockIdx.y * 256 + tid;
@@ -310,7 +356,7 @@ __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw)
     const int el = (int)((unsigned)t / (unsigned)p.nch);
     const int chunk = t - el * p.nch;
     const PPEdgeSetupBody* S = reinterpret_cast<const PPEdgeSetupBody*>(&s_setup[el * PP_SETUP_LDS_STRIDE]);
-    pp_plan_skips_chunk<GAUSSIAN, OBST_LDS>(p, S, OBST_LDS ? s_obst : p.obst, p.ws_base + el0 + el, chunk);
+    pp_plan_skips_chunk<GAUSSIAN>(p, S, OBST_LDS ? s_obst : p.obst, p.ws_base + el0 + el, chunk);
 }
 #ifndef PP_PLAN_MIN_WAVES
 #define PP_PLAN_MIN_WAVES 8   // 62 VGPRs, no spills; 0.28 -> 0.27 ms against the compiler's own choice (6 waves)
@@ -322,18 +368,15 @@ __global__ __launch_bounds__(256) void pp_k_plan_skips_many(PPParams p, int epw)
 __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<true, true>(p, epw); }
 __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p, int epw) { pp_plan_skips_thread<true, false>(p, epw); }
 
-// The same decisions with two pieces of work taken out of the thread (up to 64 obstacles, the table in LDS).  The workgroup goes
-// through three phases, and every thread stays to the last barrier (what were early returns above are predicates here):
+// The span caller (up to 64 obstacles, the table in LDS): the same decisions with two pieces of work taken out of the thread.  The
+// workgroup goes through three phases, and every thread stays to the last barrier (what is an early return above is a predicate
+// here):
 //
 //   boundary poses   The chord of chunk c runs from its first step 64c to step 64c + 64, the first step of chunk c + 1, where that
 //                    step exists, lies before the edge's end time and on the curve proper, and belongs to a thread of this
 //                    workgroup: each thread samples ONE pose, its first step's, leaves it in LDS, and takes the far end from its
-//                    neighbour.  Otherwise it samples its own last step 64c + 63 as above.  Everything the chord argument uses is
-//                    stated for the steps [64c, E] the chord spans, E = 64c + 64 or 64c + 63: L = d_E - d_F (so dev, the grid's two
-//                    balls and the circle around the chord's midpoint), ht = the farthest of t_F and t_E from the middle step's time
-//                    (the time row rises with the step, as every bound above already takes for granted).  The steps of the chunk
-//                    are among those of the chord, so "no pose inside" and "every pose inside" (both ends inside the shrunk convex
-//                    box) hold for them as before.  (`hs` above is a leftover of the ball test and bounds nothing any more.)
+//                    neighbour.  Otherwise it samples its own last step 64c + 63 as the chunkwise caller does.  pp_plan_chunk
+//                    states every bound for the steps [64c, E] the chord spans, whichever E it is given.
 //   span masks       A span is PP_PLAN_SPAN consecutive chunks of an edge, and its PP_PLAN_SPAN threads share out the edge's omask
 //                    (obstacle j goes to thread j mod PP_PLAN_SPAN; a short last span deals the residues round) to test each obstacle
 //                    ONCE for the whole span.  With A the pose at the span's first step (time tA, arc length dA):
@@ -345,13 +388,13 @@ __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p,
 //                                 all lie before the end time on the curve proper, so every covered step has t <= tE = min(time of
 //                                 the step after the span's last, or of the row's last entry; end time) and d <= dE = min((tE - wStart) speed, length), and
 //                                 |PA| <= dE - dA; the obstacle's centre is within |Speed| (tE - tA) of where it is at tA.
-//                    An obstacle farther from that centre than reach + the pose radius + the obstacle's drift + 1e-3 (the slack of the
-//                    bounds above; the pose radius carries 1e-9 relative and 1e-3 besides) cannot hold a pose any chord of the span
-//                    covers: against() above would answer "out" or not run its box test, and leaving the obstacle out answers the
+//                    An obstacle farther from that centre than reach + the pose radius + the obstacle's drift + 1e-3 (the slack of
+//                    pp_plan_chunk's bounds; the pose radius carries 1e-9 relative and 1e-3 besides) cannot hold a pose any chord of
+//                    the span covers: against() would answer "out" or not run its box test, and leaving the obstacle out answers the
 //                    same.  (It can answer "out" where the box test's four faces could not decide: the span planner may skip a chunk
 //                    the chunkwise one samples, never the other way round for these obstacles.)  A span whose first pose is not
 //                    there keeps the whole omask.
-//   chunks           as above, over the span's mask.
+//   chunks           pp_plan_chunk, over the span's mask.
 #ifndef PP_PLAN_SPAN
 #define PP_PLAN_SPAN 4        // 2 / 4 / 8: profiles/plan_spans_ab.txt
 #endif
@@ -367,17 +410,8 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
     const int tid = (int)threadIdx.x;
     const long long el0 = (long long)blockIdx.x * epw;
     const int ne = (int)((p.n_edges - el0 < (long long)epw) ? (p.n_edges - el0) : (long long)epw);
-    {
-        const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
-        for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
-            const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
-            if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
-        }
-        const double* os = reinterpret_cast<const double*>(p.obst);
-        double* od = reinterpret_cast<double*>(s_obst);
-        for (int i = tid; i < p.n_obst * (int)(sizeof(PPObst) / sizeof(double)); i += 256) od[i] = os[i];
-        if (tid < PP_PLAN_SPANS_MAX) s_span[tid] = 0ull;
-    }
+    pp_plan_stage<true>(p, el0, ne, s_setup, s_obst);
+    if (tid < PP_PLAN_SPANS_MAX) s_span[tid] = 0ull;
     __syncthreads();
     // (blockIdx.y: further tiles of 256 chunks when one edge alone has more than 256 of them)
     const int t = (int)blockIdx.y * 256 + tid;
@@ -385,25 +419,17 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
     const int el = live ? (int)((unsigned)t / (unsigned)p.nch) : 0;
     const int chunk = live ? t - el * p.nch : 0;
     const PPEdgeSetupBody* S = reinterpret_cast<const PPEdgeSetupBody*>(&s_setup[el * PP_SETUP_LDS_STRIDE]);
-    const long long e = p.ws_base + el0 + el;
     const int k0 = chunk * PP_WAVE;
     const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
     const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
     const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
     const double tF = (live && sane && k0 < p.ng) ? tg[k0] : INFINITY;
-    const bool reached = tF < endTime;                         // the sweep reaches this chunk
-    const double wStart = S->wStart, speed = S->speed, length = S->length, rho = S->rho, rho_inv = S->rho_inv;
-    const double hi0 = S->p0, hi1 = S->hi1;
-    const double dF = (tF - wStart) * speed;
+    const double wStart = S->wStart, speed = S->speed;
     // ---- boundary poses
     {
+        const double dF = (tF - wStart) * speed;
         double x = NAN, y = 0.0;
-        if (reached && dF >= 0.0 && dF <= length) {
-            const double tpF = (rho_inv != 0.0) ? dF * rho_inv : dF / rho;
-            double ux, uy, uth;
-            pp_setup_seg_pose(S, pp_seg_of(tpF, hi0, hi1), tpF, ux, uy, uth);
-            x = ux * rho + S->qx; y = uy * rho + S->qy;
-        }
+        if (tF < endTime && dF >= 0.0 && dF <= S->length) pp_plan_pose(S, dF, x, y);
         s_bx[tid] = x; s_by[tid] = y;
     }
     __syncthreads();
@@ -428,7 +454,7 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
                 cx = 0.5 * (xA + xB); cy = 0.5 * (yA + yB); rad = 0.5 * (dB - dA); tc = 0.5 * (tA + tB); th = 0.5 * (tB - tA);
             } else {
                 const int kE = (cB * PP_WAVE < p.ng) ? cB * PP_WAVE : p.ng - 1;
-                const double tE = fmin(tg[kE], endTime), dE = fmin((tE - wStart) * speed, length);
+                const double tE = fmin(tg[kE], endTime), dE = fmin((tE - wStart) * speed, S->length);
                 cx = xA; cy = yA; rad = dE - dA; tc = tA; th = tE - tA;
             }
             if (rad >= 0.0 && th >= 0.0) {
@@ -447,120 +473,29 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
         if (keep != 0ull) atomicOr(&s_span[sp], keep);
     }
     __syncthreads();
-    // ---- the chunk (no barrier from here on)
+    // ---- the chunk (no barrier from here on).  The lambdas take what they need from the record again: a value loaded in front of
+    // the barriers and captured here stays in a register through the whole decision, and pp_k_plan_skips has none to spare.
     if (!live) return;
-    unsigned char* skipb = p.track_skip + (size_t)e * p.nch + chunk;
-    if (!reached) { *skipb = 0; return; }                      // the sweep never reaches this chunk: most threads of a short edge
-    const bool whole = k0 + PP_WAVE - 1 < p.ng;                // only whole chunks can be skipped (a cut one: see above)
-    const bool cov = (S->cbits & PPGPU_EDGE_COVERAGE) != 0;
-    const double tM = whole ? tg[k0 + PP_WAVE / 2] : tF, tL = whole ? tg[k0 + PP_WAVE - 1] : tF;
-    const double tP = (k0 > 0) ? tg[k0 - 1] : 0.0;
-    const double dP = (tP - wStart) * speed, dL = (tL - wStart) * speed;
-    const bool okGeom = whole && tL < endTime && (dF >= 0.0) && (dL <= length);   // 64 steps, all before the end time, on the curve proper
-    unsigned long long eqWord = ~0ull;
-    double tpP = 0.0;
-    int segP = 0;
-    bool okHead = true;                                        // the heading-unchanged bits of the chunk are known without sampling
-    if (!cov) {
-        // (the heading logic of pp_plan_skips_chunk, over the chunk's own 64 steps)
-        tpP = (rho_inv != 0.0) ? dP * rho_inv : dP / rho;
-        const double tpL = (rho_inv != 0.0) ? dL * rho_inv : dL / rho;
-        segP = pp_seg_of(tpP, hi0, hi1);
-        const int segL = pp_seg_of(tpL, hi0, hi1);
-        const bool straight = pp_word_seg_type(S->type, segL) == 1;
-        eqWord = straight ? ~0ull : 0ull;
-        if (k0 > 0) {
-            okHead = (dP >= 0.0) && (segP == segL) && (straight || (tpL - tpP) > 65.0 * 1e-9);
-        } else {
-            const double tpF = (rho_inv != 0.0) ? dF * rho_inv : dF / rho;
-            const int segF = pp_seg_of(tpF, hi0, hi1);
-            okHead = (dF >= 0.0) && (segF == segL) && (straight || (tpL - tpF) > 64.0 * 1e-9);
-            const PPSegBase* g = &S->seg[segF];
-            const int gtype = pp_word_seg_type(S->type, segF);
-            const double tt = (tpF - pp_seg_o1(segF, S->p0)) - pp_seg_o2(segF, S->p1);
-            const double uth0 = (gtype == 1) ? (0.0 + g->bth) : ((gtype == 0) ? (tt + g->bth) : (-tt + g->bth));
-            const bool same0 = pp_heading_from_yaw(pp_mod2pi(uth0)) == S->srcH;
-            eqWord = (eqWord & ~1ull) | (same0 ? 1ull : 0ull);
-        }
-    }
-    bool gridClear = false, obstClear = false;
-    int nInside = 0;                                           // obstacles that hold EVERY pose of the chunk (binary model)
-    bool decided = false;                                      // every obstacle either holds all poses or none
-    if (okGeom) {
-        const double xF = s_bx[tid], yF = s_by[tid];           // (okGeom: 0 <= dF <= dL <= length, so this thread left its pose there)
-        // the far end E of the chord: the neighbour's first step, or this chunk's last
-        double xE = NAN, yE = 0.0, tE = tL, dE = dL;
-        if (tid + 1 < 256 && chunk + 1 < p.nch) { xE = s_bx[tid + 1]; yE = s_by[tid + 1]; }
-        if (xE == xE) {
-            tE = tg[k0 + PP_WAVE]; dE = (tE - wStart) * speed;
-        } else {
-            const double tpL2 = (rho_inv != 0.0) ? dL * rho_inv : dL / rho;
-            double uxL, uyL, uthU;
-            pp_setup_seg_pose(S, pp_seg_of(tpL2, hi0, hi1), tpL2, uxL, uyL, uthU);
-            xE = uxL * rho + S->qx; yE = uyL * rho + S->qy;
-        }
-        const double ht = fmax(tE - tM, tM - tF);
-        const double Lc = dE - dF;
-        // (rho a power of two: the product is the quotient, to the bit, without the division's thirty instructions)
-        const double dev = ((rho_inv != 0.0) ? Lc * Lc * (0.125 * rho_inv) : Lc * Lc / (8.0 * rho)) * (1.0 + 1e-9) + 1e-3;
-        gridClear = true;
-        if (p.grid.rows != 0) {
-            // two balls around the quarter points of the chord: every chord point is within L/4 of one of them, every pose within dev
-            // of the chord
-            const int need = (int)((0.25 * Lc + dev) * p.grid.inv_res) + 2;
-            for (int h = 0; h < 2; h++) {
-                const double f = h ? 0.75 : 0.25;
-                const double x = xF + f * (xE - xF), y = yF + f * (yE - yF);
-                const double cx = x * p.grid.inv_res, cy = y * p.grid.inv_res;
-                const bool inside = (x >= 0.0) & (y >= 0.0) & (cx < (double)p.grid.cols) & (cy < (double)p.grid.rows);
-                int clear = 0;
-                if (inside) clear = (int)p.grid.clearance[(size_t)(unsigned)cy * p.grid.cols + (unsigned)cx];
-                gridClear = gridClear && inside && (need < PP_CLEAR_CAP) && (clear > need);
+    pp_plan_chunk<GAUSSIAN>(p, S, p.ws_base + el0 + el, chunk, tg, endTime, tF,
+        [&](double, double dL, double& xF, double& yF, double& xE, double& yE, double& tE, double& dE) {
+            xF = s_bx[tid]; yF = s_by[tid];                    // (0 <= dF <= dL <= length, so this thread left its pose there)
+            // the far end E of the chord: the neighbour's first step, or this chunk's last
+            xE = NAN; yE = 0.0;
+            if (tid + 1 < 256 && chunk + 1 < p.nch) { xE = s_bx[tid + 1]; yE = s_by[tid + 1]; }
+            if (xE == xE) {
+                tE = tg[chunk * PP_WAVE + PP_WAVE]; dE = (tE - S->wStart) * S->speed;
+            } else {
+                pp_plan_pose(S, dL, xE, yE);
             }
-        }
-        decided = true;
-        unsigned long long m = s_span[sp];                     // the obstacles that can come near this span of the edge
-        while (decided && m) {
-            const int j = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const PPObst& o = s_obst[j];
-            if (GAUSSIAN) {
-                // the 1e-13 radius around the chord's midpoint (no "inside": the density varies)
-                if (!pp_chunk_clear_of<true>(o, 0.5 * (xF + xE), 0.5 * (yF + yE), tM, 0.5 * Lc + dev, ht)) decided = false;
-                continue;
+        },
+        [&](auto& against, const bool& decided) {
+            unsigned long long m = s_span[sp];                 // the obstacles that can come near this span of the edge
+            while (decided && m) {
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                against(s_obst[j]);
             }
-            {
-                // every pose lies within Lc/2 + dev of the chord's midpoint, the box within its own reach of its centre, which moves
-                // at most |Speed| ht around where it is at the middle step
-                const double dtM = tM - o.Time;
-                const double ddx = 0.5 * (xF + xE) - (o.X + o.Speed * dtM * o.cosYaw), ddy = 0.5 * (yF + yE) - (o.Y + o.Speed * dtM * o.sinYaw);
-                const double R = o.reach + 0.5 * Lc + dev + fabs(o.Speed) * ht + 1e-3;
-                if (ddx * ddx + ddy * ddy > R * R) continue;
-            }
-            const double dtF = tF - o.Time, dtE = tE - o.Time;
-            const double txF = xF - (o.X + o.Speed * dtF * o.cosYaw), tyF = yF - (o.Y + o.Speed * dtF * o.sinYaw);
-            const double txE = xE - (o.X + o.Speed * dtE * o.cosYaw), tyE = yE - (o.Y + o.Speed * dtE * o.sinYaw);
-            const double rxF = txF * o.cosYaw - tyF * o.sinYaw, ryF = txF * o.sinYaw + tyF * o.cosYaw;
-            const double rxE = txE * o.cosYaw - tyE * o.sinYaw, ryE = txE * o.sinYaw + tyE * o.cosYaw;
-            const bool out = (fmin(rxF, rxE) > o.halfL + dev) | (fmax(rxF, rxE) < -o.halfL - dev) | (fmin(ryF, ryE) > o.halfW + dev) | (fmax(ryF, ryE) < -o.halfW - dev);
-            const bool in = (fmax(fabs(rxF), fabs(rxE)) < o.halfL - dev) & (fmax(fabs(ryF), fabs(ryE)) < o.halfW - dev);
-            if (in) nInside++;
-            else if (!out) decided = false;
-        }
-        obstClear = decided && nInside == 0;
-    }
-    const bool ok = okGeom && okHead && gridClear && decided;
-    *skipb = ok ? (unsigned char)(PP_SKIP_ALL | (nInside > 0 ? PP_SKIP_HITS : 0)) : (unsigned char)((gridClear ? PP_SKIP_GRID : 0) | (obstClear ? PP_SKIP_OBST : 0));
-    if (ok) {
-        p.track_chunk_hits[(size_t)e * p.nch + chunk] = (unsigned)(PP_WAVE * nInside);
-        if (!cov) p.track_eq[(size_t)e * p.nch + chunk] = eqWord;
-        if (GAUSSIAN) p.track_chunk_pen[(size_t)e * p.nch + chunk] = 0.0;
-    } else if (!cov && k0 > 0 && dP >= 0.0 && dP <= length) {
-        // not skipped: if the chunk before this one is, the sweep takes `lastHeading` from here
-        double ux, uy, uth;
-        pp_setup_seg_pose(S, segP, tpP, ux, uy, uth);
-        p.track_eq[(size_t)e * p.nch + chunk] = (unsigned long long)__double_as_longlong(pp_heading_from_yaw(pp_mod2pi(uth)));   // (the sweep replaces it by the chunk's bits)
-    }
+        });
 }
 __global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips(PPParams p, int epw) { pp_plan_skips_spans<false>(p, epw); }
 __global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussian(PPParams p, int epw) { pp_plan_skips_spans<true>(p, epw); }

@@ -1,5 +1,5 @@
 """Directed worlds for the static map on the device (ppgpu_set_grid's packing into words, pp_is_blocked / pp_blocked_cell, the clearance
-map of pp_k_grid_row_clear / pp_k_grid_clear and its lookup in pp_plan_skips_chunk, the sampler's map filter): grids that
+map of pp_k_grid_row_clear / pp_k_grid_clear and its lookup in pp_plan_chunk, the sampler's map filter): grids that
 workloads.config1/2/3, sweep_worlds.py and tools/fuzz_parity.py never draw.  Non-square maps whose width is no multiple of 32 (padding
 bits in every row, r * cols != c * rows), single blocked cells that an edge touches with one sample, one-cell walls with a gap, an
 empty map whose centre reaches the clearance cap, maps of one row and of one column, resolutions whose reciprocal is not exact
@@ -484,7 +484,7 @@ def edge_classes(name):
 
 # ------------------------------------------------------------------------------------------------------------ the skip planner's bound
 def need_cells(w, Lc, rho, plus=2, with_dev=True):
-    """pp_plan_skips_chunk's `need`: the clearance (in cells) around both quarter points of a chunk's chord above which the chunk
+    """pp_plan_chunk's `need`: the clearance (in cells) around both quarter points of a chunk's chord above which the chunk
     is not sampled.  plus / with_dev: the same bound with a term left out, to ask which edges hinge on that term."""
     dev = Lc * Lc / (8.0 * rho) * (1.0 + 1e-9) + 1e-3 if with_dev else 0.0
     return int((0.25 * Lc + dev) * (1.0 / w.res)) + plus

@@ -5,6 +5,10 @@ per-chunk tests), beside tests/sweep_worlds.py and built from its pieces.
   short<H>     time horizons of 3.0, 4.9, 5.1 and 11.6 s on the common map and samples: time rows of 3, 4, 5 and 10 chunks — less than
                a span of four, exactly one, one and a short one, two and a short one — under a fleet that passes through the disc the
                vehicle can reach in that time.
+  offpower     turning radii of 10 and 12.5 m, neither a power of two, under the graze fleet and under the Gaussian rows of the fast
+               fleet: the planner's forms for a radius without an exact reciprocal (d / rho, L^2 / (8 rho)), which the radii 8 and 16
+               of every other world never reach.  Outside NAMES: at such a radius device and oracle poses may differ in the last bit
+               at a grazing step, and these worlds are for comparing the two planners.
 
 A plain module: no fixtures, no device.  tests/test_sweep_worlds_spans.py asserts on the oracle alone that every world holds its case;
 tests/test_gpu_plan_spans.py costs them on the device."""
@@ -47,9 +51,27 @@ def short(H):
     return SweepWorld(base.name, cfg, base.grid, base.res, base.rib, base._root5(), base.sx, base.sy, base.sh, obst=base.obst)
 
 
+OFFPOWER_RADII = (10.0, 12.5)
+
+
+def _offpower(base):
+    cfg = make_config(start_state_time=sw.T0, heuristic=H_MAX_DISTANCE, turning_radius=OFFPOWER_RADII[0], coverage_turning_radius=OFFPOWER_RADII[1])
+    return SweepWorld(base.name, cfg, base.grid, base.res, base.rib, base._root5(), base.sx, base.sy, base.sh, obst=base.obst, gauss=base.gauss)
+
+
+def offpower():
+    return _offpower(_common("offpower", graze().obst))
+
+
+def gaussian_offpower():
+    return _offpower(_common("gaussian_offpower", gauss=sw.gaussian("fast").gauss))
+
+
 WORLDS = {"graze": graze}
 WORLDS.update({"short%g" % H: functools.partial(short, H) for H in SHORT_HORIZONS})
-NAMES = list(WORLDS)
+NAMES = list(WORLDS)                   # the worlds held to the oracle to the bit
+OFFPOWER = ["offpower", "gaussian_offpower"]
+WORLDS.update({"offpower": offpower, "gaussian_offpower": gaussian_offpower})
 
 _CACHE = {}
 

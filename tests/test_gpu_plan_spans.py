@@ -1,7 +1,8 @@
 """-m gpu: the skip planner's span masks and shared boundary poses (pp_k_plan_skips) against the chunkwise planner it replaces
 (PPGPU_PLAN_SPANS=0, the same library) and against the oracle.  The planner only decides what the pose sweep need not sample, and what
 it stores for a skipped chunk is what sampling would have stored: so both planners must leave the same bytes in every record and
-child ribbon, whichever chunks each of them skips.  The worlds of tests/sweep_worlds_spans.py (boxes that graze an edge for a few
+child ribbon, whichever chunks each of them skips (the off-power worlds among them: turning radii without an exact reciprocal, where
+both take their d / rho forms).  The worlds of tests/sweep_worlds_spans.py (boxes that graze an edge for a few
 steps; time rows of less than one span, exactly one, one or two and a short one) are also held to the oracle with the bar of
 tests/test_gpu_sweep_inputs.py: flags and info equal, on binary fleets the penalty of every feasible edge equal to the bit, with the
 planner on and with every chunk sampled.  Every launch is a dense one of at most 1 024 edges with PPGPU_PREPASS_MIN_EDGES=0, without
@@ -15,7 +16,7 @@ from test_gpu_sweep_inputs import ROUTES, _dense, _against_oracle, _same_answers
 
 pytestmark = pytest.mark.gpu
 
-BOTH = sw.BINARY + ["done_inside", "long16377"] + ["gaussian_" + g for g in sw.GAUSSIAN] + sp.NAMES
+BOTH = sw.BINARY + ["done_inside", "long16377"] + ["gaussian_" + g for g in sw.GAUSSIAN] + sp.NAMES + sp.OFFPOWER
 
 
 @pytest.fixture(scope="module")

@@ -49,7 +49,7 @@ def test_cells_block_edges_late_and_every_side_is_left(name):
 
 @pytest.mark.parametrize("name", gw.PILLARS + ["apex"])
 def test_blocking_chunks_hinge_on_the_terms_of_the_skip_planners_bound(name):
-    """pp_plan_skips_chunk skips a chunk when the clearance at both quarter points of its chord exceeds
+    """pp_plan_chunk skips a chunk when the clearance at both quarter points of its chord exceeds
     need = int((Lc / 4 + dev) / res) + 2.  Restated on the oracle's poses (gw.blocking_chunk_skippable): with the bound as it is no
     chunk that holds a blocking pose is skippable; with `+ 2` dropped several are (the device test then loses those edges); with
     `dev` dropped the chunks of `apex` are, and only those: elsewhere int() swallows it.  `+ 1` in place of `+ 2`, which is what
@@ -101,7 +101,7 @@ def test_open_reaches_the_cap_and_chunks_are_skippable_far_from_the_border_only(
     assert w.grid.sum() == 0
     cl = gw.clearance_numpy(w.grid)
     assert cl.max() == gw.CLEAR_CAP and (cl == gw.CLEAR_CAP).sum() > 1000 and cl.min() == 1
-    # need = int((0.25 Lc + dev) / res) + 2 of pp_plan_skips_chunk for a full-speed chunk at the tighter radius
+    # need = int((0.25 Lc + dev) / res) + 2 of pp_plan_chunk for a full-speed chunk at the tighter radius
     Lc = 63 * w.cfg.collision_checking_increment
     need = int((0.25 * Lc + Lc * Lc / (8 * w.cfg.turning_radius) + 1e-3) / w.res) + 2
     assert need < gw.CLEAR_CAP and (cl > need).sum() > 0.5 * cl.size and (cl <= need).sum() >= 5000

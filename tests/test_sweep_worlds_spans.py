@@ -1,5 +1,7 @@
 """The worlds of tests/sweep_worlds_spans.py hold their cases, on the oracle alone (no device).  Conditions, not measurements: if a
 fleet misses a bar, the fleet changes, not the bar."""
+import math
+
 import numpy as np
 import pytest
 
@@ -36,3 +38,18 @@ def test_short_horizon_rows_and_hits(H):
     assert hit >= 150
     assert few >= 100
     assert none >= 100
+
+
+def test_offpower_worlds_hold_their_case():
+    """Radii that are no power of two, so the device takes its d / rho forms; the binary world has edges with hits and edges without."""
+    for name in sp.OFFPOWER:
+        w = sp.WORLDS[name]()
+        for r in (w.cfg.turning_radius, w.cfg.coverage_turning_radius):
+            assert math.frexp(r)[0] != 0.5, (name, r)
+    assert not sp.WORLDS["gaussian_offpower"]().binary and not set(sp.OFFPOWER) & set(sp.NAMES)
+    w, feas, hits = _shape("offpower")
+    hit, none = int((feas & (hits > 0)).sum()), int((feas & (hits == 0)).sum())
+    print("offpower: feasible", int(feas.sum()), "hit:", hit, "no hit:", none)
+    assert w.binary and w.obst.shape == (16, 7)
+    assert hit >= 1
+    assert none >= 1
