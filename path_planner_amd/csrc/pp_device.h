@@ -190,6 +190,9 @@ __device__ __forceinline__ double pp_cr_acos(double v) {
 // mod2pi(t) = t - 2pi * floor(t / 2pi).  floor() of the quotient only depends on the division's rounding when the
 // quotient is within rounding distance of an integer, so the quotient is first taken as t * (1/2pi) and the true
 // division is evaluated only if some lane is within 1e-9 of an integer (same result, one division less).
+// Domain: |t| < 1e7.  The product is off from the quotient by up to ~2^-52 |t| / 2pi, which must stay well below the 1e-9 guard; near
+// |t| = 1e9 it does not, and the result is then wrong by a multiple of 2pi on some arguments.  Every caller stays below ~1e5
+// (pp_k_solve_edges refuses curves whose |start yaw| + arcs reaches 9e4); the device tests cover |t| < 1e5.
 __device__ __forceinline__ double pp_mod2pi(double t) {
     const double q = t * 0.15915494309189533576888376337251;
     double k = floor(q);

@@ -1,8 +1,11 @@
 // Host check of path_planner_amd/csrc/pp_cr.h (tests/test_cr_trig.py): the double-double sin / cos / atan2 / acos against glibc and
 // against the x87 long-double functions rounded to double.  Prints, per function, how many of N arguments differ from each.
+// `cr_trig_check --stdin` instead evaluates what it is given (tests/test_device_probe_inputs.py): one request per line of standard input,
+// arguments as hex doubles — `s x` prints sin and cos, `t y x` atan2, `a v` acos — one line of hex doubles out per request.
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include "../path_planner_amd/csrc/pp_cr.h"
 static double cr_sin(double x) { PPdd s, c; pp_cr_sincos_dd(x, &s, &c); return s.h + s.l; }
 static double cr_cos(double x) { PPdd s, c; pp_cr_sincos_dd(x, &s, &c); return c.h + c.l; }
@@ -25,7 +28,19 @@ static bool near_midpoint(long double v) {
     const double u = fabs(nextafter(d, INFINITY) - d);
     return fabsl(e - 0.5L * u) < u * (1.0L / 512);
 }
+static int from_stdin() {
+    char f;
+    double a, b;
+    while (std::scanf(" %c", &f) == 1) {
+        if (f == 's' && std::scanf("%la", &a) == 1) std::printf("%a %a\n", cr_sin(a), cr_cos(a));
+        else if (f == 't' && std::scanf("%la %la", &a, &b) == 2) std::printf("%a\n", cr_atan2(a, b));
+        else if (f == 'a' && std::scanf("%la", &a) == 1) std::printf("%a\n", cr_acos(a));
+        else { std::fprintf(stderr, "cr_trig_check: bad request '%c'\n", f); return 2; }
+    }
+    return 0;
+}
 int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "--stdin")) return from_stdin();
     const long n = argc > 1 ? atol(argv[1]) : 2000000;
     long bad[4] = {0, 0, 0, 0}, hard[4] = {0, 0, 0, 0}, glibc[4] = {0, 0, 0, 0};
     for (long i = 0; i < n; i++) {

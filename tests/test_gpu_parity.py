@@ -1242,3 +1242,99 @@ def test_slow_edges_crawling_along_ribbons(torch_cuda):
     steps = cpu["info"] >> 16
     changed = np.any(np.abs(cchild[:, :len(rib)] - rib[None, :, :]) > 1e-9, axis=(1, 2)) | (((cpu["info"] >> 8) & 0xFF) != len(rib))
     assert np.count_nonzero(slow_cov & (steps > 600) & changed) > 200
+
+
+# ----------------------------------------------------------------------------------------------
+# Incumbent reduction at its edges: synthetic records, so that ties sit exactly where the reduction changes hands.
+def _best_edge(torch, ctx, rec, goal_only, base):
+    d_res = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to("cuda:0") if len(rec) else None
+    d_key = torch.zeros(2, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()      # the copies ran on torch's stream, the library works on its own
+    ctx.best_edge(len(rec), d_res.data_ptr() if d_res is not None else None, d_key.data_ptr(), goal_only=goal_only, base=base)
+    ctx.synchronize()
+    return d_key.cpu().numpy().view(np.uint64)
+
+
+def _synthetic_records(n, seed):
+    """n records, two in three feasible with f in [10, 20), the others infeasible with a smaller f that must not win; every eleventh
+    feasible one is a goal edge."""
+    from path_planner_amd.types import RESULT_DTYPE, F_INFEASIBLE, F_GOAL
+    rng = np.random.default_rng(seed)
+    rec = np.zeros(n, dtype=RESULT_DTYPE)
+    i = np.arange(n)
+    infeasible = i % 3 == 2
+    rec["f"] = np.where(infeasible, rng.uniform(0.0, 1.0, n), rng.uniform(10.0, 20.0, n))
+    rec["flags"] = np.where(infeasible, F_INFEASIBLE, np.where(i % 11 == 0, F_GOAL, 0))
+    return rec
+
+
+@pytest.mark.parametrize("n,first,second", [(300, 63, 64), (300, 255, 256), (1024 * 256 + 300, 100, 100 + 262144),
+                                            (1024 * 256 + 300, 262143, 262144), (1024 * 256 + 300, 299, 262144 + 299)],
+                         ids=["wave", "workgroup", "grid_stride", "last_block_first_block", "last_element"])
+def test_best_edge_tie_takes_the_smaller_index(torch_cuda, n, first, second):
+    """Two feasible edges with the same smallest f on either side of a wave boundary, a workgroup boundary and two passes of the
+    grid-stride loop (1 024 workgroups of 256): the smaller index wins, with an index base above 2^32."""
+    from path_planner_amd import api, sharding
+    from path_planner_amd.types import F_INFEASIBLE, F_GOAL
+    ctx = api.Context(0)
+    base = (1 << 32) + 12345
+    rec = _synthetic_records(n, n + first)
+    for tie_flags in (0, F_GOAL):
+        rec["f"][[first, second]] = 3.5
+        rec["flags"][[first, second]] = tie_flags
+        ok = (rec["flags"] & F_INFEASIBLE) == 0
+        for goal_only in (False, True):
+            use = ok & ((rec["flags"] & F_GOAL) != 0) if goal_only else ok
+            exp = sharding.local_best_key(rec["f"], use, base=base)
+            key = _best_edge(torch_cuda, ctx, rec, goal_only, base)
+            assert key.tolist() == exp.tolist(), (tie_flags, goal_only)
+            if tie_flags or not goal_only:
+                assert exp.tolist() == [sharding.f_bits(3.5).item(), base + first]
+    # the later of the two alone: the winner really is decided by the index, not by where the reduction starts
+    rec["flags"][first] = F_INFEASIBLE
+    key = _best_edge(torch_cuda, ctx, rec, False, base)
+    assert key.tolist() == [sharding.f_bits(3.5).item(), base + second]
+
+
+def test_best_edge_without_a_candidate_and_single_records(torch_cuda):
+    from path_planner_amd import api, sharding
+    from path_planner_amd.types import RESULT_DTYPE, F_INFEASIBLE, F_GOAL
+    ctx = api.Context(0)
+    none = sharding.NO_KEY.tolist()
+    rec = _synthetic_records(1000, 5)
+    rec["flags"] &= ~np.uint32(F_GOAL)
+    assert _best_edge(torch_cuda, ctx, rec, True, 7).tolist() == none                  # no goal edge
+    rec["flags"] |= F_INFEASIBLE
+    assert _best_edge(torch_cuda, ctx, rec, False, 7).tolist() == none                 # no feasible edge
+    assert _best_edge(torch_cuda, ctx, rec[:0], False, 7).tolist() == none             # n = 0
+    assert _best_edge(torch_cuda, ctx, rec[:0], True, (1 << 40)).tolist() == none
+    one = np.zeros(1, dtype=RESULT_DTYPE)
+    one["f"] = 2.25
+    assert _best_edge(torch_cuda, ctx, one, False, (1 << 33) + 1).tolist() == [sharding.f_bits(2.25).item(), (1 << 33) + 1]
+    assert _best_edge(torch_cuda, ctx, one, True, 0).tolist() == none
+    one["flags"] = F_GOAL
+    assert _best_edge(torch_cuda, ctx, one, True, 0).tolist() == sharding.local_best_key(one["f"], [True]).tolist()
+    one["flags"] = F_INFEASIBLE | F_GOAL
+    assert _best_edge(torch_cuda, ctx, one, False, 0).tolist() == none
+
+
+def test_key_min_on_one_key_and_on_equal_keys(torch_cuda):
+    from path_planner_amd import api, sharding
+    torch = torch_cuda
+    ctx = api.Context(0)
+    f2, f3 = int(sharding.f_bits(2.0)), int(sharding.f_bits(3.0))
+    cases = [
+        [[f2, (1 << 32) + 5]],                                                         # n = 1
+        [sharding.NO_KEY.tolist()],                                                    # n = 1, no incumbent
+        [[f2, 900]] * 8,                                                               # all equal
+        [sharding.NO_KEY.tolist()] * 5,
+        [[f3, 1], [f2, (1 << 32) + 9], [f2, (1 << 32) + 2], [f3, 0], sharding.NO_KEY.tolist()],     # equal f: the smaller index
+    ]
+    for keys in cases:
+        k = np.array(keys, dtype=np.uint64)
+        d_all = torch.from_numpy(k.view(np.int64).copy()).to("cuda:0")
+        d_key = torch.zeros(2, dtype=torch.int64, device="cuda:0")
+        torch.cuda.synchronize()
+        ctx.key_min(len(k), d_all.data_ptr(), d_key.data_ptr())
+        ctx.synchronize()
+        assert d_key.cpu().numpy().view(np.uint64).tolist() == sharding.combine_keys(k).tolist(), keys
