@@ -380,16 +380,21 @@ class Context:
         self._ck(LIB.ppgpu_trace_edges_list(self._h, n, _ptr(d_edges), _ptr(d_results), step_stride, _ptr(d_counts), _ptr(d_steps)),
                  "ppgpu_trace_edges_list")
 
-    def _trace_host(self, fn, name, e, step_stride, steps):
-        from .types import STEP_DTYPE
+    def _trace_records_host(self, fn, name, e, records, dtype, per_edge, before=(), after=(), none_when_empty=False):
+        """The host form `fn` of a trace over the list e: (records as cost_edges_host returns them, step counts, records[n, per_edge]).
+        `records`: an array to write into, a zeroed one by default.  before / after: what fn takes ahead of the counts and behind the records."""
         n = e.shape[0]
         res = np.zeros(n, dtype=RESULT_DTYPE)
         counts = np.zeros(n, dtype=np.int32)
-        if steps is None:
-            steps = np.zeros((n, step_stride), dtype=STEP_DTYPE)
-        assert steps.dtype == STEP_DTYPE and steps.shape == (n, step_stride) and steps.flags["C_CONTIGUOUS"]
-        self._ck(fn(self._h, n, _ptr(e), _ptr(res), step_stride, _ptr(counts), _ptr(steps)), name)
-        return res, counts, steps
+        if records is None:
+            records = np.zeros((n, per_edge), dtype=dtype)
+        assert records.dtype == dtype and records.shape == (n, per_edge) and records.flags["C_CONTIGUOUS"]
+        self._ck(fn(self._h, n, _ptr(e), _ptr(res), *before, _ptr(counts), _ptr(records) if records.size or not none_when_empty else None, *after), name)
+        return res, counts, records
+
+    def _trace_host(self, fn, name, e, step_stride, steps):
+        from .types import STEP_DTYPE
+        return self._trace_records_host(fn, name, e, steps, STEP_DTYPE, step_stride, before=(step_stride,))
 
     def trace_edges(self, edges, step_stride, steps=None):
         """Edge::computeTrueCost step by step: (records as cost_edges_host returns them, step counts, steps[n, step_stride]).
@@ -414,14 +419,10 @@ class Context:
     def _trace_cover_host(self, fn, name, e, step_stride, cover, ribbon_stride):
         from .types import COVER_DTYPE, COVER_SUMMARY_DTYPE
         n = e.shape[0]
-        res = np.zeros(n, dtype=RESULT_DTYPE)
-        counts = np.zeros(n, dtype=np.int32)
         summaries = np.zeros(n, dtype=COVER_SUMMARY_DTYPE)
         child = np.zeros((n, ribbon_stride, 4), dtype=np.float64) if ribbon_stride > 0 else None
-        if cover is None:
-            cover = np.zeros((n, step_stride), dtype=COVER_DTYPE)
-        assert cover.dtype == COVER_DTYPE and cover.shape == (n, step_stride) and cover.flags["C_CONTIGUOUS"]
-        self._ck(fn(self._h, n, _ptr(e), _ptr(res), step_stride, _ptr(counts), _ptr(cover), _ptr(summaries), _ptr(child), ribbon_stride), name)
+        res, counts, cover = self._trace_records_host(fn, name, e, cover, COVER_DTYPE, step_stride, before=(step_stride,),
+                                                      after=(_ptr(summaries), _ptr(child), ribbon_stride))
         return res, counts, cover, summaries, child
 
     def trace_cover(self, edges, step_stride, cover=None, ribbon_stride=0):
@@ -454,15 +455,8 @@ class Context:
 
     def _trace_contacts_host(self, fn, name, e, contacts):
         from .types import CONTACT_DTYPE
-        n = e.shape[0]
-        n_obst = self.obstacle_count()[0]
-        res = np.zeros(n, dtype=RESULT_DTYPE)
-        counts = np.zeros(n, dtype=np.int32)
-        if contacts is None:
-            contacts = np.zeros((n, n_obst), dtype=CONTACT_DTYPE)
-        assert contacts.dtype == CONTACT_DTYPE and contacts.shape == (n, n_obst) and contacts.flags["C_CONTIGUOUS"]
-        self._ck(fn(self._h, n, _ptr(e), _ptr(res), _ptr(counts), _ptr(contacts) if contacts.size else None), name)
-        return res, counts, contacts
+        # (without obstacles there is no record to hand over)
+        return self._trace_records_host(fn, name, e, contacts, CONTACT_DTYPE, self.obstacle_count()[0], none_when_empty=True)
 
     def trace_contacts(self, edges, contacts=None):
         """Edge::computeTrueCost contact by contact: (records as cost_edges_host returns them, step counts, contacts[n, n_obst]).

@@ -3,19 +3,16 @@
 // adds to the penalty, and how close the vehicle comes to it otherwise.  Included by pp_kernels.h.
 #pragma once
 // The step trace (pp_k_trace.h) gives collisionExists per step, summed over the contacts; this kernel gives the same sweep per
-// contact.  It runs AFTER a costing launch over the same edge list, on the same PPEdgeSetup records, takes the step count from the
-// record (pp_trace_edge's rule) and the poses from pp_window_pose on the same 64-step windows as the step trace (the same doubles).
-// One wavefront per edge, no skipping, no culling.  Per window
-//     lane = step          pose, time, isBlocked as pp_trace_edge has them; Gaussian model: the step's own collisionExists
+// contact, on the shared trace core (pp_k_trace_common.h): the step count is pp_trace_head's and the windows are pp_trace_window's,
+// without headings, so the steps and poses are those of the step trace (the same doubles).  No skipping, no culling.  Per window
+//     lane = step          pose, time, isBlocked from pp_trace_window; Gaussian model: the step's own collisionExists
 //                          (pp_obstacle_density_chunk, the floored sum the costing launch counts).  {x, y} {time, flags} go to LDS.
 //     lane = obstacle row  walks the window's steps from LDS (every lane reads the same address: a broadcast) with the arithmetic of
 //                          pp_obstacle_hit / pp_obstacle_pdf and keeps the contact's accumulators in registers: strict `<` on the
 //                          squared distance keeps the earliest step on ties, and nothing crosses lanes.
 // More than 64 rows: passes of 64, each walking the edge again (the accumulators stay in registers; fleets that large are rare).
-// A pass's records are contiguous (4 KB for 64 rows) and leave through LDS as four coalesced 16-byte-per-lane stores, the
-// pp_trace_edge idiom.  With 16 rows the second phase uses a quarter of the wave; DESIGN.md 4.2 says why that form was kept.
-#define PP_KTRACE_WPB 4
-#define PP_KTRACE_LDS_STRIDE 65    // 16-byte units between the four pieces of the records in LDS (odd: spreads the banks)
+// A pass's records are contiguous (4 KB for 64 rows) and leave through pp_trace_store, from the LDS block that held the window's
+// steps.  With 16 rows the second phase uses a quarter of the wave; DESIGN.md 4.2 says why that form was kept.
 #define PP_KTRACE_VALID   1u       // flags of a step in LDS: the step was executed,
 #define PP_KTRACE_BLOCKED 2u       // ... Map::isBlocked at its pose (Edge.cpp:144: the loop broke before collisionExists),
 #define PP_KTRACE_COUNTED 4u       // ... it adds to the penalty (:150-151): not blocked and, Gaussian model, a floored sum that is not 0
@@ -23,30 +20,17 @@ static_assert(sizeof(ppgpu_contact_record) == 64, "a contact record is 64 bytes:
 static_assert(sizeof(PPObst) == sizeof(PPGauss) && offsetof(PPGauss, i00) == offsetof(PPObst, halfL) && offsetof(PPGauss, i10) == offsetof(PPObst, pad),
               "a PPGauss row is read through PPObst's fields");
 
-// el = the edge's position in the slice; lds = this wave's 4 * PP_KTRACE_LDS_STRIDE double2 (the window's steps, then the records)
+// el = the edge's position in the slice; lds = this wave's 4 * PP_TRACE_LDS_STRIDE double2 (the window's steps, then the records)
 template <bool GAUSSIAN>
 __device__ __forceinline__ void pp_contact_trace_edge(const PPParams& p, const long long el, ppgpu_contact_record* recs, const long long rec_base,
                                                       int* counts, double2* lds) {
     const int lane = pp_lane();
-    const long long e = p.ws_base + el;                                   // slot in the workspace
-    const long long eg = pp_edge_position(p, p.e_base + el);              // position in the caller's list
-    const PPEdgeSetup* S = p.setup + e;
-    const ppgpu_edge_result* rec = p.out + eg;
-    const unsigned rflags = (unsigned)pp_const_i32(&rec->flags)[0], info = (unsigned)pp_const_i32(&rec->info)[0];
-    const unsigned sflags = (unsigned)PP_SI32(sflags);
-    const int dubType = PP_SI32(type);
-    int count = (int)(info >> 16);
-    if ((sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || dubType < 0 || (rflags & PPGPU_F_THROWS)) count = 0;
-    if (count > p.ng) count = p.ng;                                       // (a step has a time: never more steps than the grid holds)
-    if (lane == 0) counts[eg] = count;
+    const PPTraceHead h = pp_trace_head(p, el);
+    const int count = h.count;
+    if (lane == 0) counts[h.eg] = count;
     const int nob = p.n_obst;
     if (nob <= 0) return;
-    const unsigned vi = (unsigned)PP_SI32(vi);
-    const PPCurveHot hot = pp_curve_hot(S);
-    const double* tg = p.tgrid + (size_t)vi * p.ng;
-    const double chunkTime = 64.0 * (p.inc_d / p.max_speed);
-    const double chunkSpan = chunkTime * hot.speed;
-    double2* out = reinterpret_cast<double2*>(recs + (size_t)(eg - rec_base) * (size_t)nob);
+    double2* out = reinterpret_cast<double2*>(recs + (size_t)(h.eg - rec_base) * (size_t)nob);
     for (int b = 0; b < nob; b += PP_WAVE) {
         const int rows = (nob - b) < PP_WAVE ? (nob - b) : PP_WAVE;
         PPObst o = {0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
@@ -55,30 +39,18 @@ __device__ __forceinline__ void pp_contact_trace_edge(const PPParams& p, const l
         const double i00 = o.halfL, i01 = o.halfW, i10 = o.pad[0], i11 = o.pad[1], norm = o.pad[2];
         double minD2 = INFINITY, cpaTime = -1.0, firstT = -1.0, lastT = -1.0, exposure = 0.0, peak = 0.0;
         int cpaStep = -1, hitSteps = 0, firstK = -1, lastK = -1;
-        int cur = 0;
-        PPSeg cs = pp_seg_load_uniform(&S->seg[0], 0, PP_SF64(p0), PP_SF64(p1), PP_SF64(hi1), PP_SI32(type));
-        bool dubErr = false;
+        PPTraceWalk walk = pp_trace_walk_begin(h, 0.0);
         for (int base = 0; base < count; base += PP_WAVE) {
-            const int k = base + lane;
-            const bool valid = k < count;
-            const double t = tg[valid ? k : base];
-            const double tFirst = pp_readlane(t, 0);
-            double x, y, uth;
-            pp_window_pose(S, hot, cur, cs, t, tFirst, valid, x, y, uth, dubErr);
-            const bool blk = valid & pp_is_blocked(p.grid, x, y);          // Edge.cpp:144
-            bool counted = valid & !blk;
-            if (GAUSSIAN) {
-                const double dens = pp_obstacle_density_chunk(reinterpret_cast<const PPGauss*>(p.obst), nob, x, y, t, valid, pp_readlane(x, 0),
-                                                              pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
-                counted = counted & (dens != 0.0);
-            }
-            const unsigned sf = (valid ? PP_KTRACE_VALID : 0u) | (blk ? PP_KTRACE_BLOCKED : 0u) | (counted ? PP_KTRACE_COUNTED : 0u);
-            lds[lane] = make_double2(x, y);
-            lds[PP_KTRACE_LDS_STRIDE + lane] = make_double2(t, __longlong_as_double((long long)(unsigned long long)sf));
+            const PPTraceWindow n = pp_trace_window<false>(p, h, walk, base, count);
+            bool counted = n.valid & !n.blocked;
+            if (GAUSSIAN) counted = counted & (pp_trace_density(p, h, n) != 0.0);
+            const unsigned sf = (n.valid ? PP_KTRACE_VALID : 0u) | (n.blocked ? PP_KTRACE_BLOCKED : 0u) | (counted ? PP_KTRACE_COUNTED : 0u);
+            lds[lane] = make_double2(n.x, n.y);
+            lds[PP_TRACE_LDS_STRIDE + lane] = make_double2(n.t, __longlong_as_double((long long)(unsigned long long)sf));
             pp_wave_lds_fence();
             const int nsteps = (count - base) < PP_WAVE ? (count - base) : PP_WAVE;
             for (int s = 0; s < nsteps; s++) {
-                const double2 xy = lds[s], tf = lds[PP_KTRACE_LDS_STRIDE + s];
+                const double2 xy = lds[s], tf = lds[PP_TRACE_LDS_STRIDE + s];
                 const double st = tf.x;
                 const unsigned f = (unsigned)(unsigned long long)__double_as_longlong(tf.y);
                 // pp_obstacle_hit / pp_obstacle_pdf, term for term
@@ -113,36 +85,26 @@ __device__ __forceinline__ void pp_contact_trace_edge(const PPParams& p, const l
         const double cpaDist = cpaStep >= 0 ? sqrt(minD2) : -1.0;
         // the record, as four 16-byte pieces: {cpa_distance, cpa_time} {first, last hit time} {exposure, cpa_step | hit_steps}
         // {first | last hit step, peak}
-        lds[0 * PP_KTRACE_LDS_STRIDE + lane] = make_double2(cpaDist, cpaTime);
-        lds[1 * PP_KTRACE_LDS_STRIDE + lane] = make_double2(firstT, lastT);
-        lds[2 * PP_KTRACE_LDS_STRIDE + lane] =
+        lds[0 * PP_TRACE_LDS_STRIDE + lane] = make_double2(cpaDist, cpaTime);
+        lds[1 * PP_TRACE_LDS_STRIDE + lane] = make_double2(firstT, lastT);
+        lds[2 * PP_TRACE_LDS_STRIDE + lane] =
             make_double2(exposure, __longlong_as_double((long long)(((unsigned long long)(unsigned)hitSteps << 32) | (unsigned long long)(unsigned)cpaStep)));
-        lds[3 * PP_KTRACE_LDS_STRIDE + lane] =
+        lds[3 * PP_TRACE_LDS_STRIDE + lane] =
             make_double2(__longlong_as_double((long long)(((unsigned long long)(unsigned)lastK << 32) | (unsigned long long)(unsigned)firstK)), peak);
-        pp_wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int q = j * PP_WAVE + lane;                              // 16-byte piece q of the pass's 4 KB
-            const int r = q >> 2;                                          // ... belongs to the record of row b + r
-            const double2 v = lds[(q & 3) * PP_KTRACE_LDS_STRIDE + r];
-            if (r < rows) out[(size_t)b * 4 + q] = v;
-        }
-        pp_wave_lds_fence();
+        pp_trace_store<4>(lds, out, b, nob);                               // row b + r: of the pass's 64 rows, those the table has
     }
 }
 
 // n_edges = slice size; recs[(edge - rec_base) * p.n_obst + row]; counts[edge]
-__global__ __launch_bounds__(PP_KTRACE_WPB * 64) void pp_k_trace_contacts(PPParams p, ppgpu_contact_record* recs, long long rec_base, int* counts) {
-    __shared__ double2 s_rec[PP_KTRACE_WPB][4 * PP_KTRACE_LDS_STRIDE];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long el = (long long)blockIdx.x * PP_KTRACE_WPB + wave;
-    if (el >= p.n_edges) return;
-    pp_contact_trace_edge<false>(p, el, recs, rec_base, counts, s_rec[wave]);
+__global__ __launch_bounds__(PP_TRACE_WPB * 64) void pp_k_trace_contacts(PPParams p, ppgpu_contact_record* recs, long long rec_base, int* counts) {
+    __shared__ double2 s_rec[PP_TRACE_WPB][4 * PP_TRACE_LDS_STRIDE];
+    int wave;
+    long long el;
+    if (pp_trace_entry(p, wave, el)) pp_contact_trace_edge<false>(p, el, recs, rec_base, counts, s_rec[wave]);
 }
-__global__ __launch_bounds__(PP_KTRACE_WPB * 64) void pp_k_trace_contacts_gaussian(PPParams p, ppgpu_contact_record* recs, long long rec_base, int* counts) {
-    __shared__ double2 s_rec[PP_KTRACE_WPB][4 * PP_KTRACE_LDS_STRIDE];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long el = (long long)blockIdx.x * PP_KTRACE_WPB + wave;
-    if (el >= p.n_edges) return;
-    pp_contact_trace_edge<true>(p, el, recs, rec_base, counts, s_rec[wave]);
+__global__ __launch_bounds__(PP_TRACE_WPB * 64) void pp_k_trace_contacts_gaussian(PPParams p, ppgpu_contact_record* recs, long long rec_base, int* counts) {
+    __shared__ double2 s_rec[PP_TRACE_WPB][4 * PP_TRACE_LDS_STRIDE];
+    int wave;
+    long long el;
+    if (pp_trace_entry(p, wave, el)) pp_contact_trace_edge<true>(p, el, recs, rec_base, counts, s_rec[wave]);
 }

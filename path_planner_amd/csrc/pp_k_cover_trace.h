@@ -4,23 +4,19 @@
 #pragma once
 // The cover sweep (pp_k_cover.h) visits event steps only and takes whole stretches of them as corridor, quiet and long runs; the
 // step trace (pp_k_trace.h) has the poses but no coverage state machine.  This kernel is the state machine itself, executed
-// literally: it runs AFTER a costing launch over the same edge list, on the same PPEdgeSetup records, takes the step count from the
-// record (pp_trace_edge's rule) and the poses from pp_window_pose on the same 64-step windows as the step trace (the same
-// doubles), and for step k = 0 .. steps - 1 does what the reference does —
+// literally, on the shared trace core (pp_k_trace_common.h): the step count is pp_trace_head's and the windows are pp_trace_window's,
+// so the steps, poses, headings, straight and blocked bits are those of the step trace (the same doubles).  For step
+// k = 0 .. steps - 1 it does what the reference does —
 //     blocked (Edge.cpp:144-146)                        nothing: the loop broke before the coverage branch
 //     toCoverDistance > increment (:153-154)            the literal subtraction, one per step
 //     otherwise, an EVENT (:155-171)                    pp_ribbons_event at the step's pose: D = minDistanceFrom, then cover(pose, strict)
 //                                                       when the edge covers or the heading did not change (:159); an emptied list
 //                                                       sets coverageCompletedTime if it is still -1
-// — with no skipping and no runs.  One wavefront per edge.  The lanes compute a window's 64 poses, headings, straight and blocked
-// bits; the wave then walks the window's steps in a wave-uniform loop (a countdown step is a compare and a subtraction on
+// — with no skipping and no runs.  The lanes have a window's 64 poses, straight and blocked bits; the wave then walks the window's steps in a wave-uniform loop (a countdown step is a compare and a subtraction on
 // wave-uniform values; an event step broadcasts its pose with a readlane and runs pp_ribbons_event across the lanes, ribbon i in
-// lane i), lane j keeping step j's record.  The window's 64 records are 2 KB contiguous and leave through LDS as two fully coalesced
-// 16-byte-per-lane stores, as pp_trace_edge's do.  toCoverDistance, lastHeading, the list, its length and coverageCompletedTime
+// lane i), lane j keeping step j's record.  The window's 64 records are 2 KB contiguous and leave through pp_trace_store.  toCoverDistance, lastHeading, the list, its length and coverageCompletedTime
 // carry from window to window.  A step_stride below the edge's count cuts the records, not the walk: summary and final list are
 // those of the whole edge.
-#define PP_CTRACE_WPB 4
-#define PP_CTRACE_LDS_STRIDE 65    // 16-byte units between the two pieces of the records in LDS (odd: spreads the banks)
 static_assert(sizeof(ppgpu_cover_record) == 32 && sizeof(ppgpu_cover_summary) == 32, "cover records and summaries are two 16-byte pieces");
 
 // sum of the end-to-end lengths of the n ribbons the lanes hold (wave-uniform)
@@ -53,33 +49,27 @@ __device__ __forceinline__ void pp_cover_trace_summary(ppgpu_cover_summary* s, i
     }
 }
 
-// el = the edge's position in the slice; lds_rec = this wave's 2 * PP_CTRACE_LDS_STRIDE double2; lds_ev = its 64 x 4 doubles for pp_ribbons_event
+// el = the edge's position in the slice; lds_rec = this wave's 2 * PP_TRACE_LDS_STRIDE double2; lds_ev = its 64 x 4 doubles for pp_ribbons_event
 __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const long long el, ppgpu_cover_record* recs, const long long rec_base,
                                                     const int stride, int* counts, ppgpu_cover_summary* sums, double* child, const int cstride,
                                                     double2* lds_rec, double* lds_ev) {
     const int lane = pp_lane();
-    const long long e = p.ws_base + el;                                   // slot in the workspace
-    const long long eg = pp_edge_position(p, p.e_base + el);              // position in the caller's list
-    const PPEdgeSetup* S = p.setup + e;
-    const ppgpu_edge_result* rec = p.out + eg;
-    const unsigned rflags = (unsigned)pp_const_i32(&rec->flags)[0], info = (unsigned)pp_const_i32(&rec->info)[0];
-    const unsigned sflags = (unsigned)PP_SI32(sflags);
-    const int dubType = PP_SI32(type);
+    const PPTraceHead h = pp_trace_head(p, el);
+    const PPEdgeSetup* S = h.S;
+    const long long eg = h.eg;
+    const int count = h.count;
     ppgpu_cover_summary* sum = sums + eg;
-    if ((sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || dubType < 0 || (rflags & PPGPU_F_THROWS)) {
+    if (h.throws) {
         // the reference throws out of computeTrueCost (Edge.cpp:178 at the latest, before the last cover): there is no child
         if (lane == 0) counts[eg] = 0;
         pp_cover_trace_summary(sum, 0, 0, 0, PPGPU_CS_THROWS, -1.0, 0.0);
         return;
     }
-    int count = (int)(info >> 16);
-    if (count > p.ng) count = p.ng;                                       // (a step has a time: never more steps than the grid holds)
-    const unsigned vi = (unsigned)PP_SI32(vi);
-    const ppgpu_vertex* V = p.verts + vi;
+    const ppgpu_vertex* V = p.verts + h.vi;
     const bool cov = ((unsigned)PP_SI32(cbits) & PPGPU_EDGE_COVERAGE) != 0u;    // end()->coverageAllowed()
     double cct = pp_sgpr(V->coverage_completed_time);
     int nrib = __builtin_amdgcn_readfirstlane(V->ribbon_count);
-    if (nrib > PP_WAVE || (rflags & PPGPU_F_RIBBON_LOST)) {              // a list the device cannot hold: refused before anything is written
+    if (nrib > PP_WAVE || (h.rflags & PPGPU_F_RIBBON_LOST)) {            // a list the device cannot hold: refused before anything is written
         if (lane == 0) counts[eg] = 0;
         pp_cover_trace_summary(sum, 0, 0, 0, PPGPU_CS_REFUSED, -1.0, 0.0);
         return;
@@ -97,26 +87,13 @@ __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const lon
     double lastX = pp_sgpr(V->x), lastY = pp_sgpr(V->y);
     bool lastBlocked = false, lastStraight = true;
     const int nw = count < stride ? count : stride;                       // records written: the ribbon_stride idiom
-    const double* tg = p.tgrid + (size_t)vi * p.ng;
     double2* out = reinterpret_cast<double2*>(recs + (size_t)(eg - rec_base) * (size_t)stride);
     if (count > 0) {
-        const PPCurveHot hot = pp_curve_hot(S);
-        int cur = 0;
-        PPSeg cs = pp_seg_load_uniform(&S->seg[0], 0, PP_SF64(p0), PP_SF64(p1), PP_SF64(hi1), PP_SI32(type));
-        double carryHeading = pp_sgpr(V->heading);                        // `lastHeading`, Edge.cpp:96
-        bool dubErr = false;
+        PPTraceWalk walk = pp_trace_walk_begin(h, pp_sgpr(V->heading));
         for (int base = 0; base < count; base += PP_WAVE) {
-            const int k = base + lane;
-            const bool valid = k < count;
-            const double t = tg[valid ? k : base];
-            double x, y, uth;
-            pp_window_pose(S, hot, cur, cs, t, pp_readlane(t, 0), valid, x, y, uth, dubErr);
-            const double heading = pp_heading_from_yaw(pp_mod2pi(uth));    // DubinsWrapper.cpp:47
-            double prevHeading = __shfl_up(heading, 1, PP_WAVE);
-            if (lane == 0) prevHeading = carryHeading;
-            carryHeading = pp_readlane(heading, PP_WAVE - 1);
-            const unsigned long long blkMask = __ballot(valid & pp_is_blocked(p.grid, x, y));       // Edge.cpp:144
-            const unsigned long long strMask = __ballot(prevHeading == heading);                    // :159
+            const PPTraceWindow n = pp_trace_window<true>(p, h, walk, base, count);
+            const unsigned long long blkMask = __ballot(n.blocked);                                 // Edge.cpp:144
+            const unsigned long long strMask = __ballot(n.straight);                                // :159
             const int nsteps = (count - base) < PP_WAVE ? (count - base) : PP_WAVE;
             double myToCover = 0.0, myRemaining = 0.0;
             unsigned myFlags = 0u;
@@ -130,7 +107,7 @@ __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const lon
                         const bool doCover = cov || ((strMask >> j) & 1ull) != 0ull;
                         bool changed;
                         double D;
-                        if (!pp_cover_trace_event(rib, nrib, w, pp_readlane(x, j), pp_readlane(y, j), doCover, lds_ev, D, changed)) {
+                        if (!pp_cover_trace_event(rib, nrib, w, pp_readlane(n.x, j), pp_readlane(n.y, j), doCover, lds_ev, D, changed)) {
                             // (only where the literal walk splits a piece the costing launch's runs did not: records of earlier windows stay)
                             if (lane == 0) counts[eg] = 0;
                             pp_cover_trace_summary(sum, 0, 0, 0, PPGPU_CS_REFUSED, -1.0, 0.0);
@@ -140,30 +117,22 @@ __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const lon
                         f = PPGPU_C_EVENT | (doCover ? PPGPU_C_COVER : 0u) | (changed ? PPGPU_C_CHANGED : 0u);
                         events++;
                         if (changed) { changes++; remaining = pp_ribbons_total_length(rib, nrib); }
-                        if (nrib == 0 && cct == -1) cct = pp_readlane(t, j);       // :162-166
+                        if (nrib == 0 && cct == -1) cct = pp_readlane(n.t, j);       // :162-166
                     }
                 }
                 if (nrib == 0) f |= PPGPU_C_DONE;
                 if (lane == j) { myToCover = toCover; myRemaining = remaining; myFlags = f; myRibbons = nrib; }
             }
-            lastX = pp_readlane(x, nsteps - 1); lastY = pp_readlane(y, nsteps - 1);
+            lastX = pp_readlane(n.x, nsteps - 1); lastY = pp_readlane(n.y, nsteps - 1);
             lastBlocked = ((blkMask >> (nsteps - 1)) & 1ull) != 0ull;
             lastStraight = ((strMask >> (nsteps - 1)) & 1ull) != 0ull;
             if (base < nw) {
                 // the record, as two 16-byte pieces: {to_cover, remaining} {flags | step, ribbons | reserved}
-                lds_rec[0 * PP_CTRACE_LDS_STRIDE + lane] = make_double2(myToCover, myRemaining);
-                lds_rec[1 * PP_CTRACE_LDS_STRIDE + lane] =
-                    make_double2(__longlong_as_double((long long)(((unsigned long long)(unsigned)k << 32) | (unsigned long long)myFlags)),
+                lds_rec[0 * PP_TRACE_LDS_STRIDE + lane] = make_double2(myToCover, myRemaining);
+                lds_rec[1 * PP_TRACE_LDS_STRIDE + lane] =
+                    make_double2(__longlong_as_double((long long)(((unsigned long long)(unsigned)n.k << 32) | (unsigned long long)myFlags)),
                                  __longlong_as_double((long long)(unsigned long long)(unsigned)myRibbons));
-                pp_wave_lds_fence();
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    const int q = j * PP_WAVE + lane;                      // 16-byte piece q of the window's 2 KB
-                    const int r = q >> 1;                                  // ... belongs to the record of step base + r
-                    const double2 v = lds_rec[(q & 1) * PP_CTRACE_LDS_STRIDE + r];
-                    if (base + r < nw) out[(size_t)base * 2 + q] = v;
-                }
-                pp_wave_lds_fence();
+                pp_trace_store<2>(lds_rec, out, base, nw);
             }
         }
     }
@@ -184,7 +153,7 @@ __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const lon
     if (nrib == 0) {
         sf |= PPGPU_CS_DONE;
         // `intermediate.time()` where the loop stopped (:187-189): the blocked step's own time, else one increment past the last step
-        if (cct == -1) cct = lastBlocked ? pp_const_f64(tg + count - 1)[0] : ((count < p.ng) ? pp_const_f64(tg + count)[0] : INFINITY);
+        if (cct == -1) cct = lastBlocked ? pp_const_f64(h.tg + count - 1)[0] : ((count < p.ng) ? pp_const_f64(h.tg + count)[0] : INFINITY);
     }
     if (lane == 0) counts[eg] = count;
     pp_cover_trace_summary(sum, events, changes, nrib, sf, cct, remaining);
@@ -195,12 +164,11 @@ __device__ __forceinline__ void pp_cover_trace_edge(const PPParams& p, const lon
 }
 
 // n_edges = slice size; recs[(edge - rec_base) * stride + k]; counts[edge], sums[edge], child[edge * cstride + i] (may be NULL)
-__global__ __launch_bounds__(PP_CTRACE_WPB * 64) void pp_k_trace_cover(PPParams p, ppgpu_cover_record* recs, long long rec_base, int stride, int* counts,
-                                                                      ppgpu_cover_summary* sums, double* child, int cstride) {
-    __shared__ double2 s_rec[PP_CTRACE_WPB][2 * PP_CTRACE_LDS_STRIDE];
-    __shared__ double s_ev[PP_CTRACE_WPB][PP_WAVE * 4];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long el = (long long)blockIdx.x * PP_CTRACE_WPB + wave;
-    if (el >= p.n_edges) return;
-    pp_cover_trace_edge(p, el, recs, rec_base, stride, counts, sums, child, cstride, s_rec[wave], s_ev[wave]);
+__global__ __launch_bounds__(PP_TRACE_WPB * 64) void pp_k_trace_cover(PPParams p, ppgpu_cover_record* recs, long long rec_base, int stride, int* counts,
+                                                                     ppgpu_cover_summary* sums, double* child, int cstride) {
+    __shared__ double2 s_rec[PP_TRACE_WPB][2 * PP_TRACE_LDS_STRIDE];
+    __shared__ double s_ev[PP_TRACE_WPB][PP_WAVE * 4];
+    int wave;
+    long long el;
+    if (pp_trace_entry(p, wave, el)) pp_cover_trace_edge(p, el, recs, rec_base, stride, counts, sums, child, cstride, s_rec[wave], s_ev[wave]);
 }

@@ -140,11 +140,9 @@ struct ppgpu_ctx {
     DevBuf<ppgpu_wrapper_edge> tmp_wedges;
     DevBuf<ppgpu_edge_result> tmp_results;
     DevBuf<double> tmp_child, tmp_lengths, tmp_len_out, int_child;
-    DevBuf<ppgpu_step_record> tmp_steps;   // device end of the host forms of ppgpu_trace_*: the step records of one trace slice
-    DevBuf<ppgpu_cover_record> tmp_cover;  // ... and of ppgpu_trace_cover_*: the cover records of one slice,
-    DevBuf<ppgpu_cover_summary> tmp_summaries;   // the summaries and final lists of the whole list
+    DevBuf<unsigned char> tmp_trace;       // device end of the host forms of the traces: the step, cover or contact records of one trace slice
+    DevBuf<ppgpu_cover_summary> tmp_summaries;   // ... of ppgpu_trace_cover_*: the summaries and final lists of the whole list
     DevBuf<double> tmp_cover_child;
-    DevBuf<ppgpu_contact_record> tmp_contacts;   // ... of ppgpu_trace_contacts_*: the contact records of one slice
     DevBuf<int> tmp_counts;
     TraceTimer t_steps, t_cover, t_contacts;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
@@ -251,12 +249,6 @@ static int check_wrapper_edges(const ppgpu_ctx* c, const char* who, int64_t n, c
         if (!(w[i].rho > 0) || !(w[i].speed > 0)) return fail(PPGPU_EINVAL, std::string(who) + ": rho and speed must be positive");
         if (w[i].vertex < 0 || w[i].vertex >= c->nverts) return fail(PPGPU_EINVAL, std::string(who) + ": vertex out of range");
     }
-    return PPGPU_OK;
-}
-
-static int trace_args(const char* who, int64_t n, const void* edges, int32_t stride, const void* counts, const void* steps) {
-    if (n < 0 || (n > 0 && (!edges || !counts || !steps))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
-    if (stride <= 0 || stride > 65535) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
     return PPGPU_OK;
 }
 
@@ -1259,24 +1251,80 @@ int ppgpu_cost_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgp
 }
 
 // ------------------------------------------------------------------------------ edge traces
-// A per-step trace of the list the launch L just costed: `launch(q, dst, rec_base)` starts the trace kernel on one slice q, its
-// records going to dst[(edge - rec_base) * stride + k].  A trace kernel reads the PPEdgeSetup records of the costing launch: they are
-// all still in the workspace when that launch ran as one slice; a launch that ran as several has only its last slice's left, and
-// pp_k_solve_edges writes them again, slice by slice (a fraction of the time the records take to write).  Host form (h_recs !=
-// NULL): the records of one pass go through `tmp`, at most the handle's slice budget at a time; what the caller's array
-// holds beyond an edge's count stays as it is (the pass starts from the caller's bytes).
-extern "C++" {
-template <typename Rec, typename Launch>
-static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, int stride, DevBuf<Rec>& tmp, TraceTimer& tm, Rec* d_recs, Rec* h_recs, Launch launch) {
+// One trace of an edge list: which kernel, and where its output goes.  The _list entries fill it with the caller's device arrays,
+// the host forms with the caller's host arrays (cost_host_list then swaps in the device ends of all but the records).
+enum TraceKind { TRACE_STEPS, TRACE_COVER, TRACE_CONTACTS };
+struct TraceRequest {
+    TraceKind kind;
+    int32_t stride;                     // step and cover records per edge (a contact trace has n_obst records per edge)
+    int32_t* counts;                    // steps of each edge
+    void* records;                      // ppgpu_step_record / ppgpu_cover_record / ppgpu_contact_record ...
+    size_t rec_bytes;                   // ... of this size
+    ppgpu_cover_summary* summaries;     // coverage traces only: one summary per edge,
+    double* child;                      // the final lists (may be NULL)
+    int32_t ribbon_stride;
+};
+static TraceRequest steps_request(int32_t stride, int32_t* counts, ppgpu_step_record* steps) {
+    return TraceRequest{TRACE_STEPS, stride, counts, steps, sizeof(ppgpu_step_record), nullptr, nullptr, 0};
+}
+static TraceRequest cover_request(int32_t stride, int32_t* counts, ppgpu_cover_record* cover, ppgpu_cover_summary* summaries, double* child, int32_t ribbon_stride) {
+    return TraceRequest{TRACE_COVER, stride, counts, cover, sizeof(ppgpu_cover_record), summaries, child, ribbon_stride};
+}
+static TraceRequest contacts_request(int32_t* counts, ppgpu_contact_record* contacts) {
+    return TraceRequest{TRACE_CONTACTS, 0, counts, contacts, sizeof(ppgpu_contact_record), nullptr, nullptr, 0};
+}
+
+// What a trace entry was handed; `who` is its name in the message.  `device`: a _list entry (device arrays, the records stored
+// 16 bytes at a time; it needs the results array).  Contact records may be missing only when there is no obstacle to report on.
+static int trace_request_args(const ppgpu_ctx* c, const char* who, bool device, int64_t n, const void* edges, const void* results, const TraceRequest& r) {
+    static const char* const records_name[] = {"d_steps", "d_cover", "d_contacts"};
+    const bool cover = r.kind == TRACE_COVER, contacts = r.kind == TRACE_CONTACTS;
+    if (n < 0 || (n > 0 && (!edges || !r.counts || ((!contacts || c->n_obst > 0) && !r.records)))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
+    if (!contacts && (r.stride <= 0 || r.stride > 65535)) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
+    if (device) {
+        if (n > 0 && (!results || (cover && !r.summaries))) return fail(PPGPU_EINVAL, std::string(who) + (cover ? ": null results or summaries" : ": null results"));
+    } else if (cover && n > 0 && !r.summaries) {
+        return fail(PPGPU_EINVAL, std::string(who) + ": null summaries");
+    }
+    if (cover && r.child && r.ribbon_stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
+    if (device && ((unsigned long long)r.records & 15ull) != 0ull)
+        return fail(PPGPU_EINVAL, std::string(who) + ": " + records_name[r.kind] + " must be 16-byte aligned");
+    return PPGPU_OK;
+}
+
+// the trace kernel of r on one slice q, its records going to dst[(edge - rec_base) * stride + k]
+static void trace_kernel(ppgpu_ctx* c, const CostLaunch& L, const PPParams& q, const TraceRequest& r, void* dst, long long rec_base) {
+    const dim3 grid((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)), block(PP_TRACE_WPB * 64);
+    switch (r.kind) {
+    case TRACE_STEPS:
+        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_steps_gaussian : pp_k_trace_steps, grid, block, 0, c->stream, q, (ppgpu_step_record*)dst, rec_base, r.stride, r.counts);
+        break;
+    case TRACE_COVER:
+        hipLaunchKernelGGL(pp_k_trace_cover, grid, block, 0, c->stream, q, (ppgpu_cover_record*)dst, rec_base, r.stride, r.counts, r.summaries, r.child,
+                           r.child ? r.ribbon_stride : 0);
+        break;
+    case TRACE_CONTACTS:
+        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_contacts_gaussian : pp_k_trace_contacts, grid, block, 0, c->stream, q, (ppgpu_contact_record*)dst, rec_base, r.counts);
+        break;
+    }
+}
+
+// A trace of the list the launch L just costed, `stride` records per edge to `recs`.  A trace kernel reads the PPEdgeSetup records of
+// the costing launch: they are all still in the workspace when that launch ran as one slice; a launch that ran as several has only
+// its last slice's left, and pp_k_solve_edges writes them again, slice by slice (a fraction of the time the records take to write).
+// Host form (`host`: recs is a host array): the records of one pass go through tmp_trace, at most the handle's slice budget at a
+// time; what the caller's array holds beyond an edge's count stays as it is (the pass starts from the caller's bytes).
+static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r, TraceTimer& tm, int stride, unsigned char* recs, bool host) {
     const PPParams& p = L.p;
     const long long total = p.n_edges;            // (> 0: an empty list never gets as far as a launch)
     const bool reuse = L.slice >= total;
+    const size_t edge_bytes = (size_t)stride * r.rec_bytes;
     long long pass = reuse ? total : L.slice;
-    if (h_recs) {
-        long long cap = (long long)(c->slice_bytes / ((size_t)stride * sizeof(Rec)));
+    if (host) {
+        long long cap = (long long)(c->slice_bytes / edge_bytes);
         if (cap < 1) cap = 1;
         if (pass > cap) pass = cap;
-        int rc = tmp.reserve((size_t)pass * stride, false, c->stream);
+        int rc = c->tmp_trace.reserve((size_t)pass * edge_bytes, false, c->stream);
         if (rc) return rc;
     }
     tm.ms_earlier = 0;
@@ -1289,9 +1337,9 @@ static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, int stride, DevBuf<Re
             q.live_count = nullptr; q.defer_count = nullptr; q.hw_count = nullptr;     // (counters of the costing launch: ppgpu_last_cover_edges still reads them)
             hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
         }
-        Rec* dst = h_recs ? tmp.p : d_recs;
-        const size_t bytes = (size_t)q.n_edges * stride * sizeof(Rec);
-        if (h_recs) HIP_TRY(hipMemcpyAsync(dst, h_recs + (size_t)e0 * stride, bytes, hipMemcpyHostToDevice, c->stream));
+        unsigned char* dst = host ? c->tmp_trace.p : recs;
+        const size_t bytes = (size_t)q.n_edges * edge_bytes;
+        if (host) HIP_TRY(hipMemcpyAsync(dst, recs + (size_t)e0 * edge_bytes, bytes, hipMemcpyHostToDevice, c->stream));
         if (c->timing && tm.timed) {                    // a further slice re-uses the events: bank the one before
             float ms = 0;
             HIP_TRY(hipEventSynchronize(tm.ev[1]));
@@ -1299,17 +1347,16 @@ static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, int stride, DevBuf<Re
             tm.ms_earlier += ms;
         }
         if (c->timing) HIP_TRY(hipEventRecord(tm.ev[0], c->stream));
-        launch(q, dst, h_recs ? e0 : 0ll);
+        trace_kernel(c, L, q, r, dst, host ? e0 : 0ll);
         if (c->timing) { HIP_TRY(hipEventRecord(tm.ev[1], c->stream)); tm.timed = true; }
         HIP_TRY(hipGetLastError());
-        if (h_recs) {
-            HIP_TRY(hipMemcpyAsync(h_recs + (size_t)e0 * stride, dst, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (host) {
+            HIP_TRY(hipMemcpyAsync(recs + (size_t)e0 * edge_bytes, dst, bytes, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));   // the next pass writes the same buffer
         }
     }
     return PPGPU_OK;
 }
-}  // extern "C++"
 
 static int trace_timing(ppgpu_ctx* c, TraceTimer& tm, double* ms_out) {
     if (!c || !ms_out) return fail(PPGPU_EINVAL, "null argument");
@@ -1322,35 +1369,14 @@ static int trace_timing(ppgpu_ctx* c, TraceTimer& tm, double* ms_out) {
     return PPGPU_OK;
 }
 
-// pp_k_trace_steps over the list of L
-static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_step_record* d_steps, ppgpu_step_record* h_steps) {
-    return trace_passes(c, L, stride, c->tmp_steps, c->t_steps, d_steps, h_steps, [&](const PPParams& q, ppgpu_step_record* dst, long long rec_base) {
-        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_steps_gaussian : pp_k_trace_steps, dim3((unsigned)((q.n_edges + PP_TRACE_WPB - 1) / PP_TRACE_WPB)),
-                           dim3(PP_TRACE_WPB * 64), 0, c->stream, q, dst, rec_base, stride, d_counts);
-    });
-}
-
-// What a coverage trace gives per edge beside its records (device arrays over the whole list; child may be NULL).
-struct CoverOut { ppgpu_cover_summary* summaries; double* child; int32_t ribbon_stride; };
-
-// pp_k_trace_cover over the list of L
-static int launch_cover_trace(ppgpu_ctx* c, const CostLaunch& L, int stride, int* d_counts, ppgpu_cover_record* d_cover, ppgpu_cover_record* h_cover,
-                              const CoverOut& o) {
-    return trace_passes(c, L, stride, c->tmp_cover, c->t_cover, d_cover, h_cover, [&](const PPParams& q, ppgpu_cover_record* dst, long long rec_base) {
-        hipLaunchKernelGGL(pp_k_trace_cover, dim3((unsigned)((q.n_edges + PP_CTRACE_WPB - 1) / PP_CTRACE_WPB)), dim3(PP_CTRACE_WPB * 64), 0, c->stream,
-                           q, dst, rec_base, stride, d_counts, o.summaries, o.child, o.child ? o.ribbon_stride : 0);
-    });
-}
-
-// pp_k_trace_contacts over the list of L: n_obst records per edge (the stride of the passes).  Without obstacles the kernel still runs,
-// for the counts, and is handed no records.
-static int launch_contact_trace(ppgpu_ctx* c, const CostLaunch& L, int* d_counts, ppgpu_contact_record* d_contacts, ppgpu_contact_record* h_contacts) {
+// The trace r over the list of L; r's counts (summaries, child) are device arrays, its records the caller's host array when
+// `host_records`.  A contact trace has n_obst records per edge; without obstacles the kernel still runs, for the counts, and is
+// handed no records.
+static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r, bool host_records) {
+    TraceTimer& tm = r.kind == TRACE_STEPS ? c->t_steps : r.kind == TRACE_COVER ? c->t_cover : c->t_contacts;
+    if (r.kind != TRACE_CONTACTS) return trace_passes(c, L, r, tm, r.stride, (unsigned char*)r.records, host_records);
     const bool none = L.p.n_obst <= 0;
-    return trace_passes(c, L, none ? 1 : L.p.n_obst, c->tmp_contacts, c->t_contacts, none ? nullptr : d_contacts, none ? nullptr : h_contacts,
-                        [&](const PPParams& q, ppgpu_contact_record* dst, long long rec_base) {
-        hipLaunchKernelGGL(L.gaussian ? pp_k_trace_contacts_gaussian : pp_k_trace_contacts, dim3((unsigned)((q.n_edges + PP_KTRACE_WPB - 1) / PP_KTRACE_WPB)),
-                           dim3(PP_KTRACE_WPB * 64), 0, c->stream, q, dst, rec_base, d_counts);
-    });
+    return trace_passes(c, L, r, tm, none ? 1 : L.p.n_obst, none ? nullptr : (unsigned char*)r.records, host_records && !none);
 }
 
 int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) { return c ? trace_timing(c, c->t_steps, ms_trace) : fail(PPGPU_EINVAL, "null argument"); }
@@ -1358,33 +1384,31 @@ int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_t
 int ppgpu_last_contact_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_contacts, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
-int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
-                           int32_t* d_counts, ppgpu_step_record* d_steps) {
+// A device list in, device records out: cost the list, then trace it.
+static int trace_device_list(ppgpu_ctx* c, const char* who, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, const TraceRequest& r) {
     int rc = require_world(c);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = trace_args("trace_edges_list", n, d_edges, stride, d_counts, d_steps))) return rc;
-    if (n > 0 && !d_results) return fail(PPGPU_EINVAL, "trace_edges_list: null results");
-    if (((unsigned long long)d_steps & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_edges_list: d_steps must be 16-byte aligned");
+    if ((rc = trace_request_args(c, who, true, n, d_edges, d_results, r))) return rc;
     if (n == 0) return PPGPU_OK;
     CostLaunch L;
     if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
-    return launch_trace(c, L, stride, d_counts, d_steps, nullptr);
+    return launch_trace(c, L, r, false);
+}
+
+int ppgpu_trace_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride,
+                           int32_t* d_counts, ppgpu_step_record* d_steps) {
+    return trace_device_list(c, "trace_edges_list", n, d_edges, d_results, steps_request(stride, d_counts, d_steps));
 }
 
 int ppgpu_trace_cover_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t stride, int32_t* d_counts,
                            ppgpu_cover_record* d_cover, ppgpu_cover_summary* d_summaries, double* d_child, int32_t ribbon_stride) {
-    int rc = require_world(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = trace_args("trace_cover_list", n, d_edges, stride, d_counts, d_cover))) return rc;
-    if (n > 0 && (!d_results || !d_summaries)) return fail(PPGPU_EINVAL, "trace_cover_list: null results or summaries");
-    if (d_child && ribbon_stride <= 0) return fail(PPGPU_EINVAL, "trace_cover_list: ribbon_stride must be positive");
-    if (((unsigned long long)d_cover & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_cover_list: d_cover must be 16-byte aligned");
-    if (n == 0) return PPGPU_OK;
-    CostLaunch L;
-    if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
-    return launch_cover_trace(c, L, stride, d_counts, d_cover, nullptr, CoverOut{d_summaries, d_child, ribbon_stride});
+    return trace_device_list(c, "trace_cover_list", n, d_edges, d_results, cover_request(stride, d_counts, d_cover, d_summaries, d_child, ribbon_stride));
+}
+
+int ppgpu_trace_contacts_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
+                              ppgpu_contact_record* d_contacts) {
+    return trace_device_list(c, "trace_contacts_list", n, d_edges, d_results, contacts_request(d_counts, d_contacts));
 }
 
 int ppgpu_obstacle_count(ppgpu_ctx* c, int32_t* n, int32_t* model) {
@@ -1394,53 +1418,18 @@ int ppgpu_obstacle_count(ppgpu_ctx* c, int32_t* n, int32_t* model) {
     return PPGPU_OK;
 }
 
-// what a contact-trace entry was handed: the records may be missing only when there is no obstacle to report on
-static int contact_args(const ppgpu_ctx* c, const char* who, int64_t n, const void* edges, const void* counts, const void* contacts) {
-    if (n < 0 || (n > 0 && (!edges || !counts || (c->n_obst > 0 && !contacts)))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
-    return PPGPU_OK;
-}
-
-int ppgpu_trace_contacts_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
-                              ppgpu_contact_record* d_contacts) {
-    int rc = require_world(c);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = contact_args(c, "trace_contacts_list", n, d_edges, d_counts, d_contacts))) return rc;
-    if (n > 0 && !d_results) return fail(PPGPU_EINVAL, "trace_contacts_list: null results");
-    if (((unsigned long long)d_contacts & 15ull) != 0ull) return fail(PPGPU_EINVAL, "trace_contacts_list: d_contacts must be 16-byte aligned");
-    if (n == 0) return PPGPU_OK;
-    CostLaunch L;
-    if ((rc = launch_cost(c, list_params(c, n, (const unsigned long long*)d_edges, nullptr, d_results, nullptr, 0), &L))) return rc;
-    return launch_contact_trace(c, L, d_counts, d_contacts, nullptr);
-}
-
 // ------------------------------------------------------------------------------ host lists
-// The host arrays of a trace form: step records at `stride` per edge, and how many steps each edge has.
-struct TraceOut { int32_t stride; int32_t* counts; ppgpu_step_record* steps; };
-// ... of a coverage-trace form: cover records at `stride` per edge, counts, summaries, and (may be NULL) the final lists.
-struct CoverTraceOut { int32_t stride; int32_t* counts; ppgpu_cover_record* cover; ppgpu_cover_summary* summaries; double* child; int32_t ribbon_stride; };
-// ... of a contact-trace form: counts, and one record per edge and obstacle row.
-struct ContactTraceOut { int32_t* counts; ppgpu_contact_record* contacts; };
-
 // A host list in, host records out: `who`'s n packed descriptors, or wrapper edges (`wrapper`), go up to tmp_edges / tmp_wedges,
-// are costed into tmp_results (child ribbons into a zeroed tmp_child when the caller wants them) and, for the trace forms, traced;
-// records, child ribbons and counts come home; one synchronise at the end.  h_results may be NULL for a trace.  A coverage trace
-// (`cover`) walks the list instead and brings its summaries and final lists home as well; a contact trace (`contact`) brings
-// its records and counts.
+// are costed into tmp_results (child ribbons into a zeroed tmp_child when the caller wants them) and, for the trace forms (`trace`:
+// the caller's host arrays), traced; records, child ribbons and counts come home, a coverage trace's summaries and final lists as
+// well; one synchronise at the end.  h_results may be NULL for a trace.
 static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n, const void* h_list, ppgpu_edge_result* h_results,
-                          double* h_child, int32_t stride, const TraceOut* trace = nullptr, const CoverTraceOut* cover = nullptr,
-                          const ContactTraceOut* contact = nullptr) {
+                          double* h_child, int32_t stride, const TraceRequest* trace = nullptr) {
     int rc = wrapper ? require_vertices(c) : require_world(c);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (trace) {
-        if ((rc = trace_args(who, n, h_list, trace->stride, trace->counts, trace->steps))) return rc;
-    } else if (cover) {
-        if ((rc = trace_args(who, n, h_list, cover->stride, cover->counts, cover->cover))) return rc;
-        if (n > 0 && !cover->summaries) return fail(PPGPU_EINVAL, std::string(who) + ": null summaries");
-        if (cover->child && cover->ribbon_stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
-    } else if (contact) {
-        if ((rc = contact_args(c, who, n, h_list, contact->counts, contact->contacts))) return rc;
+        if ((rc = trace_request_args(c, who, false, n, h_list, nullptr, *trace))) return rc;
     } else if (n < 0 || (n > 0 && (!h_list || !h_results))) {
         return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
     }
@@ -1448,12 +1437,13 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
     if (h_child && stride <= 0) return fail(PPGPU_EINVAL, std::string(who) + ": ribbon_stride must be positive");
     if (wrapper && (rc = check_wrapper_edges(c, who, n, (const ppgpu_wrapper_edge*)h_list))) return rc;
     hipStream_t st = c->stream;
+    const bool cover = trace && trace->kind == TRACE_COVER;
     const size_t child_bytes = h_child ? (size_t)n * stride * 4 * sizeof(double) : 0;
     if ((rc = wrapper ? c->tmp_wedges.reserve((size_t)n, false, st) : c->tmp_edges.reserve((size_t)n, false, st)) ||
         (rc = c->tmp_results.reserve((size_t)n, false, st)) || (h_child && (rc = c->tmp_child.reserve((size_t)n * stride * 4, false, st))) ||
-        ((trace || cover || contact) && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        (trace && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
         return rc;
-    const size_t final_bytes = (cover && cover->child) ? (size_t)n * cover->ribbon_stride * 4 * sizeof(double) : 0;
+    const size_t final_bytes = (cover && trace->child) ? (size_t)n * trace->ribbon_stride * 4 * sizeof(double) : 0;
     if (cover && ((rc = c->tmp_summaries.reserve((size_t)n, false, st)) ||
                   (final_bytes && (rc = c->tmp_cover_child.reserve(final_bytes / sizeof(double), false, st)))))
         return rc;
@@ -1467,21 +1457,14 @@ static int cost_host_list(ppgpu_ctx* c, const char* who, bool wrapper, int64_t n
     if (h_results) HIP_TRY(hipMemcpyAsync(h_results, c->tmp_results.p, (size_t)n * sizeof(ppgpu_edge_result), hipMemcpyDeviceToHost, st));
     if (h_child) HIP_TRY(hipMemcpyAsync(h_child, c->tmp_child.p, child_bytes, hipMemcpyDeviceToHost, st));
     if (trace) {
-        if ((rc = launch_trace(c, L, trace->stride, c->tmp_counts.p, nullptr, trace->steps))) return rc;
-        HIP_TRY(hipMemcpyAsync(trace->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (cover) {
+        TraceRequest d = *trace;                    // the caller's records, the device ends of the rest
+        d.counts = c->tmp_counts.p;
+        if (cover) { d.summaries = c->tmp_summaries.p; d.child = final_bytes ? c->tmp_cover_child.p : nullptr; }
         if (final_bytes) HIP_TRY(hipMemsetAsync(c->tmp_cover_child.p, 0, final_bytes, st));
-        if ((rc = launch_cover_trace(c, L, cover->stride, c->tmp_counts.p, nullptr, cover->cover,
-                                     CoverOut{c->tmp_summaries.p, final_bytes ? c->tmp_cover_child.p : nullptr, cover->ribbon_stride})))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(cover->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cover->summaries, c->tmp_summaries.p, (size_t)n * sizeof(ppgpu_cover_summary), hipMemcpyDeviceToHost, st));
-        if (final_bytes) HIP_TRY(hipMemcpyAsync(cover->child, c->tmp_cover_child.p, final_bytes, hipMemcpyDeviceToHost, st));
-    }
-    if (contact) {
-        if ((rc = launch_contact_trace(c, L, c->tmp_counts.p, nullptr, contact->contacts))) return rc;
-        HIP_TRY(hipMemcpyAsync(contact->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if ((rc = launch_trace(c, L, d, true))) return rc;
+        HIP_TRY(hipMemcpyAsync(trace->counts, c->tmp_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (cover) HIP_TRY(hipMemcpyAsync(trace->summaries, c->tmp_summaries.p, (size_t)n * sizeof(ppgpu_cover_summary), hipMemcpyDeviceToHost, st));
+        if (final_bytes) HIP_TRY(hipMemcpyAsync(trace->child, c->tmp_cover_child.p, final_bytes, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return PPGPU_OK;
@@ -1499,39 +1482,39 @@ int ppgpu_cost_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_e
 
 int ppgpu_trace_edges_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t stride,
                            int32_t* h_counts, ppgpu_step_record* h_steps) {
-    const TraceOut trace{stride, h_counts, h_steps};
+    const TraceRequest trace = steps_request(stride, h_counts, h_steps);
     return cost_host_list(c, "trace_edges_host", false, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
                                    int32_t stride, int32_t* h_counts, ppgpu_step_record* h_steps) {
-    const TraceOut trace{stride, h_counts, h_steps};
+    const TraceRequest trace = steps_request(stride, h_counts, h_steps);
     return cost_host_list(c, "trace_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_cover_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t stride, int32_t* h_counts,
                            ppgpu_cover_record* h_cover, ppgpu_cover_summary* h_summaries, double* h_child, int32_t ribbon_stride) {
-    const CoverTraceOut cover{stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride};
-    return cost_host_list(c, "trace_cover_host", false, n, h_edges, h_results, nullptr, 0, nullptr, &cover);
+    const TraceRequest trace = cover_request(stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride);
+    return cost_host_list(c, "trace_cover_host", false, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_cover_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results, int32_t stride,
                                          int32_t* h_counts, ppgpu_cover_record* h_cover, ppgpu_cover_summary* h_summaries, double* h_child,
                                          int32_t ribbon_stride) {
-    const CoverTraceOut cover{stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride};
-    return cost_host_list(c, "trace_cover_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, nullptr, &cover);
+    const TraceRequest trace = cover_request(stride, h_counts, h_cover, h_summaries, h_child, ribbon_stride);
+    return cost_host_list(c, "trace_cover_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_contacts_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t* h_counts,
                               ppgpu_contact_record* h_contacts) {
-    const ContactTraceOut contact{h_counts, h_contacts};
-    return cost_host_list(c, "trace_contacts_host", false, n, h_edges, h_results, nullptr, 0, nullptr, nullptr, &contact);
+    const TraceRequest trace = contacts_request(h_counts, h_contacts);
+    return cost_host_list(c, "trace_contacts_host", false, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 int ppgpu_trace_contacts_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
                                             int32_t* h_counts, ppgpu_contact_record* h_contacts) {
-    const ContactTraceOut contact{h_counts, h_contacts};
-    return cost_host_list(c, "trace_contacts_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, nullptr, nullptr, &contact);
+    const TraceRequest trace = contacts_request(h_counts, h_contacts);
+    return cost_host_list(c, "trace_contacts_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own
