@@ -160,6 +160,7 @@ __device__ __forceinline__ void pp_sincos_bounded(double x, double* sn, double* 
 // ----------------------------------------------------------------------------- correctly rounded sin / cos / atan2 / acos (pp_cr.h)
 #define PP_CR_FN __device__ __forceinline__
 #define PP_CR_CONST static __device__ const
+#define PP_CR_MEMBER __device__ __forceinline__
 #include "pp_cr.h"
 __device__ __forceinline__ void pp_cr_sincos(double x, double* sn, double* cs) {
     if (!(fabs(x) < PP_CR_MAX_ARG)) { sincos(x, sn, cs); return; }
@@ -317,6 +318,35 @@ __device__ inline void pp_dubins_shortest(double q0x, double q0y, double q0t, do
     }
 }
 
+// pp_dubins_shortest<true> with the work its result does not need left out (pp_solve_rank.h): the same preamble — theta, and sin / cos
+// of alpha, beta and alpha - beta, correctly rounded — then the words ranked on the library's atan2 / acos and only the contenders
+// evaluated correctly rounded.  The same bits in `out`.
+#include "pp_solve_rank.h"
+struct PPRankOps {
+    static __device__ __forceinline__ double mod2pi(double t) { return pp_mod2pi(t); }
+    static __device__ __forceinline__ double atan2(double y, double x) { return ::atan2(y, x); }
+    static __device__ __forceinline__ double acos(double v) { return ::acos(v); }
+};
+__device__ inline void pp_dubins_shortest_ranked(double q0x, double q0y, double q0t, double q1x, double q1y, double q1t,
+                                                 double rho, PPDubins& out) {
+    double dx = q1x - q0x;
+    double dy = q1y - q0y;
+    double D = sqrt(dx * dx + dy * dy);
+    PPWordIn in;
+    in.d = D / rho;
+    double theta = 0;
+    if (in.d > 0) theta = pp_mod2pi(pp_cr_atan2(dy, dx));
+    in.alpha = pp_mod2pi(q0t - theta);
+    in.beta = pp_mod2pi(q1t - theta);
+    in.mbeta = pp_mod2pi(in.beta);
+    double s_ab_unused;
+    pp_cr_sincos(in.alpha, &in.sa, &in.ca);
+    pp_cr_sincos(in.beta, &in.sb, &in.cb);
+    pp_cr_sincos(in.alpha - in.beta, &s_ab_unused, &in.c_ab);
+    in.d_sq = in.d * in.d;
+    pp_solve_contenders<PPRankOps>(in, pp_rank_contenders<PPRankOps>(in), out.p0, out.p1, out.p2, out.type);
+}
+
 // dubins_path_length(): ((p0 + p1) + p2) * rho
 __device__ __forceinline__ double pp_dubins_length(const PPDubins& d, double rho) {
     double length = 0.;
@@ -326,27 +356,34 @@ __device__ __forceinline__ double pp_dubins_length(const PPDubins& d, double rho
     return length * rho;
 }
 
+// sin / cos of the curve's base headings, remembering the last evaluation (MEMO): an argument with the bits of the one before it
+// (-0.0 and +0.0 are different arguments) takes that result instead of evaluating again.  dubins_path_sample() asks for the end of an arc
+// and then for the next base heading, which is the same double: bth + t and t + bth, bth - t and -t + bth; and 0.0 + bth after a straight.
+struct PPSincosMemo { double x, s, c; bool have; };
+template <bool CR, bool MEMO>
+__device__ __forceinline__ void pp_dub_sincos_memo(PPSincosMemo& m, double x, double* s, double* c) {
+    if constexpr (MEMO) {
+        if (m.have && __double_as_longlong(x) == __double_as_longlong(m.x)) { *s = m.s; *c = m.c; return; }
+    }
+    pp_dub_sincos<CR>(x, s, c);
+    if constexpr (MEMO) { m.x = x; m.s = *s; m.c = *c; m.have = true; }
+}
 // One Dubins segment advanced by t from (bx, by, bth) with sin/cos(bth) precomputed
 // (dubins_segment()).  Writes the un-normalised pose.
-template <bool CR = false>
+template <bool CR = false, bool MEMO = false>
 __device__ __forceinline__ void pp_segment(int type, double t, double bx, double by, double bth, double sb, double cb,
-                                           double& x, double& y, double& th) {
-    if (type == 0) {  // L
-        double s, c;
-        pp_dub_sincos<CR>(bth + t, &s, &c);
-        x = (+s - sb) + bx;
-        y = (-c + cb) + by;
-        th = t + bth;
-    } else if (type == 2) {  // R
-        double s, c;
-        pp_dub_sincos<CR>(bth - t, &s, &c);
-        x = (-s + sb) + bx;
-        y = (+c - cb) + by;
-        th = -t + bth;
-    } else {  // S
+                                           double& x, double& y, double& th, PPSincosMemo& m) {
+    if (type == 1) {  // S
         x = cb * t + bx;
         y = sb * t + by;
         th = 0.0 + bth;
+    } else {          // L (0), R (2): one evaluation for both, bth - t being bth + (-t)
+        const double st = (type == 0) ? t : -t;
+        double s, c;
+        pp_dub_sincos_memo<CR, MEMO>(m, bth + st, &s, &c);
+        if (type == 0) { x = (+s - sb) + bx; y = (-c + cb) + by; }
+        else           { x = (-s + sb) + bx; y = (+c - cb) + by; }
+        th = st + bth;
     }
 }
 
@@ -361,7 +398,8 @@ struct PPCurve {
     double s0, c0, s1, c1, s2, c2;             // sin/cos of the three base headings
 };
 
-template <bool CR = false>
+// MEMO: with the repeated evaluations left out (a CSC curve then takes two, a CCC curve three, instead of five)
+template <bool CR = false, bool MEMO = false>
 __device__ inline void pp_curve_init(PPCurve& c, double qx, double qy, double qth, double rho, const PPDubins& d) {
     c.qx = qx; c.qy = qy; c.qth = qth; c.rho = rho;
     {
@@ -372,11 +410,13 @@ __device__ inline void pp_curve_init(PPCurve& c, double qx, double qy, double qt
     c.length = pp_dubins_length(d, rho);
     int w = d.type < 0 ? 0 : d.type;
     c.t0 = pp_seg_type(w, 0); c.t1 = pp_seg_type(w, 1); c.t2 = pp_seg_type(w, 2);
-    pp_dub_sincos<CR>(qth, &c.s0, &c.c0);
-    pp_segment<CR>(c.t0, d.p0, 0.0, 0.0, qth, c.s0, c.c0, c.b1x, c.b1y, c.b1th);
-    pp_dub_sincos<CR>(c.b1th, &c.s1, &c.c1);
-    pp_segment<CR>(c.t1, d.p1, c.b1x, c.b1y, c.b1th, c.s1, c.c1, c.b2x, c.b2y, c.b2th);
-    pp_dub_sincos<CR>(c.b2th, &c.s2, &c.c2);
+    PPSincosMemo m;
+    m.have = false;
+    pp_dub_sincos_memo<CR, MEMO>(m, qth, &c.s0, &c.c0);
+    pp_segment<CR, MEMO>(c.t0, d.p0, 0.0, 0.0, qth, c.s0, c.c0, c.b1x, c.b1y, c.b1th, m);
+    pp_dub_sincos_memo<CR, MEMO>(m, c.b1th, &c.s1, &c.c1);
+    pp_segment<CR, MEMO>(c.t1, d.p1, c.b1x, c.b1y, c.b1th, c.s1, c.c1, c.b2x, c.b2y, c.b2th, m);
+    pp_dub_sincos_memo<CR, MEMO>(m, c.b2th, &c.s2, &c.c2);
 }
 // one segment of dubins_path_sample(): advance by tt from base (bx, by, bth) whose sin/cos are (sb, cb)
 template <bool TAB = false>

@@ -77,8 +77,11 @@ __device__ __forceinline__ PPBoxScan pp_box_scan(RP r, int n, double x, double y
     }
     return s;
 }
+// Four waves per SIMD (127 VGPRs): with the 34 KB of LDS below, 4 workgroups per CU, 1 024 resident ones — the 923 of a config-3 launch
+// run as ONE round.  At 3 (142 VGPRs, what the compiler takes unbounded) 768 fit, and the last 155 ran as a second round on a
+// nearly empty machine (profiles/solve_approach_ab.txt: 113 -> 106 us).  The bound costs 8 spilled VGPRs, 36 B of scratch per lane.
 #ifndef PP_APPROACH_MIN_WAVES
-#define PP_APPROACH_MIN_WAVES 1
+#define PP_APPROACH_MIN_WAVES 4
 #endif
 #ifndef PP_APPROACH_THREADS
 #define PP_APPROACH_THREADS 256

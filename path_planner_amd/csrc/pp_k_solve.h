@@ -7,7 +7,12 @@
 #ifndef PP_SOLVE_MIN_WAVES
 #define PP_SOLVE_MIN_WAVES 1
 #endif
-__global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPParams p) {
+// ALL_WORDS: the solver evaluates all six words correctly rounded and pp_curve_init every base heading (pp_k_solve_edges_all_words,
+// PPGPU_SOLVE_ALL_WORDS=1, for the tests that compare the two); else only the words that can win, and no sin / cos of the curve's
+// bases twice (pp_solve_rank.h, PPSincosMemo): the same records.  Two kernels, so that the test path does not set the registers of
+// the production one.
+template <bool ALL_WORDS>
+__device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     // the queue heads of the kernels that follow (all of them start after this kernel has ended, in stream order)
     if (e < 4 * PP_NQ) p.work[(size_t)e * PP_QSTRIDE] = 0ull;
@@ -61,13 +66,18 @@ __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPPa
             dub.p0 = W->param[0]; dub.p1 = W->param[1]; dub.p2 = W->param[2]; dub.type = W->type;
             if (dub.type < 0 || dub.type > 5) dub.type = -1;
             rho = W->rho; wSpeed = W->speed;
-            pp_curve_init<PP_CR_SOLVE>(cv, W->qi[0], W->qi[1], W->qi[2], rho, dub);
+            pp_curve_init<PP_CR_SOLVE, PP_CR_SOLVE && !ALL_WORDS>(cv, W->qi[0], W->qi[1], W->qi[2], rho, dub);
             wStart = W->start_time; wEnd = W->end_time;
         } else {
             const double tgtX = p.sx[target], tgtY = p.sy[target], tgtH = p.sh[target];
             if ((srcX == tgtX) && (srcY == tgtY) && (srcH == tgtH)) sflags |= PP_SETUP_COLOCATED;   // State::isCoLocated
-            pp_dubins_shortest<PP_CR_SOLVE>(srcX, srcY, pp_yaw(srcH), tgtX, tgtY, pp_yaw(tgtH), rho, dub);
-            pp_curve_init<PP_CR_SOLVE>(cv, srcX, srcY, pp_yaw(srcH), rho, dub);
+            if constexpr (ALL_WORDS || !PP_CR_SOLVE) {
+                pp_dubins_shortest<PP_CR_SOLVE>(srcX, srcY, pp_yaw(srcH), tgtX, tgtY, pp_yaw(tgtH), rho, dub);
+                pp_curve_init<PP_CR_SOLVE>(cv, srcX, srcY, pp_yaw(srcH), rho, dub);
+            } else {
+                pp_dubins_shortest_ranked(srcX, srcY, pp_yaw(srcH), tgtX, tgtY, pp_yaw(tgtH), rho, dub);
+                pp_curve_init<PP_CR_SOLVE, true>(cv, srcX, srcY, pp_yaw(srcH), rho, dub);
+            }
         }
         // the sweeps take sin/cos of (segment base heading +- arc) with the bounded-argument routine: refuse curves whose
         // angles leave its range (a heading of tens of thousands of radians, or NaN) instead of sampling them wrongly
@@ -124,3 +134,5 @@ __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPPa
         O->omask = omask;
     }
 }
+__global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPParams p) { pp_solve_edges_body<false>(p); }
+__global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges_all_words(PPParams p) { pp_solve_edges_body<true>(p); }

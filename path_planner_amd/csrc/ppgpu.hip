@@ -147,6 +147,7 @@ struct ppgpu_ctx {
     TraceTimer t_steps, t_cover, t_contacts;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
+    bool solve_all_words = false;       // env PPGPU_SOLVE_ALL_WORDS=1: the solver evaluates all six words correctly rounded (tests compare the two)
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
     bool plan_spans = true;             // env PPGPU_PLAN_SPANS=0: the skip planner tests every obstacle of an edge's list per chunk (the tests compare the two)
@@ -285,6 +286,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* qf = std::getenv("PPGPU_QUIET_FINISH")) c->quiet_finish = std::atoi(qf) != 0;
     if (const char* lf = std::getenv("PPGPU_LANE_FINISH")) c->lane_finish = std::atoi(lf) != 0;
     if (const char* ls = std::getenv("PPGPU_LANE_SPLIT")) c->lane_split = std::atoi(ls) != 0;
+    if (const char* aw = std::getenv("PPGPU_SOLVE_ALL_WORDS")) c->solve_all_words = std::atoi(aw) != 0;
     if (const char* pc = std::getenv("PPGPU_POSE_CHUNKS")) c->pose_chunks = std::atoi(pc);
     if (const char* ps = std::getenv("PPGPU_PLAN_SPANS")) c->plan_spans = std::atoi(ps) != 0;
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
@@ -1102,7 +1104,7 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
     hipStream_t st = c->stream;
     hipEvent_t* ev = c->ev_ring[c->ev_slot];
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_BEGIN], st));
-    hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_SOLVED], st));
     if (m.skip_chunks) {                                         // timed with the pose sweep
         // one workgroup per epw consecutive edges: as many as give it 256 (edge, chunk) threads
@@ -1335,7 +1337,7 @@ static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r
         q.ws_base = reuse ? e0 : 0;
         if (!reuse) {
             q.live_count = nullptr; q.defer_count = nullptr; q.hw_count = nullptr;     // (counters of the costing launch: ppgpu_last_cover_edges still reads them)
-            hipLaunchKernelGGL(pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
+            hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
         }
         unsigned char* dst = host ? c->tmp_trace.p : recs;
         const size_t bytes = (size_t)q.n_edges * edge_bytes;
