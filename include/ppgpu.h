@@ -556,6 +556,66 @@ int ppgpu_trace_contacts_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppg
  * summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
 int ppgpu_last_contact_trace_timing(ppgpu_ctx* ctx, double* ms_contact_trace);
 
+/* --------------------------------------------------------------- chart clearance */
+
+/* How close a pose, an edge or a plan comes to a charted hazard.  The reference asks the static map a yes/no question at every
+ * sampled pose (Map::isBlocked: GridWorldMap.cpp:84-93, called at Edge.cpp:144); this is the distance behind that answer.
+ * A HAZARD CELL is a cell that is blocked or lies outside the grid (isBlocked is true there).  With g(d) = max(|d| - 1, 0),
+ *     gap2((r, c), (r', c')) = g(r - r')^2 + g(c - c')^2      the squared distance, in cells, between the nearest edges of two cells
+ *     gap2(A) = min over hazard cells B of gap2(A, B)         0 on a blocked cell and on its eight neighbours
+ * Every point of cell A is at least resolution * sqrt(gap2(A)) from every point of every hazard cell (a certified lower bound), and
+ * at most resolution * (sqrt(gap2(A)) + sqrt(2)) from some hazard cell.  The device holds min(gap2, PPGPU_DIST_CAP2) as uint16_t,
+ * one value per cell at r * cols + c: an exact integer map, built on the first call that needs it after a ppgpu_set_grid
+ * (pp_k_dist_cols, pp_k_dist_rows) and kept until the next one.  The clearance of a pose is that of the cell isBlocked puts it
+ * in; a pose outside the grid has gap2 0.  clearance = resolution * sqrt((double)gap2), in metres. */
+#define PPGPU_DIST_CAP  255     /* cells */
+#define PPGPU_DIST_CAP2 65025   /* PPGPU_DIST_CAP squared: a stored value this large means "at least" */
+/* For tests and tools: the whole map (rows*cols values).  Copied on the handle's stream; the call waits for it.  PPGPU_EINVAL
+ * without a grid (rows == 0) or when capacity < rows*cols. */
+int ppgpu_get_grid_distance(ppgpu_ctx* ctx, uint16_t* h_out, int64_t capacity);
+/* The certified lower bound at n points {x, y} of h_xy2: h_clearance[i] in metres, h_gap2[i] in cells squared; either output may
+ * be NULL.  A point on a blocked cell or outside the grid gives 0.  Without a grid (the base Map, rows == 0) nothing is charted:
+ * clearance = DBL_MAX and gap2 = PPGPU_DIST_CAP2.  Synchronous. */
+int ppgpu_grid_clearance_at(ppgpu_ctx* ctx, int64_t n, const double* h_xy2, double* h_clearance, uint32_t* h_gap2);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds the two passes of the last build of the map took together
+ * (HIP events on the handle's stream around the two kernels).  PPGPU_ESTATE when no build was timed. */
+int ppgpu_last_grid_distance_timing(ppgpu_ctx* ctx, double* ms_build);
+
+/* The clearance of an edge: one record per edge, from a walk over the executed steps of its sweep — the steps of
+ * ppgpu_step_record, same count, same poses and times — that takes the gap2 of every step's cell. */
+#define PPGPU_CL_EMPTY   0x1u  /* no executed step (PPGPU_F_THROWS, malformed, a curve starting after the vertex's first step) */
+#define PPGPU_CL_BLOCKED 0x2u  /* the last executed step is the blocked one (Edge.cpp:144-146): clearance 0 */
+#define PPGPU_CL_CAPPED  0x4u  /* min gap2 == PPGPU_DIST_CAP2: clearance is "at least" */
+#define PPGPU_CL_NO_MAP  0x8u  /* base Map (rows == 0): clearance DBL_MAX, gap2 = PPGPU_DIST_CAP2, always with CAPPED */
+typedef struct ppgpu_clearance_record {   /* 64 bytes */
+    double clearance;          /* res * sqrt(min gap2) over EVERY executed step, the blocked one included; -1 when EMPTY */
+    double time, x, y;         /* of the step that attains it (the earliest on equal gap2); -1, 0, 0 when EMPTY */
+    double first_below_time;   /* time of the first step with gap2 < limit2; -1 without one */
+    int32_t step;              /* -1 when EMPTY */
+    uint32_t gap2;             /* 0 when EMPTY */
+    int32_t below_steps, first_below_step;   /* 0 / -1 */
+    uint32_t flags, reserved;  /* PPGPU_CL_*; 0 */
+} ppgpu_clearance_record;
+
+/* The calls take a margin in metres.  margin <= 0 (or no grid): no step is counted.  margin > 255 * resolution: PPGPU_EINVAL.
+ * Otherwise the host computes limit2 once, the smallest non-negative integer k with resolution * sqrt((double)k) >= margin, and
+ * a step is "below" iff its gap2 < limit2: the device compares integers only.
+ * The clearance records of a list of n packed descriptors: first the costing launch of ppgpu_cost_edges_list on the same list
+ * (d_results receives exactly its records), then the walk.  d_counts[i] receives the edge's step count (what
+ * ppgpu_trace_edges_list reports), d_clearance[i] the edge's record; every record is written.  d_clearance must be 16-byte
+ * aligned.  Asynchronous on the handle's stream (the first call after a ppgpu_set_grid builds the map on it first). */
+int ppgpu_trace_clearance_list(ppgpu_ctx* ctx, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
+                               ppgpu_clearance_record* d_clearance, double margin);
+/* The same with host descriptors in and host arrays out, synchronous.  h_results may be NULL. */
+int ppgpu_trace_clearance_host(ppgpu_ctx* ctx, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t* h_counts,
+                               ppgpu_clearance_record* h_clearance, double margin);
+/* ... for edges whose curve is given (as ppgpu_trace_wrapper_edges_host traces them): the clearance of a plan's segments. */
+int ppgpu_trace_clearance_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const ppgpu_wrapper_edge* h_wedges, ppgpu_edge_result* h_results,
+                                             int32_t* h_counts, ppgpu_clearance_record* h_clearance, double margin);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_trace_clearance took in the last clearance-trace
+ * call, summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
+int ppgpu_last_clearance_trace_timing(ppgpu_ctx* ctx, double* ms_clearance_trace);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

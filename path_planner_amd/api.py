@@ -90,6 +90,13 @@ def _load():
         "ppgpu_trace_contacts_host": (C.c_int, [vp, i64, vp, vp, vp, vp]),
         "ppgpu_trace_contacts_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, vp]),
         "ppgpu_last_contact_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_get_grid_distance": (C.c_int, [vp, vp, i64]),
+        "ppgpu_grid_clearance_at": (C.c_int, [vp, i64, vp, vp, vp]),
+        "ppgpu_last_grid_distance_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_trace_clearance_list": (C.c_int, [vp, i64, vp, vp, vp, vp, dbl]),
+        "ppgpu_trace_clearance_host": (C.c_int, [vp, i64, vp, vp, vp, vp, dbl]),
+        "ppgpu_trace_clearance_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, vp, dbl]),
+        "ppgpu_last_clearance_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -472,6 +479,52 @@ class Context:
     def last_contact_trace_timing(self):
         ms = C.c_double()
         self._ck(LIB.ppgpu_last_contact_trace_timing(self._h, C.byref(ms)), "ppgpu_last_contact_trace_timing")
+        return ms.value
+
+    def get_grid_distance(self, rows, cols):
+        """The device's distance map of the grid last set: min(gap2, DIST_CAP2) per cell, rows x cols uint16; for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint16)
+        self._ck(LIB.ppgpu_get_grid_distance(self._h, _ptr(out), out.size), "ppgpu_get_grid_distance")
+        return out
+
+    def grid_clearance_at(self, xy):
+        """(clearance in metres, gap2 in cells squared) of the cells the points xy[n, 2] lie in: the certified lower bound."""
+        p = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        clearance = np.zeros(p.shape[0], dtype=np.float64)
+        gap2 = np.zeros(p.shape[0], dtype=np.uint32)
+        self._ck(LIB.ppgpu_grid_clearance_at(self._h, p.shape[0], _ptr(p), _ptr(clearance), _ptr(gap2)), "ppgpu_grid_clearance_at")
+        return clearance, gap2
+
+    def last_grid_distance_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_grid_distance_timing(self._h, C.byref(ms)), "ppgpu_last_grid_distance_timing")
+        return ms.value
+
+    def trace_clearance_list(self, n, d_edges, d_results, d_counts, d_clearance, margin=0.0):
+        self._ck(LIB.ppgpu_trace_clearance_list(self._h, n, _ptr(d_edges), _ptr(d_results), _ptr(d_counts), _ptr(d_clearance), float(margin)),
+                 "ppgpu_trace_clearance_list")
+
+    def _trace_clearance_host(self, fn, name, e, margin, records):
+        from .types import CLEARANCE_DTYPE
+        if records is not None:
+            records = records.reshape(-1, 1)
+        res, counts, records = self._trace_records_host(fn, name, e, records, CLEARANCE_DTYPE, 1, after=(float(margin),))
+        return res, counts, records.reshape(-1)
+
+    def trace_clearance(self, edges, margin=0.0, records=None):
+        """How close each edge comes to a charted hazard: (records as cost_edges_host returns them, step counts, clearance[n]).
+        `records`: an array to write into (every record is written); a zeroed one by default."""
+        e = np.ascontiguousarray(edges, dtype=np.uint64)
+        return self._trace_clearance_host(LIB.ppgpu_trace_clearance_host, "ppgpu_trace_clearance_host", e, margin, records)
+
+    def trace_clearance_wrapper_edges(self, wedges, margin=0.0, records=None):
+        from .types import WRAPPER_EDGE_DTYPE
+        e = np.ascontiguousarray(wedges, dtype=WRAPPER_EDGE_DTYPE)
+        return self._trace_clearance_host(LIB.ppgpu_trace_clearance_wrapper_edges_host, "ppgpu_trace_clearance_wrapper_edges_host", e, margin, records)
+
+    def last_clearance_trace_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_clearance_trace_timing(self._h, C.byref(ms)), "ppgpu_last_clearance_trace_timing")
         return ms.value
 
     @staticmethod

@@ -1,8 +1,8 @@
-// pp_k_trace_common.h — what the three edge traces (pp_k_trace.h, pp_k_cover_trace.h, pp_k_contact_trace.h) share: which edge a wave
+// pp_k_trace_common.h — what the edge traces (pp_k_trace.h, pp_k_cover_trace.h, pp_k_contact_trace.h, pp_k_clearance_trace.h) share: which edge a wave
 // has, how many steps it walks, the poses of a 64-step window and how a window's records leave.  Included by pp_kernels.h before them.
 #pragma once
 // A trace kernel runs AFTER a costing launch over the same edge list, on the same PPEdgeSetup records, one wavefront per edge, and
-// does not skip.  The three must see the same steps and the same poses as each other and as the costing launch, bit for bit, so
+// does not skip.  They must see the same steps and the same poses as each other and as the costing launch, bit for bit, so
 // the step count (pp_trace_head) and the window (pp_trace_window: pp_window_pose, the sweeps' own segment arithmetic, with the
 // state it carries from window to window) exist here once.
 #define PP_TRACE_WPB 4             // waves (edges) per workgroup

@@ -7,10 +7,12 @@
 #include "pp_k_sweep.h"        // pp_k_plan_skips, pp_k_pose_sweep
 #include "pp_k_finish.h"       // phase C of an edge: the pieces every route shares, pp_lane_phase_c, pp_k_cover_finish
 #include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep
-#include "pp_k_trace_common.h"  // what the three traces share: edge head, window walk, record store
+#include "pp_k_trace_common.h"  // what the traces share: edge head, window walk, record store
 #include "pp_k_trace.h"        // pp_k_trace_steps
 #include "pp_k_cover_trace.h"  // pp_k_trace_cover
 #include "pp_k_contact_trace.h"  // pp_k_trace_contacts
+#include "pp_k_distance.h"     // pp_k_dist_cols, pp_k_dist_rows, pp_k_grid_clearance_at: the distance map behind the chart clearance
+#include "pp_k_clearance_trace.h"  // pp_k_trace_clearance
 #include "pp_k_chain.h"        // pp_k_chain_advance
 #include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
 #include "pp_k_tsp_table.h"    // pp_k_tsp_table_list, pp_k_tsp_table

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -87,7 +88,8 @@ struct DevBuf {
 };
 
 #define PP_TIMING_RING 8
-// The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing, ppgpu_last_contact_trace_timing).
+// The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing, ppgpu_last_contact_trace_timing,
+// ppgpu_last_clearance_trace_timing).
 struct TraceTimer {
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_earlier = 0;              // ... of the slices before the last one
@@ -110,6 +112,8 @@ struct ppgpu_ctx {
     DevBuf<unsigned char> grid_clear, grid_rowclear;   // clearance map of the grid (PPGrid::clearance) and its row pass
     int rows = 0, cols = 0, wpr = 0;
     double res = 0;
+    DevBuf<uint16_t> grid_dist;         // distance map of the grid (ppgpu.h, "chart clearance"): built by the first call that needs it ...
+    bool grid_dist_built = false;       // ... after a ppgpu_set_grid (grid_distance)
     // dynamic obstacles
     DevBuf<PPObst> obst;
     int n_obst = 0;
@@ -140,12 +144,13 @@ struct ppgpu_ctx {
     DevBuf<ppgpu_wrapper_edge> tmp_wedges;
     DevBuf<ppgpu_edge_result> tmp_results;
     DevBuf<double> tmp_child, tmp_lengths, tmp_len_out, int_child;
-    DevBuf<unsigned char> tmp_trace;       // device end of the host forms of the traces: the step, cover or contact records of one trace slice
+    DevBuf<unsigned char> tmp_trace;       // device end of the host forms of the traces: the step, cover, contact or clearance records of one trace slice
     DevBuf<ppgpu_cover_summary> tmp_summaries;   // ... of ppgpu_trace_cover_*: the summaries and final lists of the whole list
     DevBuf<double> tmp_cover_child;
     DevBuf<int> tmp_counts;
-    TraceTimer t_steps, t_cover, t_contacts;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts
+    TraceTimer t_steps, t_cover, t_contacts, t_clearance;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts / pp_k_trace_clearance
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
+    TraceTimer t_dist;                  // around the two passes of the distance map (grid_distance)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool solve_all_words = false;       // env PPGPU_SOLVE_ALL_WORDS=1: the solver evaluates all six words correctly rounded (tests compare the two)
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
@@ -206,7 +211,7 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_tsp.ev[0], t_tsp.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -319,7 +324,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     HIP_TRY(hipSetDevice(c->device));
     if (on && !c->ev_ring[0][0])
         for (int r = 0; r < PP_TIMING_RING; r++) for (int i = 0; i < EV_COUNT; i++) HIP_TRY(hipEventCreate(&c->ev_ring[r][i]));
-    for (TraceTimer* tm : {&c->t_steps, &c->t_cover, &c->t_contacts, &c->t_tsp}) {
+    for (TraceTimer* tm : {&c->t_steps, &c->t_cover, &c->t_contacts, &c->t_clearance, &c->t_tsp, &c->t_dist}) {
         if (on && !tm->ev[0])
             for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm->ev[i]));
         tm->timed = false;
@@ -503,6 +508,7 @@ int ppgpu_set_config(ppgpu_ctx* c, const ppgpu_config* cfg) {
 int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t cols, double res) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));
+    c->grid_dist_built = false;
     if (rows == 0) { c->rows = c->cols = c->wpr = 0; c->res = 0; return PPGPU_OK; }
     if (!cells || rows < 0 || cols <= 0 || !(res > 0)) return fail(PPGPU_EINVAL, "grid: bad shape or resolution");
     int wpr = (cols + 31) / 32;
@@ -538,6 +544,71 @@ int ppgpu_get_grid_clearance(ppgpu_ctx* c, uint8_t* h_out, int64_t capacity) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(h_out, c->grid_clear.p, (size_t)ncell, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ chart clearance
+// The distance map of the grid that is set (rows > 0), built on the stream by the first caller after a ppgpu_set_grid and kept
+// until the next: the column pass into a scratch array that lives for the build only, then the row pass (pp_k_distance.h).
+static int grid_distance(ppgpu_ctx* c) {
+    if (c->grid_dist_built) return PPGPU_OK;
+    const size_t ncell = (size_t)c->rows * c->cols;
+    int rc = c->grid_dist.reserve(ncell, false, c->stream);
+    if (rc) return rc;
+    DevBuf<uint16_t> v;
+    if ((rc = v.reserve(ncell, false, c->stream))) return rc;
+    const unsigned ctiles = (unsigned)((c->cols + 255) / 256), rtiles = (unsigned)((c->rows + PP_DIST_TILE - 1) / PP_DIST_TILE);
+    if (ctiles > 65535u || rtiles > 65535u) return fail(PPGPU_ECAPACITY, "grid distance: the grid is too large for the map's launch shape");
+    c->t_dist.ms_earlier = 0;
+    c->t_dist.timed = false;
+    if (c->timing) HIP_TRY(hipEventRecord(c->t_dist.ev[0], c->stream));
+    hipLaunchKernelGGL(pp_k_dist_cols, dim3(ctiles, rtiles), dim3(256), 0, c->stream, c->grid.p, c->rows, c->cols, c->wpr, v.p);
+    hipLaunchKernelGGL(pp_k_dist_rows, dim3((unsigned)c->rows, ctiles), dim3(256), 0, c->stream, v.p, c->rows, c->cols, c->grid_dist.p);
+    if (c->timing) { HIP_TRY(hipEventRecord(c->t_dist.ev[1], c->stream)); c->t_dist.timed = true; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));       // the scratch goes with this scope
+    c->grid_dist_built = true;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_distance(ppgpu_ctx* c, uint16_t* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, "grid distance: null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, "grid distance: no grid is set");
+    const int64_t ncell = (int64_t)c->rows * c->cols;
+    if (capacity < ncell) return fail(PPGPU_EINVAL, "grid distance: capacity below rows * cols");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = grid_distance(c);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out, c->grid_dist.p, (size_t)ncell * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_grid_clearance_at(ppgpu_ctx* c, int64_t n, const double* h_xy2, double* h_clearance, uint32_t* h_gap2) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n < 0 || (n > 0 && !h_xy2)) return fail(PPGPU_EINVAL, "grid_clearance_at: bad arguments");
+    if (n == 0 || (!h_clearance && !h_gap2)) return PPGPU_OK;
+    if (c->rows == 0) {                             // the base Map charts nothing
+        for (int64_t i = 0; i < n; i++) {
+            if (h_clearance) h_clearance[i] = DBL_MAX;
+            if (h_gap2) h_gap2[i] = PPGPU_DIST_CAP2;
+        }
+        return PPGPU_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    int rc = grid_distance(c);
+    if (rc || (rc = c->tmp_lengths.reserve((size_t)n * 2, false, st)) || (h_clearance && (rc = c->tmp_len_out.reserve((size_t)n, false, st))) ||
+        (h_gap2 && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->tmp_lengths.p, h_xy2, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    const PPGrid g{c->grid.p, c->rows, c->cols, c->wpr, c->res, 1.0 / c->res, nullptr};
+    hipLaunchKernelGGL(pp_k_grid_clearance_at, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, c->grid_dist.p, (long long)n, c->tmp_lengths.p,
+                       h_clearance ? c->tmp_len_out.p : nullptr, h_gap2 ? (unsigned*)c->tmp_counts.p : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (h_clearance) HIP_TRY(hipMemcpyAsync(h_clearance, c->tmp_len_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (h_gap2) HIP_TRY(hipMemcpyAsync(h_gap2, c->tmp_counts.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return PPGPU_OK;
 }
 
@@ -1255,31 +1326,49 @@ int ppgpu_cost_edges_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgp
 // ------------------------------------------------------------------------------ edge traces
 // One trace of an edge list: which kernel, and where its output goes.  The _list entries fill it with the caller's device arrays,
 // the host forms with the caller's host arrays (cost_host_list then swaps in the device ends of all but the records).
-enum TraceKind { TRACE_STEPS, TRACE_COVER, TRACE_CONTACTS };
+enum TraceKind { TRACE_STEPS, TRACE_COVER, TRACE_CONTACTS, TRACE_CLEARANCE };
 struct TraceRequest {
     TraceKind kind;
-    int32_t stride;                     // step and cover records per edge (a contact trace has n_obst records per edge)
+    int32_t stride;                     // step and cover records per edge (a contact trace has n_obst records per edge, a clearance trace one)
     int32_t* counts;                    // steps of each edge
-    void* records;                      // ppgpu_step_record / ppgpu_cover_record / ppgpu_contact_record ...
+    void* records;                      // ppgpu_step_record / ppgpu_cover_record / ppgpu_contact_record / ppgpu_clearance_record ...
     size_t rec_bytes;                   // ... of this size
     ppgpu_cover_summary* summaries;     // coverage traces only: one summary per edge,
     double* child;                      // the final lists (may be NULL)
     int32_t ribbon_stride;
+    uint32_t limit2;                    // clearance traces only: a step is below the margin iff its gap2 < limit2
 };
 static TraceRequest steps_request(int32_t stride, int32_t* counts, ppgpu_step_record* steps) {
-    return TraceRequest{TRACE_STEPS, stride, counts, steps, sizeof(ppgpu_step_record), nullptr, nullptr, 0};
+    return TraceRequest{TRACE_STEPS, stride, counts, steps, sizeof(ppgpu_step_record), nullptr, nullptr, 0, 0};
 }
 static TraceRequest cover_request(int32_t stride, int32_t* counts, ppgpu_cover_record* cover, ppgpu_cover_summary* summaries, double* child, int32_t ribbon_stride) {
-    return TraceRequest{TRACE_COVER, stride, counts, cover, sizeof(ppgpu_cover_record), summaries, child, ribbon_stride};
+    return TraceRequest{TRACE_COVER, stride, counts, cover, sizeof(ppgpu_cover_record), summaries, child, ribbon_stride, 0};
 }
 static TraceRequest contacts_request(int32_t* counts, ppgpu_contact_record* contacts) {
-    return TraceRequest{TRACE_CONTACTS, 0, counts, contacts, sizeof(ppgpu_contact_record), nullptr, nullptr, 0};
+    return TraceRequest{TRACE_CONTACTS, 0, counts, contacts, sizeof(ppgpu_contact_record), nullptr, nullptr, 0, 0};
+}
+static TraceRequest clearance_request(int32_t* counts, ppgpu_clearance_record* clearance, uint32_t limit2) {
+    return TraceRequest{TRACE_CLEARANCE, 1, counts, clearance, sizeof(ppgpu_clearance_record), nullptr, nullptr, 0, limit2};
+}
+// limit2 of a margin in metres (ppgpu.h): the smallest non-negative integer k with res * sqrt((double)k) >= margin, so that the
+// device compares integers only.  Without a grid, or with margin <= 0, no step is ever below: 0.
+static int clearance_limit2(const ppgpu_ctx* c, const char* who, double margin, uint32_t* limit2) {
+    *limit2 = 0;
+    if (c->rows == 0 || !(margin > 0)) return PPGPU_OK;
+    if (margin > PPGPU_DIST_CAP * c->res) return fail(PPGPU_EINVAL, std::string(who) + ": margin above 255 cells");
+    const double q = margin / c->res;               // the real answer is ceil(q * q); the roundings move it by a few at most
+    long long k = (long long)(q * q) - 2;
+    if (k < 0) k = 0;
+    while (c->res * std::sqrt((double)k) < margin) k++;                       // (ends by PPGPU_DIST_CAP2: the check above)
+    while (k > 0 && c->res * std::sqrt((double)(k - 1)) >= margin) k--;
+    *limit2 = (uint32_t)k;
+    return PPGPU_OK;
 }
 
 // What a trace entry was handed; `who` is its name in the message.  `device`: a _list entry (device arrays, the records stored
 // 16 bytes at a time; it needs the results array).  Contact records may be missing only when there is no obstacle to report on.
 static int trace_request_args(const ppgpu_ctx* c, const char* who, bool device, int64_t n, const void* edges, const void* results, const TraceRequest& r) {
-    static const char* const records_name[] = {"d_steps", "d_cover", "d_contacts"};
+    static const char* const records_name[] = {"d_steps", "d_cover", "d_contacts", "d_clearance"};
     const bool cover = r.kind == TRACE_COVER, contacts = r.kind == TRACE_CONTACTS;
     if (n < 0 || (n > 0 && (!edges || !r.counts || ((!contacts || c->n_obst > 0) && !r.records)))) return fail(PPGPU_EINVAL, std::string(who) + ": bad arguments");
     if (!contacts && (r.stride <= 0 || r.stride > 65535)) return fail(PPGPU_EINVAL, std::string(who) + ": step_stride must be in 1 .. 65535");
@@ -1307,6 +1396,9 @@ static void trace_kernel(ppgpu_ctx* c, const CostLaunch& L, const PPParams& q, c
         break;
     case TRACE_CONTACTS:
         hipLaunchKernelGGL(L.gaussian ? pp_k_trace_contacts_gaussian : pp_k_trace_contacts, grid, block, 0, c->stream, q, (ppgpu_contact_record*)dst, rec_base, r.counts);
+        break;
+    case TRACE_CLEARANCE:
+        hipLaunchKernelGGL(pp_k_trace_clearance, grid, block, 0, c->stream, q, c->grid_dist.p, r.limit2, (ppgpu_clearance_record*)dst, rec_base, r.counts);
         break;
     }
 }
@@ -1375,7 +1467,11 @@ static int trace_timing(ppgpu_ctx* c, TraceTimer& tm, double* ms_out) {
 // `host_records`.  A contact trace has n_obst records per edge; without obstacles the kernel still runs, for the counts, and is
 // handed no records.
 static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r, bool host_records) {
-    TraceTimer& tm = r.kind == TRACE_STEPS ? c->t_steps : r.kind == TRACE_COVER ? c->t_cover : c->t_contacts;
+    TraceTimer& tm = r.kind == TRACE_STEPS ? c->t_steps : r.kind == TRACE_COVER ? c->t_cover : r.kind == TRACE_CONTACTS ? c->t_contacts : c->t_clearance;
+    if (r.kind == TRACE_CLEARANCE && c->rows > 0) {       // the walk reads the distance map: the first one after a ppgpu_set_grid builds it
+        const int rc = grid_distance(c);
+        if (rc) return rc;
+    }
     if (r.kind != TRACE_CONTACTS) return trace_passes(c, L, r, tm, r.stride, (unsigned char*)r.records, host_records);
     const bool none = L.p.n_obst <= 0;
     return trace_passes(c, L, r, tm, none ? 1 : L.p.n_obst, none ? nullptr : (unsigned char*)r.records, host_records && !none);
@@ -1384,6 +1480,8 @@ static int launch_trace(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r
 int ppgpu_last_trace_timing(ppgpu_ctx* c, double* ms_trace) { return c ? trace_timing(c, c->t_steps, ms_trace) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_cover, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_contact_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_contacts, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_clearance_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_clearance, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_grid_distance_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_dist, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 // A device list in, device records out: cost the list, then trace it.
@@ -1411,6 +1509,14 @@ int ppgpu_trace_cover_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppg
 int ppgpu_trace_contacts_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
                               ppgpu_contact_record* d_contacts) {
     return trace_device_list(c, "trace_contacts_list", n, d_edges, d_results, contacts_request(d_counts, d_contacts));
+}
+
+int ppgpu_trace_clearance_list(ppgpu_ctx* c, int64_t n, const uint64_t* d_edges, ppgpu_edge_result* d_results, int32_t* d_counts,
+                               ppgpu_clearance_record* d_clearance, double margin) {
+    uint32_t limit2;
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (int rc = clearance_limit2(c, "trace_clearance_list", margin, &limit2)) return rc;
+    return trace_device_list(c, "trace_clearance_list", n, d_edges, d_results, clearance_request(d_counts, d_clearance, limit2));
 }
 
 int ppgpu_obstacle_count(ppgpu_ctx* c, int32_t* n, int32_t* model) {
@@ -1517,6 +1623,24 @@ int ppgpu_trace_contacts_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu
                                             int32_t* h_counts, ppgpu_contact_record* h_contacts) {
     const TraceRequest trace = contacts_request(h_counts, h_contacts);
     return cost_host_list(c, "trace_contacts_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
+}
+
+int ppgpu_trace_clearance_host(ppgpu_ctx* c, int64_t n, const uint64_t* h_edges, ppgpu_edge_result* h_results, int32_t* h_counts,
+                               ppgpu_clearance_record* h_clearance, double margin) {
+    uint32_t limit2;
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (int rc = clearance_limit2(c, "trace_clearance_host", margin, &limit2)) return rc;
+    const TraceRequest trace = clearance_request(h_counts, h_clearance, limit2);
+    return cost_host_list(c, "trace_clearance_host", false, n, h_edges, h_results, nullptr, 0, &trace);
+}
+
+int ppgpu_trace_clearance_wrapper_edges_host(ppgpu_ctx* c, int64_t n, const ppgpu_wrapper_edge* h_edges, ppgpu_edge_result* h_results,
+                                             int32_t* h_counts, ppgpu_clearance_record* h_clearance, double margin) {
+    uint32_t limit2;
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (int rc = clearance_limit2(c, "trace_clearance_wrapper_edges_host", margin, &limit2)) return rc;
+    const TraceRequest trace = clearance_request(h_counts, h_clearance, limit2);
+    return cost_host_list(c, "trace_clearance_wrapper_edges_host", true, n, h_edges, h_results, nullptr, 0, &trace);
 }
 
 // ------------------------------------------------------------------------------ heuristic on its own

@@ -58,6 +58,9 @@ public:
     void setDeviceTspTable(int maxRibbons) { m_PlannerConfig.setDeviceTspTable(maxRibbons); }
     // PlannerConfig::setPlanContacts: every cycle's Stats carry the per-contact reports of the plan it returns
     void setPlanContacts(bool on) { m_PlannerConfig.setPlanContacts(on); }
+    // PlannerConfig::setPlanClearance / setPlanClearanceMargin: every cycle's Stats carry the plan's clearance to charted hazards
+    void setPlanClearance(bool on) { m_PlannerConfig.setPlanClearance(on); }
+    void setPlanClearanceMargin(double metres) { m_PlannerConfig.setPlanClearanceMargin(metres); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

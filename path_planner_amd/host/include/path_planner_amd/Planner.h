@@ -91,6 +91,43 @@ public:
             }
             return out;
         }
+        // With PlannerConfig::setPlanClearance: Clearance[s] = how close Plan's segment s passes to a charted hazard (a cell that is
+        // blocked or outside the grid): the fields of ppgpu_clearance_record from one ppgpu_trace_clearance_wrapper_edges_host call
+        // over the segments, with PlannerConfig::planClearanceMargin.  `clearance` is a certified lower bound in metres (the true
+        // distance is at most a cell's diagonal more).  PlanClearance = the segments merged (mergeClearance).
+        struct ClearanceReport {
+            enum : uint32_t { Empty = 0x1, Blocked = 0x2, Capped = 0x4, NoMap = 0x8 };      // PPGPU_CL_*
+            double clearance = -1, time = -1, x = 0, y = 0, firstBelowTime = -1;
+            int32_t step = -1;                    // steps count within their segment ...
+            uint32_t gap2 = 0;
+            int32_t belowSteps = 0, firstBelowStep = -1;
+            uint32_t flags = Empty;
+            int32_t segment = -1;                 // ... a merged report says which one `step` counts in (-1: none)
+            int32_t firstBelowSegment = -1;       // ... and firstBelowStep
+        };
+        std::vector<ClearanceReport> Clearance;
+        ClearanceReport PlanClearance;
+        // The smallest clearance wins, the earlier segment on equality; belowSteps summed; the earliest firstBelowTime; flags ORed,
+        // except Empty, which is set only when every segment is empty (no segment at all included).
+        static ClearanceReport mergeClearance(const std::vector<ClearanceReport>& segments) {
+            ClearanceReport out;
+            uint32_t flags = 0;
+            for (size_t s = 0; s < segments.size(); s++) {
+                const ClearanceReport& c = segments[s];
+                flags |= c.flags & ~(uint32_t)ClearanceReport::Empty;
+                if (c.flags & ClearanceReport::Empty) continue;
+                if (out.step < 0 || c.clearance < out.clearance) {
+                    out.clearance = c.clearance; out.time = c.time; out.x = c.x; out.y = c.y; out.step = c.step; out.gap2 = c.gap2;
+                    out.segment = (int32_t)s;
+                }
+                out.belowSteps += c.belowSteps;
+                if (c.firstBelowStep >= 0 && (out.firstBelowStep < 0 || c.firstBelowTime < out.firstBelowTime)) {
+                    out.firstBelowTime = c.firstBelowTime; out.firstBelowStep = c.firstBelowStep; out.firstBelowSegment = (int32_t)s;
+                }
+            }
+            out.flags = out.step < 0 ? (uint32_t)ClearanceReport::Empty : flags;
+            return out;
+        }
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -288,6 +325,7 @@ public:
         bool goalReached = false;
         RibbonManager ribbons;                // ... and what it has left to cover
         std::vector<Planner::Stats::Contact> contacts;   // PlannerConfig::setPlanContacts: the costed legs merged, per contact (Stats::mergeContacts)
+        Planner::Stats::ClearanceReport clearance;       // PlannerConfig::setPlanClearance: the costed legs merged (Stats::mergeClearance)
     };
     // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
     // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
@@ -370,8 +408,8 @@ private:
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
     void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);
-    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage / Stats::Contacts for the plan that ends at node v
-    void evaluationContacts(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage / Stats::Contacts / Stats::Clearance for the plan that ends at node v
+    void evaluationReports(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
                             const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
                             std::vector<PlanEvaluation>& out);
     void visualizePlan(const DubinsPlan& plan);

@@ -245,6 +245,16 @@ public:
     // (GpuAStarPlanner::PlanEvaluation::contacts): one more device call over the plan's segments.  Off by default.
     bool planContacts() const { return m_PlanContacts; }
     void setPlanContacts(bool on) { m_PlanContacts = on; }
+    // How close the returned plan passes to a charted hazard (Planner::Stats::Clearance / PlanClearance), and evaluated plans
+    // (GpuAStarPlanner::PlanEvaluation::clearance): one more device call over the plan's segments, which reads the device's distance
+    // map of the grid.  The first such call after a new grid builds that map (a fraction of a millisecond for a 2048 x 2048 chart:
+    // DESIGN.md 7); a replan loop with the switch on pays it once per map.  Off by default; with it off nothing changes.
+    bool planClearance() const { return m_PlanClearance; }
+    void setPlanClearance(bool on) { m_PlanClearance = on; }
+    // ... and how many steps of the plan lie closer to a hazard than this many metres (below_steps, first_below_time).  0, the
+    // default: nothing is counted.  At most 255 cells.  It does not change what the planner considers blocked.
+    double planClearanceMargin() const { return m_PlanClearanceMargin; }
+    void setPlanClearanceMargin(double metres) { m_PlanClearanceMargin = metres; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -267,7 +277,8 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_ChainedPreviousPlan = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false;
+    double m_PlanClearanceMargin = 0;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;

@@ -1108,7 +1108,18 @@ static Planner::Stats::Contact contactOf(uint32_t mmsi, const ppgpu_contact_reco
     return c;
 }
 
-// PlannerConfig::planTrace / planCoverage / planContacts: the returned plan's segments swept once more, step by step, in one device call each —
+// A device clearance record as the planner reports it.
+static Planner::Stats::ClearanceReport clearanceOf(const ppgpu_clearance_record& r) {
+    Planner::Stats::ClearanceReport c;
+    c.clearance = r.clearance; c.time = r.time; c.x = r.x; c.y = r.y; c.firstBelowTime = r.first_below_time;
+    c.step = r.step; c.gap2 = r.gap2; c.belowSteps = r.below_steps; c.firstBelowStep = r.first_below_step; c.flags = r.flags;
+    return c;
+}
+static_assert(Planner::Stats::ClearanceReport::Empty == PPGPU_CL_EMPTY && Planner::Stats::ClearanceReport::Blocked == PPGPU_CL_BLOCKED &&
+              Planner::Stats::ClearanceReport::Capped == PPGPU_CL_CAPPED && Planner::Stats::ClearanceReport::NoMap == PPGPU_CL_NO_MAP,
+              "Stats::ClearanceReport's flags are PPGPU_CL_*");
+
+// PlannerConfig::planTrace / planCoverage / planContacts / planClearance: the returned plan's segments swept once more, step by step, in one device call each —
 // segment s from its parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
 static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
 void GpuAStarPlanner::tracePlanSteps(int v) {
@@ -1116,6 +1127,8 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
     m_Stats.Coverage.clear();
     m_Stats.Contacts.clear();
     m_Stats.PlanContacts.clear();
+    m_Stats.Clearance.clear();
+    m_Stats.PlanClearance = Stats::ClearanceReport();
     const std::vector<int> nodes = branch(v);
     const size_t n = nodes.size();
     if (n == 0) return;
@@ -1180,6 +1193,14 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
         for (size_t s = 0; s < n; s++)
             for (size_t j = 0; j < ids.size(); j++) m_Stats.Contacts[s].push_back(contactOf(ids[j], recs[s * ids.size() + j]));
         m_Stats.PlanContacts = Stats::mergeContacts(m_Stats.Contacts);
+    }
+    if (m_Config.planClearance()) {
+        std::vector<ppgpu_clearance_record> recs(n);
+        check(ppgpu_trace_clearance_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.data(), m_Config.planClearanceMargin()),
+              "ppgpu_trace_clearance_wrapper_edges_host");
+        sameCounts("plan clearance");
+        for (size_t s = 0; s < n; s++) m_Stats.Clearance.push_back(clearanceOf(recs[s]));
+        m_Stats.PlanClearance = Stats::mergeClearance(m_Stats.Clearance);
     }
 }
 
@@ -1275,21 +1296,25 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
             e.ribbons.assign(child.data() + at * (size_t)kRibbonStride * 4, std::min(recChildRibbons(r), kRibbonStride), r.coverage_completed_time);
         }
     }
-    if (m_Config.planContacts()) evaluationContacts(root, offsets, legs, res, child, costed, out);
+    if (m_Config.planContacts() || m_Config.planClearance()) evaluationReports(root, offsets, legs, res, child, costed, out);
     return out;
 }
 
-// PlanEvaluation::contacts: every costed leg of every plan swept once more from the vertex the leg before it left (the root for a
-// plan's first leg; state, g, ribbons and coverageCompletedTime from that leg's record and child list), all in one contact-trace call.
-void GpuAStarPlanner::evaluationContacts(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+// PlanEvaluation::contacts / clearance: every costed leg of every plan swept once more from the vertex the leg before it left (the root
+// for a plan's first leg; state, g, ribbons and coverageCompletedTime from that leg's record and child list), all in one contact-trace
+// call and one clearance-trace call, whichever of the two switches are on.
+void GpuAStarPlanner::evaluationReports(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
                                          const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
                                          std::vector<PlanEvaluation>& out) {
+    const bool contacts = m_Config.planContacts(), clearance = m_Config.planClearance();
     std::vector<uint32_t> ids;
-    m_Config.obstaclesManager().deviceIds(ids);
     ppgpu_ctx* h = m_Ctx->handle();
-    int32_t rows = 0;
-    check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
-    if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
+    if (contacts) {
+        m_Config.obstaclesManager().deviceIds(ids);
+        int32_t rows = 0;
+        check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
+        if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
+    }
     std::vector<ppgpu_vertex> verts{makeVertex(root)};
     std::vector<double> pool;
     ribbonsToArray(root.ribbons, pool);
@@ -1318,26 +1343,45 @@ void GpuAStarPlanner::evaluationContacts(const Node& root, const std::vector<int
         }
     }
     const size_t n = wedges.size();
-    if (n == 0) {
+    if (n == 0) {           // (clearance: the default report is the empty one)
         for (PlanEvaluation& e : out) { e.contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) e.contacts[j].mmsi = ids[j]; }
         return;
     }
     check(ppgpu_set_vertices(h, (int32_t)verts.size(), verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
     std::vector<int32_t> counts(n, 0);
-    std::vector<ppgpu_contact_record> recs(n * ids.size());
-    check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
-          "ppgpu_trace_contacts_wrapper_edges_host");
-    size_t w = 0;
-    for (size_t i = 0; i < out.size(); i++) {
-        std::vector<std::vector<Stats::Contact>> segs((size_t)costed[i]);
-        for (int k = 0; k < costed[i]; k++, w++) {
-            if (counts[w] != steps[w])
-                throw std::runtime_error("plan contacts: leg " + std::to_string(k) + " of plan " + std::to_string(i) + " traced " + std::to_string(counts[w]) +
-                                         " steps, its edge executed " + std::to_string(steps[w]));
-            for (size_t j = 0; j < ids.size(); j++) segs[(size_t)k].push_back(contactOf(ids[j], recs[w * ids.size() + j]));
+    const auto sameCounts = [&](const char* what) {
+        size_t w = 0;
+        for (size_t i = 0; i < out.size(); i++)
+            for (int k = 0; k < costed[i]; k++, w++)
+                if (counts[w] != steps[w])
+                    throw std::runtime_error(std::string(what) + ": leg " + std::to_string(k) + " of plan " + std::to_string(i) + " traced " + std::to_string(counts[w]) +
+                                             " steps, its edge executed " + std::to_string(steps[w]));
+    };
+    if (contacts) {
+        std::vector<ppgpu_contact_record> recs(n * ids.size());
+        check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
+              "ppgpu_trace_contacts_wrapper_edges_host");
+        sameCounts("plan contacts");
+        size_t w = 0;
+        for (size_t i = 0; i < out.size(); i++) {
+            std::vector<std::vector<Stats::Contact>> segs((size_t)costed[i]);
+            for (int k = 0; k < costed[i]; k++, w++)
+                for (size_t j = 0; j < ids.size(); j++) segs[(size_t)k].push_back(contactOf(ids[j], recs[w * ids.size() + j]));
+            out[i].contacts = Stats::mergeContacts(segs);
+            if (out[i].contacts.empty()) { out[i].contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) out[i].contacts[j].mmsi = ids[j]; }
         }
-        out[i].contacts = Stats::mergeContacts(segs);
-        if (out[i].contacts.empty()) { out[i].contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) out[i].contacts[j].mmsi = ids[j]; }
+    }
+    if (clearance) {
+        std::vector<ppgpu_clearance_record> recs(n);
+        check(ppgpu_trace_clearance_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.data(), m_Config.planClearanceMargin()),
+              "ppgpu_trace_clearance_wrapper_edges_host");
+        sameCounts("plan clearance");
+        size_t w = 0;
+        for (size_t i = 0; i < out.size(); i++) {
+            std::vector<Stats::ClearanceReport> segs;
+            for (int k = 0; k < costed[i]; k++, w++) segs.push_back(clearanceOf(recs[w]));
+            out[i].clearance = Stats::mergeClearance(segs);
+        }
     }
     setOpenVertex(root);      // (the handle's open vertices are the call's again)
 }
@@ -1558,7 +1602,7 @@ void GpuAStarPlanner::reportPlan() {
     m_Stats.PlanTimePenalty = (m_Nodes[m_Best].state.time() - m_StartStateTime) * kTimePenaltyFactor;
     m_Stats.PlanHValue = m_Nodes[m_Best].h;
     m_Stats.Plan = tracePlan(m_Best);
-    if (m_Config.planTrace() || m_Config.planCoverage() || m_Config.planContacts()) tracePlanSteps(m_Best);
+    if (m_Config.planTrace() || m_Config.planCoverage() || m_Config.planContacts() || m_Config.planClearance()) tracePlanSteps(m_Best);
 }
 
 Planner::Stats GpuAStarPlanner::plan(const RibbonManager& ribbonManager, const State& start, PlannerConfig config,

@@ -8,6 +8,8 @@
 //                  plan_coverage_file path (with cfg plan_coverage 1: one line per step, what it did to the ribbons) |
 //                  plan_contacts_file path (with cfg plan_contacts 1: one line per segment and contact, what the segment has to do with it;
 //                  the MMSIs are those the obstacle / gaussian lines were given, 1, 2, ... in file order) |
+//                  plan_clearance_file path (with cfg plan_clearance 1, and cfg plan_clearance_margin M in metres: one line per segment, how
+//                  close it passes to a charted hazard and how many of its steps lie inside the margin) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -44,6 +46,14 @@ static std::string contactKeys(const std::vector<Planner::Stats::Contact>& conta
     return buf;
 }
 
+// ", plan_clearance ..., plan_clearance_time ..., plan_below_margin_steps ..." of a plan's merged clearance report (-1 / -1 / 0 for an
+// empty plan)
+static std::string clearanceKeys(const Planner::Stats::ClearanceReport& c) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, ", \"plan_clearance\": %.17g, \"plan_clearance_time\": %.17g, \"plan_below_margin_steps\": %d", c.clearance, c.time, c.belowSteps);
+    return buf;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: plan_cli scenario.txt\n"); return 2; }
     std::ifstream in(argv[1]);
@@ -68,7 +78,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planLogPath;
     bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -93,6 +103,8 @@ int main(int argc, char** argv) {
             else if (name == "plan_trace") config.setPlanTrace(v != 0);
             else if (name == "plan_coverage") config.setPlanCoverage(v != 0);
             else if (name == "plan_contacts") config.setPlanContacts(v != 0);
+            else if (name == "plan_clearance") config.setPlanClearance(v != 0);
+            else if (name == "plan_clearance_margin") config.setPlanClearanceMargin(v);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -124,6 +136,7 @@ int main(int argc, char** argv) {
         } else if (k == "plan_trace_file") { s >> planTracePath;   // segment step x y heading time collision penalty_before flags
         } else if (k == "plan_coverage_file") { s >> planCoveragePath;   // segment step time to_cover remaining ribbons flags
         } else if (k == "plan_contacts_file") { s >> planContactsPath;   // segment mmsi hit_steps first_hit_time last_hit_time cpa_distance cpa_time exposure peak
+        } else if (k == "plan_clearance_file") { s >> planClearancePath;   // segment clearance time x y step gap2 below_steps first_below_time flags
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -194,7 +207,7 @@ int main(int argc, char** argv) {
                 for (size_t k = 0; k < e.legs.size(); k++)
                     std::printf("%s{\"feasible\": %s, \"g\": %.17g, \"collision_penalty\": %.17g}", k ? ", " : "", e.legs[k].feasible ? "true" : "false", e.legs[k].g,
                                 e.legs[k].collisionPenalty);
-                std::printf("]%s}", config.planContacts() ? contactKeys(e.contacts).c_str() : "");
+                std::printf("]%s%s}", config.planContacts() ? contactKeys(e.contacts).c_str() : "", config.planClearance() ? clearanceKeys(e.clearance).c_str() : "");
             }
             std::printf("]}\n");
             return 0;
@@ -395,6 +408,18 @@ int main(int argc, char** argv) {
                     for (const auto& c : st.Contacts[sg])
                         std::fprintf(f, "%zu %u %d %.17g %.17g %.17g %.17g %.17g %.17g\n", sg, c.mmsi, c.hitSteps, c.firstHitTime, c.lastHitTime, c.cpaDistance, c.cpaTime,
                                      c.exposure, c.peak);
+                std::fclose(f);
+            }
+        }
+        if (config.planClearance()) {             // (only with the switch on: without it the line is what it always was)
+            tail += clearanceKeys(st.PlanClearance);
+            if (!planClearancePath.empty()) {
+                FILE* f = std::fopen(planClearancePath.c_str(), "w");
+                if (!f) { std::fprintf(stderr, "cannot write %s\n", planClearancePath.c_str()); return 2; }
+                for (size_t sg = 0; sg < st.Clearance.size(); sg++) {
+                    const auto& c = st.Clearance[sg];
+                    std::fprintf(f, "%zu %.17g %.17g %.17g %.17g %d %u %d %.17g %u\n", sg, c.clearance, c.time, c.x, c.y, c.step, c.gap2, c.belowSteps, c.firstBelowTime, c.flags);
+                }
                 std::fclose(f);
             }
         }

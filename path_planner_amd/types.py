@@ -95,6 +95,16 @@ CONTACT_DTYPE = np.dtype([
 ])
 assert CONTACT_DTYPE.itemsize == 64
 
+# struct ppgpu_clearance_record, 64 bytes, per edge: the closest approach to a charted hazard (ppgpu_trace_clearance_*).  The
+# distance map behind it holds min(gap2, DIST_CAP2) per cell, in cells squared (ppgpu_get_grid_distance)
+DIST_CAP, DIST_CAP2 = 255, 65025
+CL_EMPTY, CL_BLOCKED, CL_CAPPED, CL_NO_MAP = 0x1, 0x2, 0x4, 0x8
+CLEARANCE_DTYPE = np.dtype([
+    ("clearance", "<f8"), ("time", "<f8"), ("x", "<f8"), ("y", "<f8"), ("first_below_time", "<f8"),
+    ("step", "<i4"), ("gap2", "<u4"), ("below_steps", "<i4"), ("first_below_step", "<i4"), ("flags", "<u4"), ("reserved", "<u4"),
+])
+assert CLEARANCE_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
