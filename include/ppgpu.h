@@ -584,7 +584,9 @@ int ppgpu_last_grid_distance_timing(ppgpu_ctx* ctx, double* ms_build);
 /* The clearance of an edge: one record per edge, from a walk over the executed steps of its sweep — the steps of
  * ppgpu_step_record, same count, same poses and times — that takes the gap2 of every step's cell. */
 #define PPGPU_CL_EMPTY   0x1u  /* no executed step (PPGPU_F_THROWS, malformed, a curve starting after the vertex's first step) */
-#define PPGPU_CL_BLOCKED 0x2u  /* the last executed step is the blocked one (Edge.cpp:144-146): clearance 0 */
+#define PPGPU_CL_BLOCKED 0x2u  /* the last executed step is the blocked one (Edge.cpp:144-146): clearance 0.  With a keep-out active
+                                * (below) "blocked" is blocked in the effective grid, as it is for PPGPU_S_BLOCKED of a step record:
+                                * the step's own gap2, and so the clearance, may then be greater than 0 */
 #define PPGPU_CL_CAPPED  0x4u  /* min gap2 == PPGPU_DIST_CAP2: clearance is "at least" */
 #define PPGPU_CL_NO_MAP  0x8u  /* base Map (rows == 0): clearance DBL_MAX, gap2 = PPGPU_DIST_CAP2, always with CAPPED */
 typedef struct ppgpu_clearance_record {   /* 64 bytes */
@@ -615,6 +617,33 @@ int ppgpu_trace_clearance_wrapper_edges_host(ppgpu_ctx* ctx, int64_t n, const pp
 /* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_trace_clearance took in the last clearance-trace
  * call, summed over its slices (HIP events on the handle's stream around the kernel alone).  Waits for the launch. */
 int ppgpu_last_clearance_trace_timing(ppgpu_ctx* ctx, double* ms_clearance_trace);
+
+/* The keep-out margin: planning with the distance map, not only reporting on it.
+ * limit2 of a margin in metres is the smallest non-negative integer k with resolution * sqrt((double)k) >= margin; margin <= 0
+ * gives 0.  ppgpu_keepout_limit2 is the one statement of this rule (no handle, no device): PPGPU_EINVAL for a NaN and for
+ * margin > PPGPU_DIST_CAP * resolution.  The trace calls above use it; they go on counting nothing for a margin that is not above 0.
+ * The EFFECTIVE GRID at limit2: cell (r, c) is blocked iff gap2(r, c) < limit2, or it is blocked in the grid that was set.  For
+ * limit2 >= 1 the first clause contains the second; for limit2 == 0 the effective grid is the grid as set.  Outside the grid stays
+ * blocked, and because the outside is a hazard in gap2 the band also runs along the grid's border: this is the hazard set the
+ * clearance report measures against.  Every free cell of the effective grid has certified clearance of at least
+ * resolution * sqrt(limit2) metres.
+ * With a non-zero limit the effective grid (pp_k_keepout_bits) and the chessboard clearance map over it are what every launch
+ * reads: the sampler's map filter, all costing routes, all four traces.  The grid as set stays on the device beside it: the
+ * distance map, ppgpu_get_grid_distance, ppgpu_grid_clearance_at and the gap2 of the clearance records keep their meaning
+ * whatever the limit is.  A handle whose limit was never set does nothing it did not do before. */
+int ppgpu_keepout_limit2(double resolution, double margin, uint32_t* limit2);
+/* limit2 in cells squared (resolution-free).  limit2 > PPGPU_DIST_CAP2: PPGPU_EINVAL, nothing changed.  The handle keeps the value
+ * across ppgpu_set_grid (a grid set under a non-zero limit builds the distance map at once); with the base Map (rows == 0) it is
+ * stored and has no effect.  Before or after ppgpu_set_grid: the resulting state is the same.  Synchronous: waits for the stream,
+ * then rebuilds the effective grid and its clearance map when the value changes. */
+int ppgpu_set_keepout_limit2(ppgpu_ctx* ctx, uint32_t limit2);
+int ppgpu_get_keepout_limit2(ppgpu_ctx* ctx, uint32_t* limit2);
+/* For tests and tools: the effective grid, one byte 0/1 per cell at r*cols + c.  PPGPU_EINVAL without a grid (rows == 0) or when
+ * capacity < rows*cols.  Synchronous. */
+int ppgpu_get_grid_blocked(ppgpu_ctx* ctx, uint8_t* h_out, int64_t capacity);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds the last change of the effective grid took:
+ * pp_k_keepout_bits (not run on the way back to 0) and the rebuild of the chessboard clearance map.  PPGPU_ESTATE when none was timed. */
+int ppgpu_last_keepout_timing(ppgpu_ctx* ctx, double* ms_keepout);
 
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);

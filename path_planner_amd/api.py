@@ -97,6 +97,11 @@ def _load():
         "ppgpu_trace_clearance_host": (C.c_int, [vp, i64, vp, vp, vp, vp, dbl]),
         "ppgpu_trace_clearance_wrapper_edges_host": (C.c_int, [vp, i64, vp, vp, vp, vp, dbl]),
         "ppgpu_last_clearance_trace_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_keepout_limit2": (C.c_int, [dbl, dbl, C.POINTER(u32)]),
+        "ppgpu_set_keepout_limit2": (C.c_int, [vp, u32]),
+        "ppgpu_get_keepout_limit2": (C.c_int, [vp, C.POINTER(u32)]),
+        "ppgpu_get_grid_blocked": (C.c_int, [vp, vp, i64]),
+        "ppgpu_last_keepout_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -116,6 +121,15 @@ def _load():
 
 
 LIB, EXPORTS = _load()
+
+
+def keepout_limit2(res, margin):
+    """limit2 of a margin in metres at a resolution (ppgpu_keepout_limit2: no handle, no device)."""
+    k = C.c_uint32()
+    rc = LIB.ppgpu_keepout_limit2(float(res), float(margin), C.byref(k))
+    if rc != 0:
+        raise PpgpuError(f"ppgpu_keepout_limit2 failed ({rc}): {LIB.ppgpu_last_error().decode()}")
+    return k.value
 
 
 def _ptr(a):
@@ -525,6 +539,26 @@ class Context:
     def last_clearance_trace_timing(self):
         ms = C.c_double()
         self._ck(LIB.ppgpu_last_clearance_trace_timing(self._h, C.byref(ms)), "ppgpu_last_clearance_trace_timing")
+        return ms.value
+
+    def set_keepout_limit2(self, limit2):
+        """Plan on the effective grid: a cell is blocked iff its gap2 < limit2 (0: the grid as set)."""
+        self._ck(LIB.ppgpu_set_keepout_limit2(self._h, int(limit2)), "ppgpu_set_keepout_limit2")
+
+    def get_keepout_limit2(self):
+        k = C.c_uint32()
+        self._ck(LIB.ppgpu_get_keepout_limit2(self._h, C.byref(k)), "ppgpu_get_keepout_limit2")
+        return k.value
+
+    def get_grid_blocked(self, rows, cols):
+        """The effective grid the launches read, rows x cols bytes of 0/1; for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint8)
+        self._ck(LIB.ppgpu_get_grid_blocked(self._h, _ptr(out), out.size), "ppgpu_get_grid_blocked")
+        return out
+
+    def last_keepout_timing(self):
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_keepout_timing(self._h, C.byref(ms)), "ppgpu_last_keepout_timing")
         return ms.value
 
     @staticmethod

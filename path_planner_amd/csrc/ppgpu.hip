@@ -114,6 +114,10 @@ struct ppgpu_ctx {
     double res = 0;
     DevBuf<uint16_t> grid_dist;         // distance map of the grid (ppgpu.h, "chart clearance"): built by the first call that needs it ...
     bool grid_dist_built = false;       // ... after a ppgpu_set_grid (grid_distance)
+    // keep-out margin (ppgpu.h, "chart clearance").  `grid` is always the grid as set: the distance map is built from it.  With
+    // keepout_limit2 > 0 the launches read grid_keepout instead (grid_bits), and grid_clear is the map of that grid.
+    uint32_t keepout_limit2 = 0;
+    DevBuf<uint32_t> grid_keepout;      // the effective grid, allocated by the first non-zero limit on a grid
     // dynamic obstacles
     DevBuf<PPObst> obst;
     int n_obst = 0;
@@ -151,6 +155,7 @@ struct ppgpu_ctx {
     TraceTimer t_steps, t_cover, t_contacts, t_clearance;   // around pp_k_trace_steps / pp_k_trace_cover / pp_k_trace_contacts / pp_k_trace_clearance
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
     TraceTimer t_dist;                  // around the two passes of the distance map (grid_distance)
+    TraceTimer t_keepout;               // around pp_k_keepout_bits and the rebuild of grid_clear (apply_keepout)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool solve_all_words = false;       // env PPGPU_SOLVE_ALL_WORDS=1: the solver evaluates all six words correctly rounded (tests compare the two)
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
@@ -211,7 +216,7 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -329,6 +334,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
             for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm->ev[i]));
         tm->timed = false;
     }
+    c->t_keepout.timed = false;         // (its events are made by the first timed change of the keep-out: apply_keepout)
     c->timing = on != 0;
     c->ev_launches = 0;
     return PPGPU_OK;
@@ -505,6 +511,16 @@ int ppgpu_set_config(ppgpu_ctx* c, const ppgpu_config* cfg) {
     return PPGPU_OK;
 }
 
+// The bit grid the launches read (PPGrid::bits): the grid as set, or the effective grid of the keep-out.
+static const uint32_t* grid_bits(const ppgpu_ctx* c) { return c->keepout_limit2 ? c->grid_keepout.p : c->grid.p; }
+// The chessboard clearance map of `bits` into grid_clear (two separable passes on the stream).
+static void launch_grid_clear(ppgpu_ctx* c, const uint32_t* bits, int rows, int cols, int wpr) {
+    const long long ncell = (long long)rows * cols;
+    hipLaunchKernelGGL(pp_k_grid_row_clear, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, bits, rows, cols, wpr, c->grid_rowclear.p);
+    hipLaunchKernelGGL(pp_k_grid_clear, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, c->grid_rowclear.p, rows, cols, c->grid_clear.p);
+}
+static int apply_keepout(ppgpu_ctx* c);                  // (further down, with the distance map it thresholds)
+
 int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t cols, double res) {
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));
@@ -525,12 +541,12 @@ int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t col
     // clearance map: chessboard distance to the nearest blocked-or-outside cell, capped (two separable passes on the device)
     if ((rc = c->grid_clear.reserve((size_t)rows * cols, false, c->stream)) || (rc = c->grid_rowclear.reserve((size_t)rows * cols, false, c->stream)))
         return rc;
-    {
-        const long long ncell = (long long)rows * cols;
-        hipLaunchKernelGGL(pp_k_grid_row_clear, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, c->grid.p, rows, cols, wpr, c->grid_rowclear.p);
-        hipLaunchKernelGGL(pp_k_grid_clear, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream, c->grid_rowclear.p, rows, cols, c->grid_clear.p);
-        HIP_TRY(hipGetLastError());
+    if (c->keepout_limit2) {                            // the kernels read the effective grid: the map is built over that one
+        c->rows = rows; c->cols = cols; c->wpr = wpr; c->res = res;
+        return apply_keepout(c);
     }
+    launch_grid_clear(c, c->grid.p, rows, cols, wpr);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->rows = rows; c->cols = cols; c->wpr = wpr; c->res = res;
     return PPGPU_OK;
@@ -609,6 +625,87 @@ int ppgpu_grid_clearance_at(ppgpu_ctx* c, int64_t n, const double* h_xy2, double
     if (h_clearance) HIP_TRY(hipMemcpyAsync(h_clearance, c->tmp_len_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (h_gap2) HIP_TRY(hipMemcpyAsync(h_gap2, c->tmp_counts.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ keep-out margin
+int ppgpu_keepout_limit2(double resolution, double margin, uint32_t* limit2) {
+    if (!limit2) return fail(PPGPU_EINVAL, "keepout_limit2: null argument");
+    if (margin != margin) return fail(PPGPU_EINVAL, "keepout_limit2: the margin is not a number");
+    *limit2 = 0;
+    if (!(margin > 0)) return PPGPU_OK;
+    if (!(resolution > 0)) return fail(PPGPU_EINVAL, "keepout_limit2: the resolution must be positive");
+    if (margin > PPGPU_DIST_CAP * resolution) return fail(PPGPU_EINVAL, "keepout_limit2: margin above 255 cells");
+    const double q = margin / resolution;           // the real answer is ceil(q * q); the roundings move it by a few at most
+    long long k = (long long)(q * q) - 2;
+    if (k < 0) k = 0;
+    while (resolution * std::sqrt((double)k) < margin) k++;                   // (ends by PPGPU_DIST_CAP2: the check above)
+    while (k > 0 && resolution * std::sqrt((double)(k - 1)) >= margin) k--;
+    *limit2 = (uint32_t)k;
+    return PPGPU_OK;
+}
+
+// The grid that is set (rows > 0) follows keepout_limit2 from here on: the effective bits (pp_k_keepout_bits over the distance
+// map; at limit 0 they are the grid as set, no copy) and the chessboard clearance map over them, which the skip planner culls with.
+static int apply_keepout(ppgpu_ctx* c) {
+    hipStream_t st = c->stream;
+    int rc = PPGPU_OK;
+    if (c->keepout_limit2) {
+        const unsigned ctiles = (unsigned)((c->cols + 255) / 256);
+        if (ctiles > 65535u) return fail(PPGPU_ECAPACITY, "keep-out: the grid is too wide for the kernel's launch shape");
+        if ((rc = grid_distance(c)) || (rc = c->grid_keepout.reserve((size_t)c->rows * c->wpr, false, st)) ||
+            (rc = c->grid_clear.reserve((size_t)c->rows * c->cols, false, st)) || (rc = c->grid_rowclear.reserve((size_t)c->rows * c->cols, false, st)))
+            return rc;
+    }
+    TraceTimer& tm = c->t_keepout;
+    tm.ms_earlier = 0;
+    tm.timed = false;
+    if (c->timing) {
+        if (!tm.ev[0])
+            for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm.ev[i]));
+        HIP_TRY(hipEventRecord(tm.ev[0], st));
+    }
+    if (c->keepout_limit2)
+        hipLaunchKernelGGL(pp_k_keepout_bits, dim3((unsigned)c->rows, (unsigned)((c->cols + 255) / 256)), dim3(256), 0, st, c->grid_dist.p, c->rows, c->cols,
+                           c->wpr, c->keepout_limit2, c->grid_keepout.p);
+    launch_grid_clear(c, grid_bits(c), c->rows, c->cols, c->wpr);
+    if (c->timing) { HIP_TRY(hipEventRecord(tm.ev[1], st)); tm.timed = true; }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return PPGPU_OK;
+}
+
+int ppgpu_set_keepout_limit2(ppgpu_ctx* c, uint32_t limit2) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (limit2 > PPGPU_DIST_CAP2) return fail(PPGPU_EINVAL, "set_keepout_limit2: limit2 above PPGPU_DIST_CAP2");
+    if (limit2 == c->keepout_limit2) return PPGPU_OK;
+    if (c->rows == 0) { c->keepout_limit2 = limit2; return PPGPU_OK; }      // the base Map charts nothing: kept for the next grid
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));       // launches under way still read the bits and the map this call rewrites
+    const uint32_t was = c->keepout_limit2;
+    c->keepout_limit2 = limit2;
+    const int rc = apply_keepout(c);
+    if (rc && was == 0) c->keepout_limit2 = 0;      // (the effective grid may not exist: the launches stay on the grid as set)
+    return rc;
+}
+
+int ppgpu_get_keepout_limit2(ppgpu_ctx* c, uint32_t* limit2) {
+    if (!c || !limit2) return fail(PPGPU_EINVAL, "get_keepout_limit2: null argument");
+    *limit2 = c->keepout_limit2;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_blocked(ppgpu_ctx* c, uint8_t* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, "grid blocked: null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, "grid blocked: no grid is set");
+    const int64_t ncell = (int64_t)c->rows * c->cols;
+    if (capacity < ncell) return fail(PPGPU_EINVAL, "grid blocked: capacity below rows * cols");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint32_t> bits((size_t)c->rows * c->wpr);
+    HIP_TRY(hipMemcpyAsync(bits.data(), grid_bits(c), bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < c->rows; r++)
+        for (int x = 0; x < c->cols; x++) h_out[(size_t)r * c->cols + x] = (uint8_t)((bits[(size_t)r * c->wpr + (x >> 5)] >> (x & 31)) & 1u);
     return PPGPU_OK;
 }
 
@@ -891,7 +988,7 @@ int ppgpu_sampler_add(ppgpu_ctx* c, int64_t n_attempts, int64_t* n_total_out) {
     unsigned* qpos = c->s_u32a.p;
     unsigned* blk32 = c->s_u32b.p;
     // 4. generate the n candidate states (thread per sample) + 5a. SamplingBasedPlanner::addSamples' map filter
-    PPGrid g{c->grid.p, c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, nullptr};
+    PPGrid g{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, nullptr};
     unsigned char* keep = c->s_bytes.p + (size_t)nq + 64;          // (the projection bits are still being read by this launch)
     hipLaunchKernelGGL(pp_k_generate_keep, dim3((unsigned)nblk_n), dim3(256), 0, st, s, s.on_ribbons ? qpos : nullptr, s.on_ribbons ? proj : nullptr,
                        c->samp_ribbons.p, n, c->s_cand.p, g, keep, blk32);
@@ -928,7 +1025,7 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.heuristic = g.heuristic; p.tsp_k = g.tsp_k; p.h_rho = g.heuristic_turning_radius;
     p.fuse_h = 0;
     p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.defer_count = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.live_count = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.hw_count = nullptr;
-    p.grid = PPGrid{c->grid.p, c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
+    p.grid = PPGrid{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
     p.obst = c->obst.p; p.n_obst = c->n_obst; p.obst_model = c->obst_model;
     p.verts = c->verts.p; p.ribbons = c->ribbons.p; p.tgrid = c->tgrid.p; p.ng = c->ng; p.nverts = c->nverts;
     p.sx = c->sx.p; p.sy = c->sy.p; p.sh = c->sh.p; p.n_samples = c->n_samples + c->n_extra;
@@ -1350,18 +1447,12 @@ static TraceRequest contacts_request(int32_t* counts, ppgpu_contact_record* cont
 static TraceRequest clearance_request(int32_t* counts, ppgpu_clearance_record* clearance, uint32_t limit2) {
     return TraceRequest{TRACE_CLEARANCE, 1, counts, clearance, sizeof(ppgpu_clearance_record), nullptr, nullptr, 0, limit2};
 }
-// limit2 of a margin in metres (ppgpu.h): the smallest non-negative integer k with res * sqrt((double)k) >= margin, so that the
-// device compares integers only.  Without a grid, or with margin <= 0, no step is ever below: 0.
+// limit2 of a trace call's margin in metres (ppgpu_keepout_limit2 states the rule), so that the device compares integers only.
+// Without a grid, or with a margin that is not above 0 (a NaN among them), no step is ever below: 0.
 static int clearance_limit2(const ppgpu_ctx* c, const char* who, double margin, uint32_t* limit2) {
     *limit2 = 0;
     if (c->rows == 0 || !(margin > 0)) return PPGPU_OK;
-    if (margin > PPGPU_DIST_CAP * c->res) return fail(PPGPU_EINVAL, std::string(who) + ": margin above 255 cells");
-    const double q = margin / c->res;               // the real answer is ceil(q * q); the roundings move it by a few at most
-    long long k = (long long)(q * q) - 2;
-    if (k < 0) k = 0;
-    while (c->res * std::sqrt((double)k) < margin) k++;                       // (ends by PPGPU_DIST_CAP2: the check above)
-    while (k > 0 && c->res * std::sqrt((double)(k - 1)) >= margin) k--;
-    *limit2 = (uint32_t)k;
+    if (ppgpu_keepout_limit2(c->res, margin, limit2)) return fail(PPGPU_EINVAL, std::string(who) + ": margin above 255 cells");
     return PPGPU_OK;
 }
 
@@ -1482,6 +1573,7 @@ int ppgpu_last_cover_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_t
 int ppgpu_last_contact_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_contacts, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_clearance_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_clearance, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_grid_distance_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_dist, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_keepout_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_keepout, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 // A device list in, device records out: cost the list, then trace it.

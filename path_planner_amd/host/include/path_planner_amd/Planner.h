@@ -128,6 +128,17 @@ public:
             out.flags = out.step < 0 ? (uint32_t)ClearanceReport::Empty : flags;
             return out;
         }
+        // PlannerConfig::keepoutMargin as this call applied it.  Limit2Requested = limit2 of the margin (ppgpu_keepout_limit2);
+        // Limit2Applied = min(Limit2Requested, StartGap2): the planner never demands more clearance than the vehicle has at its
+        // start, so a start inside the band (Relaxed) can still plan its way out, and one on a hazard's neighbour plans on the
+        // grid as set.  Every free cell the call planned over has certified clearance of at least CertifiedMetres.  With the
+        // margin off (or the base Map) everything is 0 and the start's gap2 is not asked for.
+        struct KeepoutReport {
+            double Margin = 0, CertifiedMetres = 0;           // metres; CertifiedMetres = resolution * sqrt(Limit2Applied)
+            uint32_t Limit2Requested = 0, Limit2Applied = 0, StartGap2 = 0;     // cells squared
+            bool Relaxed = false;                             // Limit2Applied < Limit2Requested
+        };
+        KeepoutReport Keepout;
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -279,6 +290,7 @@ public:
     int tspTableRibbons = -1;
     const void* gridOf = nullptr;
     unsigned long gridVersion = 0;
+    double gridResolution = 0;             // cell size of the grid the device holds (0: the base Map, no grid), whichever call uploaded it
     // round-trip result blocks not referred to by any planner any more are handed out again (used by this context's thread only)
     std::vector<std::shared_ptr<TripBlock>> tripPool;
     std::shared_ptr<TripBlock> takeTripBlock(size_t nEdges, size_t childDoubles);
@@ -326,6 +338,7 @@ public:
         RibbonManager ribbons;                // ... and what it has left to cover
         std::vector<Planner::Stats::Contact> contacts;   // PlannerConfig::setPlanContacts: the costed legs merged, per contact (Stats::mergeContacts)
         Planner::Stats::ClearanceReport clearance;       // PlannerConfig::setPlanClearance: the costed legs merged (Stats::mergeClearance)
+        Planner::Stats::KeepoutReport keepout;           // PlannerConfig::setKeepoutMargin as the call applied it (the same for every plan)
     };
     // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
     // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
@@ -395,6 +408,7 @@ private:
     struct DeviceCounters;
     DeviceCounters deviceCounters() const;
     Node beginCall(const RibbonManager& ribbonManager, const State& start);      // shared with evaluatePlans
+    void applyKeepout(const State& start);                                        // ... PlannerConfig::keepoutMargin on every context
     void initSampler(const State& start, unsigned long seed);
     struct WalkedLegs;                     // the previous-plan leg filter
     size_t costGivenLegs(const WalkedLegs& walked, std::vector<::ppgpu_edge_result>& res, std::vector<double>& child);

@@ -252,9 +252,16 @@ public:
     bool planClearance() const { return m_PlanClearance; }
     void setPlanClearance(bool on) { m_PlanClearance = on; }
     // ... and how many steps of the plan lie closer to a hazard than this many metres (below_steps, first_below_time).  0, the
-    // default: nothing is counted.  At most 255 cells.  It does not change what the planner considers blocked.
+    // default: nothing is counted.  At most 255 cells.  It does not change what the planner considers blocked (keepoutMargin does).
     double planClearanceMargin() const { return m_PlanClearanceMargin; }
     void setPlanClearanceMargin(double metres) { m_PlanClearanceMargin = metres; }
+    // Plan with a keep-out margin around charted hazards: every cell whose certified clearance (ppgpu.h, "chart clearance") is
+    // below this many metres counts as blocked for the sampler, every costing route and every trace, on the device
+    // (ppgpu_set_keepout_limit2).  The outside of the grid is a hazard too, so the band also runs along the grid's border.  A
+    // start inside the band relaxes the margin for that call to the clearance the vehicle has now (Planner::Stats::Keepout), so
+    // that it can still plan its way out.  0, the default: off, nothing changes.  At most 255 cells; a NaN is refused.
+    double keepoutMargin() const { return m_KeepoutMargin; }
+    void setKeepoutMargin(double metres) { m_KeepoutMargin = metres; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -278,7 +285,7 @@ private:
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
     bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false;
-    double m_PlanClearanceMargin = 0;
+    double m_PlanClearanceMargin = 0, m_KeepoutMargin = 0;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;
     std::ostream* m_VisualizationStream = nullptr;

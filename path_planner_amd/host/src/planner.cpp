@@ -433,6 +433,7 @@ static bool uploadSnapshot(const std::vector<std::shared_ptr<GpuContext>>& ctxs,
         if (needGrid) {
             ctx->gridOf = nullptr; ctx->gridVersion = 0;       // until the upload below has succeeded
             check(ppgpu_set_grid(h, rows ? cells.data() : nullptr, rows, cols, res), "ppgpu_set_grid");
+            ctx->gridResolution = rows ? res : 0;
             if (mapVersion != 0) { ctx->gridOf = (const void*)map; ctx->gridVersion = mapVersion; }
         }
         if (om.deviceModel() == PPGPU_OBST_GAUSSIAN)
@@ -441,6 +442,29 @@ static bool uploadSnapshot(const std::vector<std::shared_ptr<GpuContext>>& ctxs,
             check(ppgpu_set_obstacles(h, om.deviceModel(), (int32_t)(orows.size() / 7), orows.empty() ? nullptr : orows.data()), "ppgpu_set_obstacles");
     }
     return needGrid;
+}
+
+// PlannerConfig::keepoutMargin on every context (after uploadSnapshot; -> what was applied).  The devices hold the grid as set
+// whatever the limit is, so a change of margin alone costs one ppgpu_set_keepout_limit2 per context and no upload; a context that
+// already holds the limit returns at once.  Contexts outlive planners: with the margin off the limit is put back to 0.
+// A vehicle inside the band must still be able to plan its way out: applied = min(limit2(margin), gap2(start cell)), from one
+// ppgpu_grid_clearance_at of the start; with the margin off (or without a grid) it is not called.
+static Planner::Stats::KeepoutReport applyKeepoutMargin(const std::vector<std::shared_ptr<GpuContext>>& ctxs, const PlannerConfig& config, const State& start) {
+    Planner::Stats::KeepoutReport k;
+    k.Margin = config.keepoutMargin();
+    const double res = ctxs.at(0)->gridResolution;
+    if (res > 0 && !(k.Margin <= 0)) {              // (a NaN goes on to be refused)
+        check(ppgpu_keepout_limit2(res, k.Margin, &k.Limit2Requested), "ppgpu_keepout_limit2");
+        if (k.Limit2Requested > 0) {
+            const double xy[2] = {start.x(), start.y()};
+            check(ppgpu_grid_clearance_at(ctxs[0]->handle(), 1, xy, nullptr, &k.StartGap2), "ppgpu_grid_clearance_at");
+        }
+        k.Limit2Applied = std::min(k.Limit2Requested, k.StartGap2);
+        k.Relaxed = k.Limit2Applied < k.Limit2Requested;
+        k.CertifiedMetres = res * std::sqrt((double)k.Limit2Applied);
+    }
+    for (const auto& ctx : ctxs) check(ppgpu_set_keepout_limit2(ctx->handle(), k.Limit2Applied), "ppgpu_set_keepout_limit2");
+    return k;
 }
 
 // ------------------------------------------------------------------------------------------------ budget bookkeeping
@@ -1207,6 +1231,8 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
 // ------------------------------------------------------------------------------------------------ the start of a call
 // What evaluatePlans() and plan() begin with once m_Config is the call's (AStarPlanner.cpp:14-26, :35-37): start time, the call's own
 // RibbonManager, the world on every device.  -> the root vertex (h left unset: only plan() needs it)
+void GpuAStarPlanner::applyKeepout(const State& start) { m_Stats.Keepout = applyKeepoutMargin(m_Ctxs, m_Config, start); }
+
 GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonManager, const State& start) {
     m_Config.setStartStateTime(start.time());
     m_RibbonManager = ribbonManager;
@@ -1214,6 +1240,7 @@ GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonMana
     if (m_RibbonManager.done()) m_RibbonManager.setCoverageCompletedTime(start.time());
     m_StartStateTime = start.time();
     m_Stats.Budget.GridUploaded = uploadSnapshot(m_Ctxs, m_Config, m_RibbonManager, start.time());
+    applyKeepout(start);
     // PlannerConfig::deviceTspTable on every context, on or off: contexts outlive planners, and the last call's range must not serve this one
     for (const auto& ctx : m_Ctxs) {
         const int ribbons = m_Config.deviceTspTable();
@@ -1277,6 +1304,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
     for (size_t i = 0; i < n; i++) {
         PlanEvaluation& e = out[i];
         e.legsCosted = costed[i];
+        e.keepout = m_Stats.Keepout;
         e.stop = (PlanEvaluation::Stop)why[i];
         e.goalReached = why[i] == PPGPU_CHAIN_GOAL;
         e.ribbons = root.ribbons;
@@ -1692,6 +1720,7 @@ ShardedIteration::Result ShardedIteration::run(const RibbonManager& ribbonManage
     RibbonManager rm = ribbonManager;
     rm.changeHeuristicIfTooManyRibbons();                                  // AStarPlanner.cpp:18
     uploadSnapshot(m_Ctxs, config, rm, start.time());
+    applyKeepoutMargin(m_Ctxs, config, start);
     // the sampling box and the root vertex of AStarPlanner::plan (:27-37)
     double bounds[6];
     samplingBox(config, start, bounds);

@@ -72,7 +72,7 @@ int main(int argc, char** argv) {
     std::string mapFile;
     double cfg[11] = {8, 16, 2.5, 0.5, 1.5, 9, 1, 30, 5, 0.05, 100};
     int flags[3] = {0, 0, 0};
-    double planningTime = 0.1, maxSeconds = 60;
+    double planningTime = 0.1, maxSeconds = 60, keepoutMargin = 0;
     int speculation = 16;
     std::vector<int> devices;
     std::string line;
@@ -88,6 +88,7 @@ int main(int argc, char** argv) {
         else if (k == "planning_time") s >> planningTime;
         else if (k == "max_seconds") s >> maxSeconds;
         else if (k == "speculation") s >> speculation;
+        else if (k == "keepout_margin") s >> keepoutMargin;      // metres (Executive::setKeepoutMargin)
         else if (k == "devices") { int d; while (s >> d) devices.push_back(d); }
     }
     SimulatedVehicle vehicle(start);
@@ -96,6 +97,7 @@ int main(int argc, char** argv) {
     exec.setPlanningTimeSeconds(planningTime);
     exec.setSpeculation(speculation);
     if (!devices.empty()) exec.setDevices(devices);
+    exec.setKeepoutMargin(keepoutMargin);
     exec.setConfiguration(cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], (int)cfg[5], (int)cfg[6], cfg[7], cfg[8], cfg[9], (int)cfg[10], flags[0] != 0, flags[1] != 0,
                           flags[2] != 0, false);
     if (!mapFile.empty()) exec.refreshMap(mapFile, 0, 0);

@@ -10,6 +10,8 @@
 //                  the MMSIs are those the obstacle / gaussian lines were given, 1, 2, ... in file order) |
 //                  plan_clearance_file path (with cfg plan_clearance 1, and cfg plan_clearance_margin M in metres: one line per segment, how
 //                  close it passes to a charted hazard and how many of its steps lie inside the margin) |
+//                  cfg keepout_margin M (PlannerConfig::setKeepoutMargin: plan M metres clear of charted hazards; a value other than 0 adds
+//                  keepout_margin, keepout_limit2, keepout_certified and keepout_relaxed to the JSON, and to every plan under evaluate) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -51,6 +53,15 @@ static std::string contactKeys(const std::vector<Planner::Stats::Contact>& conta
 static std::string clearanceKeys(const Planner::Stats::ClearanceReport& c) {
     char buf[160];
     std::snprintf(buf, sizeof buf, ", \"plan_clearance\": %.17g, \"plan_clearance_time\": %.17g, \"plan_below_margin_steps\": %d", c.clearance, c.time, c.belowSteps);
+    return buf;
+}
+
+// ", keepout_margin ..., keepout_limit2 ..., keepout_certified ..., keepout_relaxed ..." of a call's Stats::Keepout: the margin asked for, the
+// limit2 applied (cells squared), the clearance that certifies in metres, and whether the start's own clearance lowered it
+static std::string keepoutKeys(const Planner::Stats::KeepoutReport& k) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, ", \"keepout_margin\": %.17g, \"keepout_limit2\": %u, \"keepout_certified\": %.17g, \"keepout_relaxed\": %s", k.Margin, k.Limit2Applied,
+                  k.CertifiedMetres, k.Relaxed ? "true" : "false");
     return buf;
 }
 
@@ -105,6 +116,7 @@ int main(int argc, char** argv) {
             else if (name == "plan_contacts") config.setPlanContacts(v != 0);
             else if (name == "plan_clearance") config.setPlanClearance(v != 0);
             else if (name == "plan_clearance_margin") config.setPlanClearanceMargin(v);
+            else if (name == "keepout_margin") config.setKeepoutMargin(v);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -207,7 +219,9 @@ int main(int argc, char** argv) {
                 for (size_t k = 0; k < e.legs.size(); k++)
                     std::printf("%s{\"feasible\": %s, \"g\": %.17g, \"collision_penalty\": %.17g}", k ? ", " : "", e.legs[k].feasible ? "true" : "false", e.legs[k].g,
                                 e.legs[k].collisionPenalty);
-                std::printf("]%s%s}", config.planContacts() ? contactKeys(e.contacts).c_str() : "", config.planClearance() ? clearanceKeys(e.clearance).c_str() : "");
+                std::printf("]%s%s", config.planContacts() ? contactKeys(e.contacts).c_str() : "", config.planClearance() ? clearanceKeys(e.clearance).c_str() : "");
+                if (config.keepoutMargin() != 0) std::printf("%s", keepoutKeys(e.keepout).c_str());
+                std::printf("}");
             }
             std::printf("]}\n");
             return 0;
@@ -423,6 +437,7 @@ int main(int argc, char** argv) {
                 std::fclose(f);
             }
         }
+        if (config.keepoutMargin() != 0) tail += keepoutKeys(st.Keepout);      // (only with a margin named: without it the line is what it always was)
         if (config.planTrace()) {
             size_t nSteps = 0;
             for (const auto& seg : st.Trace) nSteps += seg.size();
