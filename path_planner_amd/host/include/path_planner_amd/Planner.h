@@ -422,7 +422,16 @@ private:
     // the reference's search dump (SamplingBasedPlanner.cpp:210-238, Edge.cpp:122-143); no-ops unless the config enables it
     void visualizeVertex(int v, const char* tag, bool expanded);
     void visualizeTrajectory(const Node& child, const Stats::TraceStep* steps = nullptr, int count = 0);
-    void tracePlanSteps(int v);            // Stats::Trace / Stats::Coverage / Stats::Contacts / Stats::Clearance for the plan that ends at node v
+    // Reports about a plan, one route (planner.cpp): Segments = what the device sweeps again (open vertices, one wrapper edge per segment,
+    // the steps its costed edge executed), built from a branch of the tree or from the records of a ppgpu_cost_plans_host call;
+    // sweepSegments = one device call per report asked for -> out.Trace / Coverage / Contacts / Clearance, per segment.  tracePlanSteps: those of
+    // the plan that ends at node v into m_Stats (whatever m_Config has on); evaluationReports: contacts and clearance merged per candidate plan.
+    struct Segments;
+    Segments branchSegments(int v) const;
+    static Segments chainSegments(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+                                  const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed);
+    std::vector<uint32_t> sweepSegments(const Segments& seg, bool trace, bool coverage, bool contacts, bool clearance, Stats& out);
+    void tracePlanSteps(int v);
     void evaluationReports(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
                             const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
                             std::vector<PlanEvaluation>& out);

@@ -351,6 +351,18 @@ static ppgpu_vertex makeVertex(const GpuAStarPlanner::Node& n) {
     return v;
 }
 
+// The vertex a costed record leaves: what makeVertex makes of the node fillChild fills from it.  Its ribbons are the first ribbon_count
+// rows of the record's child slot.
+static ppgpu_vertex makeVertex(const ppgpu_edge_result& r) {
+    ppgpu_vertex v;
+    v.x = r.end_x; v.y = r.end_y; v.heading = r.end_heading; v.speed = r.end_speed; v.time = r.end_time;
+    v.g = r.g;
+    v.coverage_completed_time = r.coverage_completed_time;
+    v.ribbon_offset = 0;
+    v.ribbon_count = std::min(recChildRibbons(r), kRibbonStride);
+    return v;
+}
+
 // The device's open vertices := this node alone, with its own ribbons.
 void GpuAStarPlanner::setOpenVertex(const Node& n) {
     const ppgpu_vertex v = makeVertex(n);
@@ -1143,89 +1155,133 @@ static_assert(Planner::Stats::ClearanceReport::Empty == PPGPU_CL_EMPTY && Planne
               Planner::Stats::ClearanceReport::Capped == PPGPU_CL_CAPPED && Planner::Stats::ClearanceReport::NoMap == PPGPU_CL_NO_MAP,
               "Stats::ClearanceReport's flags are PPGPU_CL_*");
 
-// PlannerConfig::planTrace / planCoverage / planContacts / planClearance: the returned plan's segments swept once more, step by step, in one device call each —
-// segment s from its parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along the node's own curve.
-static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
-void GpuAStarPlanner::tracePlanSteps(int v) {
-    m_Stats.Trace.clear();
-    m_Stats.Coverage.clear();
-    m_Stats.Contacts.clear();
-    m_Stats.PlanContacts.clear();
-    m_Stats.Clearance.clear();
-    m_Stats.PlanClearance = Stats::ClearanceReport();
-    const std::vector<int> nodes = branch(v);
-    const size_t n = nodes.size();
-    if (n == 0) return;
-    std::vector<int> parents(n);
-    std::vector<ppgpu_wrapper_edge> wedges(n);
-    int most = 1;
-    for (size_t s = 0; s < n; s++) {
-        const Node& c = m_Nodes[nodes[s]];
-        parents[s] = c.parent;
-        wedges[s] = wrapperEdge(c.wrapper, (int32_t)s, c.coverageAllowed);
-        most = std::max(most, c.steps);
-    }
+// PlannerConfig::planTrace / planCoverage / planContacts / planClearance: segments swept once more, step by step, in one device call per
+// report.  What is swept: open vertices with their ribbon pool, one wrapper edge per segment from its vertex, the steps each segment's
+// costed edge executed (every trace must reproduce them), and what a message calls each segment when one does not.
+struct GpuAStarPlanner::Segments {
     std::vector<ppgpu_vertex> verts;
     std::vector<double> pool;
-    packVertices(parents, verts, pool);
-    ppgpu_ctx* h = m_Ctx->handle();
-    check(ppgpu_set_vertices(h, (int32_t)n, verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
-    std::vector<int32_t> counts(n, 0);
-    const auto sameCounts = [&](const char* what) {
-        for (size_t s = 0; s < n; s++)
-            if (counts[s] != m_Nodes[nodes[s]].steps)
-                throw std::runtime_error(std::string(what) + ": segment " + std::to_string(s) + " traced " + std::to_string(counts[s]) + " steps, its edge executed " +
-                                         std::to_string(m_Nodes[nodes[s]].steps));
-    };
-    if (m_Config.planTrace()) {
-        std::vector<Stats::TraceStep> steps(n * (size_t)most);
-        check(ppgpu_trace_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), reinterpret_cast<ppgpu_step_record*>(steps.data())),
-              "ppgpu_trace_wrapper_edges_host");
-        sameCounts("plan trace");
-        m_Stats.Trace.resize(n);
-        for (size_t s = 0; s < n; s++)
-            m_Stats.Trace[s].assign(steps.begin() + (long)(s * (size_t)most), steps.begin() + (long)(s * (size_t)most) + counts[s]);
+    std::vector<ppgpu_wrapper_edge> edges;
+    std::vector<int> steps;
+    std::vector<std::string> names;
+};
+
+// The plan that ends at node v: segment s from its parent vertex (state, g, ribbons, coverageCompletedTime as the search left them) along
+// the node's own curve.
+GpuAStarPlanner::Segments GpuAStarPlanner::branchSegments(int v) const {
+    Segments seg;
+    std::vector<int> parents;
+    for (int node : branch(v)) {
+        const Node& c = m_Nodes[node];
+        seg.names.push_back("segment " + std::to_string(parents.size()));
+        seg.edges.push_back(wrapperEdge(c.wrapper, (int32_t)parents.size(), c.coverageAllowed));
+        seg.steps.push_back(c.steps);
+        parents.push_back(c.parent);
     }
-    if (m_Config.planCoverage()) {
-        std::vector<ppgpu_cover_record> cover(n * (size_t)most);
-        std::vector<ppgpu_cover_summary> summaries(n);
-        check(ppgpu_trace_cover_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, most, counts.data(), cover.data(), summaries.data(), nullptr, 0),
-              "ppgpu_trace_cover_wrapper_edges_host");
-        sameCounts("plan coverage");
-        m_Stats.Coverage.resize(n);
-        const double timeIncrement = m_Config.collisionCheckingIncrement() / m_Config.maxSpeed();
-        for (size_t s = 0; s < n; s++) {
-            double t = verts[s].time;
-            t += std::fmod(t - m_StartStateTime, timeIncrement);                                  // Edge.cpp:116-120
-            for (int k = 0; k < counts[s]; k++, t += timeIncrement) {                              // :173
-                const ppgpu_cover_record& c = cover[s * (size_t)most + (size_t)k];
-                m_Stats.Coverage[s].push_back(Stats::CoverStep{t, c.to_cover, c.remaining, c.flags, c.step, c.ribbons});
+    packVertices(parents, seg.verts, seg.pool);
+    return seg;
+}
+
+// The costed legs of a ppgpu_cost_plans_host call, plan after plan: every plan's first leg from the root (vertex 0), leg k > 0 from the
+// vertex leg k - 1 left (its record and child list).
+GpuAStarPlanner::Segments GpuAStarPlanner::chainSegments(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
+                                                         const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child,
+                                                         const std::vector<int32_t>& costed) {
+    Segments seg;
+    seg.verts.push_back(makeVertex(root));
+    ribbonsToArray(root.ribbons, seg.pool);
+    for (size_t i = 0; i < costed.size(); i++) {
+        for (int k = 0; k < costed[i]; k++) {
+            const size_t at = (size_t)offsets[i] + (size_t)k;
+            ppgpu_wrapper_edge we = legs[at];
+            we.vertex = 0;
+            if (k > 0) {
+                ppgpu_vertex v = makeVertex(res[at - 1]);
+                v.ribbon_offset = (int32_t)(seg.pool.size() / 4);
+                const double* rows = child.data() + (at - 1) * (size_t)kRibbonStride * 4;
+                seg.pool.insert(seg.pool.end(), rows, rows + 4 * (size_t)v.ribbon_count);
+                we.vertex = (int32_t)seg.verts.size();
+                seg.verts.push_back(v);
             }
+            seg.names.push_back("leg " + std::to_string(k) + " of plan " + std::to_string(i));
+            seg.edges.push_back(we);
+            seg.steps.push_back(recThrows(res[at]) ? 0 : recSteps(res[at]));
         }
     }
-    if (m_Config.planContacts()) {
-        std::vector<uint32_t> ids;
+    return seg;
+}
+
+// The one route from segments to their reports, per segment in out.Trace / Coverage / Contacts / Clearance (one not asked for stays empty):
+// the segments' vertices become the handle's open vertices (and stay), then one device call per report asked for, in this order, each
+// checked to have traced the steps the costed edges executed.  -> with `contacts`, the MMSI of contact j (also when there is no segment)
+static_assert(sizeof(Planner::Stats::TraceStep) == sizeof(ppgpu_step_record), "Stats::TraceStep mirrors ppgpu_step_record");
+std::vector<uint32_t> GpuAStarPlanner::sweepSegments(const Segments& seg, bool trace, bool coverage, bool contacts, bool clearance, Stats& out) {
+    out.Trace.clear(); out.Coverage.clear(); out.Contacts.clear(); out.Clearance.clear();
+    std::vector<uint32_t> ids;
+    ppgpu_ctx* h = m_Ctx->handle();
+    if (contacts) {
         m_Config.obstaclesManager().deviceIds(ids);                                               // row j of the snapshot uploadSnapshot made
         int32_t rows = 0;
         check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
         if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
-        std::vector<ppgpu_contact_record> recs(n * ids.size());
-        check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
-              "ppgpu_trace_contacts_wrapper_edges_host");
-        sameCounts("plan contacts");
-        m_Stats.Contacts.resize(n);
+    }
+    const size_t n = seg.edges.size(), nc = ids.size();
+    if (n == 0) return ids;
+    const size_t most = (size_t)std::max(1, *std::max_element(seg.steps.begin(), seg.steps.end()));
+    check(ppgpu_set_vertices(h, (int32_t)seg.verts.size(), seg.verts.data(), (int32_t)(seg.pool.size() / 4), seg.pool.empty() ? nullptr : seg.pool.data()),
+          "ppgpu_set_vertices");
+    std::vector<int32_t> counts(n, 0);
+    const auto traced = [&](int rc, const char* call, const char* what) {
+        check(rc, call);
+        for (size_t w = 0; w < n; w++)
+            if (counts[w] != seg.steps[w])
+                throw std::runtime_error(std::string(what) + ": " + seg.names[w] + " traced " + std::to_string(counts[w]) + " steps, its edge executed " +
+                                         std::to_string(seg.steps[w]));
+    };
+    if (trace) {
+        std::vector<Stats::TraceStep> steps(n * most);
+        traced(ppgpu_trace_wrapper_edges_host(h, (int64_t)n, seg.edges.data(), nullptr, (int32_t)most, counts.data(), reinterpret_cast<ppgpu_step_record*>(steps.data())),
+               "ppgpu_trace_wrapper_edges_host", "plan trace");
+        for (size_t s = 0; s < n; s++) out.Trace.emplace_back(steps.begin() + (long)(s * most), steps.begin() + (long)(s * most) + counts[s]);
+    }
+    if (coverage) {
+        std::vector<ppgpu_cover_record> cover(n * most);
+        std::vector<ppgpu_cover_summary> summaries(n);
+        traced(ppgpu_trace_cover_wrapper_edges_host(h, (int64_t)n, seg.edges.data(), nullptr, (int32_t)most, counts.data(), cover.data(), summaries.data(), nullptr, 0),
+               "ppgpu_trace_cover_wrapper_edges_host", "plan coverage");
+        out.Coverage.resize(n);
+        const double timeIncrement = m_Config.collisionCheckingIncrement() / m_Config.maxSpeed();
+        for (size_t s = 0; s < n; s++) {
+            double t = seg.verts[(size_t)seg.edges[s].vertex].time;
+            t += std::fmod(t - m_StartStateTime, timeIncrement);                                  // Edge.cpp:116-120
+            for (int k = 0; k < counts[s]; k++, t += timeIncrement) {                              // :173
+                const ppgpu_cover_record& c = cover[s * most + (size_t)k];
+                out.Coverage[s].push_back(Stats::CoverStep{t, c.to_cover, c.remaining, c.flags, c.step, c.ribbons});
+            }
+        }
+    }
+    if (contacts) {
+        std::vector<ppgpu_contact_record> recs(n * nc);
+        traced(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, seg.edges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
+               "ppgpu_trace_contacts_wrapper_edges_host", "plan contacts");
+        out.Contacts.resize(n);
         for (size_t s = 0; s < n; s++)
-            for (size_t j = 0; j < ids.size(); j++) m_Stats.Contacts[s].push_back(contactOf(ids[j], recs[s * ids.size() + j]));
-        m_Stats.PlanContacts = Stats::mergeContacts(m_Stats.Contacts);
+            for (size_t j = 0; j < nc; j++) out.Contacts[s].push_back(contactOf(ids[j], recs[s * nc + j]));
     }
-    if (m_Config.planClearance()) {
+    if (clearance) {
         std::vector<ppgpu_clearance_record> recs(n);
-        check(ppgpu_trace_clearance_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.data(), m_Config.planClearanceMargin()),
-              "ppgpu_trace_clearance_wrapper_edges_host");
-        sameCounts("plan clearance");
-        for (size_t s = 0; s < n; s++) m_Stats.Clearance.push_back(clearanceOf(recs[s]));
-        m_Stats.PlanClearance = Stats::mergeClearance(m_Stats.Clearance);
+        traced(ppgpu_trace_clearance_wrapper_edges_host(h, (int64_t)n, seg.edges.data(), nullptr, counts.data(), recs.data(), m_Config.planClearanceMargin()),
+               "ppgpu_trace_clearance_wrapper_edges_host", "plan clearance");
+        for (size_t s = 0; s < n; s++) out.Clearance.push_back(clearanceOf(recs[s]));
     }
+    return ids;
+}
+
+// Stats::Trace / Coverage / Contacts / Clearance and the two merged reports of the plan that ends at node v, whichever m_Config has on.
+void GpuAStarPlanner::tracePlanSteps(int v) {
+    sweepSegments(branchSegments(v), m_Config.planTrace(), m_Config.planCoverage(), m_Config.planContacts(), m_Config.planClearance(), m_Stats);
+    m_Stats.PlanContacts = Stats::mergeContacts(m_Stats.Contacts);
+    m_Stats.PlanClearance = Stats::mergeClearance(m_Stats.Clearance);
 }
 
 // ------------------------------------------------------------------------------------------------ the start of a call
@@ -1329,89 +1385,28 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
 }
 
 // PlanEvaluation::contacts / clearance: every costed leg of every plan swept once more from the vertex the leg before it left (the root
-// for a plan's first leg; state, g, ribbons and coverageCompletedTime from that leg's record and child list), all in one contact-trace
-// call and one clearance-trace call, whichever of the two switches are on.
+// for a plan's first leg; state, g, ribbons and coverageCompletedTime from that leg's record and child list: chainSegments), all in one
+// contact-trace call and one clearance-trace call, whichever of the two switches are on (sweepSegments), then merged plan by plan.
 void GpuAStarPlanner::evaluationReports(const Node& root, const std::vector<int32_t>& offsets, const std::vector<ppgpu_wrapper_edge>& legs,
                                          const std::vector<ppgpu_edge_result>& res, const std::vector<double>& child, const std::vector<int32_t>& costed,
                                          std::vector<PlanEvaluation>& out) {
-    const bool contacts = m_Config.planContacts(), clearance = m_Config.planClearance();
-    std::vector<uint32_t> ids;
-    ppgpu_ctx* h = m_Ctx->handle();
-    if (contacts) {
-        m_Config.obstaclesManager().deviceIds(ids);
-        int32_t rows = 0;
-        check(ppgpu_obstacle_count(h, &rows, nullptr), "ppgpu_obstacle_count");
-        if ((size_t)rows != ids.size()) throw std::runtime_error("plan contacts: the device holds " + std::to_string(rows) + " contacts, the manager names " + std::to_string(ids.size()));
-    }
-    std::vector<ppgpu_vertex> verts{makeVertex(root)};
-    std::vector<double> pool;
-    ribbonsToArray(root.ribbons, pool);
-    std::vector<ppgpu_wrapper_edge> wedges;
-    std::vector<int> steps;
-    for (size_t i = 0; i < out.size(); i++) {
-        for (int k = 0; k < costed[i]; k++) {
-            const size_t at = (size_t)offsets[i] + (size_t)k;
-            ppgpu_wrapper_edge we = legs[at];
-            we.vertex = 0;
-            if (k > 0) {
-                const ppgpu_edge_result& r = res[at - 1];
-                ppgpu_vertex v;
-                v.x = r.end_x; v.y = r.end_y; v.heading = r.end_heading; v.speed = r.end_speed; v.time = r.end_time;
-                v.g = r.g;
-                v.coverage_completed_time = r.coverage_completed_time;
-                v.ribbon_offset = (int32_t)(pool.size() / 4);
-                v.ribbon_count = std::min(recChildRibbons(r), kRibbonStride);
-                const double* rows4 = child.data() + (at - 1) * (size_t)kRibbonStride * 4;
-                pool.insert(pool.end(), rows4, rows4 + 4 * (size_t)v.ribbon_count);
-                we.vertex = (int32_t)verts.size();
-                verts.push_back(v);
-            }
-            wedges.push_back(we);
-            steps.push_back(recThrows(res[at]) ? 0 : recSteps(res[at]));
-        }
-    }
-    const size_t n = wedges.size();
-    if (n == 0) {           // (clearance: the default report is the empty one)
-        for (PlanEvaluation& e : out) { e.contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) e.contacts[j].mmsi = ids[j]; }
-        return;
-    }
-    check(ppgpu_set_vertices(h, (int32_t)verts.size(), verts.data(), (int32_t)(pool.size() / 4), pool.empty() ? nullptr : pool.data()), "ppgpu_set_vertices");
-    std::vector<int32_t> counts(n, 0);
-    const auto sameCounts = [&](const char* what) {
-        size_t w = 0;
-        for (size_t i = 0; i < out.size(); i++)
-            for (int k = 0; k < costed[i]; k++, w++)
-                if (counts[w] != steps[w])
-                    throw std::runtime_error(std::string(what) + ": leg " + std::to_string(k) + " of plan " + std::to_string(i) + " traced " + std::to_string(counts[w]) +
-                                             " steps, its edge executed " + std::to_string(steps[w]));
+    const Segments seg = chainSegments(root, offsets, legs, res, child, costed);
+    Stats r;
+    const std::vector<uint32_t> ids = sweepSegments(seg, false, false, m_Config.planContacts(), m_Config.planClearance(), r);
+    // plan i's legs are segments w ..; of a report that was not made it has none, and the merge of no leg is the empty report
+    size_t w = 0;
+    const auto legsOf = [&](const auto& all, size_t count) {
+        return all.empty() ? all : std::decay_t<decltype(all)>(all.begin() + (long)w, all.begin() + (long)(w + count));
     };
-    if (contacts) {
-        std::vector<ppgpu_contact_record> recs(n * ids.size());
-        check(ppgpu_trace_contacts_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.empty() ? nullptr : recs.data()),
-              "ppgpu_trace_contacts_wrapper_edges_host");
-        sameCounts("plan contacts");
-        size_t w = 0;
-        for (size_t i = 0; i < out.size(); i++) {
-            std::vector<std::vector<Stats::Contact>> segs((size_t)costed[i]);
-            for (int k = 0; k < costed[i]; k++, w++)
-                for (size_t j = 0; j < ids.size(); j++) segs[(size_t)k].push_back(contactOf(ids[j], recs[w * ids.size() + j]));
-            out[i].contacts = Stats::mergeContacts(segs);
-            if (out[i].contacts.empty()) { out[i].contacts.resize(ids.size()); for (size_t j = 0; j < ids.size(); j++) out[i].contacts[j].mmsi = ids[j]; }
+    for (size_t i = 0; i < out.size(); w += (size_t)costed[i], i++) {
+        out[i].contacts = Stats::mergeContacts(legsOf(r.Contacts, costed[i]));
+        if (out[i].contacts.empty()) {      // a plan with no costed leg still names every contact
+            out[i].contacts.resize(ids.size());
+            for (size_t j = 0; j < ids.size(); j++) out[i].contacts[j].mmsi = ids[j];
         }
+        out[i].clearance = Stats::mergeClearance(legsOf(r.Clearance, costed[i]));
     }
-    if (clearance) {
-        std::vector<ppgpu_clearance_record> recs(n);
-        check(ppgpu_trace_clearance_wrapper_edges_host(h, (int64_t)n, wedges.data(), nullptr, counts.data(), recs.data(), m_Config.planClearanceMargin()),
-              "ppgpu_trace_clearance_wrapper_edges_host");
-        sameCounts("plan clearance");
-        size_t w = 0;
-        for (size_t i = 0; i < out.size(); i++) {
-            std::vector<Stats::ClearanceReport> segs;
-            for (int k = 0; k < costed[i]; k++, w++) segs.push_back(clearanceOf(recs[w]));
-            out[i].clearance = Stats::mergeClearance(segs);
-        }
-    }
-    setOpenVertex(root);      // (the handle's open vertices are the call's again)
+    if (!seg.edges.empty()) setOpenVertex(root);      // (the handle's open vertices are the call's again)
 }
 
 // ------------------------------------------------------------------------------------------------ plan(), step by step
@@ -1726,10 +1721,11 @@ ShardedIteration::Result ShardedIteration::run(const RibbonManager& ribbonManage
     samplingBox(config, start, bounds);
     std::vector<double> rib;
     ribbonsToArray(rm, rib);
-    ppgpu_vertex root{};
-    root.x = start.x(); root.y = start.y(); root.heading = start.heading(); root.speed = config.maxSpeed(); root.time = start.time();
-    root.g = 0; root.coverage_completed_time = rm.done() ? start.time() : rm.coverageCompletedTime();
-    root.ribbon_offset = 0; root.ribbon_count = (int32_t)rm.count();
+    GpuAStarPlanner::Node rootNode;                                        // (the root GpuAStarPlanner::beginCall makes)
+    rootNode.state = start; rootNode.state.speed() = config.maxSpeed(); rootNode.g = 0;
+    rootNode.ribbons = rm;
+    if (rm.done()) rootNode.ribbons.setCoverageCompletedTime(start.time());
+    const ppgpu_vertex root = makeVertex(rootNode);
     // contiguous slices of the batch, sizes differing by at most one (path_planner_amd/sharding.py: shard_attempts)
     const int64_t base = attempts / (int64_t)D, extra = attempts % (int64_t)D;
     const int64_t edgesPerShard = 4 * (base + (extra ? 1 : 0));            // global edge ids: shard * edgesPerShard + local index

@@ -65,6 +65,17 @@ static std::string keepoutKeys(const Planner::Stats::KeepoutReport& k) {
     return buf;
 }
 
+// One report file: rows(f, s) prints the lines of segment s.  No path, no file; -> false (and the complaint) when it cannot be written.
+template <class Rows>
+static bool writeReport(const std::string& path, size_t segments, Rows rows) {
+    if (path.empty()) return true;
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return false; }
+    for (size_t sg = 0; sg < segments; sg++) rows(f, sg);
+    std::fclose(f);
+    return true;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: plan_cli scenario.txt\n"); return 2; }
     std::ifstream in(argv[1]);
@@ -404,52 +415,35 @@ int main(int argc, char** argv) {
             char buf[64];
             std::snprintf(buf, sizeof buf, ", \"plan_coverage_steps\": %zu", nSteps);
             tail += buf;
-            if (!planCoveragePath.empty()) {
-                FILE* f = std::fopen(planCoveragePath.c_str(), "w");
-                if (!f) { std::fprintf(stderr, "cannot write %s\n", planCoveragePath.c_str()); return 2; }
-                for (size_t sg = 0; sg < st.Coverage.size(); sg++)
+            if (!writeReport(planCoveragePath, st.Coverage.size(), [&](FILE* f, size_t sg) {
                     for (const auto& c : st.Coverage[sg])
                         std::fprintf(f, "%zu %u %.17g %.17g %.17g %u %u\n", sg, c.step, c.time, c.toCover, c.remaining, c.ribbons, c.flags);
-                std::fclose(f);
-            }
+                })) return 2;
         }
         if (config.planContacts()) {              // (only with the switch on: without it the line is what it always was)
             tail += contactKeys(st.PlanContacts);
-            if (!planContactsPath.empty()) {
-                FILE* f = std::fopen(planContactsPath.c_str(), "w");
-                if (!f) { std::fprintf(stderr, "cannot write %s\n", planContactsPath.c_str()); return 2; }
-                for (size_t sg = 0; sg < st.Contacts.size(); sg++)
+            if (!writeReport(planContactsPath, st.Contacts.size(), [&](FILE* f, size_t sg) {
                     for (const auto& c : st.Contacts[sg])
                         std::fprintf(f, "%zu %u %d %.17g %.17g %.17g %.17g %.17g %.17g\n", sg, c.mmsi, c.hitSteps, c.firstHitTime, c.lastHitTime, c.cpaDistance, c.cpaTime,
                                      c.exposure, c.peak);
-                std::fclose(f);
-            }
+                })) return 2;
         }
         if (config.planClearance()) {             // (only with the switch on: without it the line is what it always was)
             tail += clearanceKeys(st.PlanClearance);
-            if (!planClearancePath.empty()) {
-                FILE* f = std::fopen(planClearancePath.c_str(), "w");
-                if (!f) { std::fprintf(stderr, "cannot write %s\n", planClearancePath.c_str()); return 2; }
-                for (size_t sg = 0; sg < st.Clearance.size(); sg++) {
+            if (!writeReport(planClearancePath, st.Clearance.size(), [&](FILE* f, size_t sg) {
                     const auto& c = st.Clearance[sg];
                     std::fprintf(f, "%zu %.17g %.17g %.17g %.17g %d %u %d %.17g %u\n", sg, c.clearance, c.time, c.x, c.y, c.step, c.gap2, c.belowSteps, c.firstBelowTime, c.flags);
-                }
-                std::fclose(f);
-            }
+                })) return 2;
         }
         if (config.keepoutMargin() != 0) tail += keepoutKeys(st.Keepout);      // (only with a margin named: without it the line is what it always was)
         if (config.planTrace()) {
             size_t nSteps = 0;
             for (const auto& seg : st.Trace) nSteps += seg.size();
             std::printf("], \"plan_trace_segments\": %zu, \"plan_trace_steps\": %zu%s}\n", st.Trace.size(), nSteps, tail.c_str());
-            if (!planTracePath.empty()) {
-                FILE* f = std::fopen(planTracePath.c_str(), "w");
-                if (!f) { std::fprintf(stderr, "cannot write %s\n", planTracePath.c_str()); return 2; }
-                for (size_t sg = 0; sg < st.Trace.size(); sg++)
+            if (!writeReport(planTracePath, st.Trace.size(), [&](FILE* f, size_t sg) {
                     for (const auto& t : st.Trace[sg])
                         std::fprintf(f, "%zu %u %.17g %.17g %.17g %.17g %.17g %.17g %u\n", sg, t.step, t.x, t.y, t.heading, t.time, t.collision, t.penaltyBefore, t.flags);
-                std::fclose(f);
-            }
+                })) return 2;
         } else {
             std::printf("]%s}\n", tail.c_str());
         }
