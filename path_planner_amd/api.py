@@ -10,7 +10,7 @@ import numpy as np
 from .types import PpgpuConfig, RESULT_DTYPE, VERTEX_DTYPE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("PPGPU_LIB_OVERRIDE") or os.path.join(_HERE, "csrc", "libppgpu.so")   # override: tools/ablate.py only
+LIB_PATH = os.environ.get("PPGPU_LIB_OVERRIDE") or os.path.join(_HERE, "csrc", "libppgpu.so")   # override: the A/B tools (tools/ab_libs.sh, tools/records_hash.py, tools/kernel_times.py)
 
 
 class PpgpuError(RuntimeError):

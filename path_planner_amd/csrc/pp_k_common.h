@@ -1,5 +1,5 @@
 // pp_k_common.h — what every costing kernel shares: the launch parameters (PPParams), the per-edge setup record, the clearance map
-// and time-grid kernels, edge decoding, the work queues of the resident grids.  Included by pp_kernels.h.
+// and time-grid kernels, edge decoding, the work queues of the cover sweep.  Included by pp_kernels.h.
 #pragma once
 #include "../../include/ppgpu.h"
 #include "pp_device.h"
@@ -46,7 +46,7 @@ struct PPParams {
     struct PPTrackSummary* track_summary;
     unsigned char* track_skip;           // [edge][nch]  1: the pose sweep skips this 64-step chunk (pp_k_plan_skips); NULL: no skipping
     int2* track_far;                     // [edge] {first event the cover sweep's wave has to visit, last event before it} (pp_k_approach_events)
-    unsigned long long* work;            // work-queue heads of the per-edge kernels (PP_Q_*), zeroed by pp_k_solve_edges
+    unsigned long long* work;            // the cover sweep's work-queue heads (pp_next_edge), zeroed by pp_k_solve_edges
     unsigned* live_list; unsigned* live_count;     // {workspace slot, list position} of the edges the cover sweep still has to visit (pp_k_approach_events)
     unsigned* defer_list; unsigned* defer_count;   // edges whose heuristic the cover sweep left to pp_k_heuristic_lanes
     unsigned* need_big;                  // set by the cover sweep when some child has 9..12 ribbons (pp_k_heuristic_big then has work)
@@ -227,64 +227,47 @@ __device__ __forceinline__ void pp_edge_decode(const PPParams& p, long long e, u
 // (Rounds 1-2 also worked out, per edge, the curve parameter beyond which the curve stays clear of every ribbon of its source vertex, so
 // that the event walkers could stop there: pp_curve_clear_after, commit c2b5b03.  Round 3 measured it again — 38 us of the solve kernel
 // for events the approach lane walks at ~60 instructions each — and switched it off; round 4 removed it.)
-// A per-edge kernel can be launched as a resident grid whose waves pull edges from queues, in launch order, instead of one
-// workgroup per PP_WPB edges.  Edges differ in length by two orders of magnitude (blocked at the first step ... the full
+// The edge of this wave in a kernel launched with one wave per edge (the pose sweep, the heuristic kernels, the traces): its
+// position in the slice, for the caller to hold against p.n_edges.  wave = the wave's number in its workgroup of WPB waves.
+template <int WPB>
+__device__ __forceinline__ long long pp_wave_edge(int& wave) {
+    wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return (long long)blockIdx.x * WPB + wave;
+}
+// The cover sweep is launched as a resident grid whose waves pull edges from queues, in launch order, instead of one workgroup
+// per PP_WPB edges.  Edges differ in length by two orders of magnitude (blocked at the first step ... the full
 // horizon); the cover sweep runs 4 waves per SIMD (128 VGPRs) and with dispatcher-placed workgroups the counters show 3.15 of
 // those 4 slots occupied on average - a wave that takes its next edge itself leaves none empty (cover sweep: -9 %).  The pose
 // sweep (6 waves per SIMD, VALU 97 % busy either way) and the heuristic (3 us of work per edge, about the latency of the
-// atomic) measure 4 % and 8 % SLOWER that way and keep the plain launch (tools/ablate.py q0 / q2 / q7).
+// atomic) measured 4 % and 8 % SLOWER that way and are launched with one wave per edge (pp_wave_edge); the queue-fed form of
+// both is in commit cb7806b.
 // One queue head would serialise: a device-scope atomic on one address completes every ~12.5 ns on this part (measured: 236 140
 // of them stretch any kernel to 3 ms), so the edges are dealt round-robin onto PP_NQ queues whose heads sit in different memory
 // channels; a workgroup works on queue (blockIdx mod PP_NQ) and, when that is empty, on the next ones (a plain look first: an
 // exhausted queue stays exhausted).
-#define PP_Q_POSE 0
-#define PP_Q_COVER 1
-#define PP_Q_HEUR 2
-#define PP_Q_BIG 3
 #define PP_NQ 32
 #define PP_QSTRIDE 544               // unsigned long longs between queue heads: 4 KiB + 256 B
-#define PP_WORK_WORDS (4 * PP_NQ * PP_QSTRIDE)
-#ifndef PP_QUEUE_MASK
-#define PP_QUEUE_MASK 2              // which kernels pull from queues: 1 pose sweep, 2 cover sweep, 4 heuristics (others: one workgroup per PP_WPB edges)
-#endif
-#ifndef PP_Q_CHUNK_COVER
-#define PP_Q_CHUNK_COVER 1           // edges a cover-sweep wave takes per atomic
-#endif
-#ifndef PP_Q_CHUNK_HEUR
-#define PP_Q_CHUNK_HEUR 4            // edges a heuristic wave takes per atomic (its edges are short: see pp_next_edge)
-#endif
-struct PPQueue { int q, dry, left; unsigned long long k; };   // queue drawn from, empty queues seen in a row, rest of the chunk in hand
+#define PP_WORK_WORDS (PP_NQ * PP_QSTRIDE)
+struct PPQueue { int q, dry; };      // queue drawn from, empty queues seen in a row
 __device__ __forceinline__ PPQueue pp_queue_init() {
-    PPQueue s; s.q = (int)(blockIdx.x % PP_NQ); s.dry = 0; s.left = 0; s.k = 0; return s;
+    PPQueue s; s.q = (int)(blockIdx.x % PP_NQ); s.dry = 0; return s;
 }
-// for (PP_EACH_EDGE(idx, kernel bit, queue, n, chunk)) body;  -- either this wave's one edge, or edges from the queues until they are dry
-#define PP_EACH_EDGE(idx, bit, kern, n, chunk)                                                                              \
-    long long idx = ((PP_QUEUE_MASK) & (bit)) ? pp_next_edge<chunk>(p, kern, qs, n)                                         \
-                                              : (long long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
-    idx < (n);                                                                                                              \
-    idx = ((PP_QUEUE_MASK) & (bit)) ? pp_next_edge<chunk>(p, kern, qs, n) : (n)
-// next edge of kernel `kern` for this wave, or n when every queue is empty (every wave gets there: the grid always drains).
-// Queue q holds the edges q, q + NQ, q + 2 NQ, ...; one atomic takes CHUNK consecutive ones of them.
-template <int CHUNK>
-__device__ __forceinline__ long long pp_next_edge(const PPParams& p, int kern, PPQueue& s, long long n) {
-    if (CHUNK > 1 && s.left > 0) {
-        const long long idx = (long long)(s.k * PP_NQ) + __builtin_amdgcn_readfirstlane(s.q);
-        if (idx < n) { s.left--; s.k++; return idx; }
-        s.left = 0;
-    }
+// next edge for this wave, or n when every queue is empty (every wave gets there: the grid always drains).
+// Queue q holds the edges q, q + NQ, q + 2 NQ, ...; one atomic takes one of them.
+__device__ __forceinline__ long long pp_next_edge(const PPParams& p, PPQueue& s, long long n) {
     while (s.dry < PP_NQ) {
-        unsigned long long* head = p.work + (size_t)(kern * PP_NQ + s.q) * PP_QSTRIDE;
+        unsigned long long* head = p.work + (size_t)s.q * PP_QSTRIDE;
         unsigned long long k = 0;
         if (pp_lane() == 0) {
             k = (s.dry > 0) ? __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;   // someone else's queue: look first
-            if ((long long)(k * PP_NQ) + s.q < n) k = atomicAdd(head, (unsigned long long)CHUNK);
+            if ((long long)(k * PP_NQ) + s.q < n) k = atomicAdd(head, 1ull);
         }
         const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)k);
         const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(k >> 32));
         const int q = __builtin_amdgcn_readfirstlane(s.q);
         const unsigned long long kk = ((unsigned long long)hi << 32) | lo;
         const long long idx = (long long)(kk * PP_NQ) + q;
-        if (idx < n) { s.dry = 0; s.left = CHUNK - 1; s.k = kk + 1; return idx; }
+        if (idx < n) { s.dry = 0; return idx; }
         s.q = (s.q + 1 == PP_NQ) ? 0 : s.q + 1;
         s.dry++;
     }

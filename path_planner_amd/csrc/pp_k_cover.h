@@ -261,9 +261,6 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
 }
 
 // e = the edge's slot in the workspace, eg = its position in the caller's edge list, lds = 256 doubles private to the wave
-#ifndef PP_LANE_HEUR
-#define PP_LANE_HEUR 1   // untouched ribbon lists: heuristic by pp_k_heuristic_lanes
-#endif
 #ifndef PP_FUSE_HEUR
 #define PP_FUSE_HEUR 1
 #endif
@@ -780,7 +777,7 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
 // The wave that finished an edge's cover sweep goes straight on to the edge's heuristic (point heuristics, binary-obstacle
 // sweep; the Dubins heuristics and the 12-ribbon pass keep their own kernels): the child ribbons and the record it needs were
 // just written by the same wave, there is no second launch, and the two phases' stalls fall at different times in the four
-// waves of a SIMD.  Cover sweep + heuristic 2.26 -> 2.18 ms (tools/ablate.py fuse0).
+// waves of a SIMD.  Cover sweep + heuristic 2.26 -> 2.18 ms (against -DPP_FUSE_HEUR=0).
 #define PP_COVER_LDS ((PP_FUSE_HEUR) ? (PPTsp<PP_TSP_MAX>::LDS > PP_WAVE * 4 ? PPTsp<PP_TSP_MAX>::LDS : PP_WAVE * 4) : PP_WAVE * 4)
 // lds_all = the workgroup's scratch, [PP_WPB][LDS] doubles: a row per wave
 template <bool GAUSSIAN, int LDS>
@@ -788,7 +785,7 @@ __device__ __forceinline__ void pp_cover_sweep_waves(PPParams p, double (*lds_al
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     PPQueue qs = pp_queue_init();
     const long long n = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_count)[0] : p.n_edges;
-    for (PP_EACH_EDGE(i, 2, PP_Q_COVER, n, PP_Q_CHUNK_COVER)) {
+    for (long long i = pp_next_edge(p, qs, n); i < n; i = pp_next_edge(p, qs, n)) {
         const long long idx = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[0] : i;
         const long long eg = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[1] : pp_edge_position(p, p.e_base + idx);
         pp_cover_sweep_edge<GAUSSIAN>(p, p.ws_base + idx, eg, lds_all[wave]);

@@ -112,17 +112,15 @@ __device__ __forceinline__ void pp_heuristic_edge(const PPParams& p, const long 
 #endif
 __global__ __launch_bounds__(PP_H_WPB * 64, PP_H_MIN_WAVES) void pp_k_heuristic(PPParams p) {
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    PPQueue qs = pp_queue_init();
-    for (PP_EACH_EDGE(e, 4, PP_Q_HEUR, p.n_edges, PP_Q_CHUNK_HEUR))
-        pp_heuristic_edge<false, PP_TSP_MAX>(p, e, lds_all[wave]);
+    int wave;
+    const long long e = pp_wave_edge<PP_H_WPB>(wave);
+    if (e < p.n_edges) pp_heuristic_edge<false, PP_TSP_MAX>(p, e, lds_all[wave]);
 }
 __global__ __launch_bounds__(PP_H_WPB * 64) void pp_k_heuristic_dubins(PPParams p) {
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    PPQueue qs = pp_queue_init();
-    for (PP_EACH_EDGE(e, 4, PP_Q_HEUR, p.n_edges, PP_Q_CHUNK_HEUR))
-        pp_heuristic_edge<true, PP_TSP_MAX>(p, e, lds_all[wave]);
+    int wave;
+    const long long e = pp_wave_edge<PP_H_WPB>(wave);
+    if (e < p.n_edges) pp_heuristic_edge<true, PP_TSP_MAX>(p, e, lds_all[wave]);
 }
 // TspPointRobotNoSplitKRibbons on child lists of 9..12 ribbons (rare: a vertex whose ribbons were split many times).  A whole
 // WORKGROUP of sixteen wavefronts per such edge (round 4): every wave builds the same tables and takes every sixteenth pass of 64
@@ -170,8 +168,8 @@ __global__ __launch_bounds__(PP_BIG_WPB * 64) void pp_k_heuristic_big(PPParams p
 // The edges pp_k_cover_finish listed (a TSP enumeration of 7 or 8 child ribbons: up to 32 768 leaves): Vertex::computeApproxToGo from
 // the record and the child ribbons, as pp_heuristic_edge does it, by a whole WORKGROUP per edge — its four waves build the
 // same tables, take every fourth pass of 64 prefixes each, and the smallest of their four minima is the minimum (exact).  One wave per
-// edge was ~170 us of a single wave's time for each of config 3's ~1 100 such edges.  A grid as large as pp_k_heuristic keeps
-// resident, striding over the list; usually the list is short or empty.
+// edge was ~170 us of a single wave's time for each of config 3's ~1 100 such edges.  The grid pp_k_heuristic would get
+// (the list's length is on the device), striding over the list; usually the list is short or empty.
 __global__ __launch_bounds__(PP_H_WPB * 64, PP_H_MIN_WAVES) void pp_k_heuristic_listed(PPParams p) {
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
     __shared__ double s_part[PP_H_WPB];

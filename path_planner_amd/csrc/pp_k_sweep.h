@@ -505,17 +505,17 @@ __global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussi
 //
 // The wave is short (some 760 VALU instructions) and spent seven eighths of its life waiting on a chain of dependent loads: record,
 // then vertex and time row, then the obstacle row of the lane, then per sampled chunk the times, the grid words, the obstacle rows
-// and the branch on `stop`.  So the loads are issued in as few rounds as the data dependences allow:
+// and the branch that ends the edge.  So the loads are issued in as few rounds as the data dependences allow:
 //   * at wave start everything whose address follows from the work item alone: the record, the skip bytes, the lane's obstacle row
 //     (the source heading travels in the record: pp_k_solve_edges);
-//   * the loop steps through the set bits of "not skipped" instead of 64 trips with `continue`, G chunks at a time: their times (and
-//     `carry` words) together, their poses, then their grid words together;
-//   * the chunks of a batch are then resolved one after the other with exactly the sequential code: a chunk that stops the sweep
-//     discards the later ones of its batch, which have stored nothing and changed nothing the sweep keeps (dubErr is per chunk).
-// G = 1 is the same walk with one chunk at a time, and what pp_k_pose_sweep is built with: at config 3 a second chunk in flight
-// measured slower.  pp_k_pose_sweep_single is always G = 1 (PPGPU_POSE_CHUNKS=1: a test demands the same bytes
-// from both, whatever PP_POSE_CHUNKS the library was built with).
-template <bool GAUSSIAN, int G>
+//   * the loop steps through the set bits of "not skipped" instead of 64 trips with `continue`, one sampled chunk per trip: its
+//     times (and `carry` word) are asked for at the end of the trip before (next_chunk; the first chunk's before the obstacle lanes
+//     are set up), then its poses, then its grid words;
+//   * the loop is left where the edge ends: the chunk's first step lies at or after the end time, a step is blocked, or the chunk
+//     is cut by the end time.
+// (Two or three sampled chunks in flight per wave measured slower at config 3: registers the kernel does not have at 6 waves per
+// SIMD, and poses a blocked first chunk throws away.  DESIGN.md Appendix B has the figures and the commit that holds that walk.)
+template <bool GAUSSIAN>
 __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long long e) {
     const int lane = pp_lane();
     const PPEdgeSetup* S = p.setup + e;
@@ -587,11 +587,11 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
     int g0 = -PP_WAVE;
     unsigned long long skips = 0ull, todo = 0ull, gclear = 0ull, oclear = 0ull;
     bool lastSkipped = false;                                         // the last chunk of the group before was skipped
-    // the next G chunks to sample: their times and, after a skipped chunk, the planner's `lastHeading`
-    int ci[G];
-    double t[G], carryW[G];
-    bool have[G], after[G];
-    auto next_batch = [&]() {
+    // the next chunk to sample: its times and, after a skipped chunk, the planner's `lastHeading`
+    int ci;
+    double t, carryW;
+    bool after;
+    auto next_chunk = [&]() {
         while (todo == 0ull) {
             lastSkipped = (g0 >= 0) && ((skips >> 63) & 1ull) != 0ull;
             g0 += PP_WAVE;
@@ -601,19 +601,15 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
             oclear = anyObstacle ? __ballot((sbits & PP_SKIP_OBST) != 0u) : ~0ull;   // (no obstacle near the edge: as good as none near any chunk)
             todo = ~skips;                                            // (chunks past the row's end count as sampled: the walk ends at the first of them)
         }
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            have[i] = i == 0 || todo != 0ull;                         // (the first always exists: the walk above ended on a group with chunks to sample)
-            ci[i] = have[i] ? (__ffsll((long long)todo) - 1) : 0;
-            if (have[i]) todo &= todo - 1ull;
-            after[i] = have[i] && (ci[i] > 0 ? (((skips >> (ci[i] - 1)) & 1ull) != 0ull) : lastSkipped);
-            const int k = (g0 + ci[i]) * PP_WAVE + lane;
-            t[i] = (have[i] && k < p.ng) ? tg[k] : INFINITY;
-            carryW[i] = 0.0;
-            if (!cov && after[i] && g0 + ci[i] < p.nch) carryW[i] = pp_const_f64(carry + (g0 + ci[i]))[0];
-        }
+        ci = __ffsll((long long)todo) - 1;                            // (the walk above ended on a group with chunks to sample)
+        todo &= todo - 1ull;
+        after = ci > 0 ? (((skips >> (ci - 1)) & 1ull) != 0ull) : lastSkipped;
+        const int k = (g0 + ci) * PP_WAVE + lane;
+        t = (k < p.ng) ? tg[k] : INFINITY;
+        carryW = 0.0;
+        if (!cov && after && g0 + ci < p.nch) carryW = pp_const_f64(carry + (g0 + ci))[0];
     };
-    next_batch();                                                     // (the first batch's times travel while the obstacle lanes are set up)
+    next_chunk();                                                     // (the first chunk's times travel while the obstacle lanes are set up)
     // The five doubles a lane keeps about its obstacle are read once per sampled chunk, by the culling alone: they wait in LDS, not
     // in ten registers the pose arithmetic in between needs (at 6 waves per SIMD the kernel has 80; kept in registers, one of the
     // five went to scratch and came back from memory in every chunk).  A wave reads only what it wrote itself.
@@ -635,90 +631,85 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
         cullL[0 * PP_WAVE] = oX0; cullL[1 * PP_WAVE] = oY0; cullL[2 * PP_WAVE] = oVx; cullL[3 * PP_WAVE] = oVy; cullL[4 * PP_WAVE] = oR2;
         pp_wave_lds_fence();
     }
-    bool stop = false;
     for (;;) {
-        // ---- their poses; the grid words set off together
-        double tFirst[G], x[G], y[G], heading[G];
-        bool live[G], dubErr[G];
-        PPCellRef cell[G];
-        uint32_t word[G];
-        unsigned long long near[G];
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            tFirst[i] = pp_readlane(t[i], 0);
-            live[i] = have[i] && (tFirst[i] < endTime);               // `while (intermediate.time() < endTime)`
-            dubErr[i] = false;
-            near[i] = 0ull;
-            if (live[i]) {
-                const bool gridClear = ((gclear >> ci[i]) & 1ull) != 0ull, obstClear = ((oclear >> ci[i]) & 1ull) != 0ull;
-                const bool valid = t[i] < endTime;
-                double uth;
-                pp_window_pose(S, hot, cur, cs, t[i], tFirst[i], valid, x[i], y[i], uth, dubErr[i]);
-                // the heading itself (:47) only matters for "unchanged since the last step" (Edge.cpp:159), which only matters
-                // on edges that may not cover while turning
-                heading[i] = cov ? 0.0 : pp_heading_from_yaw(pp_mod2pi(uth));
-                if (!gridClear && p.grid.rows != 0) {                 // Edge.cpp:144 (pp_k_plan_skips may have ruled it out for the whole chunk)
-                    cell[i] = pp_blocked_cell(p.grid, x[i], y[i]);
-                    word[i] = p.grid.bits[cell[i].word];
-                }
-                if (!obstClear && laneCull) {                         // :150-151
-                    // which obstacles can come near this chunk: lane j answers for obstacle j from its registers
-                    const double dtc = tFirst[i] - cullT0;
-                    const double oX0 = cullL[0 * PP_WAVE], oY0 = cullL[1 * PP_WAVE], oVx = cullL[2 * PP_WAVE], oVy = cullL[3 * PP_WAVE], oR2 = cullL[4 * PP_WAVE];
-                    const double ddx = pp_readlane(x[i], 0) - (oX0 + oVx * dtc), ddy = pp_readlane(y[i], 0) - (oY0 + oVy * dtc);
-                    near[i] = __ballot(!(ddx * ddx + ddy * ddy > oR2));      // oR2 = -1 in lanes without an obstacle
-                }
+        // ---- its poses; the grid words set off
+        const double tFirst = pp_readlane(t, 0);
+        const bool live = tFirst < endTime;                           // `while (intermediate.time() < endTime)`
+        double x, y, heading;
+        bool dubErr = false;
+        PPCellRef cell;
+        uint32_t word;
+        unsigned long long near = 0ull;
+        if (live) {
+            const bool gridClear = ((gclear >> ci) & 1ull) != 0ull, obstClear = ((oclear >> ci) & 1ull) != 0ull;
+            const bool valid = t < endTime;
+            double uth;
+            pp_window_pose(S, hot, cur, cs, t, tFirst, valid, x, y, uth, dubErr);
+            // the heading itself (:47) only matters for "unchanged since the last step" (Edge.cpp:159), which only matters
+            // on edges that may not cover while turning
+            heading = cov ? 0.0 : pp_heading_from_yaw(pp_mod2pi(uth));
+            if (!gridClear && p.grid.rows != 0) {                     // Edge.cpp:144 (pp_k_plan_skips may have ruled it out for the whole chunk)
+                cell = pp_blocked_cell(p.grid, x, y);
+                word = p.grid.bits[cell.word];
+            }
+            if (!obstClear && laneCull) {                             // :150-151
+                // which obstacles can come near this chunk: lane j answers for obstacle j from its registers
+                const double dtc = tFirst - cullT0;
+                const double oX0 = cullL[0 * PP_WAVE], oY0 = cullL[1 * PP_WAVE], oVx = cullL[2 * PP_WAVE], oVy = cullL[3 * PP_WAVE], oR2 = cullL[4 * PP_WAVE];
+                const double ddx = pp_readlane(x, 0) - (oX0 + oVx * dtc), ddy = pp_readlane(y, 0) - (oY0 + oVy * dtc);
+                near = __ballot(!(ddx * ddx + ddy * ddy > oR2));      // oR2 = -1 in lanes without an obstacle
             }
         }
-        // ---- resolved in order, with the sequential semantics: the first chunk that ends the sweep discards the rest of the batch
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            if (!have[i]) break;
-            const int base = (g0 + ci[i]) * PP_WAVE;
-            const int k = base + lane;
+        // ---- resolved with the sequential code.  (Keep this part a block of its own, the two indices ahead of it: its `break`s
+        // then leave through one common exit.  Without the braces the compiler lays the loop out differently — 1 690 instructions
+        // against 1 655, 44 spilled scalars against 46 — and pp_k_pose_sweep measures 440 us against 422,
+        // profiles/pose_queue_cleanup.txt.)
+        const int base = (g0 + ci) * PP_WAVE;
+        const int k = base + lane;
+        {
 #ifdef PP_DBG_TRACE
             if (pp_edge_position(p, p.e_base + (e - p.ws_base)) == (long long)(PP_DBG_TRACE) && lane == 0 && base < 400)
-                printf("[pose] chunk at %d: sampled after skip %d (eq word %llx)\n", base, (int)after[i], (unsigned long long)teq[base >> 6]);
+                printf("[pose] chunk at %d: sampled after skip %d (eq word %llx)\n", base, (int)after, (unsigned long long)teq[base >> 6]);
 #endif
-            if (!live[i]) { limit = base; stop = true; break; }
+            if (!live) { limit = base; break; }
             // `lastHeading` (Edge.cpp:96,174) of the step before this chunk: the chunks in between were skipped, pp_k_plan_skips left it
-            if (!cov && after[i]) carryHeading = carryW[i];
-            const bool obstClear = ((oclear >> ci[i]) & 1ull) != 0ull;
-            const bool valid = t[i] < endTime;
-            const bool gridTested = !(((gclear >> ci[i]) & 1ull) != 0ull) && p.grid.rows != 0;
-            const bool blk = gridTested ? (valid & pp_blocked_test(cell[i], word[i])) : false;
+            if (!cov && after) carryHeading = carryW;
+            const bool obstClear = ((oclear >> ci) & 1ull) != 0ull;
+            const bool valid = t < endTime;
+            const bool gridTested = !(((gclear >> ci) & 1ull) != 0ull) && p.grid.rows != 0;
+            const bool blk = gridTested ? (valid & pp_blocked_test(cell, word)) : false;
             int hits = 0;
             double dens = 0;
             if (obstClear) {
                 // pp_k_plan_skips: no obstacle can hold a pose of this chunk
             } else if (laneCull) {
-                unsigned long long m = near[i];
+                unsigned long long m = near;
                 while (m) {
                     const int j = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    if (!gaussian) { if (valid) hits += pp_obstacle_hit(pp_obst_load_uniform(p.obst + j), x[i], y[i], t[i]); }
-                    else dens += pp_obstacle_pdf(reinterpret_cast<const PPGauss*>(p.obst)[j], x[i], y[i], t[i]);
+                    if (!gaussian) { if (valid) hits += pp_obstacle_hit(pp_obst_load_uniform(p.obst + j), x, y, t); }
+                    else dens += pp_obstacle_pdf(reinterpret_cast<const PPGauss*>(p.obst)[j], x, y, t);
                 }
                 if (gaussian) { if (dens < 1e-5) dens = 0; if (!valid) dens = 0; }   // GaussianDynamicObstaclesManager.cpp:11
             } else {
                 if (!gaussian)
-                    hits = pp_obstacle_hits_chunk(p.obst, p.n_obst, x[i], y[i], t[i], valid, pp_readlane(x[i], 0), pp_readlane(y[i], 0), tFirst[i], chunkSpan, chunkTime);
+                    hits = pp_obstacle_hits_chunk(p.obst, p.n_obst, x, y, t, valid, pp_readlane(x, 0), pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
                 else
-                    dens = pp_obstacle_density_chunk(reinterpret_cast<const PPGauss*>(p.obst), p.n_obst, x[i], y[i], t[i], valid, pp_readlane(x[i], 0),
-                                                     pp_readlane(y[i], 0), tFirst[i], chunkSpan, chunkTime);
+                    dens = pp_obstacle_density_chunk(reinterpret_cast<const PPGauss*>(p.obst), p.n_obst, x, y, t, valid, pp_readlane(x, 0),
+                                                     pp_readlane(y, 0), tFirst, chunkSpan, chunkTime);
             }
             unsigned long long eqMask = ~0ull;
             if (!cov) {
-                double prevHeading = __shfl_up(heading[i], 1, PP_WAVE);
+                double prevHeading = __shfl_up(heading, 1, PP_WAVE);
                 if (lane == 0) prevHeading = carryHeading;
-                eqMask = __ballot(prevHeading == heading[i]);
+                eqMask = __ballot(prevHeading == heading);
 #ifdef PP_DBG_TRACE
                 if (pp_edge_position(p, p.e_base + (e - p.ws_base)) == (long long)(PP_DBG_TRACE) && lane == 0 && base < 400)
-                    printf("[pose] chunk at %d sampled: carry %.17g heading0 %.17g heading1 %.17g eq %llx\n", base, prevHeading, heading[i], pp_readlane(heading[i], 1), (unsigned long long)eqMask);
+                    printf("[pose] chunk at %d sampled: carry %.17g heading0 %.17g heading1 %.17g eq %llx\n", base, prevHeading, heading, pp_readlane(heading, 1), (unsigned long long)eqMask);
 #endif
-                carryHeading = pp_readlane(heading[i], 63);           // (the next chunk's, when that one is adjacent)
+                carryHeading = pp_readlane(heading, 63);           // (the next chunk's, when that one is adjacent)
             }
-            if (__ballot(dubErr[i]) != 0ull) anyErr = 1;
+            if (__ballot(dubErr) != 0ull) anyErr = 1;
 
             const unsigned long long bm = __ballot(blk);
             const int fb = bm ? (__ffsll((long long)bm) - 1) : PP_WAVE;
@@ -744,12 +735,11 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
                 if (!cov) teq[base >> 6] = eqMask;                        // only read for edges that may not cover while turning
             }
 
-            if (fb < nvalid) { limit = base + fb; blocked = 1; stop = true; break; }
-            if (nvalid < PP_WAVE) { limit = base + nvalid; stop = true; break; }
+            if (fb < nvalid) { limit = base + fb; blocked = 1; break; }
+            if (nvalid < PP_WAVE) { limit = base + nvalid; break; }
             limit = base + PP_WAVE;
         }
-        if (stop) break;
-        next_batch();
+        next_chunk();
     }
     if (lane == 0) { sum->limit = limit; sum->blocked = blocked; sum->dub_err = anyErr; sum->pad = 0; }
 }
@@ -757,24 +747,14 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
 #ifndef PP_POSE_MIN_WAVES
 #define PP_POSE_MIN_WAVES 6
 #endif
-#ifndef PP_POSE_CHUNKS
-#define PP_POSE_CHUNKS 1     // sampled chunks a wave of pp_k_pose_sweep has in flight.  1 / 2 / 3 measured (profiles/pose_chain_ab.txt): a second
-                             // chunk costs registers the kernel does not have at 6 waves per SIMD and poses that a blocked first chunk throws away
-#endif
 // n_edges = slice size (ppgpu.hip: launch_cost)
 __global__ __launch_bounds__(PP_WPB * 64, PP_POSE_MIN_WAVES) void pp_k_pose_sweep(PPParams p) {
-    PPQueue qs = pp_queue_init();
-    for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
-        pp_pose_sweep_edge<false, PP_POSE_CHUNKS>(p, p.ws_base + idx);
-}
-// one chunk at a time (handle switch PPGPU_POSE_CHUNKS=1)
-__global__ __launch_bounds__(PP_WPB * 64, 6) void pp_k_pose_sweep_single(PPParams p) {
-    PPQueue qs = pp_queue_init();
-    for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
-        pp_pose_sweep_edge<false, 1>(p, p.ws_base + idx);
+    int wave;
+    const long long idx = pp_wave_edge<PP_WPB>(wave);
+    if (idx < p.n_edges) pp_pose_sweep_edge<false>(p, p.ws_base + idx);
 }
 __global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian(PPParams p) {
-    PPQueue qs = pp_queue_init();
-    for (PP_EACH_EDGE(idx, 1, PP_Q_POSE, p.n_edges, 1))
-        pp_pose_sweep_edge<true, 1>(p, p.ws_base + idx);
+    int wave;
+    const long long idx = pp_wave_edge<PP_WPB>(wave);
+    if (idx < p.n_edges) pp_pose_sweep_edge<true>(p, p.ws_base + idx);
 }

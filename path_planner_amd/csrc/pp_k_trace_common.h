@@ -10,8 +10,7 @@
 
 // The edge of this wave: el = its position in the slice.  False past the end of the slice.
 __device__ __forceinline__ bool pp_trace_entry(const PPParams& p, int& wave, long long& el) {
-    wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    el = (long long)blockIdx.x * PP_TRACE_WPB + wave;
+    el = pp_wave_edge<PP_TRACE_WPB>(wave);
     return el < p.n_edges;
 }
 

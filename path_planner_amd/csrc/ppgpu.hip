@@ -161,7 +161,6 @@ struct ppgpu_ctx {
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
     bool lane_finish = true;            // env PPGPU_LANE_FINISH=0: every wave of the cover sweep finishes its own edges (tests compare the two)
     bool plan_spans = true;             // env PPGPU_PLAN_SPANS=0: the skip planner tests every obstacle of an edge's list per chunk (the tests compare the two)
-    int pose_chunks = 0;                // env PPGPU_POSE_CHUNKS=1: the pose sweep samples one chunk at a time (tests compare it with the batched default)
     bool lane_heuristic = true;         // env PPGPU_LANE_HEURISTIC=0: large launches keep the wave-per-edge enumeration too (tests compare the two)
     long long prepass_min_edges = PP_PREPASS_MIN_EDGES;   // env PPGPU_PREPASS_MIN_EDGES overrides (tests run the prepasses on small launches too)
     size_t slice_bytes = PP_SLICE_BYTES; // workspace budget of one costing slice (env PPGPU_SLICE_BYTES overrides: tests)
@@ -175,9 +174,9 @@ struct ppgpu_ctx {
     DevBuf<unsigned> need_big;          // [0] need_big, [1 + n] number of deferred edges with n ribbons (pp_k_deferred_list)
     DevBuf<unsigned> defer_list, live_list, hw_list;
     DevBuf<PPCoverState> cover_state;
-    DevBuf<unsigned long long> work;    // queue heads of the resident per-edge grids (PP_Q_*)
+    DevBuf<unsigned long long> work;    // queue heads of the cover sweep's resident grid (pp_next_edge)
     int n_cu = 0;
-    int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // workgroups of each per-edge kernel the device holds at once (0 = not asked yet)
+    int resident[2] = {0, 0};           // workgroups of pp_k_cover_sweep / pp_k_cover_sweep_gaussian the device holds at once (0 = not asked yet)
     DevBuf<double> track_pen, track_chunk_pen;   // Gaussian obstacle model only
     // optional per-kernel timing of costing launches (ppgpu_enable_timing)
     bool timing = false;
@@ -297,7 +296,6 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* lf = std::getenv("PPGPU_LANE_FINISH")) c->lane_finish = std::atoi(lf) != 0;
     if (const char* ls = std::getenv("PPGPU_LANE_SPLIT")) c->lane_split = std::atoi(ls) != 0;
     if (const char* aw = std::getenv("PPGPU_SOLVE_ALL_WORDS")) c->solve_all_words = std::atoi(aw) != 0;
-    if (const char* pc = std::getenv("PPGPU_POSE_CHUNKS")) c->pose_chunks = std::atoi(pc);
     if (const char* ps = std::getenv("PPGPU_PLAN_SPANS")) c->plan_spans = std::atoi(ps) != 0;
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
@@ -1128,19 +1126,18 @@ int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask) {
     return (int64_t)nv * ns * (int64_t)__builtin_popcount(cfg_mask & 0xFu);
 }
 
-// Grid of a per-edge kernel: as many workgroups as the device keeps resident (its waves pull edges from the queue), or fewer
+// Grid of a cover sweep: as many workgroups as the device keeps resident (its waves pull edges from the queues), or fewer
 // when the launch has fewer edges than that.
-static unsigned resident_grid(ppgpu_ctx* c, int slot, void (*kernel)(PPParams), long long n_edges) {
-    const int bit = slot < 2 ? 1 : (slot < 4 ? 2 : 4);
-    const int wpb = slot < 4 ? PP_WPB : PP_H_WPB;
-    if (!((PP_QUEUE_MASK) & bit)) return (unsigned)((n_edges + wpb - 1) / wpb);   // this kernel takes one edge per wave
-    if (c->resident[slot] == 0) {
+static unsigned resident_grid(ppgpu_ctx* c, bool gaussian, long long n_edges) {
+    int& resident = c->resident[gaussian ? 1 : 0];
+    if (resident == 0) {
+        const void* kernel = gaussian ? (const void*)pp_k_cover_sweep_gaussian : (const void*)pp_k_cover_sweep;
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, wpb * 64, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-        c->resident[slot] = per_cu * (c->n_cu > 0 ? c->n_cu : 256);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PP_WPB * 64, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
+        resident = per_cu * (c->n_cu > 0 ? c->n_cu : 256);
     }
-    const long long need = (n_edges + wpb - 1) / wpb;
-    return (unsigned)(need < c->resident[slot] ? need : c->resident[slot]);
+    const long long need = (n_edges + PP_WPB - 1) / PP_WPB;
+    return (unsigned)(need < resident ? need : resident);
 }
 
 // "Cost this list of n edges": packed descriptors on the device (d_edges), or wrapper edges on the device (d_wedges).  Records go
@@ -1193,7 +1190,7 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
     m.skip_chunks = m.prepasses && !p.wedges && (c->rows == 0 || c->grid_clear.p) && p.ng >= PP_WAVE;
     const bool dubinsH = p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K;
     m.fuse_h = PP_FUSE_HEUR && !dubinsH && !m.gaussian;
-    m.defer_h = m.fuse_h && m.prepasses && PP_LANE_HEUR && c->lane_heuristic && total < (1ll << 32) &&
+    m.defer_h = m.fuse_h && m.prepasses && c->lane_heuristic && total < (1ll << 32) &&
                 (p.heuristic == PPGPU_H_TSP_POINT_ALL || p.heuristic == PPGPU_H_TSP_POINT_K);
     m.quiet_finish = m.prepasses && c->quiet_finish;
     m.lane_split = m.prepasses && c->lane_split && !m.gaussian;
@@ -1285,13 +1282,11 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
                                                     : (many ? pp_k_plan_skips_many : (c->plan_spans ? pp_k_plan_skips : pp_k_plan_skips_chunkwise));
         hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, st, p, epw);
     }
-    void (*pose)(PPParams) = m.gaussian ? pp_k_pose_sweep_gaussian : (c->pose_chunks == 1 ? pp_k_pose_sweep_single : pp_k_pose_sweep);
-    hipLaunchKernelGGL(pose, dim3(resident_grid(c, m.gaussian ? 0 : 1, pose, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
+    hipLaunchKernelGGL(m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep, dim3((unsigned)((p.n_edges + PP_WPB - 1) / PP_WPB)), dim3(PP_WPB * 64), 0, st, p);   // a wave per edge
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_POSED], st));
     if (m.prepasses) hipLaunchKernelGGL(pp_k_approach_events, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_APPROACHED], st));
-    void (*cover)(PPParams) = m.gaussian ? pp_k_cover_sweep_gaussian : pp_k_cover_sweep;
-    hipLaunchKernelGGL(cover, dim3(resident_grid(c, m.gaussian ? 2 : 3, cover, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
+    hipLaunchKernelGGL(m.gaussian ? pp_k_cover_sweep_gaussian : pp_k_cover_sweep, dim3(resident_grid(c, m.gaussian, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
     if (m.lane_finish)       // (the list's length is on the device: a grid for "every edge of the slice is on it", whose spare workgroups leave at once)
         hipLaunchKernelGGL(pp_k_cover_finish, dim3((unsigned)((p.n_edges + PP_FINISH_THREADS - 1) / PP_FINISH_THREADS)), dim3(PP_FINISH_THREADS), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_COVERED], st));
@@ -1332,10 +1327,11 @@ static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
     const PPParams& p = m.p;
     const long long total = p.n_edges;
     hipStream_t st = c->stream;
+    const dim3 per_wave((unsigned)((total + PP_H_WPB - 1) / PP_H_WPB));            // a wave per edge
     if (p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K)
-        hipLaunchKernelGGL(pp_k_heuristic_dubins, dim3(resident_grid(c, 4, pp_k_heuristic_dubins, total)), dim3(PP_H_WPB * 64), 0, st, p);
+        hipLaunchKernelGGL(pp_k_heuristic_dubins, per_wave, dim3(PP_H_WPB * 64), 0, st, p);
     else if (!m.fuse_h)
-        hipLaunchKernelGGL(pp_k_heuristic, dim3(resident_grid(c, 5, pp_k_heuristic, total)), dim3(PP_H_WPB * 64), 0, st, p);
+        hipLaunchKernelGGL(pp_k_heuristic, per_wave, dim3(PP_H_WPB * 64), 0, st, p);
     // The edges whose TSP enumeration the sweeps deferred: packed into one list per ribbon count, then a few lanes each
     // (pp_k_heuristic_lanes).  The rare edge pp_k_cover_finish left to a whole wave (pp_k_heuristic_listed: 7 or 8 child ribbons,
     // ~1 100 of config 3's 236 140 edges, each a single wave's work for ~170 us) runs on a second stream BESIDE it: the lane kernel
@@ -1344,8 +1340,8 @@ static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
     if (m.forked) {
         HIP_TRY(hipEventRecord(c->ev_fork, st));
         HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-        // (as many workgroups as pp_k_heuristic keeps resident: same footprint; all but a few leave at once)
-        hipLaunchKernelGGL(pp_k_heuristic_listed, dim3(resident_grid(c, 5, pp_k_heuristic, total)), dim3(PP_H_WPB * 64), 0, c->side_stream, p);
+        // (the list's length is on the device: the grid pp_k_heuristic would get, whose workgroups beyond the list leave at once)
+        hipLaunchKernelGGL(pp_k_heuristic_listed, per_wave, dim3(PP_H_WPB * 64), 0, c->side_stream, p);
         HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
     }
     if (m.defer_h) {
@@ -1761,9 +1757,8 @@ int ppgpu_heuristic_host(ppgpu_ctx* c, int32_t n, const double* poses3, const in
         off += (size_t)counts[i];
     }
     if ((rc = c->tmp_results.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_child.reserve(child.size(), false, c->stream)) ||
-        (rc = c->need_big.reserve(32, false, c->stream)) || (rc = c->work.reserve(PP_WORK_WORDS, false, c->stream)))
+        (rc = c->need_big.reserve(32, false, c->stream)))
         return rc;
-    HIP_TRY(hipMemsetAsync(c->work.p, 0, (size_t)PP_WORK_WORDS * sizeof(unsigned long long), c->stream));   // queue heads (no solve kernel runs here)
     HIP_TRY(hipMemcpyAsync(c->tmp_results.p, rec.data(), rec.size() * sizeof(ppgpu_edge_result), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->tmp_child.p, child.data(), child.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned one = 1u;       // let the 12-ribbon pass look at every record
@@ -1771,7 +1766,7 @@ int ppgpu_heuristic_host(ppgpu_ctx* c, int32_t n, const double* poses3, const in
     PPParams p;
     fill_params(c, p);
     p.edges = nullptr; p.wedges = nullptr; p.n_edges = n; p.total_edges = n; p.e_base = 0; p.ws_base = 0;
-    p.out = c->tmp_results.p; p.child = c->tmp_child.p; p.stride = stride; p.need_big = c->need_big.p; p.work = c->work.p;
+    p.out = c->tmp_results.p; p.child = c->tmp_child.p; p.stride = stride; p.need_big = c->need_big.p;
     const dim3 grid((unsigned)((n + PP_H_WPB - 1) / PP_H_WPB)), block(PP_H_WPB * 64);   // n is small: never more than fits
     if (p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K) hipLaunchKernelGGL(pp_k_heuristic_dubins, grid, block, 0, c->stream, p);
     else hipLaunchKernelGGL(pp_k_heuristic, grid, block, 0, c->stream, p);

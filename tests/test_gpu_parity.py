@@ -800,6 +800,88 @@ def test_small_launches_without_prepasses(torch_cuda, monkeypatch):
     _same_up_to_run_rounding(outs[0], outs[1])
 
 
+# ---------------------------------------------------------------------------------------------- launches that fill no workgroup
+SHORT_LISTS = (1, 3, 5, 7)           # edges per list: fewer than a workgroup's four waves, one more, fewer than two workgroups'
+SHORT_SAMPLES, SHORT_STRIDE = 48, 8
+_SHORT = {}
+
+
+def _short_lists(model, heur):
+    """Config 3's world with 48 samples of the oracle's sampler, its 16 obstacles as boxes or as Gaussian rows {x, y, heading, speed,
+    time}, under one of three heuristics, and the oracle's records of the root's 192 edges to them, computed once.  The list of n
+    edges is taken from a fixed permutation of them (an edge's record does not depend on the list it is in).  Returns
+    (workload, Gaussian rows or None, samples, {n: (edges, records, child ribbons)})."""
+    key = (model, heur)
+    if key not in _SHORT:
+        import oracle as orc
+        from path_planner_amd import workloads
+        from path_planner_amd.types import edge_pack, F_INFEASIBLE, H_MAX_DISTANCE, H_TSP_POINT_ALL, H_TSP_DUBINS_ALL
+        w = workloads.config3(n_samples=SHORT_SAMPLES)
+        w.cfg.heuristic = {"max": H_MAX_DISTANCE, "point_all": H_TSP_POINT_ALL, "dubins_all": H_TSP_DUBINS_ALL}[heur]
+        w.cfg.heuristic_turning_radius = 8.0
+        rows = np.ascontiguousarray(w.obst[:, :5]) if model == "gaussian" else None
+        world = orc.World(w.cfg, w.grid, w.res, gauss=rows) if model == "gaussian" else orc.World(w.cfg, w.grid, w.res, w.obst)
+        cs = world.add_samples(w.bounds6, w.seed, w.ribbons4, 0, SHORT_SAMPLES)
+        n = len(cs)
+        e = edge_pack(np.zeros(4 * n, dtype=np.uint64), np.repeat(np.arange(n), 4), np.tile(np.arange(4), n))
+        cpu, cchild = world.cost_edges(w.root(), w.ribbons4, cs[:, 0], cs[:, 1], cs[:, 2], e, stride=SHORT_STRIDE)
+        # list j: the j-th feasible edge of the permutation, then the next k - 1 of its other edges, whatever they are
+        perm = np.random.default_rng(41).permutation(4 * n)
+        first = perm[(cpu["flags"][perm] & F_INFEASIBLE) == 0][:len(SHORT_LISTS)]
+        rest = perm[~np.isin(perm, first)]
+        lists, at = {}, 0
+        for j, k in enumerate(SHORT_LISTS):
+            pick = np.concatenate([first[j:j + 1], rest[at:at + k - 1]])
+            at += k - 1
+            lists[k] = (e[pick].copy(), cpu[pick].copy(), cchild[pick].copy())
+        _SHORT[key] = (w, rows, cs, lists)
+    return _SHORT[key]
+
+
+@pytest.mark.parametrize("heur", ["max", "point_all", "dubins_all"])      # pp_k_heuristic (Gaussian) / fused (binary), likewise, pp_k_heuristic_dubins
+@pytest.mark.parametrize("model", ["binary", "gaussian"])
+@pytest.mark.parametrize("threshold", ["0", "1000000000"])
+def test_short_edge_lists_fill_no_workgroup(torch_cuda, monkeypatch, threshold, model, heur):
+    """Lists of 1, 3, 5 and 7 edges: the last workgroup of every wave-per-edge kernel has waves without an edge, and the cover
+    sweep's waves find most of the 32 queues empty.  Result and child buffers are one record longer than the list and hold 0xA5
+    in every byte: the records are the oracle's, and the record past the list and its child slot are untouched."""
+    from path_planner_amd import api
+    from path_planner_amd.types import RESULT_DTYPE, F_INFEASIBLE
+    from parity import compare_results
+    torch = torch_cuda
+    w, rows, cs, lists = _short_lists(model, heur)
+    monkeypatch.setenv("PPGPU_PREPASS_MIN_EDGES", threshold)
+    ctx = api.Context(0)       # (the handle reads the switches when it is created)
+    ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res)
+    if model == "gaussian":
+        ctx.set_gaussian_obstacles(rows)
+    else:
+        ctx.set_obstacles(w.obst)
+    ctx.set_vertices(w.root(), w.ribbons4)
+    ctx.set_samples(cs[:, 0], cs[:, 1], cs[:, 2])
+    rec_bytes, child_bytes = RESULT_DTYPE.itemsize, SHORT_STRIDE * 4 * 8
+    for n in SHORT_LISTS:
+        edges, cpu, cchild = lists[n]
+        assert np.count_nonzero((cpu["flags"] & F_INFEASIBLE) == 0) >= 1, "the list holds no feasible edge"
+        d_e = torch.from_numpy(edges.view(np.int64)).to("cuda:0")
+        d_res = torch.full(((n + 1) * rec_bytes,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        d_child = torch.full(((n + 1) * child_bytes,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        torch.cuda.synchronize()      # the fill ran on torch's stream, the library works on its own
+        ctx.cost_edges_list(n, d_e.data_ptr(), d_res.data_ptr(), d_child.data_ptr(), SHORT_STRIDE)
+        ctx.synchronize()
+        res, child = d_res.cpu().numpy(), d_child.cpu().numpy()
+        assert np.all(res[n * rec_bytes:] == 0xA5), "the record past the list was written"
+        assert np.all(child[n * child_bytes:] == 0xA5), "the child slot past the list was written"
+        gpu = res[:n * rec_bytes].view(RESULT_DTYPE)
+        gchild = child[:n * child_bytes].view(np.float64).reshape(n, SHORT_STRIDE, 4).copy()
+        # (a launch defines the ribbons an edge's child has, not the rest of its slot: the oracle leaves zeros there)
+        for i in range(n):
+            gchild[i, min(int((gpu["info"][i] >> 8) & 0xFF), SHORT_STRIDE):] = 0.0
+        rep = compare_results(gpu, cpu, gchild, cchild)
+        print(threshold, model, heur, n, {k: rep[k] for k in ("n_feasible", "worst_rel", "n_flag_mismatch", "n_info_mismatch")})
+        assert rep["ok"], (n, rep)
+
+
 def _same_up_to_run_rounding(a, b):
     (ga, ca), (gb, cb) = a, b
     assert np.array_equal(ga["flags"], gb["flags"]) and np.array_equal(ga["info"], gb["info"])

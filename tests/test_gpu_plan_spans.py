@@ -29,7 +29,6 @@ def torch_cuda():
 def _run(torch, monkeypatch, w, route, spans=None):
     """(records, child ribbons) of world w; the handle reads the switches when it is created."""
     monkeypatch.setenv("PPGPU_PREPASS_MIN_EDGES", route)
-    monkeypatch.delenv("PPGPU_POSE_CHUNKS", raising=False)
     if spans is None:
         monkeypatch.delenv("PPGPU_PLAN_SPANS", raising=False)
     else:

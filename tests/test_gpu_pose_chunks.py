@@ -1,7 +1,7 @@
-"""-m gpu: the pose sweep's walk over the chunks the skip planner left to sample.  PPGPU_POSE_CHUNKS=1 keeps one chunk at a time;
-the default build may have several in flight (PP_POSE_CHUNKS in pp_k_sweep.h).  Both must give the same bytes, and both the
-oracle's records and the step trace's running penalty (pp_k_trace_steps neither skips nor batches) wherever a batch could go wrong:
-an edge that ends or is blocked on the last lane of a chunk, on lane 0 of the next, in a chunk of one step."""
+"""-m gpu: the pose sweep's walk over the chunks the skip planner left to sample, one sampled chunk per trip.  The oracle's records
+and the step trace's running penalty (pp_k_trace_steps does not skip) wherever the walk could go wrong: chunks that are not
+adjacent, the heading carried from lane 63 to lane 0 or taken from the planner's word, an edge that ends or is blocked on the last
+lane of a chunk, on lane 0 of the next, in a chunk of one step, and an edge whose skip bytes come in two groups of 64."""
 import numpy as np
 import pytest
 
@@ -27,40 +27,52 @@ def _dense(torch, ctx, nv, n, mask, stride=8):
     return d_res.cpu().numpy().view(RESULT_DTYPE), d_child.cpu().numpy().reshape(ne, stride, 4)
 
 
-def _switch(monkeypatch, chunks):
-    if chunks is None:
-        monkeypatch.delenv("PPGPU_POSE_CHUNKS", raising=False)
-    else:
-        monkeypatch.setenv("PPGPU_POSE_CHUNKS", chunks)
+# ---------------------------------------------------------------------------------------------- both routes, config 3
+_CFG3 = {}
 
 
-# ---------------------------------------------------------------------------------------------- same bytes, config 3
+def _cfg3_oracle(w, samples):
+    """The oracle's records of config 3's first 2 048 kept samples, computed once and shared by the two routes."""
+    if not _CFG3:
+        import oracle as orc
+        from path_planner_amd.types import edge_pack
+        n = len(samples)
+        world = orc.World(w.cfg, w.grid, w.res, w.obst)
+        e = edge_pack(np.zeros(4 * n, dtype=np.uint64), np.repeat(np.arange(n), 4), np.tile(np.arange(4), n))
+        cpu, cchild = world.cost_edges(w.root(), w.ribbons4, samples[:, 0], samples[:, 1], samples[:, 2], e, stride=8, threads=8)
+        cpu.setflags(write=False); cchild.setflags(write=False)
+        _CFG3["samples"], _CFG3["cpu"], _CFG3["cchild"] = samples.copy(), cpu, cchild
+    assert np.array_equal(samples, _CFG3["samples"]), "the sampler drew other samples than on the first route"
+    return _CFG3["cpu"], _CFG3["cchild"]
+
+
 @pytest.mark.parametrize("threshold", ["0", "1000000000"])
-def test_one_chunk_at_a_time_gives_the_same_bytes(torch_cuda, monkeypatch, threshold):
-    """Config 3, 2 048 samples (8 192 edges), mask 0xF.  Threshold 0: the skip planner runs, a batch is made of chunks that are not
-    adjacent and the heading before a chunk comes from the planner's word.  Threshold huge: no chunk is skipped, every batch is
-    adjacent chunks and the heading is carried from lane 63 to lane 0 inside a batch (the radius-8 edges may not cover while turning)."""
+def test_both_routes_match_oracle_at_2048_samples(torch_cuda, monkeypatch, threshold):
+    """Config 3, 2 048 samples (8 192 edges), mask 0xF, against the oracle.  Threshold 0: the skip planner runs, the walk goes
+    through chunks that are not adjacent and the heading before a chunk comes from the planner's word.  Threshold huge: no chunk is
+    skipped, the walk goes through adjacent chunks and the heading is carried from lane 63 to lane 0 (the radius-8 edges may not
+    cover while turning)."""
     from path_planner_amd import api, workloads
+    from parity import compare_results
     w = workloads.config3(n_samples=2048)
     monkeypatch.setenv("PPGPU_PREPASS_MIN_EDGES", threshold)
-    outs = []
-    for chunks in ("1", None):
-        _switch(monkeypatch, chunks)
-        ctx = api.Context(0)       # (the handle reads the switches when it is created)
-        ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
-        ctx.sampler_init(w.bounds6, w.seed, w.ribbons4)
-        ctx.sampler_add(2048)
-        n = ctx.sampler_add(512)       # (the sampler keeps some nine draws in ten: the first 2 048 it kept are costed)
-        assert n >= 2048
-        outs.append(_dense(torch_cuda, ctx, 1, 2048, 0xF))
-    assert len(outs[0][0]) == 8192
-    assert np.array_equal(outs[0][0].view(np.uint8), outs[1][0].view(np.uint8)), "records differ"
-    assert np.array_equal(outs[0][1], outs[1][1]), "child ribbons differ"
-    nonturn = outs[0][0]["info"][(np.arange(8192) % 2) == 0] >> 16
-    print("threshold", threshold, "steps per edge: max", int((outs[0][0]["info"] >> 16).max()), "radius-8 edges beyond one chunk", int((nonturn > 64).sum()))
+    ctx = api.Context(0)       # (the handle reads the switches when it is created)
+    ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
+    ctx.sampler_init(w.bounds6, w.seed, w.ribbons4)
+    ctx.sampler_add(2048)
+    n = ctx.sampler_add(512)       # (the sampler keeps some nine draws in ten: the first 2 048 it kept are costed)
+    assert n >= 2048
+    gpu, gchild = _dense(torch_cuda, ctx, 1, 2048, 0xF)
+    assert len(gpu) == 8192
+    cpu, cchild = _cfg3_oracle(w, ctx.get_samples()[:2048, :3])
+    rep = compare_results(gpu, cpu, gchild, cchild)
+    nonturn = gpu["info"][(np.arange(8192) % 2) == 0] >> 16
+    print("threshold", threshold, {k: rep[k] for k in ("n_feasible", "worst_rel", "n_flag_mismatch", "n_info_mismatch")},
+          "steps per edge: max", int((gpu["info"] >> 16).max()), "radius-8 edges beyond one chunk", int((nonturn > 64).sum()))
+    assert rep["ok"], rep
 
 
-# ---------------------------------------------------------------------------------------------- where a batch can go wrong
+# ---------------------------------------------------------------------------------------------- where the walk can go wrong
 STOPS = (1, 63, 64, 65, 127, 128)       # the first blocked step of the straight fast edge of vertex i
 INC, VMAX = 0.05, 2.5                   # a fast edge advances 0.05 m per step of 0.02 s
 Y0, DY = 3.05, 3.2                      # the vertices' rows
@@ -124,7 +136,7 @@ _ORACLE = {}
 
 
 def _oracle(steps):
-    """The oracle's records of one shape, computed once and shared by the settings of the switch."""
+    """The oracle's records of one shape, computed once."""
     if steps not in _ORACLE:
         import oracle as orc
         L = _Lanes(steps)
@@ -136,7 +148,7 @@ def _oracle(steps):
 
 
 @pytest.mark.parametrize("steps", [64, 65, 128, 129, 130])
-def test_chunk_ends_against_oracle_and_trace(torch_cuda, monkeypatch, steps):
+def test_chunk_ends_against_oracle_and_trace(torch_cuda, steps):
     from path_planner_amd.types import F_INFEASIBLE
     from parity import compare_results
     L, cpu, cchild = _oracle(steps)
@@ -155,49 +167,42 @@ def test_chunk_ends_against_oracle_and_trace(torch_cuda, monkeypatch, steps):
         assert np.all(cpu["collision_penalty"][through] > 0), "the straight edges cross the box's face in the second chunk"
     cpf = L.cfg.collision_penalty_factor
     stride = steps + 8
-    for chunks in (None, "1"):
-        _switch(monkeypatch, chunks)
-        ctx = L.context()
-        gpu, gchild = _dense(torch_cuda, ctx, L.nv, L.ns, 0xF)
-        rep = compare_results(gpu, cpu, gchild, cchild)
-        print("steps", steps, "PPGPU_POSE_CHUNKS", chunks, {k: rep[k] for k in ("n_feasible", "worst_rel", "n_flag_mismatch", "n_info_mismatch")})
-        assert rep["ok"], rep
-        assert np.array_equal(gpu["flags"], cpu["flags"]) and np.array_equal(gpu["info"], cpu["info"])
-        rec, counts, st = ctx.trace_edges(L.edges, stride)
-        assert np.array_equal(counts, (gpu["info"] >> 16).astype(counts.dtype)), "trace records per edge != info >> 16"
-        has = np.nonzero(counts > 0)[0]
-        last = st[has, counts[has] - 1]
-        assert np.array_equal(last["penalty_before"] + last["collision"] * cpf, gpu["collision_penalty"][has]), "running penalty != the record's"
-        assert np.all(gpu["collision_penalty"][counts == 0] == 0.0)
+    ctx = L.context()
+    gpu, gchild = _dense(torch_cuda, ctx, L.nv, L.ns, 0xF)
+    rep = compare_results(gpu, cpu, gchild, cchild)
+    print("steps", steps, {k: rep[k] for k in ("n_feasible", "worst_rel", "n_flag_mismatch", "n_info_mismatch")})
+    assert rep["ok"], rep
+    assert np.array_equal(gpu["flags"], cpu["flags"]) and np.array_equal(gpu["info"], cpu["info"])
+    rec, counts, st = ctx.trace_edges(L.edges, stride)
+    assert np.array_equal(counts, (gpu["info"] >> 16).astype(counts.dtype)), "trace records per edge != info >> 16"
+    has = np.nonzero(counts > 0)[0]
+    last = st[has, counts[has] - 1]
+    assert np.array_equal(last["penalty_before"] + last["collision"] * cpf, gpu["collision_penalty"][has]), "running penalty != the record's"
+    assert np.all(gpu["collision_penalty"][counts == 0] == 0.0)
 
 
 # ---------------------------------------------------------------------------------------------- more than 64 chunks per edge
-def test_more_than_64_chunks_per_edge(torch_cuda, monkeypatch):
+def test_more_than_64_chunks_per_edge(torch_cuda):
     """Config 3's world with a horizon of 4 200 steps (66 chunks: the skip bytes of an edge come in two groups of 64) and 128
-    samples: both settings of the switch give the same bytes, and the oracle's records."""
+    samples, against the oracle's records."""
     from path_planner_amd import api, workloads
     from path_planner_amd.types import edge_pack
     from parity import compare_results
     import oracle as orc
     w = workloads.config3(n_samples=128)
     w.cfg.time_horizon = 4200.5 * (w.cfg.collision_checking_increment / w.cfg.max_speed)
-    outs = []
-    for chunks in (None, "1"):
-        _switch(monkeypatch, chunks)
-        ctx = api.Context(0)
-        ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
-        ctx.sampler_init(w.bounds6, w.seed, w.ribbons4)
-        n = ctx.sampler_add(w.n_samples)
-        outs.append(_dense(torch_cuda, ctx, 1, n, 0xF))
-    assert np.array_equal(outs[0][0].view(np.uint8), outs[1][0].view(np.uint8)), "records differ"
-    assert np.array_equal(outs[0][1], outs[1][1]), "child ribbons differ"
+    ctx = api.Context(0)
+    ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
+    ctx.sampler_init(w.bounds6, w.seed, w.ribbons4)
+    n = ctx.sampler_add(w.n_samples)
+    gpu, gchild = _dense(torch_cuda, ctx, 1, n, 0xF)
     world = orc.World(w.cfg, w.grid, w.res, w.obst)
     cs = world.add_samples(w.bounds6, w.seed, w.ribbons4, 0, w.n_samples)
-    ne = len(outs[0][0])
+    ne = len(gpu)
     e = edge_pack(np.zeros(ne, dtype=np.uint64), np.repeat(np.arange(n), 4), np.tile(np.arange(4), n))
     cpu, cchild = world.cost_edges(w.root(), w.ribbons4, cs[:, 0], cs[:, 1], cs[:, 2], e, stride=8, threads=8)
-    steps = outs[0][0]["info"] >> 16
+    steps = gpu["info"] >> 16
     print("steps per edge: max", int(steps.max()), "edges beyond 4 096 steps", int((steps > 4096).sum()))
     assert int(steps.max()) >= 4160, "no edge reaches the second group of skip bytes"
-    rep = compare_results(outs[0][0], cpu, outs[0][1], cchild)
+    rep = compare_results(gpu, cpu, gchild, cchild)
     assert rep["ok"], rep

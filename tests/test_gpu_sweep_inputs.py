@@ -34,13 +34,9 @@ def _dense(torch, ctx, w):
     return d_res.cpu().numpy().view(RESULT_DTYPE), d_child.cpu().numpy().reshape(ne, sw.RIBBON_STRIDE, 4)
 
 
-def _run(torch, monkeypatch, w, route, chunks=None):
+def _run(torch, monkeypatch, w, route):
     """(handle, records, child ribbons) of world w through one route; the handle reads the switches when it is created."""
     monkeypatch.setenv("PPGPU_PREPASS_MIN_EDGES", route)
-    if chunks is None:
-        monkeypatch.delenv("PPGPU_POSE_CHUNKS", raising=False)
-    else:
-        monkeypatch.setenv("PPGPU_POSE_CHUNKS", chunks)
     ctx = w.context()
     gpu, gchild = _dense(torch, ctx, w)
     return ctx, gpu, gchild
@@ -69,7 +65,7 @@ def _same_answers(a, b, what):
 
 
 def _trace_check(ctx, w, gpu, pick, stride):
-    """The step trace neither skips nor batches: as many records as info says, and its running penalty is the record's, exactly."""
+    """The step trace does not skip: as many records as info says, and its running penalty is the record's, exactly."""
     cpf = w.cfg.collision_penalty_factor
     rec, counts, st = ctx.trace_edges(w.edges[pick], stride)
     assert np.array_equal(counts, (gpu["info"][pick] >> 16).astype(counts.dtype)), "trace records per edge != info >> 16"
@@ -86,7 +82,7 @@ TRACED = ("fast", "stacked", "done_inside")
 @pytest.mark.parametrize("name", sw.BINARY + ["done_inside"])
 def test_binary_fleet_against_oracle(torch_cuda, monkeypatch, name):
     """Both routes: the oracle's flags and info on every edge, its penalty to the bit on every feasible edge, and the same answers
-    from both.  `fast` also with one chunk at a time: the same bytes.  `count64+far` against `count64`: a box 10 km away switches
+    from both.  `count64+far` against `count64`: a box 10 km away switches
     every kernel to its more-than-64 path and may change no answer."""
     w, cpu, cchild = sw.oracle_records(name)
     outs = []
@@ -100,12 +96,6 @@ def test_binary_fleet_against_oracle(torch_cuda, monkeypatch, name):
             pick = np.arange(0, ne, stride)[:128]
             assert len(np.unique(pick % 4)) == 4
             _trace_check(ctx, w, gpu, pick, w.ng)
-        if name == "fast":
-            # (a library built with the default PP_POSE_CHUNKS = 1 runs the same instantiation in both kernels: this only bites on a
-            # build that keeps several chunks in flight)
-            _, one, onechild = _run(torch_cuda, monkeypatch, w, route, chunks="1")
-            assert np.array_equal(one.view(np.uint8), gpu.view(np.uint8)), "PPGPU_POSE_CHUNKS=1: records differ"
-            assert np.array_equal(onechild, gchild), "PPGPU_POSE_CHUNKS=1: child ribbons differ"
         if name == "count64+far":
             w64, cpu64, _ = sw.oracle_records("count64")
             _same_answers(cpu, cpu64, "oracle: the far box changed an answer")
@@ -134,7 +124,7 @@ def test_long_horizon_against_oracle(torch_cuda, monkeypatch, steps):
     exactly.  16 377: a second tile (blockIdx.y = 1) is launched for one chunk, but the longest edge has 16 378 steps, all in the
     first 256 chunks, so that tile's thread leaves at once (the sweep never reaches its chunk): what is checked is that it
     disturbs nothing.  Only 16 500 has edges past step 16 384 (12 of them): there the second tile decides chunks 256 and 257 and
-    the walk enters a fifth group.  The PPGPU_POSE_CHUNKS=1 comparison proves little on a default build (see the fleet test)."""
+    the walk enters a fifth group."""
     w, cpu, cchild = sw.oracle_records("long%d" % steps)
     assert w.ng == steps + 8
     nsteps = cpu["info"] >> 16
@@ -145,9 +135,6 @@ def test_long_horizon_against_oracle(torch_cuda, monkeypatch, steps):
     for route in ROUTES:
         ctx, gpu, gchild = _run(torch_cuda, monkeypatch, w, route)
         _against_oracle("long%d route %s" % (steps, route), gpu, gchild, cpu, cchild, exact=True)
-        _, one, onechild = _run(torch_cuda, monkeypatch, w, route, chunks="1")
-        assert np.array_equal(one.view(np.uint8), gpu.view(np.uint8)), "PPGPU_POSE_CHUNKS=1: records differ"
-        assert np.array_equal(onechild, gchild), "PPGPU_POSE_CHUNKS=1: child ribbons differ"
         if steps == 16500:
             beyond = np.nonzero(nsteps > 16384)[0]
             assert beyond.size >= 5
