@@ -1060,7 +1060,7 @@ __device__ __forceinline__ unsigned long long pp_tsp_prefixes(int n, int K, int&
     return NP;
 }
 // Lists of 9..12 ribbons are enumerated (by the MAXN = 12 kernel) only for the K variant of the point-robot heuristic and
-// only while the prefix count stays below 2^21 (K = 2: up to 12 ribbons, K = 3: up to 10); everything else beyond 8 ribbons
+// only while the prefix count stays below 2^21 (K = 2: up to 12 ribbons, K = 3: up to 11); everything else beyond 8 ribbons
 // is reported as PPGPU_F_RIBBON_OVF.  (The All variants would need n! 2^n leaves: 1.9e8 at n = 9.)
 __device__ __forceinline__ bool pp_tsp_big_ok(int heuristic, int K, int n) {
     if (heuristic != PPGPU_H_TSP_POINT_K || n <= PP_TSP_MAX || n > PP_TSP_MAX_BIG) return false;
@@ -1091,6 +1091,38 @@ __device__ __forceinline__ bool pp_lane_tsp_ok(int heuristic, int tsp_k, int n) 
     return false;
 }
 
+// Vertex::computeApproxToGo: WHO computes h for a child list of nrib ribbons.  Every site asks and maps the answer to its own action
+// (pp_k_heuristic.h lists them).  fuse_h: whoever asks computes h now (the sweeps pass the launch's — without it pp_k_heuristic* does every
+// edge later — the heuristic kernels pass 1); defer_h: short TSP lists go to pp_k_heuristic_lanes.  Both are the host's (cost_modes).
+enum PPHRoute { PP_HR_NONE, PP_HR_MAX_DISTANCE, PP_HR_LANES, PP_HR_WAVE, PP_HR_BIG, PP_HR_OVERFLOW };    // who acts on each: the head of pp_k_heuristic.h
+__device__ __forceinline__ PPHRoute pp_h_route(int heuristic, int tsp_k, int nrib, int stride, int fuse_h, int defer_h) {
+    if (!fuse_h || nrib <= 0 || nrib > stride) return PP_HR_NONE;
+    if (heuristic == PPGPU_H_MAX_DISTANCE) return PP_HR_MAX_DISTANCE;
+    if (defer_h && pp_lane_tsp_ok(heuristic, tsp_k, nrib)) return PP_HR_LANES;
+    if (nrib <= PP_TSP_MAX) return PP_HR_WAVE;
+    return pp_tsp_big_ok(heuristic, tsp_k, nrib) ? PP_HR_BIG : PP_HR_OVERFLOW;
+}
+
+// h = heuristic distance / maxSpeed (Vertex.cpp:51-63) in cost units, and its store with f = g + h by the ONE thread the caller picks
+__device__ __forceinline__ double pp_h_cost(double hdist, double max_speed, double tpf) { return hdist / max_speed * tpf; }
+__device__ __forceinline__ void pp_h_store(ppgpu_edge_result* rec, double g, double hdist, double max_speed, double tpf) { const double h = pp_h_cost(hdist, max_speed, tpf); rec->h = h; rec->f = g + h; }
+
+// The point table of the wave-form heuristics, by one wave: x,y of the query point, then start / end of every ribbon (lane i asks rib for ribbon i).
+template <class Rib>
+__device__ __forceinline__ void pp_h_stage_points(double* pts, double x, double y, int nrib, Rib rib) {
+    const int lane = pp_lane();
+    if (lane == 0) { pts[0] = x; pts[1] = y; }
+    if (lane < nrib) {
+        double sx, sy, ex, ey;
+        rib(lane, sx, sy, ex, ey);
+        pts[2 * (1 + 2 * lane)] = sx; pts[2 * (1 + 2 * lane) + 1] = sy;
+        pts[2 * (2 + 2 * lane)] = ex; pts[2 * (2 + 2 * lane) + 1] = ey;
+    }
+    pp_wave_lds_fence();
+}
+
+// "give me ribbon i" over a list in memory, 4 doubles per ribbon (a child slot, a vertex's list, the staged points from the third on)
+__device__ __forceinline__ auto pp_ribbons_at(const double* c) { return [c](int i, double& sx, double& sy, double& ex, double& ey) { sx = c[4 * i]; sy = c[4 * i + 1]; ex = c[4 * i + 2]; ey = c[4 * i + 3]; }; }
 // RibbonManager::maxDistance (RibbonManager.cpp:234-248) from (x, y) over n ribbons in list order.  rib(i, sx, sy, ex, ey) gives ribbon i:
 // from global memory, from another lane's registers or from the LDS point table, whichever the caller holds them in.
 template <class Rib>
@@ -1109,8 +1141,7 @@ __device__ __forceinline__ double pp_max_distance(int n, double w, double x, dou
 }
 // ... with pts = x,y of the query point then of every ribbon's start, end
 __device__ inline double pp_h_max_distance(const double* pts, int n, double w) {
-    return pp_max_distance(n, w, pts[0], pts[1], [&](int i, double& sx, double& sy, double& ex, double& ey) {
-        sx = pts[2 * (1 + 2 * i)]; sy = pts[2 * (1 + 2 * i) + 1]; ex = pts[2 * (2 + 2 * i)]; ey = pts[2 * (2 + 2 * i) + 1]; });
+    return pp_max_distance(n, w, pts[0], pts[1], pp_ribbons_at(pts + 2));
 }
 
 // RibbonManager::tspPointRobotNoSplitAllRibbons (:53-67) and ...KRibbons (:69-94), wave-parallel.

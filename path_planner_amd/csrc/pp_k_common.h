@@ -4,6 +4,15 @@
 #include "../../include/ppgpu.h"
 #include "pp_device.h"
 
+// What the kernels of one costing launch count for one another, and for the host, in ONE 128-byte line.  pp_launch_reset clears it.
+struct __attribute__((aligned(128))) PPLaunchWords {
+    unsigned need_big;                        // raised by a cover sweep that left a child list beyond PP_TSP_MAX ribbons (pp_k_heuristic_big then has work)
+    unsigned live_count;                      // per slice: entries of live_list (pp_k_approach_events); the host sums the slices
+    unsigned hw_count;                        // entries of hw_list (pp_k_cover_finish -> pp_k_heuristic_listed)
+    unsigned defer_count[PP_HL_MAX_N + 1];    // [n] = deferred edges with n ribbons, n = 1 .. PP_HL_MAX_N (pp_k_deferred_list -> pp_k_heuristic_lanes)
+};
+static_assert(sizeof(PPLaunchWords) == 128, "the launch counters share one 128-byte line");
+
 // Everything a costing launch needs, passed by value (kernarg segment, scalar loads).
 struct PPParams {
     // PlannerConfig / Edge constants / RibbonManager settings
@@ -46,12 +55,13 @@ struct PPParams {
     struct PPTrackSummary* track_summary;
     unsigned char* track_skip;           // [edge][nch]  1: the pose sweep skips this 64-step chunk (pp_k_plan_skips); NULL: no skipping
     int2* track_far;                     // [edge] {first event the cover sweep's wave has to visit, last event before it} (pp_k_approach_events)
-    unsigned long long* work;            // the cover sweep's work-queue heads (pp_next_edge), zeroed by pp_k_solve_edges
-    unsigned* live_list; unsigned* live_count;     // {workspace slot, list position} of the edges the cover sweep still has to visit (pp_k_approach_events)
-    unsigned* defer_list; unsigned* defer_count;   // edges whose heuristic the cover sweep left to pp_k_heuristic_lanes
-    unsigned* need_big;                  // set by the cover sweep when some child has 9..12 ribbons (pp_k_heuristic_big then has work)
+    unsigned long long* work;            // the cover sweep's work-queue heads (pp_next_edge), zeroed by pp_launch_reset
+    PPLaunchWords* words;                // the launch's counters
+    int reset_words;                     // pp_launch_reset clears the queue heads AND the counters, need_big included; 0: a sliced trace's re-solve clears neither (no cover sweep follows it)
+    unsigned* live_list;                 // {workspace slot, list position} of the edges the cover sweep still has to visit (pp_k_approach_events)
+    unsigned* defer_list;                // edges whose heuristic the cover sweep left to pp_k_heuristic_lanes
     struct PPCoverState* cover_state;    // [edge] what the cover sweep's wave hands to pp_k_cover_finish (NULL: every wave finishes its own edges)
-    unsigned* hw_list; unsigned* hw_count;   // edges pp_k_cover_finish leaves to pp_k_heuristic_listed (a TSP enumeration of 7 or 8 ribbons)
+    unsigned* hw_list;                   // edges pp_k_cover_finish leaves to pp_k_heuristic_listed (a TSP enumeration of 7 or 8 ribbons)
     int ngp, nch;                        // steps per edge rounded up to whole 64-step chunks, and that many chunks
 };
 
@@ -272,4 +282,10 @@ __device__ __forceinline__ long long pp_next_edge(const PPParams& p, PPQueue& s,
         s.dry++;
     }
     return n;
+}
+// What pp_k_solve_edges (thread e) clears ahead of its slice's kernels: queue heads and live_count per slice, the other counters per launch.
+__device__ __forceinline__ void pp_launch_reset(const PPParams& p, long long e) {
+    if (!p.reset_words) return;
+    if (e < PP_NQ) p.work[(size_t)e * PP_QSTRIDE] = 0ull;
+    if (e == 0) { if (p.e_base == 0) *p.words = PPLaunchWords{}; else p.words->live_count = 0u; }
 }

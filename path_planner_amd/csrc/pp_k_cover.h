@@ -248,7 +248,7 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
         if (threadIdx.x == 0) {
             unsigned tot = 0;
             for (int w = 0; w < PP_APPROACH_THREADS / 64; w++) tot += s_cnt[w];
-            s_base = tot ? atomicAdd(p.live_count, tot) : 0u;
+            s_base = tot ? atomicAdd(&p.words->live_count, tot) : 0u;
         }
         __syncthreads();
         if (live) {
@@ -264,9 +264,6 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
 #ifndef PP_FUSE_HEUR
 #define PP_FUSE_HEUR 1
 #endif
-template <int MAXN>
-__device__ __forceinline__ double pp_h_point_from_pts(int heuristic, int tsp_k, double ribw, double* lds_wave, int nrib, unsigned passFirst = 0u, unsigned passStride = 1u);   // further down, with the heuristics
-
 template <bool GAUSSIAN>
 __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const long long e, const long long eg, double* lds) {
     const int lane = pp_lane();
@@ -729,7 +726,7 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
         if (lane < 16) reinterpret_cast<double*>(rec)[lane] = v;
     }
     if (!throwsRef) {
-        if (nrib > PP_TSP_MAX && lane == 0) atomicOr(p.need_big, 1u);
+        if (nrib > PP_TSP_MAX && lane == 0) atomicOr(&p.words->need_big, 1u);
         if (nrib > p.stride && lane == 0) rec->flags = flags | PPGPU_F_RIBBON_OVF;   // after the record store above
         if ((lane < nrib || lane < handCount) && lane < p.stride) {     // (lanes beyond nrib hold zeros: what is left of the lane's split list goes)
             double* c = p.child + ((size_t)eg * p.stride + lane) * 4;
@@ -737,41 +734,34 @@ __device__ __forceinline__ void pp_cover_sweep_edge(const PPParams& p, const lon
         }
     }
 #if PP_FUSE_HEUR
-    // The edge's heuristic, by this wave, from the ribbons it still holds in registers (point heuristics; the record and the child
-    // ribbons are stored, so nothing of the sweep is live any more): what pp_heuristic_edge<false, PP_TSP_MAX> would do.
-    // large launches: the TSP enumeration of a short list is pp_k_heuristic_lanes' (a few lanes instead of this wave)
-    const bool deferred = !GAUSSIAN && p.defer_h && !throwsRef && nrib <= p.stride && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib);
-    if (deferred && lane == 0) rec->h = PP_H_DEFERRED;
-    if (!GAUSSIAN && p.fuse_h && !deferred && !throwsRef && nrib > 0 && nrib <= p.stride) {          // = pp_heuristic_edge<false, PP_TSP_MAX>
-        const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
-        bool leaveToBigPass = false;
-        const unsigned flags0 = flags;
-        double hdist = 0;
-        if (tsp && nrib > PP_TSP_MAX) {
-            if (pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) leaveToBigPass = true;    // pp_k_heuristic_big fills it in
-            else flags |= PPGPU_F_RIBBON_OVF;
-        } else if (!tsp && nrib > 31) {
-            // MaxDistance over a long list, from the lanes' registers
-            hdist = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
-                sx = pp_readlane(rib.sx, i); sy = pp_readlane(rib.sy, i); ex = pp_readlane(rib.ex, i); ey = pp_readlane(rib.ey, i); });
-        } else {
-            pp_wave_lds_fence();                                   // the event machinery is done with this scratch
-            if (lane == 0) { lds[0] = endX; lds[1] = endY; }
-            if (lane < nrib) {
-                lds[2 * (1 + 2 * lane)] = rib.sx; lds[2 * (1 + 2 * lane) + 1] = rib.sy;
-                lds[2 * (2 + 2 * lane)] = rib.ex; lds[2 * (2 + 2 * lane) + 1] = rib.ey;
+    // The edge's heuristic, by this wave, from the ribbons in its registers (lane i holds ribbon i).  The Gaussian sweep never fuses (cost_modes)
+    // and its LDS row has no room for the tables.  The ONE site that states pp_h_route's conditions in its own words: taken from the function (nrib is
+    // a vector value here, and so is its answer) the cover stage took 0.680 -> 0.715 ms, in these words 0.674 -> 0.668 (profiles/heuristic_routes.txt).
+    // test_every_route_boundary_against_the_oracle holds the two statements together: the same lists through this wave and through those that ask.
+    if constexpr (!GAUSSIAN) {
+        const bool deferred = p.defer_h && !throwsRef && nrib <= p.stride && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib);
+        if (deferred && lane == 0) rec->h = PP_H_DEFERRED;
+        if (p.fuse_h && !deferred && !throwsRef && nrib > 0 && nrib <= p.stride) {
+            const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
+            bool leaveToBigPass = false;
+            const unsigned flags0 = flags;
+            double hdist = 0;
+            if (tsp && nrib > PP_TSP_MAX) {
+                if (pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) leaveToBigPass = true;    // pp_k_heuristic_big fills it in
+                else flags |= PPGPU_F_RIBBON_OVF;
+            } else if (!tsp && nrib > 31) {
+                hdist = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
+                    sx = pp_readlane(rib.sx, i); sy = pp_readlane(rib.sy, i); ex = pp_readlane(rib.ex, i); ey = pp_readlane(rib.ey, i); });
+            } else {
+                pp_wave_lds_fence();                                   // the event machinery is done with this scratch
+                pp_h_stage_points(lds, endX, endY, nrib, [&](int, double& sx, double& sy, double& ex, double& ey) { sx = rib.sx; sy = rib.sy; ex = rib.ex; ey = rib.ey; });
+                hdist = tsp ? pp_h_point_from_pts<PP_TSP_MAX>(p.heuristic, p.tsp_k, p.ribw, lds, nrib, 0u, 1u) : pp_h_max_distance(lds, nrib, p.ribw);
+                pp_wave_lds_fence();
             }
-            pp_wave_lds_fence();
-            hdist = pp_h_point_from_pts<PP_TSP_MAX>(p.heuristic, p.tsp_k, p.ribw, lds, nrib, 0u, 1u);
-            pp_wave_lds_fence();
-        }
-        if (!leaveToBigPass) {
-            const double hh = hdist / p.max_speed * p.tpf;
-            if (lane == 0) { rec->h = hh; rec->f = g + hh; if (flags != flags0) rec->flags = flags | ((nrib > p.stride) ? PPGPU_F_RIBBON_OVF : 0u); }
+            if (!leaveToBigPass && lane == 0) { pp_h_store(rec, g, hdist, p.max_speed, p.tpf); if (flags != flags0) rec->flags = flags; }
         }
     }
 #endif
-
 }
 
 // The wave that finished an edge's cover sweep goes straight on to the edge's heuristic (point heuristics, binary-obstacle
@@ -784,7 +774,7 @@ template <bool GAUSSIAN, int LDS>
 __device__ __forceinline__ void pp_cover_sweep_waves(PPParams p, double (*lds_all)[LDS]) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     PPQueue qs = pp_queue_init();
-    const long long n = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_count)[0] : p.n_edges;
+    const long long n = p.live_list ? (long long)(unsigned)pp_const_i32(&p.words->live_count)[0] : p.n_edges;
     for (long long i = pp_next_edge(p, qs, n); i < n; i = pp_next_edge(p, qs, n)) {
         const long long idx = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[0] : i;
         const long long eg = p.live_list ? (long long)(unsigned)pp_const_i32(p.live_list + 2 * i)[1] : pp_edge_position(p, p.e_base + idx);

@@ -191,8 +191,8 @@ __device__ __forceinline__ int pp_lane_cover_strict(double* c, int nrib, int str
 // QUIET = false, an edge its wave handed over: rin is the edge's child slot, the last cover happens in it.
 // QUIET = true, an edge whose events changed nothing: rin is the vertex's list, which becomes the child's — unless the last cover would
 // happen within reach of a ribbon or a pose is off the curve: then nothing is written and false says "the wave does this edge".
-// Heuristic, as the wave decides it: a list pp_k_heuristic_lanes enumerates is marked PP_H_DEFERRED; MaxDistance is computed here; a TSP
-// enumeration of 7 or 8 ribbons goes on pp_k_heuristic_listed's list (a wave per such edge).
+// Heuristic, by pp_h_route: a list pp_k_heuristic_lanes enumerates is marked PP_H_DEFERRED; MaxDistance is computed here; a wave-form
+// enumeration (7 or 8 ribbons) goes on pp_k_heuristic_listed's list.
 template <bool QUIET>
 __device__ __forceinline__ bool pp_lane_phase_c(const PPParams& p, const PPEdgeSetupBody* S, const PPLaneCurve& cv, const ppgpu_vertex* V, long long e, long long eg,
                                                 const PPCoverState& st, int limit, int cnt, const double* tg, const PPLaneRibbons& rin, double* r) {
@@ -239,30 +239,22 @@ __device__ __forceinline__ bool pp_lane_phase_c(const PPParams& p, const PPEdgeS
     const double trueCost = tc * p.tpf + penalty;                                 // :199
     const double g = V->g + trueCost;                                             // Vertex::setCurrentCost
     flags |= pp_done_goal_flags(p, nrib, endTime, cct);
-    if (nrib > PP_TSP_MAX) atomicOr(p.need_big, 1u);
+    if (nrib > PP_TSP_MAX) atomicOr(&p.words->need_big, 1u);
     if (nrib > p.stride) flags |= PPGPU_F_RIBBON_OVF;
-    // ---- h: Vertex::computeApproxToGo
+    // ---- h: Vertex::computeApproxToGo, as pp_h_route says.  A lane marks, computes MaxDistance in place, and lists what needs a wave.
     double h = 0;
-    bool listed = false;
-    if (p.defer_h && nrib <= p.stride && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib)) {
-        h = PP_H_DEFERRED;
-    } else if (p.fuse_h && nrib > 0 && nrib <= p.stride) {
-        const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
-        if (tsp && nrib > PP_TSP_MAX) {
-            if (!pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) flags |= PPGPU_F_RIBBON_OVF;      // else pp_k_heuristic_big fills it in
-        } else if (!tsp) {
-            h = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
-                    sx = rin.rp[4 * i]; sy = rin.rp[4 * i + 1]; ex = rin.rp[4 * i + 2]; ey = rin.rp[4 * i + 3]; }) / p.max_speed * p.tpf;
-        } else {
-            listed = true;                                      // a TSP enumeration the lanes do not take: a wave's work
-        }
-    }
+    const PPHRoute route = pp_h_route(p.heuristic, p.tsp_k, nrib, p.stride, p.fuse_h, p.defer_h);
+    if (route == PP_HR_LANES) h = PP_H_DEFERRED;
+    if (route == PP_HR_OVERFLOW) flags |= PPGPU_F_RIBBON_OVF;               // (PP_HR_BIG: pp_k_heuristic_big fills it in)
+    if (route == PP_HR_MAX_DISTANCE)
+        h = pp_h_cost(pp_max_distance(nrib, p.ribw, endX, endY, pp_ribbons_at(rin.rp)), p.max_speed, p.tpf);
+    const bool listed = route == PP_HR_WAVE;                                // pp_k_heuristic_listed: a workgroup per such edge
     PPRecordFields f;
     f.nrib = nrib; f.steps = stop.steps; f.flags = flags; f.trueCost = trueCost; f.penalty = penalty;
     f.endX = endX; f.endY = endY; f.endHeading = endHeading; f.speed = cv.speed; f.endTime = endTime; f.g = g; f.h = h; f.cct = cct;
     pp_lane_store_record(r, S, f);
     if (QUIET) pp_with_ribbons(rin, [&](auto rr, int n) { pp_copy_ribbons(c, rr, n); return 0; });
-    if (listed) p.hw_list[atomicAdd(p.hw_count, 1u)] = (unsigned)eg;
+    if (listed) p.hw_list[atomicAdd(&p.words->hw_count, 1u)] = (unsigned)eg;
     return true;
 }
 
@@ -278,7 +270,7 @@ __device__ __forceinline__ bool pp_finish_quiet_edge(const PPParams& p, const PP
     // an empty list reach this function, must relax that assumption with it — otherwise the behaviour is undefined.
     if (nrib > p.stride || nrib > PP_TSP_MAX) return false;
     if (p.n_obst > 0 && p.obst_model == PPGPU_OBST_GAUSSIAN) return false;
-    if (p.fuse_h && p.heuristic != PPGPU_H_MAX_DISTANCE && !(p.defer_h && pp_lane_tsp_ok(p.heuristic, p.tsp_k, nrib))) return false;
+    if (pp_h_route(p.heuristic, p.tsp_k, nrib, p.stride, p.fuse_h, p.defer_h) == PP_HR_WAVE) return false;
     const double wEnd = S->wEnd;
     PPCoverState st;
     st.endTime = fmin(p.horizon + 1e-12 + p.sst, wEnd);                      // Edge.cpp:90; no event shortened it
@@ -294,7 +286,7 @@ __device__ __forceinline__ bool pp_finish_quiet_edge(const PPParams& p, const PP
 #define PP_FINISH_THREADS 64
 #endif
 __global__ __launch_bounds__(PP_FINISH_THREADS) void pp_k_cover_finish(PPParams p) {
-    const unsigned nlive = (unsigned)pp_const_i32(p.live_count)[0];
+    const unsigned nlive = (unsigned)pp_const_i32(&p.words->live_count)[0];
     const unsigned li = blockIdx.x * PP_FINISH_THREADS + threadIdx.x;
     if (li >= nlive) return;
     const long long e = p.ws_base + (long long)p.live_list[2 * (size_t)li];

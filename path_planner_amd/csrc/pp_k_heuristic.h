@@ -1,27 +1,30 @@
-// pp_k_heuristic.h — Vertex::computeApproxToGo (Vertex.cpp:49-64): the wave-per-edge heuristic kernels, the workgroup-per-edge kernel for
-// lists of 7-8 ribbons and the four-lanes-per-edge kernel for short lists.  Included by pp_kernels.h.
+// pp_k_heuristic.h — Vertex::computeApproxToGo (Vertex.cpp:49-64) for every costed edge: h = heuristic(child pose, child ribbons) /
+// maxSpeed, f = g + h, patched into the edge's record.  Included by pp_kernels.h.
+//
+// Who computes it is pp_h_route's answer (pp_device.h), asked by every site with the launch's fuse_h / defer_h (the host's cost_modes):
+//   route               who acts on it
+//   PP_HR_NONE          nobody: h stays 0 (no ribbon left, a list cut at the child slot; or !fuse_h: pp_k_heuristic* asks again, later)
+//   PP_HR_MAX_DISTANCE  the asker, in place: a wave (pp_cover_sweep_edge's tail, pp_heuristic_edge), a finish or quiet lane (pp_lane_phase_c)
+//   PP_HR_LANES         the asker writes PP_H_DEFERRED; pp_k_deferred_list packs the marked records, pp_k_heuristic_lanes enumerates
+//   PP_HR_WAVE          a wave enumerates now (pp_cover_sweep_edge's tail, pp_heuristic_edge, pp_heuristic_edge_dubins); a finish
+//                       lane appends the edge to hw_list for pp_k_heuristic_listed, a workgroup per edge; the quiet lane refuses the edge
+//   PP_HR_BIG           the asker leaves it; pp_k_heuristic_big takes exactly these, a workgroup per edge
+//   PP_HR_OVERFLOW      the asker sets PPGPU_F_RIBBON_OVF, h = 0; pp_k_tsp_table_list takes the flagged records when the table is on
+// Unfused launches (Dubins heuristics, Gaussian model, -DPP_FUSE_HEUR=0) and ppgpu_heuristic_host run pp_k_heuristic / pp_k_heuristic_dubins over every
+// record, a wave per edge.  The cover sweep's wave alone states the rule's conditions in its own words instead of asking (pp_k_cover.h says why).
 #pragma once
-// ------------------------------------------------------------------------------------------
-// Vertex::computeApproxToGo (Vertex.cpp:49-64) for every costed edge: h = heuristic(child pose,
-// child ribbons) / maxSpeed, f = g + h, patched into the edge's record.  Its own kernel so that the
-// sweep kernel's register budget is not set by the TSP enumeration.  One wavefront per edge.
 #ifndef PP_H_MIN_WAVES
 #define PP_H_MIN_WAVES 6   // measured: 1 (87 VGPRs, 5 waves) 1.12 ms, 6 (72 VGPRs) 1.06 ms, 8 (63 VGPRs) 1.09 ms
 #endif
-// DUBINS = the two Dubins-TSP heuristics (RibbonManager.cpp:97-140): the same enumeration over a table of Dubins
-// distances between oriented ribbon endpoints.  A separate instantiation so that the six-word solve does not set the
-// register budget of the common kernel.  MAXN = 8: every edge; MAXN = 12: a second pass that only touches the edges whose
-// 9..12 child ribbons the first pass left for it (pp_tsp_big_ok).
-// MaxDistance / TspPointRobotNoSplit{All,K}Ribbons from the points staged in the wave's LDS (x,y of the query point, then
-// start / end of every ribbon): distance table, nearest-endpoint table, enumeration.  nrib <= MAXN for the TSP variants.
+// TspPointRobotNoSplit{All,K}Ribbons from the points staged in the wave's LDS (pp_h_stage_points): distance table, nearest-endpoint
+// table, enumeration.  nrib <= MAXN.  MAXN = 8: the common tables; MAXN = 12: pp_k_heuristic_big's.
 template <int MAXN>
-__device__ __forceinline__ double pp_h_point_from_pts(int heuristic, int tsp_k, double ribw, double* lds_wave, int nrib, unsigned passFirst, unsigned passStride) {
+__device__ __forceinline__ double pp_h_point_from_pts(int heuristic, int tsp_k, double ribw, double* lds_wave, int nrib, unsigned passFirst = 0u, unsigned passStride = 1u) {
     typedef PPTsp<MAXN> TS;
     const int lane = pp_lane();
     double* pts = lds_wave;
     double* T = lds_wave + PP_WAVE * 2;
     double* KM = T + TS::PTS * (TS::PTS - 1);
-    if (heuristic == PPGPU_H_MAX_DISTANCE) return pp_h_max_distance(pts, nrib, ribw);
     const int npts = 2 * nrib + 1;
     const int ncol = npts - 1;
     for (int idx = lane; idx < npts * ncol; idx += PP_WAVE) {      // all distances, once
@@ -38,74 +41,72 @@ __device__ __forceinline__ double pp_h_point_from_pts(int heuristic, int tsp_k, 
     return pp_h_tsp_point<MAXN>(T, KM, nrib, ribw, tsp_k, true, nullptr, passFirst, passStride);
 }
 
-
-template <bool DUBINS, int MAXN>
+// A record of an unfused launch, by one wave, as pp_h_route says (nothing is deferred where these kernels run: cost_modes): the point heuristics.
+// INVARIANT: a record gets here with h = 0 and f = g (the sweeps store them so, ppgpu_heuristic_host zeroes its records); none / big / overflow store neither.
 __device__ __forceinline__ void pp_heuristic_edge(const PPParams& p, const long long e, double* lds_wave) {
+    const int lane = pp_lane();
+    ppgpu_edge_result* rec = p.out + e;
+    const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->flags);
+    if (flags & PPGPU_F_THROWS) return;
+    const int nrib = (int)((__builtin_amdgcn_readfirstlane((int)rec->info) >> 8) & 0xff);
+    const PPHRoute route = pp_h_route(p.heuristic, p.tsp_k, nrib, p.stride, 1, 0);
+    if (route == PP_HR_OVERFLOW && lane == 0) rec->flags = flags | PPGPU_F_RIBBON_OVF;          // (h = 0, f = g: as the record stands)
+    if (route != PP_HR_MAX_DISTANCE && route != PP_HR_WAVE) return;                              // (PP_HR_BIG: pp_k_heuristic_big's)
+    const double endX = rec->end_x, endY = rec->end_y, g = rec->g;
+    const auto rib = pp_ribbons_at(p.child + (size_t)e * p.stride * 4);
+    double hdist;
+    if (route == PP_HR_MAX_DISTANCE && nrib > 31) {                   // a long list: walked directly, no table
+        hdist = pp_max_distance(nrib, p.ribw, endX, endY, rib);
+    } else {
+        pp_h_stage_points(lds_wave, endX, endY, nrib, rib);
+        hdist = (route == PP_HR_MAX_DISTANCE) ? pp_h_max_distance(lds_wave, nrib, p.ribw) : pp_h_point_from_pts<PP_TSP_MAX>(p.heuristic, p.tsp_k, p.ribw, lds_wave, nrib);
+    }
+    if (lane == 0) pp_h_store(rec, g, hdist, p.max_speed, p.tpf);
+}
+// The two Dubins-TSP heuristics (RibbonManager.cpp:97-140), as pp_h_route says (a wave up to PP_TSP_MAX ribbons, overflow beyond): the enumeration over
+// a table of Dubins distances between oriented ribbon endpoints.  Their own kernel: the six-word solve does not set the common one's register budget.
+__device__ __forceinline__ void pp_heuristic_edge_dubins(const PPParams& p, const long long e, double* lds_wave) {
+    constexpr int MAXN = PP_TSP_MAX;
     typedef PPTsp<MAXN> TS;
-    const bool bigPass = MAXN > PP_TSP_MAX;
     const int lane = pp_lane();
     double* pts = lds_wave;                      // x,y of the query point, then start/end of every child ribbon
-    double* T = lds_wave + PP_WAVE * 2;          // distance table of the TSP heuristics
-    double* KM = T + TS::PTS * (TS::PTS - 1);    // KM[p][i] = distance from point p to the nearer endpoint of ribbon i
+    double* T = lds_wave + PP_WAVE * 2;          // the table of Dubins distances
+    double* KM = T + TS::PTS * (TS::PTS - 1);
     ppgpu_edge_result* rec = p.out + e;
-    unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->flags);
+    const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->flags);
     if (flags & PPGPU_F_THROWS) return;
-    int nrib = (int)((__builtin_amdgcn_readfirstlane((int)rec->info) >> 8) & 0xff);
-    const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
-    if (bigPass && !(tsp && nrib <= p.stride && pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib))) return;
+    const int nrib = (int)((__builtin_amdgcn_readfirstlane((int)rec->info) >> 8) & 0xff);
+    const PPHRoute route = pp_h_route(p.heuristic, p.tsp_k, nrib, p.stride, 1, 0);
+    if (route == PP_HR_OVERFLOW && lane == 0) rec->flags = flags | PPGPU_F_RIBBON_OVF;          // (h = 0, f = g: as the record stands)
+    if (route != PP_HR_WAVE) return;
     const double endX = rec->end_x, endY = rec->end_y, g = rec->g;
-    double hdist = 0;
-    if (nrib > 0 && nrib <= p.stride) {          // a truncated list (already flagged) carries no heuristic
-        if (tsp && nrib > MAXN) {
-            if (pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib)) return;            // the MAXN = 12 pass fills it in
-            flags |= PPGPU_F_RIBBON_OVF;
-        } else if (!tsp && nrib > 31) {
-            // MaxDistance over a long list: straight from global memory, no table
-            hdist = pp_max_distance(nrib, p.ribw, endX, endY, [&](int i, double& sx, double& sy, double& ex, double& ey) {
-                const double* c = p.child + ((size_t)e * p.stride + i) * 4;
-                sx = c[0]; sy = c[1]; ex = c[2]; ey = c[3]; });
-        } else {
-            if (lane == 0) { pts[0] = endX; pts[1] = endY; }
-            if (lane < nrib) {
-                const double* c = p.child + ((size_t)e * p.stride + lane) * 4;
-                pts[2 * (1 + 2 * lane)] = c[0]; pts[2 * (1 + 2 * lane) + 1] = c[1];
-                pts[2 * (2 + 2 * lane)] = c[2]; pts[2 * (2 + 2 * lane) + 1] = c[3];
-            }
-            pp_wave_lds_fence();
-            const int npts = 2 * nrib + 1;
-            const int ncol = npts - 1;
-            if (!tsp || !DUBINS) {
-                hdist = pp_h_point_from_pts<MAXN>(p.heuristic, p.tsp_k, p.ribw, lds_wave, nrib);
-            } else {
-                // Oriented endpoints (Ribbon::startAsState / endAsState, Ribbon.cpp:60-70: at one end, heading towards the
-                // other); the query pose passes the child's HEADING where the callee says yaw (Vertex.cpp:51) — kept.
-                double* YAW = KM;                        // yaw of point q (q >= 1), then the ribbon lengths
-                double* LEN = KM + TS::PTS;
-                if (lane < nrib) {
-                    const double sx = pts[2 * (1 + 2 * lane)], sy = pts[2 * (1 + 2 * lane) + 1];
-                    const double ex = pts[2 * (2 + 2 * lane)], ey = pts[2 * (2 + 2 * lane) + 1];
-                    YAW[1 + 2 * lane] = pp_yaw(pp_heading_to(sx, sy, ex, ey));
-                    YAW[2 + 2 * lane] = pp_yaw(pp_heading_to(ex, ey, sx, sy));
-                    LEN[lane] = sqrt(pp_sq_len(sx, sy, ex, ey));                       // Ribbon::length()
-                }
-                if (lane == 0) YAW[0] = rec->end_heading;
-                pp_wave_lds_fence();
-                for (int idx = lane; idx < npts * ncol; idx += PP_WAVE) {      // RibbonManager::dubinsDistance for every ordered pair
-                    const int pp = (int)pp_udiv_small((unsigned)idx, (unsigned)ncol), qq = 1 + (idx - pp * ncol);
-                    PPDubins d;
-                    pp_dubins_shortest(pts[2 * pp], pts[2 * pp + 1], YAW[pp], pts[2 * qq], pts[2 * qq + 1], YAW[qq], p.h_rho, d);
-                    T[pp * (TS::PTS - 1) + (qq - 1)] = pp_dubins_length(d, p.h_rho);
-                }
-                pp_wave_lds_fence();
-                // K variant: its comparator compares r1 with r1 (:121-122), so the sort changes nothing, and its counter is
-                // never incremented (:128), so every ribbon is branched: the All enumeration, unless K <= 0 (nothing runs)
-                const int K = (p.heuristic == PPGPU_H_TSP_DUBINS_K && p.tsp_k <= 0) ? 0 : MAXN;
-                hdist = pp_h_tsp_point<MAXN>(T, KM, nrib, p.ribw, K, false, LEN);
-            }
-        }
+    pp_h_stage_points(pts, endX, endY, nrib, pp_ribbons_at(p.child + (size_t)e * p.stride * 4));
+    const int npts = 2 * nrib + 1, ncol = npts - 1;
+    // Oriented endpoints (Ribbon::startAsState / endAsState, Ribbon.cpp:60-70: at one end, heading towards the
+    // other); the query pose passes the child's HEADING where the callee says yaw (Vertex.cpp:51) — kept.
+    double* YAW = KM;                        // yaw of point q (q >= 1), then the ribbon lengths
+    double* LEN = KM + TS::PTS;
+    if (lane < nrib) {
+        const double sx = pts[2 * (1 + 2 * lane)], sy = pts[2 * (1 + 2 * lane) + 1];
+        const double ex = pts[2 * (2 + 2 * lane)], ey = pts[2 * (2 + 2 * lane) + 1];
+        YAW[1 + 2 * lane] = pp_yaw(pp_heading_to(sx, sy, ex, ey));
+        YAW[2 + 2 * lane] = pp_yaw(pp_heading_to(ex, ey, sx, sy));
+        LEN[lane] = sqrt(pp_sq_len(sx, sy, ex, ey));                       // Ribbon::length()
     }
-    const double h = hdist / p.max_speed * p.tpf;
-    if (lane == 0) { rec->h = h; rec->f = g + h; rec->flags = flags; }
+    if (lane == 0) YAW[0] = rec->end_heading;
+    pp_wave_lds_fence();
+    for (int idx = lane; idx < npts * ncol; idx += PP_WAVE) {      // RibbonManager::dubinsDistance for every ordered pair
+        const int pp = (int)pp_udiv_small((unsigned)idx, (unsigned)ncol), qq = 1 + (idx - pp * ncol);
+        PPDubins d;
+        pp_dubins_shortest(pts[2 * pp], pts[2 * pp + 1], YAW[pp], pts[2 * qq], pts[2 * qq + 1], YAW[qq], p.h_rho, d);
+        T[pp * (TS::PTS - 1) + (qq - 1)] = pp_dubins_length(d, p.h_rho);
+    }
+    pp_wave_lds_fence();
+    // K variant: its comparator compares r1 with r1 (:121-122), so the sort changes nothing, and its counter is
+    // never incremented (:128), so every ribbon is branched: the All enumeration, unless K <= 0 (nothing runs)
+    const int K = (p.heuristic == PPGPU_H_TSP_DUBINS_K && p.tsp_k <= 0) ? 0 : MAXN;
+    const double hdist = pp_h_tsp_point<MAXN>(T, KM, nrib, p.ribw, K, false, LEN);
+    if (lane == 0) pp_h_store(rec, g, hdist, p.max_speed, p.tpf);
 }
 #ifndef PP_H_WPB
 #define PP_H_WPB PP_WPB   // wavefronts per workgroup of the heuristic kernels
@@ -114,93 +115,65 @@ __global__ __launch_bounds__(PP_H_WPB * 64, PP_H_MIN_WAVES) void pp_k_heuristic(
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
     int wave;
     const long long e = pp_wave_edge<PP_H_WPB>(wave);
-    if (e < p.n_edges) pp_heuristic_edge<false, PP_TSP_MAX>(p, e, lds_all[wave]);
+    if (e < p.n_edges) pp_heuristic_edge(p, e, lds_all[wave]);
 }
 __global__ __launch_bounds__(PP_H_WPB * 64) void pp_k_heuristic_dubins(PPParams p) {
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
     int wave;
     const long long e = pp_wave_edge<PP_H_WPB>(wave);
-    if (e < p.n_edges) pp_heuristic_edge<true, PP_TSP_MAX>(p, e, lds_all[wave]);
+    if (e < p.n_edges) pp_heuristic_edge_dubins(p, e, lds_all[wave]);
 }
-// TspPointRobotNoSplitKRibbons on child lists of 9..12 ribbons (rare: a vertex whose ribbons were split many times).  A whole
-// WORKGROUP of sixteen wavefronts per such edge (round 4): every wave builds the same tables and takes every sixteenth pass of 64
-// prefixes, the smallest of their minima is the minimum (exact, as in pp_k_heuristic_listed).  One wave per edge took a
-// millisecond per edge — up to two million prefixes — and in a planner round trip, where such an edge comes alone, that
-// millisecond was the round trip's: the deadline guard's largest under-predictions.
+
+// A TSP enumeration by a whole WORKGROUP of WPB wavefronts for one edge (0 < nrib <= MAXN, nrib <= p.stride): every wave builds the
+// same tables in its own row of lds_all and takes every WPB-th pass of 64 prefixes; the smallest of their minima is the minimum (exact).
+template <int MAXN, int WPB>
+__device__ __forceinline__ void pp_heuristic_workgroup_edge(const PPParams& p, const long long e, const int nrib, double (*lds_all)[PPTsp<MAXN>::LDS], double* s_part) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    ppgpu_edge_result* rec = p.out + e;
+    const double endX = rec->end_x, endY = rec->end_y, g = rec->g;
+    pp_h_stage_points(lds_all[wave], endX, endY, nrib, pp_ribbons_at(p.child + (size_t)e * p.stride * 4));
+    const double part = pp_h_point_from_pts<MAXN>(p.heuristic, p.tsp_k, p.ribw, lds_all[wave], nrib, (unsigned)wave, (unsigned)WPB);
+    if (pp_lane() == 0) s_part[wave] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double hdist = s_part[0];
+        for (int w = 1; w < WPB; w++) hdist = fmin(hdist, s_part[w]);
+        pp_h_store(rec, g, hdist, p.max_speed, p.tpf);
+    }
+    __syncthreads();
+}
+// PP_HR_BIG: TspPointRobotNoSplitKRibbons on child lists of 9..12 ribbons (rare: a vertex whose ribbons were split many times), sixteen
+// waves per edge (round 4).  One wave per edge took a millisecond per edge — up to two million prefixes — and in a planner round trip,
+// where such an edge comes alone, that millisecond was the round trip's: the deadline guard's largest under-predictions.
 #define PP_BIG_GRID 1024
 #define PP_BIG_WPB 16
 __global__ __launch_bounds__(PP_BIG_WPB * 64) void pp_k_heuristic_big(PPParams p) {
     __shared__ double lds_all[PP_BIG_WPB][PPTsp<PP_TSP_MAX_BIG>::LDS];
     __shared__ double s_part[PP_BIG_WPB];
-    if (pp_const_i32(p.need_big)[0] == 0) return;            // almost always: no child list beyond 8 ribbons in this launch
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = pp_lane();
-    double* pts = lds_all[wave];
-    const bool tsp = p.heuristic != PPGPU_H_MAX_DISTANCE;
+    if (pp_const_i32(&p.words->need_big)[0] == 0) return;    // almost always: no child list beyond 8 ribbons in this launch
     // a modest grid whose workgroups stride over the edges (ppgpu.hip: at most PP_BIG_GRID workgroups)
     for (long long e = (long long)blockIdx.x; e < p.n_edges; e += (long long)gridDim.x) {
-        ppgpu_edge_result* rec = p.out + e;
-        const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->flags);
-        if (flags & PPGPU_F_THROWS) continue;
+        const ppgpu_edge_result* rec = p.out + e;
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)rec->flags) & PPGPU_F_THROWS) continue;
         const int nrib = (int)((__builtin_amdgcn_readfirstlane((int)rec->info) >> 8) & 0xff);
-        if (!(tsp && nrib <= p.stride && pp_tsp_big_ok(p.heuristic, p.tsp_k, nrib))) continue;      // (pp_heuristic_edge's own gate for this pass)
-        const double endX = rec->end_x, endY = rec->end_y, g = rec->g;
-        if (lane == 0) { pts[0] = endX; pts[1] = endY; }
-        if (lane < nrib) {
-            const double* c = p.child + ((size_t)e * p.stride + lane) * 4;
-            pts[2 * (1 + 2 * lane)] = c[0]; pts[2 * (1 + 2 * lane) + 1] = c[1];
-            pts[2 * (2 + 2 * lane)] = c[2]; pts[2 * (2 + 2 * lane) + 1] = c[3];
-        }
-        pp_wave_lds_fence();
-        const double part = pp_h_point_from_pts<PP_TSP_MAX_BIG>(p.heuristic, p.tsp_k, p.ribw, pts, nrib, (unsigned)wave, (unsigned)PP_BIG_WPB);
-        if (lane == 0) s_part[wave] = part;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double hdist = s_part[0];
-            for (int w = 1; w < PP_BIG_WPB; w++) hdist = fmin(hdist, s_part[w]);
-            const double h = hdist / p.max_speed * p.tpf;
-            rec->h = h; rec->f = g + h;
-        }
-        __syncthreads();
+        if (pp_h_route(p.heuristic, p.tsp_k, nrib, p.stride, 1, p.defer_h) != PP_HR_BIG) continue;
+        pp_heuristic_workgroup_edge<PP_TSP_MAX_BIG, PP_BIG_WPB>(p, e, nrib, lds_all, s_part);
     }
 }
 
-// The edges pp_k_cover_finish listed (a TSP enumeration of 7 or 8 child ribbons: up to 32 768 leaves): Vertex::computeApproxToGo from
-// the record and the child ribbons, as pp_heuristic_edge does it, by a whole WORKGROUP per edge — its four waves build the
-// same tables, take every fourth pass of 64 prefixes each, and the smallest of their four minima is the minimum (exact).  One wave per
-// edge was ~170 us of a single wave's time for each of config 3's ~1 100 such edges.  The grid pp_k_heuristic would get
+// PP_HR_WAVE of the edges pp_k_cover_finish listed (7 or 8 child ribbons: up to 32 768 leaves; All with 5 or 6), four waves per edge.
+// One wave per edge was ~170 us of a single wave's time for each of config 3's ~1 100 such edges.  The grid pp_k_heuristic would get
 // (the list's length is on the device), striding over the list; usually the list is short or empty.
 __global__ __launch_bounds__(PP_H_WPB * 64, PP_H_MIN_WAVES) void pp_k_heuristic_listed(PPParams p) {
     __shared__ double lds_all[PP_H_WPB][PPTsp<PP_TSP_MAX>::LDS];
     __shared__ double s_part[PP_H_WPB];
-    const unsigned n = (unsigned)pp_const_i32(p.hw_count)[0];
+    const unsigned n = (unsigned)pp_const_i32(&p.words->hw_count)[0];
     if (n == 0 || blockIdx.x >= n) return;
     __builtin_amdgcn_s_setprio(3);           // few, long waves sharing their SIMDs with pp_k_heuristic_lanes' many short ones: issue first
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = pp_lane();
-    double* pts = lds_all[wave];
     for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
         const long long e = (long long)(unsigned)pp_const_i32(p.hw_list + i)[0];
-        ppgpu_edge_result* rec = p.out + e;
-        const int nrib = (int)((__builtin_amdgcn_readfirstlane((int)rec->info) >> 8) & 0xff);      // 7 or 8 (<= PP_TSP_MAX, <= p.stride)
-        const double endX = rec->end_x, endY = rec->end_y, g = rec->g;
-        if (lane == 0) { pts[0] = endX; pts[1] = endY; }
-        if (lane < nrib) {
-            const double* c = p.child + ((size_t)e * p.stride + lane) * 4;
-            pts[2 * (1 + 2 * lane)] = c[0]; pts[2 * (1 + 2 * lane) + 1] = c[1];
-            pts[2 * (2 + 2 * lane)] = c[2]; pts[2 * (2 + 2 * lane) + 1] = c[3];
-        }
-        pp_wave_lds_fence();
-        const double part = pp_h_point_from_pts<PP_TSP_MAX>(p.heuristic, p.tsp_k, p.ribw, pts, nrib, (unsigned)wave, (unsigned)PP_H_WPB);
-        if (lane == 0) s_part[wave] = part;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double hdist = s_part[0];
-            for (int w = 1; w < PP_H_WPB; w++) hdist = fmin(hdist, s_part[w]);
-            const double h = hdist / p.max_speed * p.tpf;
-            rec->h = h; rec->f = g + h;
-        }
-        __syncthreads();
+        const int nrib = (int)((__builtin_amdgcn_readfirstlane((int)p.out[e].info) >> 8) & 0xff);      // <= PP_TSP_MAX, <= p.stride
+        pp_heuristic_workgroup_edge<PP_TSP_MAX, PP_H_WPB>(p, e, nrib, lds_all, s_part);
     }
 }
 // ------------------------------------------------------------------------------------------
@@ -217,7 +190,7 @@ __global__ __launch_bounds__(PP_H_WPB * 64, PP_H_MIN_WAVES) void pp_k_heuristic_
 #endif
 #define PP_HL_TRI(MAXN) ((MAXN) * (2 * (MAXN) - 1) + 1)     // doubles per edge: pairs of 2n endpoints (+1: odd stride)
 #define PP_HL_PTS(MAXN) (4 * (MAXN) + 1)
-struct PPLaneTsp { const double* T; const double* CB; double twoW; int K; bool sortK; unsigned* cnt; };
+struct PPLaneTsp { const double* T; const double* CB; double twoW; int K; bool sortK; };
 // Branch and bound (round 3), exact.  Whatever order the remaining ribbons are visited in, the tour still has to add, for every
 // one of them, its length - 2w and a transition INTO one of its endpoints from an endpoint of another ribbon, which is at least
 // mind[r] = the smallest such distance in the edge's triangle; the fmax(., 0) clamps only raise a sum.  So every leaf below a node
@@ -412,7 +385,7 @@ __global__ __launch_bounds__(256) void pp_k_deferred_list(PPParams p) {
     if (tid < PP_HL_MAX_N) {
         unsigned tot = 0;
         for (int i = 0; i < 4 * PP_DL_PER; i++) { const unsigned c = s_cnt[tid][i]; s_cnt[tid][i] = tot; tot += c; }   // -> offsets
-        s_base[tid] = tot ? atomicAdd(p.defer_count + 1 + tid, tot) : 0u;
+        s_base[tid] = tot ? atomicAdd(&p.words->defer_count[1 + tid], tot) : 0u;
     }
     __syncthreads();
 #pragma unroll
@@ -469,7 +442,7 @@ __device__ __forceinline__ void pp_heuristic_lanes_block(const PPParams& p, cons
     __syncthreads();
     if (have) {
         PPLaneTsp c;
-        c.T = T; c.CB = CB; c.twoW = 2 * p.ribw; c.cnt = p.need_big + 14;
+        c.T = T; c.CB = CB; c.twoW = 2 * p.ribw;
         c.sortK = p.heuristic != PPGPU_H_TSP_POINT_ALL;
         c.K = c.sortK ? p.tsp_k : PP_TSP_MAX;
         double hdist = 0;
@@ -483,8 +456,7 @@ __device__ __forceinline__ void pp_heuristic_lanes_block(const PPParams& p, cons
                 default: hdist = pp_lane_tsp_root<PP_HL_MAX_N>(c, P, qx, qy, sub); break;
             }
         }
-        const double hh = hdist / p.max_speed * p.tpf;
-        if (sub == 0) { rec->h = hh; rec->f = g + hh; }
+        if (sub == 0) pp_h_store(rec, g, hdist, p.max_speed, p.tpf);
     }
 }
 __global__ __launch_bounds__(PP_HL_THREADS, PP_HL_MIN_WAVES) void pp_k_heuristic_lanes(PPParams p) {
@@ -498,7 +470,7 @@ __global__ __launch_bounds__(PP_HL_THREADS, PP_HL_MIN_WAVES) void pp_k_heuristic
     unsigned blk = blockIdx.x, count = 0;
     int n = PP_HL_MAX_N;
     for (; n >= 1; n--) {
-        count = (unsigned)pp_const_i32(p.defer_count + n)[0];
+        count = (unsigned)pp_const_i32(&p.words->defer_count[n])[0];
         const unsigned nblk = (count + (unsigned)PER - 1u) / (unsigned)PER;
         if (blk < nblk) break;
         blk -= nblk;

@@ -14,10 +14,7 @@
 template <bool ALL_WORDS>
 __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    // the queue heads of the cover sweep (it starts after this kernel has ended, in stream order)
-    if (e < PP_NQ) p.work[(size_t)e * PP_QSTRIDE] = 0ull;
-    if (e == 0 && p.live_count) *p.live_count = 0u;
-    if (e == 0 && p.e_base == 0) { *p.need_big = 0u; if (p.defer_count) for (int i = 0; i <= PP_HL_MAX_N; i++) p.defer_count[i] = 0u; if (p.hw_count) *p.hw_count = 0u; }            // raised by the cover sweeps of this launch, read by pp_k_heuristic_big
+    pp_launch_reset(p, e);
     if (e >= p.n_edges) return;
     // The two speeds of a radius (configurations c and c ^ PPGPU_EDGE_SLOW) run along the same curve: in the dense enumeration the
     // lane of the slow edge solves it once and writes both records, each where its own lane would have put it; the fast edge's lane

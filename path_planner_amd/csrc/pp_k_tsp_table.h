@@ -18,7 +18,7 @@
 // set of every reachable state is written once, next to G (M: 16 bits per state), by the lanes that made the state.
 //
 // Dubins variants (DUBINS = true, a kernel of its own): the same recursion over T[p][q] = the Dubins length from oriented point p to
-// oriented point q (pp_heuristic_edge<true, ..>: a ribbon's end faces the other end, the query pose carries the child's heading),
+// oriented point q (pp_heuristic_edge_dubins: a ribbon's end faces the other end, the query pose carries the child's heading),
 // a ribbon's own length from LEN and not from T.  T and LEN are filled by a kernel of their own (pp_k_tsp_table_dubins_T, 256
 // threads: the six-word solve needs more registers than a wave of a 1 024-thread workgroup has — built inside the table kernel it
 // took all 128 and spilled 83 more) into global memory, one block per listed record, and the table kernel copies its record's in.
@@ -116,8 +116,8 @@ __device__ __forceinline__ void pp_tsp_table_run(const PPTspTableArgs& q) {
         const int n = (int)((rec->info >> 8) & 0xffu);   // 1 .. cap (pp_k_tsp_table_list)
         if (nothing) {                                   // the reference's loop body never runs: DBL_MAX (pp_h_tsp_point)
             if (tid == 0) {
-                const double h = PP_DBL_MAX / q.max_speed * q.tpf;
-                rec->h = h; rec->f = rec->g + h; rec->flags &= ~PPGPU_F_RIBBON_OVF;
+                pp_h_store(rec, rec->g, PP_DBL_MAX, q.max_speed, q.tpf);
+                rec->flags &= ~PPGPU_F_RIBBON_OVF;
                 atomicAdd(q.stats, 1ull);
             }
             continue;
@@ -266,8 +266,8 @@ __device__ __forceinline__ void pp_tsp_table_run(const PPTspTableArgs& q) {
                     const double g = G[(size_t)full * row + j];
                     if (g >= 0) hdist = fmin(hdist, g);
                 }
-                const double h = hdist / q.max_speed * q.tpf;
-                rec->h = h; rec->f = rec->g + h; rec->flags &= ~PPGPU_F_RIBBON_OVF;
+                pp_h_store(rec, rec->g, hdist, q.max_speed, q.tpf);
+                rec->flags &= ~PPGPU_F_RIBBON_OVF;
                 atomicAdd(q.stats, 1ull);
             }
         }
@@ -276,7 +276,7 @@ __device__ __forceinline__ void pp_tsp_table_run(const PPTspTableArgs& q) {
 }
 __global__ __launch_bounds__(PP_TT_THREADS) void pp_k_tsp_table(PPTspTableArgs q) { pp_tsp_table_run<false>(q); }
 
-// T and LEN of every listed record for the Dubins variants, exactly as pp_heuristic_edge<true, ..> builds them (the same calls on the
+// T and LEN of every listed record for the Dubins variants, exactly as pp_heuristic_edge_dubins builds them (the same calls on the
 // same values: the same bits).  A workgroup per listed record, striding.
 __global__ __launch_bounds__(256) void pp_k_tsp_table_dubins_T(PPTspTableArgs q) {
     __shared__ double s_pts[2 * PP_TT_PTS];

@@ -5,6 +5,7 @@
 #include "pp_k_common.h"       // PPParams, PPEdgeSetup, clearance map, time grids, edge decoding, work queues
 #include "pp_k_solve.h"        // pp_k_solve_edges
 #include "pp_k_sweep.h"        // pp_k_plan_skips, pp_k_pose_sweep
+#include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
 #include "pp_k_finish.h"       // phase C of an edge: the pieces every route shares, pp_lane_phase_c, pp_k_cover_finish
 #include "pp_k_cover.h"        // pp_k_approach_events, pp_k_cover_sweep
 #include "pp_k_trace_common.h"  // what the traces share: edge head, window walk, record store
@@ -15,7 +16,6 @@
 #include "pp_k_clearance_trace.h"  // pp_k_trace_clearance
 #include "pp_k_keepout.h"      // pp_k_keepout_bits: the distance map thresholded into the effective grid of a keep-out margin
 #include "pp_k_chain.h"        // pp_k_chain_advance
-#include "pp_k_heuristic.h"    // pp_k_heuristic*, pp_k_deferred_list
 #include "pp_k_tsp_table.h"    // pp_k_tsp_table_list, pp_k_tsp_table
 #include "pp_k_expand.h"       // pp_k_dubins_lengths, pp_k_select_nearest, the push-order pipeline, the round trip's pack / unpack
 #include "pp_k_incumbent.h"    // pp_k_best_stage1/2, pp_k_key_min_n

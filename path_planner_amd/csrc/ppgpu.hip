@@ -171,7 +171,7 @@ struct ppgpu_ctx {
     DevBuf<PPTrackSummary> track_summary;
     DevBuf<int2> track_far;
     DevBuf<unsigned char> track_skip;
-    DevBuf<unsigned> need_big;          // [0] need_big, [1 + n] number of deferred edges with n ribbons (pp_k_deferred_list)
+    DevBuf<PPLaunchWords> words;        // the counters the kernels of a launch hand to one another (one 128-byte line)
     DevBuf<unsigned> defer_list, live_list, hw_list;
     DevBuf<PPCoverState> cover_state;
     DevBuf<unsigned long long> work;    // queue heads of the cover sweep's resident grid (pp_next_edge)
@@ -185,7 +185,7 @@ struct ppgpu_ctx {
     double ms_ring[PP_TIMING_RING][4] = {};    // solve / pose / cover / approach time of the slices before the last one of a sliced launch (slice_durations)
     int ev_slot = 0;                           // the set of the launch being recorded / recorded last
     long long last_launch_edges = 0;           // edges of the last costing launch, and whether its cover sweep took a packed list
-    bool last_launch_packed = false;           // (then the list's length is at need_big[12]: last slice)
+    bool last_launch_packed = false;           // (then the list's length is words->live_count: last slice)
     long long live_earlier_slices = 0;
     long long ev_launches = 0;                 // timed launches so far
     int max_vertex_ribbons = 0;
@@ -375,7 +375,7 @@ int ppgpu_last_cover_edges(ppgpu_ctx* c, int64_t* n_edges) {
     if (c->last_launch_packed) {
         unsigned live = 0;
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(&live, c->need_big.p + 12, sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&live, &c->words.p->live_count, sizeof(unsigned), hipMemcpyDeviceToHost));
         *n_edges = (int64_t)live + c->live_earlier_slices;
     }
     return PPGPU_OK;
@@ -1022,7 +1022,7 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.cpf = g.collision_penalty_factor; p.tpf = g.time_penalty_factor;
     p.heuristic = g.heuristic; p.tsp_k = g.tsp_k; p.h_rho = g.heuristic_turning_radius;
     p.fuse_h = 0;
-    p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.defer_count = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.live_count = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.hw_count = nullptr;
+    p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.words = nullptr; p.reset_words = 0;
     p.grid = PPGrid{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
     p.obst = c->obst.p; p.n_obst = c->n_obst; p.obst_model = c->obst_model;
     p.verts = c->verts.p; p.ribbons = c->ribbons.p; p.tgrid = c->tgrid.p; p.ng = c->ng; p.nverts = c->nverts;
@@ -1188,6 +1188,7 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
     // and solved curves (a given curve may start late or end early)
     m.prepasses = total >= c->prepass_min_edges;
     m.skip_chunks = m.prepasses && !p.wedges && (c->rows == 0 || c->grid_clear.p) && p.ng >= PP_WAVE;
+    // fuse_h / defer_h: decided here and nowhere else; every kernel that routes a child list reads them through pp_h_route (pp_device.h)
     const bool dubinsH = p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K;
     m.fuse_h = PP_FUSE_HEUR && !dubinsH && !m.gaussian;
     m.defer_h = m.fuse_h && m.prepasses && c->lane_heuristic && total < (1ll << 32) &&
@@ -1226,26 +1227,26 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
         return rc;
     if (m.gaussian && ((rc = c->track_pen.reserve(ws * p.ngp, false, st)) || (rc = c->track_chunk_pen.reserve(ws * p.nch, false, st))))
         return rc;
-    if ((rc = c->need_big.reserve(32, false, st)) || (rc = c->work.reserve(PP_WORK_WORDS, false, st))) return rc;
+    if ((rc = c->words.reserve(1, false, st)) || (rc = c->work.reserve(PP_WORK_WORDS, false, st))) return rc;
     p.setup = c->setup.p; p.track_hits = c->track_hits.p; p.track_eq = c->track_eq.p;
     p.track_chunk_hits = c->track_chunk_hits.p; p.track_summary = c->track_summary.p;
     p.track_far = m.prepasses ? c->track_far.p : nullptr;
     p.track_skip = m.skip_chunks ? c->track_skip.p : nullptr;
     p.track_pen = c->track_pen.p; p.track_chunk_pen = c->track_chunk_pen.p;
-    p.need_big = c->need_big.p;   // cleared by the first slice's pp_k_solve_edges
+    p.words = c->words.p; p.reset_words = 1;      // cleared by pp_k_solve_edges (pp_launch_reset)
     p.work = c->work.p;
     p.fuse_h = m.fuse_h; p.defer_h = m.defer_h; p.quiet_finish = m.quiet_finish; p.lane_split = m.lane_split;
     if (m.packed) {
         if ((rc = c->live_list.reserve(ws * 2, false, st))) return rc;
-        p.live_list = c->live_list.p; p.live_count = c->need_big.p + 12;
+        p.live_list = c->live_list.p;
     }
     if (m.lane_finish) {
         if ((rc = c->cover_state.reserve(ws, false, st)) || (rc = c->hw_list.reserve(total, false, st))) return rc;
-        p.cover_state = c->cover_state.p; p.hw_list = c->hw_list.p; p.hw_count = c->need_big.p + 13;
+        p.cover_state = c->cover_state.p; p.hw_list = c->hw_list.p;
     }
     if (m.defer_h) {
         if ((rc = c->defer_list.reserve(total * PP_HL_MAX_N, false, st))) return rc;
-        p.defer_list = c->defer_list.p; p.defer_count = c->need_big.p + 16;     // [n] = deferred edges with n ribbons, n = 1 .. PP_HL_MAX_N
+        p.defer_list = c->defer_list.p;
     }
     return PPGPU_OK;
 }
@@ -1259,7 +1260,7 @@ static int bank_slice_timing(ppgpu_ctx* c, bool packed) {
     int rc = slice_durations(ev, ms);
     if (rc) return rc;
     for (int i = 0; i < 4; i++) c->ms_ring[c->ev_slot][i] += ms[i];
-    if (packed) { unsigned live = 0; HIP_TRY(hipMemcpy(&live, c->need_big.p + 12, sizeof(unsigned), hipMemcpyDeviceToHost)); c->live_earlier_slices += live; }
+    if (packed) { unsigned live = 0; HIP_TRY(hipMemcpy(&live, &c->words.p->live_count, sizeof(unsigned), hipMemcpyDeviceToHost)); c->live_earlier_slices += live; }
     return PPGPU_OK;
 }
 
@@ -1515,7 +1516,7 @@ static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r
         q.e_base = e0; q.n_edges = (total - e0 < pass) ? (total - e0) : pass;
         q.ws_base = reuse ? e0 : 0;
         if (!reuse) {
-            q.live_count = nullptr; q.defer_count = nullptr; q.hw_count = nullptr;     // (counters of the costing launch: ppgpu_last_cover_edges still reads them)
+            q.reset_words = 0;       // (the counters are the costing launch's: ppgpu_last_cover_edges still reads them)
             hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
         }
         unsigned char* dst = host ? c->tmp_trace.p : recs;
@@ -1757,16 +1758,16 @@ int ppgpu_heuristic_host(ppgpu_ctx* c, int32_t n, const double* poses3, const in
         off += (size_t)counts[i];
     }
     if ((rc = c->tmp_results.reserve((size_t)n, false, c->stream)) || (rc = c->tmp_child.reserve(child.size(), false, c->stream)) ||
-        (rc = c->need_big.reserve(32, false, c->stream)))
+        (rc = c->words.reserve(1, false, c->stream)))
         return rc;
     HIP_TRY(hipMemcpyAsync(c->tmp_results.p, rec.data(), rec.size() * sizeof(ppgpu_edge_result), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->tmp_child.p, child.data(), child.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned one = 1u;       // let the 12-ribbon pass look at every record
-    HIP_TRY(hipMemcpyAsync(c->need_big.p, &one, sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(&c->words.p->need_big, &one, sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
     PPParams p;
     fill_params(c, p);
     p.edges = nullptr; p.wedges = nullptr; p.n_edges = n; p.total_edges = n; p.e_base = 0; p.ws_base = 0;
-    p.out = c->tmp_results.p; p.child = c->tmp_child.p; p.stride = stride; p.need_big = c->need_big.p;
+    p.out = c->tmp_results.p; p.child = c->tmp_child.p; p.stride = stride; p.words = c->words.p;
     const dim3 grid((unsigned)((n + PP_H_WPB - 1) / PP_H_WPB)), block(PP_H_WPB * 64);   // n is small: never more than fits
     if (p.heuristic == PPGPU_H_TSP_DUBINS_ALL || p.heuristic == PPGPU_H_TSP_DUBINS_K) hipLaunchKernelGGL(pp_k_heuristic_dubins, grid, block, 0, c->stream, p);
     else hipLaunchKernelGGL(pp_k_heuristic, grid, block, 0, c->stream, p);

@@ -1,7 +1,9 @@
 """Developer tool (GPU box): sha256 of the records and child ribbons of one costing launch of the bench workload (config 3, dense
 from the root) — to check that a variant build (PPGPU_LIB_OVERRIDE) produces the same bytes as the default one.
 
-    records_hash.py [n_samples]      the costing launch
+    records_hash.py [n_samples] [--heuristic N [--tsp-k K]] [--gaussian]
+                                     the costing launch; under heuristic N of ppgpu.h (0 MaxDistance .. 4 Dubins K) and branching K
+                                     instead of config 3's own, with the obstacles as Gaussian rows instead of boxes
     records_hash.py --traces         the three edge traces instead: results, counts, records, summaries and final lists of the step,
                                      cover and contact traces over the test worlds (test_gpu_trace's world_binary and custom-covariance
                                      Gaussian world, cover_replay's cfg3, sweep_worlds' count65, contact_replay's edges_world with its
@@ -14,16 +16,27 @@ from path_planner_amd import api, workloads
 LIB = os.environ.get("PPGPU_LIB_OVERRIDE", "default")
 
 
+def _option(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
 def costing(n_samples):
     w = workloads.config3(n_samples=n_samples)
+    w.cfg.heuristic, w.cfg.tsp_k = _option("--heuristic", w.cfg.heuristic), _option("--tsp-k", w.cfg.tsp_k)
+    gaussian = "--gaussian" in sys.argv
     ctx = api.Context(0)
-    ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res); ctx.set_obstacles(w.obst); ctx.set_vertices(w.root(), w.ribbons4)
+    ctx.set_config(w.cfg); ctx.set_grid(w.grid, w.res)
+    if gaussian:
+        ctx.set_gaussian_obstacles(np.ascontiguousarray(w.obst[:, :5]))
+    else:
+        ctx.set_obstacles(w.obst)
+    ctx.set_vertices(w.root(), w.ribbons4)
     ctx.sampler_init(w.bounds6, w.seed, w.ribbons4); n = ctx.sampler_add(w.n_samples)
     d = torch.zeros(4 * n * 128, dtype=torch.uint8, device="cuda")
     ch = torch.zeros(4 * n * 8 * 4, dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
     ctx.cost_edges_dense(0, 1, 0, n, 0xF, d.data_ptr(), ch.data_ptr(), 8); ctx.synchronize()
-    print(LIB, n, hashlib.sha256(d.cpu().numpy().tobytes()).hexdigest()[:16], hashlib.sha256(ch.cpu().numpy().tobytes()).hexdigest()[:16])
+    print(LIB, n, "heuristic %d k %d%s" % (w.cfg.heuristic, w.cfg.tsp_k, " gaussian" if gaussian else ""), hashlib.sha256(d.cpu().numpy().tobytes()).hexdigest()[:16], hashlib.sha256(ch.cpu().numpy().tobytes()).hexdigest()[:16])
 
 
 def _sha(arrays):
@@ -62,4 +75,4 @@ if __name__ == "__main__":
     if "--traces" in sys.argv[1:]:
         traces()
     else:
-        costing(int(sys.argv[1]) if len(sys.argv) > 1 else 65536)
+        costing(int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 65536)
