@@ -194,6 +194,13 @@ int ppgpu_past_timing(ppgpu_ctx* ctx, int32_t back, double* ms_solve, double* ms
  * finishes the edges whose coverage state machine has nothing to do and hands the cover sweep a packed list of the others; on
  * small launches it is every edge.  (Sliced launches: exact with timing on, the last slice's share otherwise.)  Waits for the launch. */
 int ppgpu_last_cover_edges(ppgpu_ctx* ctx, int64_t* n_edges);
+/* Shared sweeps.  On large launches of solved edges (the dense and the list form, not wrapper edges) the edges whose whole horizon
+ * lies on the first arc of their curve fall into classes (open vertex, configuration, direction of that arc) whose members have one
+ * and the same sweep: one member of each class is swept and the others take its results, their own DubinsPathType, approx_cost and
+ * param[] apart.  The records and child ribbons are the same bytes either way.  PPGPU_SHARE_SWEEPS=0 in the environment of
+ * ppgpu_create switches it off.  ppgpu_last_shared_edges: how many edges of the last costing launch took another edge's results
+ * (0 with the switch off and on small launches).  Waits for the launch; reads one word per edge back, a measurement aid. */
+int ppgpu_last_shared_edges(ppgpu_ctx* ctx, int64_t* n_edges);
 
 /* Device memory for callers that have no HIP toolchain of their own (the C++ host library is built with g++ against this header
  * only): buffers for the `d_` parameters below, on the handle's device, and a blocking copy back to the host that first waits

@@ -55,6 +55,7 @@ def _load():
         "ppgpu_last_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_past_timing": (C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_last_cover_edges": (C.c_int, [vp, C.POINTER(i64)]),
+        "ppgpu_last_shared_edges": (C.c_int, [vp, C.POINTER(i64)]),
         "ppgpu_set_config": (C.c_int, [vp, C.POINTER(PpgpuConfig)]),
         "ppgpu_set_grid": (C.c_int, [vp, vp, i32, i32, dbl]),
         "ppgpu_get_grid_clearance": (C.c_int, [vp, vp, i64]),
@@ -188,6 +189,12 @@ class Context:
         """Edges of the last costing launch that pp_k_cover_sweep visited (the others were finished by the approach prepass)."""
         n = C.c_int64()
         self._ck(LIB.ppgpu_last_cover_edges(self._h, C.byref(n)), "ppgpu_last_cover_edges")
+        return n.value
+
+    def last_shared_edges(self):
+        """Edges of the last costing launch that were not swept themselves but took the results of another edge of their class."""
+        n = C.c_int64()
+        self._ck(LIB.ppgpu_last_shared_edges(self._h, C.byref(n)), "ppgpu_last_shared_edges")
         return n.value
 
     def reserve_samples(self, max_samples, max_vertices=16):

@@ -63,6 +63,10 @@ struct PPParams {
     struct PPCoverState* cover_state;    // [edge] what the cover sweep's wave hands to pp_k_cover_finish (NULL: every wave finishes its own edges)
     unsigned* hw_list;                   // edges pp_k_cover_finish leaves to pp_k_heuristic_listed (a TSP enumeration of 7 or 8 ribbons)
     int ngp, nch;                        // steps per edge rounded up to whole 64-step chunks, and that many chunks
+    // Shared sweeps (large solved launches, pp_k_solve.h): edges whose whole horizon lies on their first arc are swept once per class
+    unsigned* share_head;                // [nverts * PP_SHARE_KEYS] lowest list position of each class, PP_SHARE_NONE: none yet; per LAUNCH (NULL: nothing is shared)
+    unsigned* share_of;                  // [list position] the position whose results the edge takes (pp_k_share_fanout), PP_SHARE_NONE: its own
+                                         //                 (between pp_k_solve_edges and pp_k_share_mark: the edge's class, PP_SHARE_NONE: in none)
 };
 
 // Phase 0 of an edge (Vertex::connect + Edge::computeApproxCost: which vertex/target/configuration, the Dubins word and
@@ -71,6 +75,11 @@ struct PPParams {
 // offsets, which follow from p0 / p1, and a never-used clear-after parameter), device-only.
 #define PP_SETUP_MALFORMED 1u   // descriptor out of range
 #define PP_SETUP_COLOCATED 2u   // State::isCoLocated(start, end): the reference throws
+#define PP_SETUP_SHARED 4u      // the edge belongs to a class of edges with one and the same sweep (pp_edge_shareable, pp_k_solve.h) and is not its
+                                // head (pp_k_share_mark): no kernel sweeps it, pp_k_share_fanout gives it the head's results
+#define PP_SETUP_NO_SWEEP (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED | PP_SETUP_SHARED)   // what the per-edge kernels of a launch leave at once
+#define PP_SHARE_KEYS 8         // classes per vertex: configuration bits (4) x direction of the first arc (2)
+#define PP_SHARE_NONE 0xffffffffu
 struct PPEdgeSetupBody {
     PPSegBase seg[3];                      // the bases of the curve's three segments (pp_seg_load_uniform / pp_setup_seg_pose make the rest)
     double p0, p1, p2, hi1;                // DubinsPath::param; hi1 = p0 + p1 as the solver rounded it (where segment 2 begins)

@@ -44,6 +44,7 @@ __device__ __forceinline__ int pp_event_stride(double D, double inc_d, double in
 // state, the function pp_k_cover_finish runs from a wave's) and marks the edge PP_FAR_DONE; the cover sweep's wave then drops it at
 // once.  Nearly half the edges of config 3.
 #define PP_FAR_DONE (-2)
+#define PP_FAR_SHARED (-3)      // inside pp_k_approach_events only: a shared edge, stored as PP_FAR_DONE
 // PPParams::track_far[e].y = (last event before the hand-over) + 1 in the low 20 bits, and, when the approach lane has already split the
 // one ribbon the vehicle entered (round 4): PP_FAR_SPLIT, which piece the corridor run that follows moves (6 bits) and which of its ends
 #define PP_FAR_LAST_MASK 0xfffff
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
     const bool oneVertex = viFirst < (unsigned)p.nverts && __ballot(valid && viMine != viFirst) == 0ull;
     const double* rpU = p.ribbons + 4 * (size_t)pp_const_i32(&p.verts[oneVertex ? viFirst : 0].ribbon_offset)[0];
     const int nribU = pp_const_i32(&p.verts[oneVertex ? viFirst : 0].ribbon_count)[0];
-    if (valid && !(sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && dubType >= 0) {
+    if (valid && !(sflags & PP_SETUP_NO_SWEEP) && dubType >= 0) {
         const ppgpu_vertex* V = p.verts + S->vi;
         const int nrib = V->ribbon_count;
         const int limit = p.track_summary[p.ws_base + e].limit;
@@ -208,7 +209,11 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
                 out.x = PP_FAR_DONE;
         }
     }
-    if (valid) p.track_far[p.ws_base + e] = out;
+    // An edge that takes another edge's results (pp_k_share_mark) skipped all of the above: it is marked PP_FAR_DONE without a record and
+    // never enters the live list.  (Its flags are read again here: a predicate kept since the top costs the loop above four more spilled registers.)
+    asm volatile("" ::: "memory");
+    if (valid && (S->sflags & PP_SETUP_SHARED) != 0u) out.x = PP_FAR_SHARED;
+    if (valid) p.track_far[p.ws_base + e] = make_int2(max(out.x, PP_FAR_DONE), out.y);
 #ifdef PP_DBG_PHASES
     {
         const long long apT3 = (long long)__builtin_readcyclecounter();
@@ -241,7 +246,7 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
         __shared__ unsigned s_cnt[PP_APPROACH_THREADS / 64];
         __shared__ unsigned s_base;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const bool live = valid && out.x != PP_FAR_DONE;
+        const bool live = valid && out.x >= 0;                                             // (neither PP_FAR_DONE nor PP_FAR_SHARED)
         const unsigned long long m = __ballot(live);
         if (lane == 0) s_cnt[wave] = (unsigned)__popcll(m);
         __syncthreads();

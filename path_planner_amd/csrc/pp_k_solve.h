@@ -7,6 +7,55 @@
 #ifndef PP_SOLVE_MIN_WAVES
 #define PP_SOLVE_MIN_WAVES 1
 #endif
+// ------------------------------------------------------------------------------------------
+// Shared sweeps.  An edge is swept up to endTime = min(horizon + 1e-12 + sst, wEnd), and every Dubins word begins with an arc.  Where
+// the horizon ends while the vehicle is still on that arc, nothing a sweep computes depends on the target: every pose is sampled on
+// segment 0, whose base is the vertex's pose, with the constants wStart (the vertex's time), speed, rho and the arc's direction.  All
+// such edges of one (vertex, configuration, direction) — a class — have the same track, events, child ribbons, end state, g, h and
+// flags, bit for bit; only the type byte, approx_cost and param[] of the record are the edge's own.  So one member of each class, its
+// head, is swept, and pp_k_share_fanout hands its results to the others.
+//
+// The rule (pp_edge_shareable), on the record as the sweeps will read it, with bound = horizon + 1e-12 + sst:
+//   * the edge is solved (type >= 0, neither malformed nor co-located);
+//   * !(wEnd < bound): endTime is `bound` for every member;
+//   * the pose at `bound`, in pp_window_pose's own arithmetic, lies strictly inside segment 0: dist = (bound - wStart) * speed has
+//     dist <= length, and tprime = dist * rho_inv (or dist / rho where rho_inv is 0) has tprime < p0.
+// Why the one test at `bound` covers every step: each time t a kernel samples (a step of the time row before endTime, endTime itself,
+// an end time an event shortened) is <= bound, and t -> (t - wStart) * speed -> tprime is a chain of roundings of non-decreasing
+// functions (a subtraction of and products with non-negative constants), so it is non-decreasing in t as computed: dist(t) <=
+// dist(bound) <= length, the retry and the clamp of DubinsWrapper::sample can only fire for dist < 0, where they do not look at
+// the curve, and tprime(t) <= tprime(bound) < p0 picks segment 0 (pp_seg_of, and the interval (-inf, p0) of pp_seg_load_uniform).
+__device__ __forceinline__ bool pp_edge_shareable(const PPParams& p, const PPCurve& cv, int type, unsigned sflags, unsigned cbits,
+                                                  double wStart, double wEnd, double speed) {
+    if (type < 0 || (sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || cbits >= 4u) return false;
+    const double bound = p.horizon + 1e-12 + p.sst;
+    if (wEnd < bound) return false;
+    const double dist = (bound - wStart) * speed;
+    if (!(dist <= cv.length)) return false;
+    const double tprime = (cv.rho_inv != 0.0) ? dist * cv.rho_inv : dist / cv.rho;
+    return tprime < cv.p0;
+}
+// The class of a shareable edge: (vertex, configuration bits, direction of segment 0), an index into PPParams::share_head.
+__device__ __forceinline__ unsigned pp_share_key(unsigned vi, unsigned cbits, int type) {
+    return vi * PP_SHARE_KEYS + (cbits & 3u) * 2u + (pp_word_seg_type(type, 0) == 0 ? 0u : 1u);
+}
+// The head of a class is its member with the lowest position in the caller's list.  The lanes of this wave that hold a position
+// below the table's entry (a plain look first: after the first waves of a launch nearly every lane leaves here) take turns by key;
+// for each key ONE lane issues the atomicMin.  It is the lowest such lane, and that lane holds the wave's lowest position of the key:
+// work items of one configuration map to list positions in rising order (pp_edge_position), in explicit lists they are the positions.
+// (One atomic per member would be 70 000 same-address atomics at ~12.5 ns each.)  No lane waits for another wave.
+__device__ __forceinline__ void pp_share_elect(const PPParams& p, bool member, unsigned key, unsigned pos) {
+    bool pend = false;
+    if (member) pend = pos < __hip_atomic_load(p.share_head + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long m;
+    while ((m = __ballot(pend)) != 0ull) {
+        const int leader = __ffsll((long long)m) - 1;
+        const unsigned k0 = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
+        if (pp_lane() == leader) atomicMin(p.share_head + k0, pos);
+        if (key == k0) pend = false;
+    }
+}
+
 // ALL_WORDS: the solver evaluates all six words correctly rounded and pp_curve_init every base heading (pp_k_solve_edges_all_words,
 // PPGPU_SOLVE_ALL_WORDS=1, for the tests that compare the two); else only the words that can win, and no sin / cos of the curve's
 // bases twice (pp_solve_rank.h, PPSincosMemo): the same records.  Two kernels, so that the test path does not set the registers of
@@ -84,6 +133,8 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
         }
     }
     // what depends on the speed, once per record: this lane's own edge, then its fast partner
+    bool member[2] = {false, false};                          // (shared sweeps: the rule, once per record)
+    unsigned key[2] = {0u, 0u}, pos[2] = {0u, 0u};
     for (int k = 0; k < (e2 >= 0 ? 2 : 1); k++) {
         PPEdgeSetup* __restrict__ O = p.setup + p.ws_base + (k ? e2 : e);
         struct { double approx, wStart, wEnd, speed; int type; unsigned vi, cbits, sflags; } S;
@@ -101,6 +152,14 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
                 S.wEnd = srcT + cv.length / S.speed;                    // DubinsWrapper::setEndTime
             }
             S.type = dub.type;
+        }
+        if (p.share_head) {
+            // (the class of a member, PP_SHARE_NONE for any other edge: pp_k_share_mark reads it there and puts the edge's head in its place)
+            const long long egk = k ? pp_edge_position(p, p.e_base + e2) : eg;
+            member[k] = pp_edge_shareable(p, cv, S.type, S.sflags, S.cbits, S.wStart, S.wEnd, S.speed);
+            key[k] = member[k] ? pp_share_key(S.vi, S.cbits, S.type) : PP_SHARE_NONE;
+            pos[k] = (unsigned)egk;
+            p.share_of[egk] = key[k];
         }
         pp_curve_segments(cv, O->seg);
         O->qx = cv.qx; O->qy = cv.qy; O->rho = cv.rho; O->rho_inv = cv.rho_inv; O->length = cv.length;
@@ -129,6 +188,53 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
             }
         }
         O->omask = omask;
+    }
+    if (p.share_head) {
+        pp_share_elect(p, member[0], key[0], pos[0]);
+        if (__ballot(e2 >= 0) != 0ull) pp_share_elect(p, member[1], key[1], pos[1]);
+    }
+}
+// After the solve of a slice, one lane per edge; every edge that is in no class leaves after one coalesced 4-byte read.  A member of a
+// class that is not its head (the table is final for every class that has a
+// member up to this slice: the head is the lowest position, and later slices hold higher ones) is marked PP_SETUP_SHARED, so that
+// every per-edge kernel of the launch leaves it at once, and gets a stub record — its own type byte, approx_cost and param[], everything
+// else zero (no flags, no ribbons, h = 0) — so that no kernel that builds a list from the records (pp_k_deferred_list,
+// pp_k_tsp_table_list, the unfused heuristic kernels) takes what the caller's array held for a deferred or overflowed record.
+__global__ __launch_bounds__(256) void pp_k_share_mark(PPParams p) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.n_edges) return;
+    const long long eg = pp_edge_position(p, p.e_base + e);
+    const unsigned key = p.share_of[eg];                       // as pp_k_solve_edges left it
+    if (key == PP_SHARE_NONE) return;
+    const unsigned head = p.share_head[key];
+    if (head == (unsigned)eg) { p.share_of[eg] = PP_SHARE_NONE; return; }
+    p.share_of[eg] = head;
+    PPEdgeSetup* S = p.setup + p.ws_base + e;
+    S->sflags |= PP_SETUP_SHARED;
+    double* r = reinterpret_cast<double*>(p.out + eg);
+    const unsigned info = (unsigned)(S->type & 0xff);
+    r[0] = __hiloint2double((int)info, 0);
+    r[1] = 0.0; r[2] = 0.0; r[3] = S->approx;
+    for (int i = 4; i < 13; i++) r[i] = 0.0;
+    r[13] = S->p0; r[14] = S->p1; r[15] = S->p2;
+}
+// Last kernel of the launch, 16 lanes per record (one 128-byte line read, one written): every member takes its head's record but for
+// the three fields that are the edge's own (type byte, approx_cost, param[]: the stub holds them) and, copy_child, the head's child slot.
+__global__ __launch_bounds__(256) void pp_k_share_fanout(PPParams p, int copy_child) {
+    const long long eg = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int sub = (int)(threadIdx.x & 15);
+    if (eg >= p.n_edges) return;
+    const unsigned h = p.share_of[eg];
+    if (h == PP_SHARE_NONE) return;
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(p.out + h);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(p.out + eg);
+    unsigned long long v = src[sub];
+    if (sub == 0) v = (v & ~(0xffull << 32)) | (dst[0] & (0xffull << 32));      // {flags (low word), info (high word): its bits 0-7 are the type}
+    if (sub != 3 && sub < 13) dst[sub] = v;
+    if (copy_child) {
+        const double* cs = p.child + (size_t)h * p.stride * 4;
+        double* cd = p.child + (size_t)eg * p.stride * 4;
+        for (int i = sub; i < p.stride * 4; i += 16) cd[i] = cs[i];
     }
 }
 __global__ __launch_bounds__(256, PP_SOLVE_MIN_WAVES) void pp_k_solve_edges(PPParams p) { pp_solve_edges_body<false>(p); }

@@ -294,7 +294,7 @@ __device__ __forceinline__ void pp_plan_chunk(const PPParams& p, const PPEdgeSet
 // the edge at all (pp_k_solve_edges left the list in the setup record), or through the whole table when it holds more than 64.
 template <bool GAUSSIAN>
 __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPEdgeSetupBody* S, const PPObst* OB, const long long e, const int chunk) {
-    const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
+    const bool sane = !(S->sflags & PP_SETUP_NO_SWEEP) && S->type >= 0;      // (a shared edge: its head is planned)
     const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
     const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
     const double tF = (sane && chunk * PP_WAVE < p.ng) ? tg[chunk * PP_WAVE] : INFINITY;
@@ -420,7 +420,7 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
     const int chunk = live ? t - el * p.nch : 0;
     const PPEdgeSetupBody* S = reinterpret_cast<const PPEdgeSetupBody*>(&s_setup[el * PP_SETUP_LDS_STRIDE]);
     const int k0 = chunk * PP_WAVE;
-    const bool sane = !(S->sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) && S->type >= 0;
+    const bool sane = !(S->sflags & PP_SETUP_NO_SWEEP) && S->type >= 0;      // (a shared edge: its head is planned)
     const double endTime = fmin(p.horizon + 1e-12 + p.sst, S->wEnd);
     const double* tg = p.tgrid + (size_t)(sane ? S->vi : 0) * p.ng;
     const double tF = (live && sane && k0 < p.ng) ? tg[k0] : INFINITY;
@@ -552,7 +552,7 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
                  "s"(hot.rho_inv), "s"(hot.qx), "s"(hot.qy), "s"(wEnd), "s"(omask), "s"(cs.bx), "s"(cs.by), "s"(cs.bth), "s"(cs.sb), "s"(cs.cb),
                  "s"(cs.hi));
     const bool cov = (cbitsW & PPGPU_EDGE_COVERAGE) != 0;
-    if ((sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || dubType < 0) {
+    if ((sflags & PP_SETUP_NO_SWEEP) || dubType < 0) {            // (a shared edge: its head is swept)
         if (lane == 0) { sum->limit = 0; sum->blocked = 0; sum->dub_err = 0; sum->pad = 0; }
         return;
     }

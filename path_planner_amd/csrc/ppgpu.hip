@@ -163,6 +163,7 @@ struct ppgpu_ctx {
     bool plan_spans = true;             // env PPGPU_PLAN_SPANS=0: the skip planner tests every obstacle of an edge's list per chunk (the tests compare the two)
     bool lane_heuristic = true;         // env PPGPU_LANE_HEURISTIC=0: large launches keep the wave-per-edge enumeration too (tests compare the two)
     long long prepass_min_edges = PP_PREPASS_MIN_EDGES;   // env PPGPU_PREPASS_MIN_EDGES overrides (tests run the prepasses on small launches too)
+    bool share_sweeps = true;           // env PPGPU_SHARE_SWEEPS=0: every edge of a large launch is swept itself (A/B runs, and the tests compare the two)
     size_t slice_bytes = PP_SLICE_BYTES; // workspace budget of one costing slice (env PPGPU_SLICE_BYTES overrides: tests)
     DevBuf<PPEdgeSetup> setup;          // workspace of the current costing slice: phase-0 records ...
     DevBuf<unsigned short> track_hits;  // ... and the pose sweep's track (see PPParams)
@@ -173,6 +174,8 @@ struct ppgpu_ctx {
     DevBuf<unsigned char> track_skip;
     DevBuf<PPLaunchWords> words;        // the counters the kernels of a launch hand to one another (one 128-byte line)
     DevBuf<unsigned> defer_list, live_list, hw_list;
+    DevBuf<unsigned> share_head, share_of;   // shared sweeps: the head of each class, and whose results each edge of the launch takes (see PPParams)
+    bool last_launch_shared = false;         // the last costing launch ran with shared sweeps (share_of then holds last_launch_edges entries)
     DevBuf<PPCoverState> cover_state;
     DevBuf<unsigned long long> work;    // queue heads of the cover sweep's resident grid (pp_next_edge)
     int n_cu = 0;
@@ -297,6 +300,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* ls = std::getenv("PPGPU_LANE_SPLIT")) c->lane_split = std::atoi(ls) != 0;
     if (const char* aw = std::getenv("PPGPU_SOLVE_ALL_WORDS")) c->solve_all_words = std::atoi(aw) != 0;
     if (const char* ps = std::getenv("PPGPU_PLAN_SPANS")) c->plan_spans = std::atoi(ps) != 0;
+    if (const char* ss = std::getenv("PPGPU_SHARE_SWEEPS")) c->share_sweeps = std::atoi(ss) != 0;
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
@@ -378,6 +382,20 @@ int ppgpu_last_cover_edges(ppgpu_ctx* c, int64_t* n_edges) {
         HIP_TRY(hipMemcpy(&live, &c->words.p->live_count, sizeof(unsigned), hipMemcpyDeviceToHost));
         *n_edges = (int64_t)live + c->live_earlier_slices;
     }
+    return PPGPU_OK;
+}
+
+int ppgpu_last_shared_edges(ppgpu_ctx* c, int64_t* n_edges) {
+    if (!c || !n_edges) return fail(PPGPU_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    *n_edges = 0;
+    if (!c->last_launch_shared || c->last_launch_edges <= 0) return PPGPU_OK;
+    std::vector<unsigned> of((size_t)c->last_launch_edges);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(of.data(), c->share_of.p, of.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (unsigned h : of) n += (h != PP_SHARE_NONE);
+    *n_edges = n;
     return PPGPU_OK;
 }
 
@@ -1023,6 +1041,7 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.heuristic = g.heuristic; p.tsp_k = g.tsp_k; p.h_rho = g.heuristic_turning_radius;
     p.fuse_h = 0;
     p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.words = nullptr; p.reset_words = 0;
+    p.share_head = nullptr; p.share_of = nullptr;
     p.grid = PPGrid{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
     p.obst = c->obst.p; p.n_obst = c->n_obst; p.obst_model = c->obst_model;
     p.verts = c->verts.p; p.ribbons = c->ribbons.p; p.tgrid = c->tgrid.p; p.ng = c->ng; p.nverts = c->nverts;
@@ -1167,6 +1186,8 @@ struct CostLaunch {
     bool defer_h;        // ... but leaves the TSP enumerations to pp_k_heuristic_lanes
     bool quiet_finish, lane_split;   // what the handle's PPGPU_QUIET_FINISH / PPGPU_LANE_SPLIT switches allow, on large launches
     bool forked;         // pp_k_heuristic_listed runs on the side stream
+    bool share;          // shared sweeps: one member of each class of edges with the same sweep is swept, the others take its results (pp_k_solve.h)
+    bool share_child;    // ... and its child ribbons, where the caller asked for them
     int nch, ngp;        // 64-step chunks per edge, and the steps they hold
     long long slice;     // edges per workspace slice (>= p.n_edges: one piece, the setup records of the whole list are still there)
 };
@@ -1203,6 +1224,9 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
 #endif
     m.lane_finish = laneFinishBuilt && m.packed && c->lane_finish && !m.gaussian;
     m.forked = m.lane_finish && m.fuse_h && p.heuristic != PPGPU_H_MAX_DISTANCE;
+    // shared sweeps: large launches of solved curves (a given curve is its caller's); positions and class keys are 32-bit words
+    m.share = m.prepasses && m.packed && !p.wedges && c->share_sweeps && (long long)p.nverts * PP_SHARE_KEYS < (1ll << 32);
+    m.share_child = m.share && p.child != nullptr;
 }
 
 // Reserves the workspace of the launch and wires it, and the modes the kernels look at, into m.p.
@@ -1248,6 +1272,10 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
         if ((rc = c->defer_list.reserve(total * PP_HL_MAX_N, false, st))) return rc;
         p.defer_list = c->defer_list.p;
     }
+    if (m.share) {
+        if ((rc = c->share_head.reserve((size_t)p.nverts * PP_SHARE_KEYS, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
+        p.share_head = c->share_head.p; p.share_of = c->share_of.p;
+    }
     return PPGPU_OK;
 }
 
@@ -1271,6 +1299,7 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
     hipEvent_t* ev = c->ev_ring[c->ev_slot];
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_BEGIN], st));
     hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);
+    if (m.share) hipLaunchKernelGGL(pp_k_share_mark, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);   // timed with the solve
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_SOLVED], st));
     if (m.skip_chunks) {                                         // timed with the pose sweep
         // one workgroup per epw consecutive edges: as many as give it 256 (edge, chunk) threads
@@ -1354,7 +1383,11 @@ static int cost_heuristic_tail(ppgpu_ctx* c, const CostLaunch& m) {
     if (p.heuristic == PPGPU_H_TSP_POINT_K)
         hipLaunchKernelGGL(pp_k_heuristic_big, dim3((unsigned)(total < PP_BIG_GRID ? total : PP_BIG_GRID)), dim3(PP_BIG_WPB * 64), 0, st, p);
     if (m.forked) HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-    return tsp_table_pass(c, p);
+    int rc = tsp_table_pass(c, p);
+    if (rc) return rc;
+    // last of all, when every head's record is final: the other members of each class take their head's results (16 lanes per record)
+    if (m.share) hipLaunchKernelGGL(pp_k_share_fanout, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, p, m.share_child ? 1 : 0);
+    return PPGPU_OK;
 }
 
 // Costs the edges `asked` describes (list_params, or the dense form's own): modes, workspace, the slices one after the other, the
@@ -1374,6 +1407,9 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     if (c->timing) c->ev_slot = (int)(c->ev_launches % PP_TIMING_RING);     // the next set of the ring
     for (double& ms : c->ms_ring[c->ev_slot]) ms = 0;
     c->live_earlier_slices = 0;
+    c->last_launch_shared = false;
+    // the heads of the classes: none yet.  Per launch, not per slice: a member in a later slice finds the head of an earlier one
+    if (m.share) HIP_TRY(hipMemsetAsync(p.share_head, 0xff, (size_t)p.nverts * PP_SHARE_KEYS * sizeof(unsigned), c->stream));
     for (long long e0 = 0; e0 < total; e0 += m.slice) {
         p.e_base = e0; p.ws_base = 0; p.n_edges = (total - e0 < m.slice) ? (total - e0) : m.slice;
         if (c->timing && e0 > 0 && (rc = bank_slice_timing(c, m.packed))) return rc;
@@ -1382,7 +1418,7 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     p.e_base = 0;
     p.n_edges = total;
     if ((rc = cost_heuristic_tail(c, m))) return rc;
-    c->last_launch_edges = total; c->last_launch_packed = m.packed;
+    c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share;
     if (c->timing) { HIP_TRY(hipEventRecord(c->ev_ring[c->ev_slot][EV_END], c->stream)); c->ev_launches++; }
     HIP_TRY(hipGetLastError());
     return PPGPU_OK;
@@ -1517,6 +1553,7 @@ static int trace_passes(ppgpu_ctx* c, const CostLaunch& L, const TraceRequest& r
         q.ws_base = reuse ? e0 : 0;
         if (!reuse) {
             q.reset_words = 0;       // (the counters are the costing launch's: ppgpu_last_cover_edges still reads them)
+            q.share_head = nullptr;  // (a trace walks every edge itself: no class is elected again)
             hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((q.n_edges + 255) / 256)), dim3(256), 0, c->stream, q);
         }
         unsigned char* dst = host ? c->tmp_trace.p : recs;
