@@ -87,6 +87,33 @@ struct DevBuf {
     }
 };
 
+// The workspace of the push-order pipeline (pp_k_expand.h; the arrays are described at PPExpandArgs), sized for nv open vertices,
+// ns stored samples and k winners per list.
+struct ExpandWork {
+    DevBuf<double> lengths;             // near lengths of the pipeline; ppgpu_select_nearest's full rows of lengths
+    DevBuf<double> probe_min, groupmin, bound, key, len;
+    DevBuf<int> near_idx, near_count, groupcnt, count, val, idx;   // idx: the output, [nv][2][k]
+    DevBuf<unsigned> fallbacks;
+    static long long list_cap(long long ns) {          // candidates per list; pp_k_expand_order filters them down to at most PP_ORD_CAP
+        long long cap = 64;
+        while (cap < ns && cap < 65536) cap <<= 1;
+        return cap;
+    }
+    static size_t groups_row(long long ns) { return (size_t)((ns + 255) / 256) * (256 / PP_NEAR_GROUP); }
+    int reserve(size_t nv, long long ns, int k, hipStream_t st) {
+        const size_t lists = nv * 2 * (size_t)list_cap(ns), groups = nv * groups_row(ns);
+        int rc;
+        if ((rc = lengths.reserve(nv * (size_t)ns * 2, false, st)) || (rc = probe_min.reserve(nv * 2 * PP_PROBE_GROUPS, false, st)) ||
+            (rc = near_idx.reserve(nv * (size_t)ns, false, st)) || (rc = near_count.reserve(nv, false, st)) ||
+            (rc = groupmin.reserve(groups * 2, false, st)) || (rc = groupcnt.reserve(groups, false, st)) ||
+            (rc = bound.reserve(nv * 2, false, st)) || (rc = count.reserve(nv * 2, false, st)) ||
+            (rc = key.reserve(lists, false, st)) || (rc = val.reserve(lists, false, st)) || (rc = len.reserve(lists, false, st)) ||
+            (rc = idx.reserve(nv * 2 * (size_t)k, false, st)) || (rc = fallbacks.reserve(1, false, st)))
+            return rc;
+        return PPGPU_OK;
+    }
+};
+
 #define PP_TIMING_RING 8
 // The events around the kernel of a trace call (ppgpu_last_trace_timing, ppgpu_last_cover_trace_timing, ppgpu_last_contact_trace_timing,
 // ppgpu_last_clearance_trace_timing).
@@ -193,10 +220,7 @@ struct ppgpu_ctx {
     long long ev_launches = 0;                 // timed launches so far
     int max_vertex_ribbons = 0;
     DevBuf<int> tmp_idx;
-    DevBuf<double> ord_key;             // pp_k_expand_order: candidate scratch beyond what LDS holds, push-order output, fallback counter
-    DevBuf<int> ord_val, ord_idx, ord_blockcnt, ord_count, near_idx, near_count;   // (near_*: the samples within a vertex's probe bound, pp_k_expand_near)
-    DevBuf<double> ord_len, ord_blockmin, ord_bound, probe_bound;
-    DevBuf<unsigned> ord_fallbacks;
+    ExpandWork expand;                  // the push-order pipeline's workspace (launch_expand_order)
     unsigned long long order_fallbacks = 0;   // (vertex, radius) lists of ppgpu_expand_host / ppgpu_expand_order that fell back to ascending length
     DevBuf<unsigned char> dstage_in, dstage_out;            // device ends of ppgpu_expand_host's single upload / download
     void* stage_in = nullptr; size_t stage_in_cap = 0;      // pinned host staging of ppgpu_expand_host
@@ -405,17 +429,11 @@ int ppgpu_reserve_samples(ppgpu_ctx* c, int64_t max_samples, int32_t max_vertice
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t ns = (size_t)max_samples, nv = (size_t)max_vertices;
-    const size_t nblk = (ns + 255) / 256;
-    size_t cap = 64;
-    while (cap < ns && cap < 65536) cap <<= 1;
     const size_t nq = 6 * (size_t)524288 + 8;                   // the sampler's largest batch (ppgpu_sampler_add)
     int rc;
     if ((rc = c->sx.reserve(ns + nv, true, st)) || (rc = c->sy.reserve(ns + nv, true, st)) || (rc = c->sh.reserve(ns + nv, true, st)) ||
         (rc = c->s_cand.reserve((size_t)524288 * 3, false, st)) || (rc = c->s_bytes.reserve(nq + 64, false, st)) || (rc = c->s_u32a.reserve(nq + 64, false, st)) ||
-        (rc = c->tmp_lengths.reserve(nv * ns * 2, false, st)) ||
-        (rc = c->ord_key.reserve(nv * 2 * cap, false, st)) || (rc = c->ord_val.reserve(nv * 2 * cap, false, st)) || (rc = c->ord_len.reserve(nv * 2 * cap, false, st)) ||
-        (rc = c->ord_blockmin.reserve(nv * nblk * 2 * (256 / PP_NEAR_GROUP), false, st)) || (rc = c->ord_blockcnt.reserve(nv * nblk * (256 / PP_NEAR_GROUP), false, st)) ||
-        (rc = c->near_idx.reserve(nv * ns, false, st)) || (rc = c->near_count.reserve(nv, false, st)) || (rc = c->probe_bound.reserve(nv * 2 * PP_PROBE_GROUPS, false, st)))
+        (rc = c->expand.reserve(nv, max_samples, 0, st)))           // (the output grows with the k of the first call)
         return rc;
     return PPGPU_OK;
 }
@@ -1069,11 +1087,11 @@ int ppgpu_select_nearest(ppgpu_ctx* c, int32_t v0, int32_t nv, int32_t k, int32_
     HIP_TRY(hipSetDevice(c->device));
     if (k <= 0 || !h_idx || !h_len) return fail(PPGPU_EINVAL, "select_nearest: bad arguments");
     const long long ns = c->n_samples;
-    if ((rc = c->tmp_lengths.reserve((size_t)nv * ns * 2, false, c->stream))) return rc;
-    if ((rc = ppgpu_dubins_lengths(c, v0, nv, c->tmp_lengths.p))) return rc;
+    if ((rc = c->expand.lengths.reserve((size_t)nv * ns * 2, false, c->stream))) return rc;
+    if ((rc = ppgpu_dubins_lengths(c, v0, nv, c->expand.lengths.p))) return rc;
     size_t nout = (size_t)nv * 2 * k;
     if ((rc = c->tmp_idx.reserve(nout, false, c->stream)) || (rc = c->tmp_len_out.reserve(nout, false, c->stream))) return rc;
-    hipLaunchKernelGGL(pp_k_select_nearest, dim3((unsigned)(nv * 2)), dim3(256), 0, c->stream, c->tmp_lengths.p, ns, k,
+    hipLaunchKernelGGL(pp_k_select_nearest, dim3((unsigned)(nv * 2)), dim3(256), 0, c->stream, c->expand.lengths.p, ns, k,
                        c->tmp_idx.p, c->tmp_len_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_idx, c->tmp_idx.p, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1082,40 +1100,40 @@ int ppgpu_select_nearest(ppgpu_ctx* c, int32_t v0, int32_t nv, int32_t k, int32_
     return PPGPU_OK;
 }
 
-// The k winners of every (vertex, radius) of vertices [0, nv) in the reference's push order -> c->ord_idx: probe bound, near list,
-// lengths of the near samples + block minima (-> c->tmp_lengths, one double2 per near slot), bound, candidate lists, sort + replay
-// (pp_k_expand.h).
-// Asynchronous; *c->ord_fallbacks.p counts lists that kept ascending length.
+// The loops of SamplingBasedPlanner::expand a configuration asks for: both speeds (SamplingBasedPlanner.cpp:57-59), both radii (:60-63).
+struct ExpandLoops { int two_speeds, two_radii; };
+static ExpandLoops expand_loops(const ppgpu_config& g) {
+    const double slow = g.slow_speed <= 0 ? g.max_speed : g.slow_speed;     // PlannerConfig::slowSpeed()
+    return {slow != g.max_speed ? 1 : 0, g.coverage_turning_radius != g.turning_radius ? 1 : 0};
+}
+
+// The k winners of every (vertex, radius) of vertices [0, nv) in the reference's push order -> c->expand.idx: the six kernels of
+// pp_k_expand.h on one argument block.  Asynchronous; *c->expand.fallbacks.p counts lists that kept ascending length.
 static int launch_expand_order(ppgpu_ctx* c, int nv, int k, bool zero_fallbacks = true) {
     const long long ns = c->n_samples;
-    long long cap = 64;
-    while (cap < ns && cap < 65536) cap <<= 1;         // candidates per list; pp_k_expand_order filters them down to at most PP_ORD_CAP
-    const int nblk = (int)((ns + 255) / 256);
+    ExpandWork& w = c->expand;
+    hipStream_t st = c->stream;
     int rc;
-    if ((rc = c->tmp_lengths.reserve((size_t)nv * ns * 2, false, c->stream)) ||
-        (rc = c->ord_key.reserve((size_t)nv * 2 * cap, false, c->stream)) || (rc = c->ord_val.reserve((size_t)nv * 2 * cap, false, c->stream)) ||
-        (rc = c->ord_len.reserve((size_t)nv * 2 * cap, false, c->stream)) || (rc = c->ord_idx.reserve((size_t)nv * 2 * k, false, c->stream)) ||
-        (rc = c->ord_fallbacks.reserve(1, false, c->stream)) || (rc = c->ord_blockmin.reserve((size_t)nv * nblk * 2 * (256 / PP_NEAR_GROUP), false, c->stream)) ||
-        (rc = c->ord_blockcnt.reserve((size_t)nv * nblk * (256 / PP_NEAR_GROUP), false, c->stream)) || (rc = c->ord_bound.reserve((size_t)nv * 2, false, c->stream)) ||
-        (rc = c->ord_count.reserve((size_t)nv * 2, false, c->stream)) || (rc = c->near_idx.reserve((size_t)nv * ns, false, c->stream)) ||
-        (rc = c->near_count.reserve((size_t)nv, false, c->stream)) || (rc = c->probe_bound.reserve((size_t)nv * 2 * PP_PROBE_GROUPS, false, c->stream)))
-        return rc;
-    if (zero_fallbacks) HIP_TRY(hipMemsetAsync(c->ord_fallbacks.p, 0, sizeof(unsigned), c->stream));      // (ppgpu_expand_host: its unpack kernel does it)
-    const int two_radii = (c->cfg.coverage_turning_radius != c->cfg.turning_radius) ? 1 : 0;
-    hipLaunchKernelGGL(pp_k_expand_probe, dim3((unsigned)(PP_PROBE / 256), (unsigned)nv), dim3(256), 0, c->stream, c->verts.p, c->sx.p, c->sy.p, c->sh.p, ns,
-                       c->cfg.turning_radius, c->cfg.coverage_turning_radius, c->cfg.collision_checking_increment, two_radii, c->probe_bound.p, c->near_count.p);
-    hipLaunchKernelGGL(pp_k_expand_near, dim3((unsigned)((ns + 256 * PP_NEAR_PER - 1) / (256 * PP_NEAR_PER)), (unsigned)nv), dim3(256), 0, c->stream, c->verts.p, c->sx.p, c->sy.p, ns,
-                       c->cfg.collision_checking_increment, c->probe_bound.p, k, c->near_idx.p, c->near_count.p);
-    hipLaunchKernelGGL(pp_k_near_lengths, dim3((unsigned)nblk, (unsigned)nv), dim3(256), 0, c->stream, c->verts.p, c->sx.p, c->sy.p, c->sh.p, ns,
-                       c->near_idx.p, c->near_count.p, c->cfg.turning_radius, c->cfg.coverage_turning_radius, two_radii, c->tmp_lengths.p,
-                       c->ord_blockmin.p, c->ord_blockcnt.p);
-    hipLaunchKernelGGL(pp_k_expand_bound, dim3((unsigned)(nv * 2)), dim3(256), 0, c->stream, c->ord_blockmin.p, c->ord_blockcnt.p, nblk * (256 / PP_NEAR_GROUP), c->near_count.p, k,
-                       c->ord_bound.p, c->ord_count.p);
-    hipLaunchKernelGGL(pp_k_expand_candidates, dim3((unsigned)nblk, (unsigned)nv), dim3(256), 0, c->stream, c->tmp_lengths.p, c->verts.p, c->sx.p,
-                       c->sy.p, ns, c->near_idx.p, c->near_count.p, two_radii, c->ord_bound.p, c->ord_key.p, c->ord_val.p, c->ord_len.p, cap, c->ord_count.p);
-    hipLaunchKernelGGL(pp_k_expand_order, dim3((unsigned)(nv * 2)), dim3(256), 0, c->stream, ns, k, c->cfg.max_speed, c->cfg.time_penalty_factor,
-                       two_radii, c->ord_bound.p, c->ord_key.p, c->ord_val.p, c->ord_len.p, cap, c->ord_count.p, c->tmp_lengths.p, c->near_idx.p,
-                       c->near_count.p, c->ord_idx.p, c->ord_fallbacks.p);
+    if ((rc = w.reserve((size_t)nv, ns, k, st))) return rc;
+    if (zero_fallbacks) HIP_TRY(hipMemsetAsync(w.fallbacks.p, 0, sizeof(unsigned), st));      // (ppgpu_expand_host: its unpack kernel does it)
+    const ppgpu_config& g = c->cfg;
+    PPExpandArgs a{};
+    a.verts = c->verts.p; a.sx = c->sx.p; a.sy = c->sy.p; a.sh = c->sh.p; a.ns = ns;
+    a.k = k; a.two_radii = expand_loops(g).two_radii;
+    a.rho = g.turning_radius; a.rho_cov = g.coverage_turning_radius; a.inc_d = g.collision_checking_increment;
+    a.max_speed = g.max_speed; a.tpf = g.time_penalty_factor;
+    a.probe_min = w.probe_min.p; a.near_idx = w.near_idx.p; a.near_count = w.near_count.p; a.lengths = w.lengths.p;
+    a.groupmin = w.groupmin.p; a.groupcnt = w.groupcnt.p; a.groups_row = (int)ExpandWork::groups_row(ns);
+    a.bound = w.bound.p; a.cand_count = w.count.p;
+    a.g_key = w.key.p; a.g_val = w.val.p; a.g_len = w.len.p; a.g_cap = ExpandWork::list_cap(ns);
+    a.out_idx = w.idx.p; a.fallbacks = w.fallbacks.p;
+    const dim3 per_sample((unsigned)((ns + 255) / 256), (unsigned)nv), per_list((unsigned)(nv * 2));
+    hipLaunchKernelGGL(pp_k_expand_probe, dim3((unsigned)(PP_PROBE / 256), (unsigned)nv), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pp_k_expand_near, dim3((unsigned)((ns + 256 * PP_NEAR_PER - 1) / (256 * PP_NEAR_PER)), (unsigned)nv), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pp_k_near_lengths, per_sample, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pp_k_expand_bound, per_list, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pp_k_expand_candidates, per_sample, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pp_k_expand_order, per_list, dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return PPGPU_OK;
 }
@@ -1130,8 +1148,8 @@ int ppgpu_expand_order(ppgpu_ctx* c, int32_t v0, int32_t nv, int32_t k, int32_t*
     const size_t nout = (size_t)nv * 2 * k;
     if ((rc = launch_expand_order(c, nv, k))) return rc;
     unsigned fb = 0;
-    HIP_TRY(hipMemcpyAsync(h_idx, c->ord_idx.p, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&fb, c->ord_fallbacks.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h_idx, c->expand.idx.p, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&fb, c->expand.fallbacks.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->order_fallbacks += fb;
     if (h_fallbacks) *h_fallbacks = fb;
@@ -1857,20 +1875,19 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
     const int E = 4 + 4 * k;
     const long long cap = (long long)nv * E;
     hipStream_t st = c->stream;
-    // ---- stage in: vertices | ribbons | extra x | extra y | extra heading | has_extra
-    const size_t o_v = 0, o_r = o_v + (size_t)nv * sizeof(ppgpu_vertex), o_x = o_r + (size_t)n_ribbons * 4 * sizeof(double),
-                 o_y = o_x + (size_t)nv * sizeof(double), o_h = o_y + (size_t)nv * sizeof(double), o_f = o_h + (size_t)nv * sizeof(double),
-                 in_bytes = o_f + (size_t)nv;
+    // ---- stage in: one block (PPExpandBlock)
+    const PPExpandBlock in(nv, n_ribbons);
+    const size_t in_bytes = in.bytes;
     if ((rc = stage_reserve(&c->stage_in, &c->stage_in_cap, in_bytes))) return rc;
     char* sin = (char*)c->stage_in;
-    std::memcpy(sin + o_v, hv, (size_t)nv * sizeof(ppgpu_vertex));
-    if (n_ribbons > 0) std::memcpy(sin + o_r, hr, (size_t)n_ribbons * 4 * sizeof(double));
+    std::memcpy(sin + in.verts, hv, (size_t)nv * sizeof(ppgpu_vertex));
+    if (n_ribbons > 0) std::memcpy(sin + in.ribbons, hr, (size_t)n_ribbons * 4 * sizeof(double));
     for (int i = 0; i < nv; i++) {
         const bool has = h_nearest && !std::isnan(h_nearest[3 * i]);
-        ((double*)(sin + o_x))[i] = has ? h_nearest[3 * i] : 0.0;
-        ((double*)(sin + o_y))[i] = has ? h_nearest[3 * i + 1] : 0.0;
-        ((double*)(sin + o_h))[i] = has ? h_nearest[3 * i + 2] : 0.0;
-        ((unsigned char*)(sin + o_f))[i] = has ? 1 : 0;
+        ((double*)(sin + in.x))[i] = has ? h_nearest[3 * i] : 0.0;
+        ((double*)(sin + in.y))[i] = has ? h_nearest[3 * i + 1] : 0.0;
+        ((double*)(sin + in.heading))[i] = has ? h_nearest[3 * i + 2] : 0.0;
+        ((unsigned char*)(sin + in.flags))[i] = has ? 1 : 0;
     }
     const size_t need = (size_t)(ns + nv);
     if ((rc = c->verts.reserve((size_t)nv, false, st)) || (rc = c->ribbons.reserve((size_t)(n_ribbons > 0 ? n_ribbons : 1) * 4, false, st)) ||
@@ -1885,20 +1902,18 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
     unsigned long long* d_edges = (unsigned long long*)(c->dstage_out.p + q_e);
     ppgpu_edge_result* d_results = (ppgpu_edge_result*)(c->dstage_out.p + q_r);
     double* d_child = h_child ? (double*)(c->dstage_out.p + q_c) : nullptr;
-    if ((rc = c->dstage_in.reserve(in_bytes, false, st)) || (rc = c->ord_fallbacks.reserve(1, false, st))) return rc;
+    if ((rc = c->dstage_in.reserve(in_bytes, false, st)) || (rc = c->expand.fallbacks.reserve(1, false, st))) return rc;
     HIP_TRY(hipMemcpyAsync(c->dstage_in.p, sin, in_bytes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pp_k_expand_unpack, dim3((unsigned)((in_bytes / 8 + nv + 255) / 256)), dim3(256), 0, st, c->dstage_in.p, nv, n_ribbons,
-                       c->verts.p, c->ribbons.p, c->sx.p + ns, c->sy.p + ns, c->sh.p + ns, c->s_bytes.p, c->ord_fallbacks.p);
+                       c->verts.p, c->ribbons.p, c->sx.p + ns, c->sy.p + ns, c->sh.p + ns, c->s_bytes.p, c->expand.fallbacks.p);
     c->nverts = nv; c->nribbons = n_ribbons; c->max_vertex_ribbons = maxr; c->n_extra = nv;
     hipLaunchKernelGGL(pp_k_time_grid, dim3((unsigned)nv), dim3(64), 0, st, c->verts.p, nv, c->cfg.start_state_time,
                        c->cfg.collision_checking_increment, c->cfg.max_speed, c->ng, c->tgrid.p);
     // ---- k nearest per (vertex, radius), on the device
     if (select && (rc = launch_expand_order(c, nv, k, false))) return rc;   // the k winners per (vertex, radius) in the order expand() pushes them
-    const double slow = c->cfg.slow_speed <= 0 ? c->cfg.max_speed : c->cfg.slow_speed;     // PlannerConfig::slowSpeed()
-    const int two_speeds = (slow != c->cfg.max_speed) ? 1 : 0;                              // SamplingBasedPlanner.cpp:57-59
-    const int two_radii = (c->cfg.coverage_turning_radius != c->cfg.turning_radius) ? 1 : 0;  // :60-63
-    hipLaunchKernelGGL(pp_k_build_expand_edges, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, nv, k, select ? c->ord_idx.p : nullptr,
-                       c->s_bytes.p, ns, two_speeds, two_radii, E, d_edges, select ? c->ord_fallbacks.p : nullptr, d_header);
+    const ExpandLoops loops = expand_loops(c->cfg);
+    hipLaunchKernelGGL(pp_k_build_expand_edges, dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st, nv, k, select ? c->expand.idx.p : nullptr,
+                       c->s_bytes.p, ns, loops.two_speeds, loops.two_radii, E, d_edges, select ? c->expand.fallbacks.p : nullptr, d_header);
     HIP_TRY(hipGetLastError());
     // ---- cost the whole list.  (The child block is NOT cleared on the device: an edge's slots beyond its own ribbon count are
     // written by nobody and read by nobody there; the copy-out below hands the caller zeros for them.)

@@ -679,8 +679,23 @@ def test_expand_host_equals_the_step_by_step_calls(torch_cuda):
     """ppgpu_expand_host = set_vertices + set_extra_targets + expand_order + the edge list of SamplingBasedPlanner::expand +
     cost_edges_host, in one round trip: same descriptors in the same order, bit-identical records and child ribbons."""
     from path_planner_amd import workloads
-    from path_planner_amd.types import edge_pack, F_INFEASIBLE
+    _expand_host_equals_the_step_by_step_calls(torch_cuda, workloads.config2())
+
+
+def test_expand_host_equals_the_step_by_step_calls_with_one_radius_and_one_speed(torch_cuda):
+    """The same with one radius and one speed in use (SamplingBasedPlanner.cpp:57-63): the single radius is the coverage radius."""
+    from path_planner_amd import workloads
     w = workloads.config2()
+    w.cfg.slow_speed = -1
+    w.cfg.coverage_turning_radius = w.cfg.turning_radius
+    _expand_host_equals_the_step_by_step_calls(torch_cuda, w)
+
+
+def _expand_host_equals_the_step_by_step_calls(torch_cuda, w):
+    from path_planner_amd.types import edge_pack, F_INFEASIBLE
+    nsp = 2 if 0 < w.cfg.slow_speed != w.cfg.max_speed else 1                   # the two loops of expand(), from the configuration
+    nrad = 2 if w.cfg.coverage_turning_radius != w.cfg.turning_radius else 1
+    cov = lambda ri: 1 if (ri == 1 or nrad == 1) else 0
     ctx, world, n, cs = _setup(w, 1500)
     gpu, gchild = _dense(torch_cuda, ctx, 1, n, 0xF)
     pick = np.nonzero((gpu["flags"] & 0x0F) == 0)[0][:9:2]            # a few feasible children as open vertices
@@ -698,20 +713,22 @@ def test_expand_host_equals_the_step_by_step_calls(torch_cuda):
     idx, fallbacks = ctx.expand_order(len(verts), k)
     assert fallbacks == 0
     asc, _ = ctx.select_nearest(0, len(verts), k)
-    assert np.array_equal(np.sort(idx, axis=2), np.sort(asc, axis=2))      # the same winners, in push order instead of ascending
+    # the same winners, in push order instead of ascending (select_nearest always fills both rows, expand_order those in use)
+    assert np.array_equal(np.sort(idx[:, :nrad], axis=2), np.sort(asc[:, :nrad], axis=2))
+    assert (idx[:, nrad:] == -1).all()
     want = []
     for v in range(len(verts)):
         if has[v]:
-            for si in range(2):
-                for ri in range(2):
-                    want.append(edge_pack(v, first + slot[v], (1 if ri == 1 else 0) | (2 if si == 1 else 0)))
-        for ri in range(2):
+            for si in range(nsp):
+                for ri in range(nrad):
+                    want.append(edge_pack(v, first + slot[v], cov(ri) | (2 if si == 1 else 0)))
+        for ri in range(nrad):
             for j in range(k):
                 s = idx[v, ri, j]
                 if s < 0:
                     break
-                for si in range(2):
-                    want.append(edge_pack(v, int(s), (1 if ri == 1 else 0) | (2 if si == 1 else 0)))
+                for si in range(nsp):
+                    want.append(edge_pack(v, int(s), cov(ri) | (2 if si == 1 else 0)))
     want = np.array(want, dtype=np.uint64)
     r2, c2 = ctx.cost_edges_host(want, stride=8)
     assert len(e1) == len(want)
@@ -723,15 +740,23 @@ def test_expand_host_equals_the_step_by_step_calls(torch_cuda):
     assert np.count_nonzero((r1["flags"] & F_INFEASIBLE) == 0) >= 10
 
 
-@pytest.mark.parametrize("cfgname,n_samples,k", [("cfg1", 64, 9), ("cfg2", 4096, 9), ("cfg2", 300, 5), ("cfg3", 65536, 9), ("cfg3", 20000, 20),
-                                                 ("cfg3", 2000, 1), ("cfg1", 6, 9)])
-def test_expand_order_is_the_reference_heap_array(torch_cuda, cfgname, n_samples, k):
+@pytest.mark.parametrize("cfgname,n_samples,k,one_radius", [
+    ("cfg1", 64, 9, False), ("cfg2", 4096, 9, False), ("cfg2", 300, 5, False), ("cfg3", 65536, 9, False), ("cfg3", 20000, 20, False),
+    ("cfg3", 2000, 1, False), ("cfg1", 6, 9, False),
+    ("cfg2", 300, 40, False),       # k above the probe's 32 groups: every valid sample is near, the replay runs with 41 lanes
+    ("cfg2", 300, 5, True), ("cfg1", 64, 9, True),      # coverage_turning_radius = turning_radius: row 1 stays empty
+    ("cfg2", 300, 64, False),       # a heap of k + 1 does not fit a wavefront: no replay, every list keeps ascending length and says so
+], ids=["cfg1-64-9", "cfg2-4096-9", "cfg2-300-5", "cfg3-65536-9", "cfg3-20000-20", "cfg3-2000-1", "cfg1-6-9",
+        "cfg2-300-40", "cfg2-300-5-one_radius", "cfg1-64-9-one_radius", "cfg2-300-64"])
+def test_expand_order_is_the_reference_heap_array(torch_cuda, cfgname, n_samples, k, one_radius):
     """The order in which expand() pushes the k winners of each radius = the array of the reference's max-heap of candidates
     when its nearest-first scan stops (SamplingBasedPlanner.cpp:82-149), replayed on the device (pp_k_expand_order) from the root
     and from children of the root, against the oracle's literal scan (std::make_heap / pop_heap / push_heap on the same samples)."""
     from path_planner_amd import workloads
     from path_planner_amd.types import F_INFEASIBLE
     w = workloads.by_name(cfgname)
+    if one_radius:
+        w.cfg.coverage_turning_radius = w.cfg.turning_radius
     ctx, world, n, cs = _setup(w, n_samples)
     gpu, gchild = _dense(torch_cuda, ctx, 1, min(n, 512), 0xF)
     feas = np.nonzero((gpu["flags"] & F_INFEASIBLE) == 0)[0]
@@ -739,14 +764,22 @@ def test_expand_order_is_the_reference_heap_array(torch_cuda, cfgname, n_samples
     verts, pool = _children_as_vertices(w, gpu, gchild, pick)
     ctx.set_vertices(verts, pool)
     idx, fallbacks = ctx.expand_order(len(verts), k)
+    asc, _ = ctx.select_nearest(0, len(verts), k)
+    if k >= 64:
+        assert fallbacks == 2 * len(verts)
+        assert np.array_equal(idx, asc)                  # per vertex and radius: ascending (length, sample)
+        idx2, fallbacks2 = ctx.expand_order(len(verts), k)
+        assert fallbacks2 == fallbacks and idx2.tobytes() == idx.tobytes()
+        return
     assert fallbacks == 0 and ctx.order_fallbacks() == 0
     differs_from_ascending = 0
-    asc, _ = ctx.select_nearest(0, len(verts), k)
+    rows = 1 if one_radius else 2                        # select_nearest always fills both rows
     for v in range(len(verts)):
         src = np.array([verts["x"][v], verts["y"][v], verts["heading"][v], verts["speed"][v], verts["time"][v]])
         want = world.expand_order(src, cs[:, 0], cs[:, 1], cs[:, 2], k)
         assert np.array_equal(idx[v], want), (cfgname, v, idx[v], want)
-        differs_from_ascending += int(not np.array_equal(idx[v], asc[v]))
+        assert (idx[v, rows:] == -1).all() and (idx[v, 0] >= 0).sum() == (asc[v, 0] >= 0).sum()
+        differs_from_ascending += int(not np.array_equal(idx[v, :rows], asc[v, :rows]))
     if k > 2 and n > 2 * k:
         assert differs_from_ascending > 0       # the heap array is not sorted: the test would be vacuous otherwise
 
