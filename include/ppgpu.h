@@ -652,6 +652,78 @@ int ppgpu_get_grid_blocked(ppgpu_ctx* ctx, uint8_t* h_out, int64_t capacity);
  * pp_k_keepout_bits (not run on the way back to 0) and the rebuild of the chessboard clearance map.  PPGPU_ESTATE when none was timed. */
 int ppgpu_last_keepout_timing(ppgpu_ctx* ctx, double* ms_keepout);
 
+/* ---------------------------------------------------------------- reachable water */
+
+/* Which water a plan can get to at all, and which ribbons lie beyond it.  Everything is exact in integers except where a ribbon's
+ * sample points are placed.
+ * COMPONENTS.  The grid is the effective grid (what ppgpu_get_grid_blocked returns: the grid as set at limit2 0).  Two free cells are
+ * neighbours when they differ by at most 1 in row and in column (8-connectivity); label(r, c) is the smallest row-major index
+ * r' * cols + c' over the cells of the component of (r, c); a blocked cell has PPGPU_REACH_NONE.  The labelling is canonical: any
+ * correct algorithm writes the same bytes.
+ *   Why 8 and not 4: Edge::computeTrueCost samples poses at most collision_checking_increment metres apart (Edge.cpp:114,173) and
+ *   declares the edge infeasible at the first pose on a blocked cell (Edge.cpp:144-147).  With increment <= resolution consecutive
+ *   poses lie in the same or in 8-neighbouring cells, and two poses either side of the corner between two diagonal hazard cells are
+ *   both free: a feasible chain of edges from the start never leaves the 8-connected component of the start's cell, and can leave
+ *   nothing smaller.
+ * REACH SET of a seed pose: the seed's cell is the one Map::isBlocked puts it in (GridWorldMap.cpp:84-93).  A seed on a blocked cell
+ * or outside the grid gives PPGPU_REACH_SEED_BLOCKED, an empty set, and no ribbon is judged.  Otherwise the set is every cell with
+ * the seed's label.
+ * REACH GAP.  rgap2(A) = min over reachable cells B of gap2(A, B), gap2 as under "chart clearance"; the map holds
+ * min(rgap2, PPGPU_DIST_CAP2) as uint16_t.  The outside of the grid is NOT a source here.  Every point of cell A is at least
+ * resolution * sqrt(rgap2(A)) from every point of every reachable cell.
+ * A RIBBON'S SAMPLES, for {sx, sy, ex, ey} with dx = ex - sx, dy = ey - sy, every product and sum rounded on its own:
+ *     len = sqrt(dx*dx + dy*dy),  n = max(1, ceil(len / (0.5 * resolution))),  sample k of 0..n at (sx + dx * (k / n), sy + dy * (k / n))
+ * so every point of the ribbon is within resolution / 4 of a sample.  A sample is clamped into [0, cols*res] x [0, rows*res]
+ * (projection onto a convex set never increases the distance to a point inside it), its cell is min(size_t(x / res), cols - 1) and
+ * likewise for rows.  A sample is OUT iff rgap2(cell) >= lim2 with lim2 = ppgpu_keepout_limit2(resolution, ribbon_width + 0.25 *
+ * resolution): an integer comparison.  Ribbon::contains (Ribbon.cpp:39-43) lets a pose cover only what lies within RibbonWidth of it,
+ * so no pose in a reachable cell covers any point of the ribbon within resolution / 4 of an OUT sample: that is what a record
+ * certifies.  A sample that is not OUT proves nothing: the turning radius may still keep the boat from covering it.
+ * Lazy, like the distance map: ppgpu_set_grid and a changed keep-out limit only mark the labels stale, the first call below that
+ * needs them builds them (three launches whatever the grid holds), and a seed that moves inside the component of the cached reach
+ * set costs one 4-byte look-up.  A handle that never makes these calls allocates and launches nothing for them. */
+#define PPGPU_REACH_NONE 0xFFFFFFFFu
+#define PPGPU_REACH_TILE 32     /* the labelling's tile edge in cells (tests place their shapes around it) */
+/* For tests and tools: the labels, rows*cols values.  PPGPU_EINVAL without a grid (rows == 0), when capacity < rows*cols or when
+ * rows*cols >= 2^32 - 1; PPGPU_ECAPACITY if a union-find loop ran into its cap (it cannot).  Synchronous. */
+int ppgpu_get_grid_labels(ppgpu_ctx* ctx, uint32_t* h_out, int64_t capacity);
+#define PPGPU_REACH_SEED_BLOCKED 0x1u  /* the seed's cell is blocked or outside the grid: nothing is reachable */
+#define PPGPU_REACH_NO_MAP       0x2u  /* base Map (rows == 0): nothing is charted, everything is reachable; the counts are 0 */
+typedef struct ppgpu_reach_info {       /* 32 bytes */
+    uint64_t free_cells, reachable_cells;   /* of the effective grid; with the seed's label (0 for a blocked seed) */
+    uint32_t components, seed_label, flags, reserved;   /* PPGPU_REACH_NONE for a blocked seed; PPGPU_REACH_*; 0 */
+} ppgpu_reach_info;
+/* The seed of the reach set (a plan's start).  Builds the labels if they are stale, and the reach bits and the reach-gap map when
+ * the seed's label is not that of the cached set.  out may be NULL.  PPGPU_EINVAL for a NaN.  Synchronous. */
+int ppgpu_set_reach_seed(ppgpu_ctx* ctx, double x, double y, ppgpu_reach_info* out);
+/* For tests and tools: the reach-gap map of the current seed, rows*cols values (all PPGPU_DIST_CAP2 for a blocked seed).
+ * PPGPU_ESTATE without a seed; PPGPU_EINVAL as ppgpu_get_grid_labels.  Synchronous. */
+int ppgpu_get_grid_reach_gap(ppgpu_ctx* ctx, uint16_t* h_out, int64_t capacity);
+#define PPGPU_RB_ANY_OUT    0x01u  /* some sample is OUT */
+#define PPGPU_RB_WHOLE_OUT  0x02u  /* every sample is */
+#define PPGPU_RB_START_OUT  0x04u  /* sample 0 is */
+#define PPGPU_RB_END_OUT    0x08u  /* the last sample is */
+#define PPGPU_RB_DEGENERATE 0x10u  /* len == 0: one sample, pitch 0 */
+#define PPGPU_RB_CAPPED     0x20u  /* max_rgap2 == PPGPU_DIST_CAP2: "at least" */
+#define PPGPU_RB_NO_SEED    0x40u  /* the seed is blocked: nothing judged, out_samples 0, first_out and last_out -1, the gaps 0 */
+#define PPGPU_RB_NO_MAP     0x80u  /* base Map: everything is reachable, nothing judged, as above */
+typedef struct ppgpu_ribbon_reach_record {  /* 64 bytes */
+    double length, pitch;                   /* len, len / n (0 for a degenerate ribbon) */
+    uint32_t samples, out_samples;          /* n + 1 (1 for a degenerate ribbon); how many of them are OUT */
+    int32_t first_out, last_out;            /* sample indices, -1 without one */
+    uint32_t min_rgap2, max_rgap2, lim2, flags;   /* over the samples' cells, capped as the map is; PPGPU_RB_* */
+    double out_length;                      /* pitch * out_samples, capped at length */
+    uint64_t reserved;                      /* 0 */
+} ppgpu_ribbon_reach_record;
+/* One record per ribbon of h_ribbons4 (n rows of {sx, sy, ex, ey}) against the reach set of the current seed.  PPGPU_ESTATE without
+ * a seed.  PPGPU_EINVAL for a NaN anywhere, a ribbon with more than 2^22 samples, and ribbon_width + resolution / 4 above 255
+ * cells.  Synchronous. */
+int ppgpu_ribbon_reach_host(ppgpu_ctx* ctx, int32_t n, const double* h_ribbons4, double ribbon_width, ppgpu_ribbon_reach_record* h_records);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds of the last build of the labels (three kernels), of the
+ * last build of a reach set (pp_k_reach_bits and the two passes of its gap map) and of the last ribbon walk; -1 for each that was
+ * not timed since ppgpu_enable_timing.  PPGPU_ESTATE with timing off.  Waits for the stream. */
+int ppgpu_last_reach_timing(ppgpu_ctx* ctx, double* ms_labels, double* ms_reach_gap, double* ms_ribbons);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

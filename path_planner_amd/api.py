@@ -103,6 +103,11 @@ def _load():
         "ppgpu_get_keepout_limit2": (C.c_int, [vp, C.POINTER(u32)]),
         "ppgpu_get_grid_blocked": (C.c_int, [vp, vp, i64]),
         "ppgpu_last_keepout_timing": (C.c_int, [vp, C.POINTER(dbl)]),
+        "ppgpu_get_grid_labels": (C.c_int, [vp, vp, i64]),
+        "ppgpu_set_reach_seed": (C.c_int, [vp, dbl, dbl, vp]),
+        "ppgpu_get_grid_reach_gap": (C.c_int, [vp, vp, i64]),
+        "ppgpu_ribbon_reach_host": (C.c_int, [vp, i32, vp, dbl, vp]),
+        "ppgpu_last_reach_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -567,6 +572,44 @@ class Context:
         ms = C.c_double()
         self._ck(LIB.ppgpu_last_keepout_timing(self._h, C.byref(ms)), "ppgpu_last_keepout_timing")
         return ms.value
+
+    # ---- reachable water: which cells a plan from a seed can get to, and which ribbons lie beyond them
+    def get_grid_labels(self, rows, cols):
+        """The canonical 8-connected component labels of the effective grid, rows x cols uint32 (REACH_NONE on a blocked cell):
+        the smallest row-major cell index of each component; for tests and tools.  Built on first use."""
+        out = np.zeros((rows, cols), dtype=np.uint32)
+        self._ck(LIB.ppgpu_get_grid_labels(self._h, _ptr(out), out.size), "ppgpu_get_grid_labels")
+        return out
+
+    def set_reach_seed(self, x, y):
+        """The pose whose component is the reach set; returns the REACH_INFO_DTYPE block (flags: REACH_SEED_BLOCKED, REACH_NO_MAP)."""
+        from .types import REACH_INFO_DTYPE
+        info = np.zeros(1, dtype=REACH_INFO_DTYPE)
+        self._ck(LIB.ppgpu_set_reach_seed(self._h, float(x), float(y), _ptr(info)), "ppgpu_set_reach_seed")
+        return info[0]
+
+    def get_grid_reach_gap(self, rows, cols):
+        """min(rgap2, DIST_CAP2) per cell, rows x cols uint16: the squared gap in cells to the nearest cell of the current seed's reach
+        set (0 on the set and beside it); for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint16)
+        self._ck(LIB.ppgpu_get_grid_reach_gap(self._h, _ptr(out), out.size), "ppgpu_get_grid_reach_gap")
+        return out
+
+    def ribbon_reach(self, ribbons4, ribbon_width):
+        """One RIBBON_REACH_DTYPE record per ribbon {sx, sy, ex, ey}: how much of it no pose in the reach set can cover.  A sample
+        that is not OUT proves nothing (the turning radius may still prevent coverage)."""
+        from .types import RIBBON_REACH_DTYPE
+        rb = np.ascontiguousarray(ribbons4, dtype=np.float64).reshape(-1, 4)
+        out = np.zeros(rb.shape[0], dtype=RIBBON_REACH_DTYPE)
+        self._ck(LIB.ppgpu_ribbon_reach_host(self._h, rb.shape[0], _ptr(rb), float(ribbon_width), _ptr(out)), "ppgpu_ribbon_reach_host")
+        return out
+
+    def last_reach_timing(self):
+        """(labels, reach set and gap map, ribbon walk) device milliseconds of the last of each, -1 where none was timed since
+        enable_timing."""
+        t = [C.c_double() for _ in range(3)]
+        self._ck(LIB.ppgpu_last_reach_timing(self._h, *[C.byref(x) for x in t]), "ppgpu_last_reach_timing")
+        return tuple(x.value for x in t)
 
     @staticmethod
     def dense_edge_count(nv, ns, cfg_mask):

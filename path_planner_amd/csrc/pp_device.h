@@ -517,7 +517,8 @@ __device__ __forceinline__ bool pp_is_blocked(const PPGrid& g, double x, double 
 // pp_is_blocked in two halves, for a caller that wants the words of several chunks on their way before it looks at any of them:
 // the same arithmetic up to the cell, then the load alone (a lane outside the grid reads word 0, which it does not use), then the test.
 struct PPCellRef { size_t word; unsigned col; bool outside; };
-__device__ __forceinline__ PPCellRef pp_blocked_cell(const PPGrid& g, double x, double y) {
+struct PPCell { unsigned r, c; bool outside; };   // the cell itself: (size_t(y / res), size_t(x / res)), meaningful inside or on the far edges
+__device__ __forceinline__ PPCell pp_cell_of(const PPGrid& g, double x, double y) {
     const double cx = x * g.inv_res, cy = y * g.inv_res;
     const unsigned cxl = (unsigned)(cx * (1.0 - 4e-9)), cxh = (unsigned)(cx * (1.0 + 4e-9));
     const unsigned cyl = (unsigned)(cy * (1.0 - 4e-9)), cyh = (unsigned)(cy * (1.0 + 4e-9));
@@ -529,10 +530,16 @@ __device__ __forceinline__ PPCellRef pp_blocked_cell(const PPGrid& g, double x, 
         r = (unsigned)qy;
         c = (unsigned)qx;
     }
+    PPCell cell;
+    cell.r = r; cell.c = c; cell.outside = outside;
+    return cell;
+}
+__device__ __forceinline__ PPCellRef pp_blocked_cell(const PPGrid& g, double x, double y) {
+    const PPCell cell = pp_cell_of(g, x, y);
     PPCellRef ref;
-    ref.word = outside ? (size_t)0 : (size_t)r * g.wpr + (c >> 5);
-    ref.col = c;
-    ref.outside = outside;
+    ref.word = cell.outside ? (size_t)0 : (size_t)cell.r * g.wpr + (cell.c >> 5);
+    ref.col = cell.c;
+    ref.outside = cell.outside;
     return ref;
 }
 __device__ __forceinline__ bool pp_blocked_test(const PPCellRef& ref, uint32_t w) { return ref.outside | (((w >> (ref.col & 31)) & 1u) != 0u); }

@@ -13,17 +13,21 @@
 static_assert(PPGPU_DIST_CAP * PPGPU_DIST_CAP == PPGPU_DIST_CAP2 && PPGPU_DIST_CAP2 <= 0xFFFF, "the capped map fits uint16_t");
 static_assert(PP_DIST_VCAP % 8 == 0, "pp_dist_scan looks at eight rows at a time");
 
+// OUTSIDE_IS_HAZARD: the chart's map, as described above.  Without it the rows and columns outside the grid hold no source: the map of
+// the distance to a set of cells alone (the reach gap of pp_k_reach.h), v = PP_DIST_VCAP in the columns outside.
+template <bool OUTSIDE_IS_HAZARD>
 __device__ __forceinline__ bool pp_dist_hazard(const uint32_t* bits, int rows, int wpr, int r, int c) {
-    if (r < 0 || r >= rows) return true;
+    if (r < 0 || r >= rows) return OUTSIDE_IS_HAZARD;
     return (bits[(size_t)r * wpr + (c >> 5)] >> (c & 31)) & 1u;
 }
 // min(PP_DIST_VCAP, the smallest d >= 1 with a hazard at row from + dir * d): eight rows' words are on their way before the first
 // is looked at (one row at a time the walk is a chain of dependent load latencies)
+template <bool OUTSIDE_IS_HAZARD>
 __device__ __forceinline__ int pp_dist_scan(const uint32_t* bits, int rows, int wpr, int from, int dir, int c) {
     for (int d0 = 1; d0 <= PP_DIST_VCAP; d0 += 8) {
         unsigned m = 0;
 #pragma unroll
-        for (int j = 0; j < 8; j++) m |= (pp_dist_hazard(bits, rows, wpr, from + dir * (d0 + j), c) ? 1u : 0u) << j;
+        for (int j = 0; j < 8; j++) m |= (pp_dist_hazard<OUTSIDE_IS_HAZARD>(bits, rows, wpr, from + dir * (d0 + j), c) ? 1u : 0u) << j;
         if (m) return d0 + __ffs((int)m) - 1;
     }
     return PP_DIST_VCAP;
@@ -32,20 +36,21 @@ __device__ __forceinline__ int pp_dist_scan(const uint32_t* bits, int rows, int 
 // Column pass.  One thread per column and tile of PP_DIST_TILE rows; adjacent lanes take adjacent columns, so a wave reads one or
 // two words of a row and writes 128 contiguous bytes of v per row (lanes striding across rows would touch 64 lines per access).
 // The thread finds the nearest hazard above its tile, walks down, finds the nearest below, walks back up.
+template <bool OUTSIDE_IS_HAZARD>
 __global__ __launch_bounds__(256) void pp_k_dist_cols(const uint32_t* bits, int rows, int cols, int wpr, uint16_t* v) {
     const int c = (int)(blockIdx.x * 256 + threadIdx.x);
     if (c >= cols) return;
     const int r0 = (int)blockIdx.y * PP_DIST_TILE;
     const int nr = (rows - r0) < PP_DIST_TILE ? (rows - r0) : PP_DIST_TILE;
     unsigned hazard = 0;
-    for (int i = 0; i < nr; i++) hazard |= (pp_dist_hazard(bits, rows, wpr, r0 + i, c) ? 1u : 0u) << i;
+    for (int i = 0; i < nr; i++) hazard |= (pp_dist_hazard<OUTSIDE_IS_HAZARD>(bits, rows, wpr, r0 + i, c) ? 1u : 0u) << i;
     uint16_t* col = v + (size_t)r0 * cols + c;
-    int d = pp_dist_scan(bits, rows, wpr, r0, -1, c) - 1;                   // what row r0 - 1 would hold
+    int d = pp_dist_scan<OUTSIDE_IS_HAZARD>(bits, rows, wpr, r0, -1, c) - 1;                   // what row r0 - 1 would hold
     for (int i = 0; i < nr; i++) {
         d = ((hazard >> i) & 1u) ? 0 : min(d + 1, PP_DIST_VCAP);
         col[(size_t)i * cols] = (uint16_t)d;
     }
-    d = pp_dist_scan(bits, rows, wpr, r0 + nr - 1, +1, c) - 1;              // what row r0 + nr would hold
+    d = pp_dist_scan<OUTSIDE_IS_HAZARD>(bits, rows, wpr, r0 + nr - 1, +1, c) - 1;              // what row r0 + nr would hold
     for (int i = nr - 1; i >= 0; i--) {
         d = ((hazard >> i) & 1u) ? 0 : min(d + 1, PP_DIST_VCAP);
         const int down = col[(size_t)i * cols];
@@ -54,15 +59,16 @@ __global__ __launch_bounds__(256) void pp_k_dist_cols(const uint32_t* bits, int 
 }
 
 // Row pass.  One workgroup per row and tile of 256 columns: the tile's v and the PP_DIST_VCAP columns on either side of it (0 outside
-// the grid) are staged in LDS, 1.5 KB whatever the grid's width.  Each thread walks outwards from its own column and leaves once
+// the grid where the outside is a hazard) are staged in LDS, 1.5 KB whatever the grid's width.  Each thread walks outwards from its own column and leaves once
 // g(dc)^2 alone reaches its best: at most PPGPU_DIST_CAP steps, on an empty grid.
+template <bool OUTSIDE_IS_HAZARD>
 __global__ __launch_bounds__(256) void pp_k_dist_rows(const uint16_t* v, int rows, int cols, uint16_t* dist) {
     __shared__ uint16_t s_v[256 + 2 * PP_DIST_VCAP];
     const int r = (int)blockIdx.x, c0 = (int)blockIdx.y * 256;
     const uint16_t* row = v + (size_t)r * cols;
     for (int j = (int)threadIdx.x; j < 256 + 2 * PP_DIST_VCAP; j += 256) {
         const int cc = c0 - PP_DIST_VCAP + j;
-        s_v[j] = (cc >= 0 && cc < cols) ? row[cc] : (uint16_t)0;
+        s_v[j] = (cc >= 0 && cc < cols) ? row[cc] : (uint16_t)(OUTSIDE_IS_HAZARD ? 0 : PP_DIST_VCAP);
     }
     __syncthreads();
     const int c = c0 + (int)threadIdx.x;

@@ -145,6 +145,22 @@ struct ppgpu_ctx {
     // keepout_limit2 > 0 the launches read grid_keepout instead (grid_bits), and grid_clear is the map of that grid.
     uint32_t keepout_limit2 = 0;
     DevBuf<uint32_t> grid_keepout;      // the effective grid, allocated by the first non-zero limit on a grid
+    // reachable water (ppgpu.h): nothing here is allocated, launched or timed before the first call of that section
+    DevBuf<uint32_t> reach_labels;      // canonical component labels of the effective grid, built by the first call that needs them ...
+    bool reach_labels_built = false;    // ... after a ppgpu_set_grid or a changed keep-out limit (reach_labels_ready)
+    DevBuf<unsigned long long> reach_words;   // PP_RW_*: the counters and the sticky error word of the labelling and the reach set
+    unsigned long long reach_free = 0, reach_components = 0, reach_cells = 0;
+    bool reach_have_seed = false;       // ppgpu_set_reach_seed was called: the seed stays across grids and limits
+    double reach_seed_x = 0, reach_seed_y = 0;
+    uint32_t reach_seed_label = PPGPU_REACH_NONE;   // of the labels as built last (reach_seed_ready looks it up again after a rebuild)
+    bool reach_seed_fresh = false;
+    DevBuf<uint32_t> reach_bits;        // the cells with reach_set_label, PPGrid's layout ...
+    DevBuf<uint16_t> reach_gap;         // ... and the reach-gap map over them
+    bool reach_set_built = false;
+    uint32_t reach_set_label = PPGPU_REACH_NONE;
+    DevBuf<double> reach_ribbons;       // {sx, sy, ex, ey, len, n} per ribbon of the last ppgpu_ribbon_reach_host
+    DevBuf<ppgpu_ribbon_reach_record> reach_records;
+    TraceTimer t_reach_labels, t_reach_gap, t_reach_ribbons;   // (events made by the first timed use, like t_keepout's)
     // dynamic obstacles
     DevBuf<PPObst> obst;
     int n_obst = 0;
@@ -242,7 +258,8 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1],
+                             t_reach_labels.ev[0], t_reach_labels.ev[1], t_reach_gap.ev[0], t_reach_gap.ev[1], t_reach_ribbons.ev[0], t_reach_ribbons.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -361,6 +378,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
         tm->timed = false;
     }
     c->t_keepout.timed = false;         // (its events are made by the first timed change of the keep-out: apply_keepout)
+    c->t_reach_labels.timed = c->t_reach_gap.timed = c->t_reach_ribbons.timed = false;   // (... by the first timed build or walk)
     c->timing = on != 0;
     c->ev_launches = 0;
     return PPGPU_OK;
@@ -559,6 +577,7 @@ int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t col
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));
     c->grid_dist_built = false;
+    c->reach_labels_built = false;                      // (stale: the first call that needs the labels builds them)
     if (rows == 0) { c->rows = c->cols = c->wpr = 0; c->res = 0; return PPGPU_OK; }
     if (!cells || rows < 0 || cols <= 0 || !(res > 0)) return fail(PPGPU_EINVAL, "grid: bad shape or resolution");
     int wpr = (cols + 31) / 32;
@@ -612,8 +631,8 @@ static int grid_distance(ppgpu_ctx* c) {
     c->t_dist.ms_earlier = 0;
     c->t_dist.timed = false;
     if (c->timing) HIP_TRY(hipEventRecord(c->t_dist.ev[0], c->stream));
-    hipLaunchKernelGGL(pp_k_dist_cols, dim3(ctiles, rtiles), dim3(256), 0, c->stream, c->grid.p, c->rows, c->cols, c->wpr, v.p);
-    hipLaunchKernelGGL(pp_k_dist_rows, dim3((unsigned)c->rows, ctiles), dim3(256), 0, c->stream, v.p, c->rows, c->cols, c->grid_dist.p);
+    hipLaunchKernelGGL(pp_k_dist_cols<true>, dim3(ctiles, rtiles), dim3(256), 0, c->stream, c->grid.p, c->rows, c->cols, c->wpr, v.p);
+    hipLaunchKernelGGL(pp_k_dist_rows<true>, dim3((unsigned)c->rows, ctiles), dim3(256), 0, c->stream, v.p, c->rows, c->cols, c->grid_dist.p);
     if (c->timing) { HIP_TRY(hipEventRecord(c->t_dist.ev[1], c->stream)); c->t_dist.timed = true; }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));       // the scratch goes with this scope
@@ -684,6 +703,7 @@ int ppgpu_keepout_limit2(double resolution, double margin, uint32_t* limit2) {
 static int apply_keepout(ppgpu_ctx* c) {
     hipStream_t st = c->stream;
     int rc = PPGPU_OK;
+    c->reach_labels_built = false;                      // the labels are those of the effective grid
     if (c->keepout_limit2) {
         const unsigned ctiles = (unsigned)((c->cols + 255) / 256);
         if (ctiles > 65535u) return fail(PPGPU_ECAPACITY, "keep-out: the grid is too wide for the kernel's launch shape");
@@ -740,6 +760,237 @@ int ppgpu_get_grid_blocked(ppgpu_ctx* c, uint8_t* h_out, int64_t capacity) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int r = 0; r < c->rows; r++)
         for (int x = 0; x < c->cols; x++) h_out[(size_t)r * c->cols + x] = (uint8_t)((bits[(size_t)r * c->wpr + (x >> 5)] >> (x & 31)) & 1u);
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ reachable water
+// Events of a reach timer are made by its first timed use; begin / end go around the launches on the stream.
+static int reach_timer_begin(ppgpu_ctx* c, TraceTimer& tm) {
+    tm.ms_earlier = 0;
+    tm.timed = false;
+    if (!c->timing) return PPGPU_OK;
+    if (!tm.ev[0])
+        for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm.ev[i]));
+    HIP_TRY(hipEventRecord(tm.ev[0], c->stream));
+    return PPGPU_OK;
+}
+static int reach_timer_end(ppgpu_ctx* c, TraceTimer& tm) {
+    if (c->timing) { HIP_TRY(hipEventRecord(tm.ev[1], c->stream)); tm.timed = true; }
+    return PPGPU_OK;
+}
+// The PP_RW_* words of the launches just issued, after a wait for the stream.
+static int reach_read_words(ppgpu_ctx* c, unsigned long long* h_words) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_words, c->reach_words.p, PP_RW_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+// What the getters of this section refuse (rows > 0 from here on).
+static int reach_check_grid(const ppgpu_ctx* c, const char* who, const void* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, std::string(who) + ": null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, std::string(who) + ": no grid is set");
+    const int64_t ncell = (int64_t)c->rows * c->cols;
+    if (capacity < ncell) return fail(PPGPU_EINVAL, std::string(who) + ": capacity below rows * cols");
+    if (ncell >= 0xFFFFFFFFll) return fail(PPGPU_EINVAL, std::string(who) + ": rows * cols must be below 2^32 - 1 (a label is a 32-bit cell index)");
+    return PPGPU_OK;
+}
+
+// The labels of the effective grid (rows > 0, rows * cols < 2^32 - 1): three launches whatever the grid holds (pp_k_reach.h), then
+// one read-back of the counters and of the error word.
+static int reach_labels_ready(ppgpu_ctx* c) {
+    if (c->reach_labels_built) return PPGPU_OK;
+    hipStream_t st = c->stream;
+    const long long ncell = (long long)c->rows * c->cols;
+    int rc;
+    if ((rc = c->reach_labels.reserve((size_t)ncell, false, st)) || (rc = c->reach_words.reserve(PP_RW_COUNT, false, st))) return rc;
+    const unsigned tx = (unsigned)((c->cols + PP_REACH_TILE - 1) / PP_REACH_TILE), ty = (unsigned)((c->rows + PP_REACH_TILE - 1) / PP_REACH_TILE);
+    if (ty > 65535u) return fail(PPGPU_ECAPACITY, "reach labels: the grid is too tall for the tile kernel's launch shape");
+    const long long hcells = (long long)((c->rows - 1) / PP_REACH_TILE) * c->cols;
+    const long long total = hcells + (long long)((c->cols - 1) / PP_REACH_TILE) * c->rows;
+    c->reach_set_built = false;
+    c->reach_seed_fresh = false;
+    HIP_TRY(hipMemsetAsync(c->reach_words.p, 0, PP_RW_COUNT * sizeof(unsigned long long), st));
+    if ((rc = reach_timer_begin(c, c->t_reach_labels))) return rc;
+    hipLaunchKernelGGL(pp_k_reach_tiles, dim3(tx, ty), dim3(PP_REACH_TILE * PP_REACH_TILE), 0, st, grid_bits(c), c->rows, c->cols, c->wpr, c->reach_labels.p,
+                       c->reach_words.p);
+    if (total > 0)
+        hipLaunchKernelGGL(pp_k_reach_merge, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grid_bits(c), c->rows, c->cols, c->wpr, c->reach_labels.p,
+                           hcells, total, c->reach_words.p);
+    hipLaunchKernelGGL(pp_k_reach_flatten, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, c->reach_labels.p, ncell, c->reach_words.p);
+    if ((rc = reach_timer_end(c, c->t_reach_labels))) return rc;
+    unsigned long long w[PP_RW_COUNT];
+    if ((rc = reach_read_words(c, w))) return rc;
+    if (w[PP_RW_ERROR]) return fail(PPGPU_ECAPACITY, "reach labels: a union-find loop ran into its iteration cap");
+    c->reach_free = w[PP_RW_FREE];
+    c->reach_components = w[PP_RW_COMPONENTS];
+    c->reach_labels_built = true;
+    return PPGPU_OK;
+}
+
+// The seed's label in the labels as they stand, and the reach bits and the reach-gap map of that label (rows > 0, a seed is set).
+static int reach_seed_ready(ppgpu_ctx* c) {
+    int rc = reach_labels_ready(c);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    if (!c->reach_seed_fresh) {
+        // the cell Map::isBlocked puts the seed in (GridWorldMap.cpp:84-93): size_t(x / res), outside when x < 0 or x / res >= cols
+        const double x = c->reach_seed_x, y = c->reach_seed_y;
+        c->reach_seed_label = PPGPU_REACH_NONE;
+        if (!(x < 0 || x / c->res >= (double)c->cols || y < 0 || y / c->res >= (double)c->rows)) {
+            const size_t cell = (size_t)(y / c->res) * (size_t)c->cols + (size_t)(x / c->res);
+            HIP_TRY(hipMemcpyAsync(&c->reach_seed_label, c->reach_labels.p + cell, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        c->reach_seed_fresh = true;
+    }
+    if (c->reach_set_built && c->reach_set_label == c->reach_seed_label) return PPGPU_OK;
+    const size_t ncell = (size_t)c->rows * c->cols;
+    const unsigned ctiles = (unsigned)((c->cols + 255) / 256), rtiles = (unsigned)((c->rows + PP_DIST_TILE - 1) / PP_DIST_TILE);
+    if (ctiles > 65535u || rtiles > 65535u) return fail(PPGPU_ECAPACITY, "reach gap: the grid is too large for the map's launch shape");
+    DevBuf<uint16_t> v;
+    if ((rc = c->reach_bits.reserve((size_t)c->rows * c->wpr, false, st)) || (rc = c->reach_gap.reserve(ncell, false, st)) || (rc = v.reserve(ncell, false, st)))
+        return rc;
+    c->reach_set_built = false;
+    HIP_TRY(hipMemsetAsync(c->reach_words.p + PP_RW_REACHABLE, 0, sizeof(unsigned long long), st));
+    if ((rc = reach_timer_begin(c, c->t_reach_gap))) return rc;
+    hipLaunchKernelGGL(pp_k_reach_bits, dim3((unsigned)c->rows, ctiles), dim3(256), 0, st, c->reach_labels.p, c->rows, c->cols, c->wpr, c->reach_seed_label,
+                       c->reach_bits.p, c->reach_words.p);
+    hipLaunchKernelGGL(pp_k_dist_cols<false>, dim3(ctiles, rtiles), dim3(256), 0, st, c->reach_bits.p, c->rows, c->cols, c->wpr, v.p);
+    hipLaunchKernelGGL(pp_k_dist_rows<false>, dim3((unsigned)c->rows, ctiles), dim3(256), 0, st, v.p, c->rows, c->cols, c->reach_gap.p);
+    if ((rc = reach_timer_end(c, c->t_reach_gap))) return rc;
+    unsigned long long w[PP_RW_COUNT];
+    if ((rc = reach_read_words(c, w))) return rc;       // (the wait also lets the scratch go with this scope)
+    c->reach_cells = c->reach_seed_label == PPGPU_REACH_NONE ? 0ull : w[PP_RW_REACHABLE];
+    c->reach_set_label = c->reach_seed_label;
+    c->reach_set_built = true;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_labels(ppgpu_ctx* c, uint32_t* h_out, int64_t capacity) {
+    int rc = reach_check_grid(c, "grid labels", h_out, capacity);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = reach_labels_ready(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out, c->reach_labels.p, (size_t)c->rows * c->cols * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_set_reach_seed(ppgpu_ctx* c, double x, double y, ppgpu_reach_info* out) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (x != x || y != y) return fail(PPGPU_EINVAL, "set_reach_seed: the seed is not a number");
+    ppgpu_reach_info info{};
+    if (c->rows == 0) {                                 // the base Map charts nothing
+        info.seed_label = PPGPU_REACH_NONE;
+        info.flags = PPGPU_REACH_NO_MAP;
+    } else {
+        if ((long long)c->rows * c->cols >= 0xFFFFFFFFll) return fail(PPGPU_EINVAL, "set_reach_seed: rows * cols must be below 2^32 - 1 (a label is a 32-bit cell index)");
+        HIP_TRY(hipSetDevice(c->device));
+    }
+    const bool had = c->reach_have_seed;
+    const double was_x = c->reach_seed_x, was_y = c->reach_seed_y;
+    c->reach_have_seed = true;
+    c->reach_seed_x = x; c->reach_seed_y = y;
+    c->reach_seed_fresh = false;
+    if (c->rows > 0) {
+        const int rc = reach_seed_ready(c);
+        if (rc) { c->reach_have_seed = had; c->reach_seed_x = was_x; c->reach_seed_y = was_y; return rc; }
+        info.free_cells = c->reach_free;
+        info.reachable_cells = c->reach_cells;
+        info.components = (uint32_t)c->reach_components;
+        info.seed_label = c->reach_seed_label;
+        info.flags = c->reach_seed_label == PPGPU_REACH_NONE ? PPGPU_REACH_SEED_BLOCKED : 0u;
+    }
+    if (out) *out = info;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_reach_gap(ppgpu_ctx* c, uint16_t* h_out, int64_t capacity) {
+    int rc = reach_check_grid(c, "grid reach gap", h_out, capacity);
+    if (rc) return rc;
+    if (!c->reach_have_seed) return fail(PPGPU_ESTATE, "grid reach gap: ppgpu_set_reach_seed must be called first");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = reach_seed_ready(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out, c->reach_gap.p, (size_t)c->rows * c->cols * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_ribbon_reach_host(ppgpu_ctx* c, int32_t n, const double* h_ribbons4, double ribbon_width, ppgpu_ribbon_reach_record* h_records) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n < 0 || (n > 0 && (!h_ribbons4 || !h_records))) return fail(PPGPU_EINVAL, "ribbon_reach: bad arguments");
+    if (ribbon_width != ribbon_width) return fail(PPGPU_EINVAL, "ribbon_reach: the ribbon width is not a number");
+    if (!c->reach_have_seed) return fail(PPGPU_ESTATE, "ribbon_reach: ppgpu_set_reach_seed must be called first");
+    const bool nomap = c->rows == 0;
+    uint32_t lim2 = 0;
+    if (!nomap) {
+        if ((long long)c->rows * c->cols >= 0xFFFFFFFFll) return fail(PPGPU_EINVAL, "ribbon_reach: rows * cols must be below 2^32 - 1 (a label is a 32-bit cell index)");
+        if (ppgpu_keepout_limit2(c->res, ribbon_width + 0.25 * c->res, &lim2)) return fail(PPGPU_EINVAL, "ribbon_reach: ribbon_width + resolution / 4 above 255 cells");
+    }
+    // len and n of every ribbon, by the rule ppgpu.h states (the base Map has no resolution: one sample per ribbon end)
+    std::vector<double> rib((size_t)n * 6);
+    for (int32_t i = 0; i < n; i++) {
+        const double* q = h_ribbons4 + 4 * (size_t)i;
+        for (int j = 0; j < 4; j++)
+            if (q[j] != q[j]) return fail(PPGPU_EINVAL, "ribbon_reach: a ribbon coordinate is not a number");
+        const double dx = q[2] - q[0], dy = q[3] - q[1];
+        const double len = std::sqrt(dx * dx + dy * dy);
+        double nd = nomap ? 1.0 : std::ceil(len / (0.5 * c->res));
+        if (!(nd >= 1.0)) nd = 1.0;
+        if (!(nd < 4194304.0)) return fail(PPGPU_EINVAL, "ribbon_reach: a ribbon has more than 2^22 samples");
+        double* o = rib.data() + 6 * (size_t)i;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; o[4] = len; o[5] = nd;
+    }
+    if (n == 0) return PPGPU_OK;
+    if (!nomap) {
+        HIP_TRY(hipSetDevice(c->device));
+        const int rc = reach_seed_ready(c);
+        if (rc) return rc;
+    }
+    if (nomap || c->reach_seed_label == PPGPU_REACH_NONE) {          // nothing is judged
+        for (int32_t i = 0; i < n; i++) {
+            const double len = rib[6 * (size_t)i + 4], nd = rib[6 * (size_t)i + 5];
+            ppgpu_ribbon_reach_record r{};
+            r.length = len;
+            r.pitch = len == 0.0 ? 0.0 : len / nd;
+            r.samples = len == 0.0 ? 1u : (uint32_t)nd + 1u;
+            r.first_out = r.last_out = -1;
+            r.lim2 = lim2;
+            r.flags = (nomap ? PPGPU_RB_NO_MAP : PPGPU_RB_NO_SEED) | (len == 0.0 ? PPGPU_RB_DEGENERATE : 0u);
+            h_records[i] = r;
+        }
+        return PPGPU_OK;
+    }
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = c->reach_ribbons.reserve((size_t)n * 6, false, st)) || (rc = c->reach_records.reserve((size_t)n, false, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->reach_ribbons.p, rib.data(), rib.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const PPGrid g{nullptr, c->rows, c->cols, c->wpr, c->res, 1.0 / c->res, nullptr};
+    if ((rc = reach_timer_begin(c, c->t_reach_ribbons))) return rc;
+    hipLaunchKernelGGL(pp_k_reach_ribbons, dim3((unsigned)((n + PP_REACH_WPB - 1) / PP_REACH_WPB)), dim3(PP_REACH_WPB * 64), 0, st, g, c->reach_gap.p, (int)n,
+                       c->reach_ribbons.p, lim2, c->reach_records.p);
+    if ((rc = reach_timer_end(c, c->t_reach_ribbons))) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_records, c->reach_records.p, (size_t)n * sizeof(ppgpu_ribbon_reach_record), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PPGPU_OK;
+}
+
+int ppgpu_last_reach_timing(ppgpu_ctx* c, double* ms_labels, double* ms_reach_gap, double* ms_ribbons) {
+    if (!c || !ms_labels || !ms_reach_gap || !ms_ribbons) return fail(PPGPU_EINVAL, "last_reach_timing: null argument");
+    if (!c->timing) return fail(PPGPU_ESTATE, "last_reach_timing: timing is off (ppgpu_enable_timing)");
+    HIP_TRY(hipSetDevice(c->device));
+    TraceTimer* tms[3] = {&c->t_reach_labels, &c->t_reach_gap, &c->t_reach_ribbons};
+    double* outs[3] = {ms_labels, ms_reach_gap, ms_ribbons};
+    for (int i = 0; i < 3; i++) {
+        *outs[i] = -1.0;
+        if (!tms[i]->timed) continue;
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(tms[i]->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, tms[i]->ev[0], tms[i]->ev[1]));
+        *outs[i] = ms;
+    }
     return PPGPU_OK;
 }
 

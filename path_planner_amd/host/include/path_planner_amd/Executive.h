@@ -64,6 +64,8 @@ public:
     // PlannerConfig::setKeepoutMargin: every cycle plans this many metres clear of charted hazards.  The "run aground" check stays
     // on the map as set: being inside the margin is not being aground.
     void setKeepoutMargin(double metres) { m_PlannerConfig.setKeepoutMargin(metres); }
+    // PlannerConfig::setPlanReach: every cycle's Stats say which water the start can reach and which ribbons lie beyond it
+    void setPlanReach(bool on) { m_PlannerConfig.setPlanReach(on); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

@@ -139,6 +139,30 @@ public:
             bool Relaxed = false;                             // Limit2Applied < Limit2Requested
         };
         KeepoutReport Keepout;
+        // PlannerConfig::setPlanReach: the water the call's start can reach and the ribbons beyond it (ppgpu.h, "reachable water"),
+        // after the keep-out margin was applied.  FreeCells .. Flags are ppgpu_reach_info's, Ribbons the fields of
+        // ppgpu_ribbon_reach_record, one per ribbon of the call's RibbonManager in its order.  Certified = collision checking
+        // increment <= resolution: consecutive collision-check poses then lie in the same or in 8-neighbouring cells, so no feasible
+        // chain of edges leaves the start's component; otherwise the report makes no claim.  A ribbon that is not out of reach is
+        // not thereby coverable (the turning radius may still prevent it).  With the switch off Valid is false and nothing was asked.
+        struct ReachReport {
+            enum : uint32_t { SeedBlocked = 0x1, NoMap = 0x2 };                                 // PPGPU_REACH_*
+            enum : uint32_t { AnyOut = 0x01, WholeOut = 0x02, StartOut = 0x04, EndOut = 0x08, Degenerate = 0x10, Capped = 0x20, NoSeed = 0x40,
+                              RibbonNoMap = 0x80 };                                             // PPGPU_RB_*
+            struct Ribbon {
+                double length = 0, pitch = 0, outLength = 0;
+                uint32_t samples = 0, outSamples = 0;
+                int32_t firstOut = -1, lastOut = -1;
+                uint32_t minRgap2 = 0, maxRgap2 = 0, lim2 = 0, flags = 0;
+            };
+            bool Valid = false, Certified = false;
+            uint64_t FreeCells = 0, ReachableCells = 0;
+            uint32_t Components = 0, SeedLabel = 0xFFFFFFFFu, Flags = 0;
+            std::vector<Ribbon> Ribbons;
+            int RibbonsWhollyOut = 0, RibbonsPartlyOut = 0;    // every sample out; some but not all
+            double OutMetres = 0;                              // the records' outLength summed
+        };
+        ReachReport Reach;
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -339,6 +363,7 @@ public:
         std::vector<Planner::Stats::Contact> contacts;   // PlannerConfig::setPlanContacts: the costed legs merged, per contact (Stats::mergeContacts)
         Planner::Stats::ClearanceReport clearance;       // PlannerConfig::setPlanClearance: the costed legs merged (Stats::mergeClearance)
         Planner::Stats::KeepoutReport keepout;           // PlannerConfig::setKeepoutMargin as the call applied it (the same for every plan)
+        Planner::Stats::ReachReport reach;               // PlannerConfig::setPlanReach: what the call's start can reach (the same for every plan)
     };
     // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
     // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
@@ -408,6 +433,7 @@ private:
     struct DeviceCounters;
     DeviceCounters deviceCounters() const;
     Node beginCall(const RibbonManager& ribbonManager, const State& start);      // shared with evaluatePlans
+    void reportReach(const State& start);                                         // ... PlannerConfig::planReach from the first context (after applyKeepout)
     void applyKeepout(const State& start);                                        // ... PlannerConfig::keepoutMargin on every context
     void initSampler(const State& start, unsigned long seed);
     struct WalkedLegs;                     // the previous-plan leg filter

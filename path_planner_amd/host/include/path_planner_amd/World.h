@@ -262,6 +262,14 @@ public:
     // that it can still plan its way out.  0, the default: off, nothing changes.  At most 255 cells; a NaN is refused.
     double keepoutMargin() const { return m_KeepoutMargin; }
     void setKeepoutMargin(double metres) { m_KeepoutMargin = metres; }
+    // Which water the call's start can reach at all and which ribbons lie beyond it (Planner::Stats::Reach,
+    // GpuAStarPlanner::PlanEvaluation::reach): the 8-connected component of the start's cell in the effective grid (the keep-out
+    // margin applied) and one record per ribbon of the call, from the first context (ppgpu.h, "reachable water").  A ribbon that is
+    // out of reach can never be covered, so no goal exists while it is in the mission.  The first call after a new grid or a changed
+    // margin labels the grid; later calls cost a 4-byte look-up and the ribbon walk.  The report reads the world and changes
+    // nothing: plan() returns the same plan with it on.  Off by default; with it off nothing changes.
+    bool planReach() const { return m_PlanReach; }
+    void setPlanReach(bool on) { m_PlanReach = on; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -284,7 +292,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false, m_PlanReach = false;
     double m_PlanClearanceMargin = 0, m_KeepoutMargin = 0;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;

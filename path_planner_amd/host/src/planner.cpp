@@ -1289,6 +1289,34 @@ void GpuAStarPlanner::tracePlanSteps(int v) {
 // RibbonManager, the world on every device.  -> the root vertex (h left unset: only plan() needs it)
 void GpuAStarPlanner::applyKeepout(const State& start) { m_Stats.Keepout = applyKeepoutMargin(m_Ctxs, m_Config, start); }
 
+// Stats::Reach of the call: the start as the seed, the call's ribbons (RibbonManager::rows: contiguous {sx, sy, ex, ey}) against its
+// reach set, on the first context, whose effective grid applyKeepout has just set.
+void GpuAStarPlanner::reportReach(const State& start) {
+    Stats::ReachReport r;
+    ppgpu_reach_info info;
+    check(ppgpu_set_reach_seed(m_Ctx->handle(), start.x(), start.y(), &info), "ppgpu_set_reach_seed");
+    r.Valid = true;
+    const double res = m_Ctx->gridResolution;
+    r.Certified = res > 0 && m_Config.collisionCheckingIncrement() <= res;
+    r.FreeCells = info.free_cells; r.ReachableCells = info.reachable_cells;
+    r.Components = info.components; r.SeedLabel = info.seed_label; r.Flags = info.flags;
+    const int n = m_RibbonManager.count();
+    std::vector<ppgpu_ribbon_reach_record> recs((size_t)n);
+    check(ppgpu_ribbon_reach_host(m_Ctx->handle(), n, m_RibbonManager.rows(), Ribbon::RibbonWidth, recs.data()), "ppgpu_ribbon_reach_host");
+    r.Ribbons.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ppgpu_ribbon_reach_record& d = recs[(size_t)i];
+        Stats::ReachReport::Ribbon& o = r.Ribbons[(size_t)i];
+        o.length = d.length; o.pitch = d.pitch; o.outLength = d.out_length;
+        o.samples = d.samples; o.outSamples = d.out_samples; o.firstOut = d.first_out; o.lastOut = d.last_out;
+        o.minRgap2 = d.min_rgap2; o.maxRgap2 = d.max_rgap2; o.lim2 = d.lim2; o.flags = d.flags;
+        if (d.flags & PPGPU_RB_WHOLE_OUT) r.RibbonsWhollyOut++;
+        else if (d.flags & PPGPU_RB_ANY_OUT) r.RibbonsPartlyOut++;
+        r.OutMetres += d.out_length;
+    }
+    m_Stats.Reach = std::move(r);
+}
+
 GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonManager, const State& start) {
     m_Config.setStartStateTime(start.time());
     m_RibbonManager = ribbonManager;
@@ -1297,6 +1325,8 @@ GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonMana
     m_StartStateTime = start.time();
     m_Stats.Budget.GridUploaded = uploadSnapshot(m_Ctxs, m_Config, m_RibbonManager, start.time());
     applyKeepout(start);
+    if (m_Config.planReach()) reportReach(start);
+    else m_Stats.Reach = Stats::ReachReport();          // (evaluatePlans keeps the planner's Stats: no report of an earlier call)
     // PlannerConfig::deviceTspTable on every context, on or off: contexts outlive planners, and the last call's range must not serve this one
     for (const auto& ctx : m_Ctxs) {
         const int ribbons = m_Config.deviceTspTable();
@@ -1361,6 +1391,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
         PlanEvaluation& e = out[i];
         e.legsCosted = costed[i];
         e.keepout = m_Stats.Keepout;
+        e.reach = m_Stats.Reach;
         e.stop = (PlanEvaluation::Stop)why[i];
         e.goalReached = why[i] == PPGPU_CHAIN_GOAL;
         e.ribbons = root.ribbons;

@@ -12,6 +12,10 @@
 //                  close it passes to a charted hazard and how many of its steps lie inside the margin) |
 //                  cfg keepout_margin M (PlannerConfig::setKeepoutMargin: plan M metres clear of charted hazards; a value other than 0 adds
 //                  keepout_margin, keepout_limit2, keepout_certified and keepout_relaxed to the JSON, and to every plan under evaluate) |
+//                  cfg plan_reach 1 (PlannerConfig::setPlanReach: which water the start can reach and which ribbons lie beyond it; adds
+//                  reach_free_cells, reach_cells, reach_components, reach_certified, reach_seed_blocked, ribbons_out_of_reach,
+//                  ribbons_partly_out_of_reach and out_of_reach_metres to the JSON, and to every plan under evaluate) |
+//                  plan_reach_file path (with cfg plan_reach 1: one line per ribbon of the call) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -65,6 +69,17 @@ static std::string keepoutKeys(const Planner::Stats::KeepoutReport& k) {
     return buf;
 }
 
+// ", reach_free_cells ..., ..., out_of_reach_metres ..." of a call's Stats::Reach: the free cells of the effective grid, those the start
+// can reach, the components, whether the collision-check pitch certifies the claim, and the ribbons no plan can get to
+static std::string reachKeys(const Planner::Stats::ReachReport& r) {
+    char buf[360];
+    std::snprintf(buf, sizeof buf, ", \"reach_free_cells\": %llu, \"reach_cells\": %llu, \"reach_components\": %u, \"reach_certified\": %s, "
+                  "\"reach_seed_blocked\": %s, \"ribbons_out_of_reach\": %d, \"ribbons_partly_out_of_reach\": %d, \"out_of_reach_metres\": %.17g",
+                  (unsigned long long)r.FreeCells, (unsigned long long)r.ReachableCells, r.Components, r.Certified ? "true" : "false",
+                  (r.Flags & Planner::Stats::ReachReport::SeedBlocked) ? "true" : "false", r.RibbonsWhollyOut, r.RibbonsPartlyOut, r.OutMetres);
+    return buf;
+}
+
 // One report file: rows(f, s) prints the lines of segment s.  No path, no file; -> false (and the complaint) when it cannot be written.
 template <class Rows>
 static bool writeReport(const std::string& path, size_t segments, Rows rows) {
@@ -100,7 +115,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planReachPath, planLogPath;
     bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -128,6 +143,7 @@ int main(int argc, char** argv) {
             else if (name == "plan_clearance") config.setPlanClearance(v != 0);
             else if (name == "plan_clearance_margin") config.setPlanClearanceMargin(v);
             else if (name == "keepout_margin") config.setKeepoutMargin(v);
+            else if (name == "plan_reach") config.setPlanReach(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -160,6 +176,7 @@ int main(int argc, char** argv) {
         } else if (k == "plan_coverage_file") { s >> planCoveragePath;   // segment step time to_cover remaining ribbons flags
         } else if (k == "plan_contacts_file") { s >> planContactsPath;   // segment mmsi hit_steps first_hit_time last_hit_time cpa_distance cpa_time exposure peak
         } else if (k == "plan_clearance_file") { s >> planClearancePath;   // segment clearance time x y step gap2 below_steps first_below_time flags
+        } else if (k == "plan_reach_file") { s >> planReachPath;   // ribbon length pitch samples out_samples first_out last_out min_rgap2 max_rgap2 lim2 out_length flags
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -232,6 +249,7 @@ int main(int argc, char** argv) {
                                 e.legs[k].collisionPenalty);
                 std::printf("]%s%s", config.planContacts() ? contactKeys(e.contacts).c_str() : "", config.planClearance() ? clearanceKeys(e.clearance).c_str() : "");
                 if (config.keepoutMargin() != 0) std::printf("%s", keepoutKeys(e.keepout).c_str());
+                if (config.planReach()) std::printf("%s", reachKeys(e.reach).c_str());
                 std::printf("}");
             }
             std::printf("]}\n");
@@ -436,6 +454,14 @@ int main(int argc, char** argv) {
                 })) return 2;
         }
         if (config.keepoutMargin() != 0) tail += keepoutKeys(st.Keepout);      // (only with a margin named: without it the line is what it always was)
+        if (config.planReach()) {                 // (only with the switch on: without it the line is what it always was)
+            tail += reachKeys(st.Reach);
+            if (!writeReport(planReachPath, st.Reach.Ribbons.size(), [&](FILE* f, size_t rb) {
+                    const auto& r = st.Reach.Ribbons[rb];
+                    std::fprintf(f, "%zu %.17g %.17g %u %u %d %d %u %u %u %.17g %u\n", rb, r.length, r.pitch, r.samples, r.outSamples, r.firstOut, r.lastOut, r.minRgap2,
+                                 r.maxRgap2, r.lim2, r.outLength, r.flags);
+                })) return 2;
+        }
         if (config.planTrace()) {
             size_t nSteps = 0;
             for (const auto& seg : st.Trace) nSteps += seg.size();

@@ -105,6 +105,21 @@ CLEARANCE_DTYPE = np.dtype([
 ])
 assert CLEARANCE_DTYPE.itemsize == 64
 
+# reachable water (ppgpu_get_grid_labels, ppgpu_set_reach_seed, ppgpu_ribbon_reach_host): struct ppgpu_reach_info, 32 bytes, and
+# struct ppgpu_ribbon_reach_record, 64 bytes, per ribbon.  REACH_TILE is the labelling's tile edge in cells
+REACH_NONE, REACH_TILE = 0xFFFFFFFF, 32
+REACH_SEED_BLOCKED, REACH_NO_MAP = 0x1, 0x2
+REACH_INFO_DTYPE = np.dtype([
+    ("free_cells", "<u8"), ("reachable_cells", "<u8"), ("components", "<u4"), ("seed_label", "<u4"), ("flags", "<u4"), ("reserved", "<u4"),
+])
+assert REACH_INFO_DTYPE.itemsize == 32
+RB_ANY_OUT, RB_WHOLE_OUT, RB_START_OUT, RB_END_OUT, RB_DEGENERATE, RB_CAPPED, RB_NO_SEED, RB_NO_MAP = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+RIBBON_REACH_DTYPE = np.dtype([
+    ("length", "<f8"), ("pitch", "<f8"), ("samples", "<u4"), ("out_samples", "<u4"), ("first_out", "<i4"), ("last_out", "<i4"),
+    ("min_rgap2", "<u4"), ("max_rgap2", "<u4"), ("lim2", "<u4"), ("flags", "<u4"), ("out_length", "<f8"), ("reserved", "<u8"),
+])
+assert RIBBON_REACH_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""

@@ -22,6 +22,8 @@ with tempfile.TemporaryDirectory() as d:
     _scenario(w, sc, mp, float(w.start5[4]), 1e-3, 1, init, speculation=spec, devices=[0] * streams)
     with open(sc, "a") as f:
         f.write(f"time_remaining {budget / 1e3!r}\nreplan {cycles} 0.1\n")
+        if os.environ.get("REPLAN_PLAN_REACH", "0") != "0":       # PlannerConfig::setPlanReach in every cycle (tools/time_reach.py's A/B)
+            f.write("cfg plan_reach 1\n")
         if os.environ.get("REPLAN_CYCLE_LOG"):
             f.write(f"cycle_log {os.environ['REPLAN_CYCLE_LOG']}\n")
     out = subprocess.run([CLI, sc], capture_output=True, text=True, timeout=900)
