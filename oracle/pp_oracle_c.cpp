@@ -608,36 +608,37 @@ void ppo_edge_event_kinds(void* w, const ppgpu_vertex* verts, const double* pool
 // the samples by Euclidean distance from the source, visit nearest first, per radius keep a max-heap of the k best by approximate
 // cost, stop a radius once its heap is full and the worst kept LENGTH is not above the next distance.  out_idx[r * k + j] = sample
 // index at position j of radius r's heap ARRAY when the scan ends (-1 beyond its size): the order in which expand() then costs
-// and pushes the children (:134-149).  `samples` keeps the order it is given in (the reference's vector is permuted by the scan;
-// with distinct distances the visit order does not depend on the starting permutation).
-void ppo_expand_order(void* w, const double* src5, long n, const double* sx, const double* sy, const double* sh, int k, int* out_idx) {
-    World* W = (World*)w;
-    Config cfg = make_config(*W);
-    struct Item { State s; int idx; };
-    std::vector<Item> items((size_t)n);
-    for (long i = 0; i < n; i++) { items[(size_t)i].s = State(sx[i], sy[i], sh[i], cfg.maxSpeed, 0); items[(size_t)i].idx = (int)i; }
-    const State origin(src5[0], src5[1], src5[2], src5[3], src5[4]);
-    auto comp = [&](const Item& a, const Item& b) { return a.s.distanceTo(origin) > b.s.distanceTo(origin); };
-    const double radii[2] = {cfg.turningRadius, cfg.coverageTurningRadius == cfg.turningRadius ? -1 : cfg.coverageTurningRadius};
+// and pushes the children (:134-149).
+}  // extern "C"
+namespace {
+// What the scan does with one visited sample (the body of the loop at :97-132), and what it keeps between samples; written once,
+// for every visit order below.
+struct ExpandScan {
     struct Cand { double cost, length; int idx; };
+    const Config& cfg;
+    const State origin;
+    const int k;
+    double radii[2];
     std::vector<Cand> temps;
-    auto dubinsComp = [&](int a, int b) { return temps[(size_t)a].cost < temps[(size_t)b].cost; };
     std::vector<int> heaps[2];
     bool done[2] = {false, false};
-    std::make_heap(items.begin(), items.end(), comp);
-    for (size_t i = 0; i < items.size() && (!done[0] || !done[1]); i++) {
-        Item sample = items.front();
-        std::pop_heap(items.begin(), items.end() - (long)i, comp);
+    ExpandScan(const Config& c, const double* src5, int k_) : cfg(c), origin(src5[0], src5[1], src5[2], src5[3], src5[4]), k(k_) {
+        radii[0] = cfg.turningRadius;
+        radii[1] = cfg.coverageTurningRadius == cfg.turningRadius ? -1 : cfg.coverageTurningRadius;
+    }
+    bool finished() const { return done[0] && done[1]; }
+    void visit(State s, int idx) {
+        auto dubinsComp = [&](int a, int b) { return temps[(size_t)a].cost < temps[(size_t)b].cost; };
         for (int j = 0; j < 2; j++) {
             if (done[j]) continue;
             if (radii[j] <= 0) { done[j] = true; continue; }
             auto& best = heaps[j];
-            if (best.size() < (size_t)k || temps[(size_t)best.front()].length > sample.s.distanceTo(origin)) {
-                if (origin.distanceTo(sample.s) > cfg.collisionCheckingIncrement) {
-                    sample.s.speed = cfg.maxSpeed;
+            if (best.size() < (size_t)k || temps[(size_t)best.front()].length > s.distanceTo(origin)) {
+                if (origin.distanceTo(s) > cfg.collisionCheckingIncrement) {
+                    s.speed = cfg.maxSpeed;
                     DubinsWrapper wr;
-                    wr.set(origin, sample.s, radii[j]);
-                    temps.push_back(Cand{wr.length() / sample.s.speed * 1.0, wr.length(), sample.idx});
+                    wr.set(origin, s, radii[j]);
+                    temps.push_back(Cand{wr.length() / s.speed * 1.0, wr.length(), idx});
                     best.push_back((int)temps.size() - 1);
                     std::push_heap(best.begin(), best.end(), dubinsComp);
                     if (best.size() > (size_t)k) {
@@ -650,8 +651,95 @@ void ppo_expand_order(void* w, const double* src5, long n, const double* sx, con
             }
         }
     }
-    for (int j = 0; j < 2; j++)
-        for (int q = 0; q < k; q++) out_idx[j * k + q] = q < (int)heaps[j].size() ? temps[(size_t)heaps[j][(size_t)q]].idx : -1;
+    void arrays(int* out_idx) const {
+        for (int j = 0; j < 2; j++)
+            for (int q = 0; q < k; q++) out_idx[j * k + q] = q < (int)heaps[j].size() ? temps[(size_t)heaps[j][(size_t)q]].idx : -1;
+    }
+};
+struct ExpandItem { State s; int idx; };
+std::vector<ExpandItem> expand_items(const Config& cfg, long n, const double* sx, const double* sy, const double* sh) {
+    std::vector<ExpandItem> items((size_t)n);
+    for (long i = 0; i < n; i++) { items[(size_t)i].s = State(sx[i], sy[i], sh[i], cfg.maxSpeed, 0); items[(size_t)i].idx = (int)i; }
+    return items;
+}
+}  // namespace
+extern "C" {
+// The reference's own visit order: std::make_heap / std::pop_heap on distance.  `samples` keeps the order it is given in (the
+// reference's vector is permuted by the scan; with distinct distances the visit order does not depend on the starting permutation,
+// with equal ones it does).
+void ppo_expand_order(void* w, const double* src5, long n, const double* sx, const double* sy, const double* sh, int k, int* out_idx) {
+    World* W = (World*)w;
+    Config cfg = make_config(*W);
+    std::vector<ExpandItem> items = expand_items(cfg, n, sx, sy, sh);
+    ExpandScan scan(cfg, src5, k);
+    const State& origin = scan.origin;
+    auto comp = [&](const ExpandItem& a, const ExpandItem& b) { return a.s.distanceTo(origin) > b.s.distanceTo(origin); };
+    std::make_heap(items.begin(), items.end(), comp);
+    for (size_t i = 0; i < items.size() && !scan.finished(); i++) {
+        ExpandItem sample = items.front();
+        std::pop_heap(items.begin(), items.end() - (long)i, comp);
+        scan.visit(sample.s, sample.idx);
+    }
+    scan.arrays(out_idx);
+}
+// The same scan with the visit order the device documents for equal distances: ascending (State::distanceTo, sample index).  On
+// distinct distances it is ppo_expand_order.
+void ppo_expand_order_by_index(void* w, const double* src5, long n, const double* sx, const double* sy, const double* sh, int k,
+                               int* out_idx) {
+    World* W = (World*)w;
+    Config cfg = make_config(*W);
+    std::vector<ExpandItem> items = expand_items(cfg, n, sx, sy, sh);
+    ExpandScan scan(cfg, src5, k);
+    std::vector<std::pair<double, int>> order((size_t)n);
+    for (long i = 0; i < n; i++) order[(size_t)i] = std::make_pair(items[(size_t)i].s.distanceTo(scan.origin), (int)i);
+    std::sort(order.begin(), order.end());
+    for (size_t i = 0; i < order.size() && !scan.finished(); i++) {
+        const ExpandItem& it = items[(size_t)order[i].second];
+        scan.visit(it.s, it.idx);
+    }
+    scan.arrays(out_idx);
+}
+
+// The heap steps of that scan alone: entries i = 0 .. nops - 1 are pushed (std::push_heap under cost[a] < cost[b]) and the largest
+// is popped (std::pop_heap + pop_back) whenever the heap holds more than k.  out_idx[i * k + q] = the heap array after operation i,
+// -1 beyond its size.  *equal_children (unless null): how many times a pop's hole met two children of equal cost on its way down.
+void ppo_heap_replay(const double* costs, int nops, int k, int* out_idx, long* equal_children) {
+    std::vector<int> heap;
+    auto comp = [&](int a, int b) { return costs[a] < costs[b]; };
+    long eq = 0;
+    for (int i = 0; i < nops; i++) {
+        heap.push_back(i);
+        std::push_heap(heap.begin(), heap.end(), comp);
+        if ((int)heap.size() > k) {
+            // count on a copy: the hole's walk of std::__adjust_heap over the first size - 1 entries
+            const int len = (int)heap.size() - 1;
+            for (int hole = 0; 2 * hole + 2 < len;) {
+                const int r = 2 * hole + 2, l = r - 1;
+                if (costs[heap[(size_t)r]] == costs[heap[(size_t)l]]) eq++;
+                hole = costs[heap[(size_t)r]] < costs[heap[(size_t)l]] ? l : r;
+            }
+            std::pop_heap(heap.begin(), heap.end(), comp);
+            heap.pop_back();
+        }
+        for (int q = 0; q < k; q++) out_idx[(size_t)i * k + q] = q < (int)heap.size() ? heap[(size_t)q] : -1;
+    }
+    if (equal_children) *equal_children = eq;
+}
+// A full heap array of k entries (their costs in array order): push one entry of extra_cost, pop; *out_same = 1 when the array of
+// indices is what it was.
+void ppo_heap_noop(const double* costs_in_array_order, int k, double extra_cost, int* out_same) {
+    std::vector<double> c(costs_in_array_order, costs_in_array_order + k);
+    c.push_back(extra_cost);
+    std::vector<int> heap((size_t)k);
+    for (int q = 0; q < k; q++) heap[(size_t)q] = q;
+    auto comp = [&](int a, int b) { return c[(size_t)a] < c[(size_t)b]; };
+    heap.push_back(k);
+    std::push_heap(heap.begin(), heap.end(), comp);
+    std::pop_heap(heap.begin(), heap.end(), comp);
+    heap.pop_back();
+    int same = 1;
+    for (int q = 0; q < k; q++) same = same && heap[(size_t)q] == q;
+    *out_same = same;
 }
 
 // SamplingBasedPlanner::expand on a root vertex, the way the reference's ExpandTest1Ribbons drives it

@@ -212,7 +212,8 @@ __global__ __launch_bounds__(256) void pp_k_select_nearest(const double* lengths
 // Equal costs are handled exactly: the heap steps are libstdc++'s, and a candidate above the root is only skipped while no pair of
 // equal costs sits where the pop would take another way down than the push came up (pp_ord_safe).  More than PP_ORD_CAP
 // candidates (8 192 after the ring filter), k above 63, or such a pair turning up while the ring filter has dropped
-// candidates fall back to ascending length and raise *fallbacks (the caller reports it).
+// candidates fall back to ascending length and raise *fallbacks (the caller reports it).  (tests/test_gpu_expand_pieces.py: the heap
+// steps and pp_ord_safe against libstdc++ on tied costs; tests/test_gpu_expand_ties.py: the pipeline on tied and crowded samples.)
 #define PP_ORD_CAP 8192
 struct PPOrdHeap { double cost, len; int idx; };
 __device__ __forceinline__ void pp_ord_set(PPOrdHeap& h, int slot, double cost, double len, int idx) {   // slot and values are wave-uniform

@@ -94,6 +94,9 @@ for _n, _r, _a in [
     ("ppo_plan", i32, [vp, i32, vp, dbl, vp, i32, i32, i32, vp, dbl, dbl, dbl, C.POINTER(PlanStats), vp, i32, vp, i32, vp, i64,
                         C.POINTER(i64)]),
     ("ppo_expand_order", None, [vp, vp, i64, vp, vp, vp, i32, vp]),
+    ("ppo_expand_order_by_index", None, [vp, vp, i64, vp, vp, vp, i32, vp]),
+    ("ppo_heap_replay", None, [vp, i32, i32, vp, C.POINTER(i64)]),
+    ("ppo_heap_noop", None, [vp, i32, dbl, C.POINTER(i32)]),
     ("ppo_expand_once", i32, [vp, i32, vp, vp, vp, u64, i64, i32, vp, i32, vp, vp, vp]),
     ("ppo_edge_event_stats", None, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
     ("ppo_hardware_threads", i32, []),
@@ -205,6 +208,15 @@ class World:
         O.ppo_expand_order(self.h, _p(s), sx.shape[0], _p(sx), _p(sy), _p(sh), k, _p(out))
         return out
 
+    def expand_order_by_index(self, src5, sx, sy, sh, k):
+        """The same scan visiting the samples in ascending (distance, sample index): the device's rule for equal distances, where the
+        reference's own order depends on how its vector happens to be permuted.  Equal to expand_order on distinct distances."""
+        O.ppo_world_set_config(self.h, C.byref(self.cfg))
+        s, sx, sy, sh = f64(src5), f64(sx), f64(sy), f64(sh)
+        out = np.full((2, k), -1, dtype=np.int32)
+        O.ppo_expand_order_by_index(self.h, _p(s), sx.shape[0], _p(sx), _p(sy), _p(sh), k, _p(out))
+        return out
+
     def plan(self, ribbons4, start5, time_remaining, clock_t0, clock_dt, initial_samples=100, cct=-1.0, prev11=None,
              use_brown_paths=False, dump_edges=0):
         """AStarPlanner::plan as the REFERENCE runs it: every heuristic enumerates ribbon lists of any length (the default mirror
@@ -225,6 +237,24 @@ class World:
         O.ppo_world_set_tsp_limit(self.h, 8)
         self.last_plan_edges = int(ne.value) if dump_edges else None      # edges the planner true-costed (counted only while dumping)
         return rc, st, plan[:max(st.plan_len, 0)].copy(), itf[:st.iterations].copy(), (dump[:min(ne.value, dump_edges)] if dump_edges else None)
+
+
+def heap_replay(costs, k):
+    """std::push_heap of entries 0 .. n - 1 under cost[a] < cost[b], std::pop_heap whenever the heap holds more than k: the heap array
+    after every operation (n x k, -1 beyond its size), and how often a pop's hole met two children of equal cost."""
+    c = f64(costs).reshape(-1)
+    out = np.full((c.shape[0], k), -1, dtype=np.int32)
+    eq = i64(0)
+    O.ppo_heap_replay(_p(c), c.shape[0], k, _p(out), C.byref(eq))
+    return out, int(eq.value)
+
+
+def heap_noop(costs_in_array_order, extra_cost):
+    """A full heap array (its costs in array order): does pushing one entry of extra_cost and popping leave the array as it was?"""
+    c = f64(costs_in_array_order).reshape(-1)
+    same = i32(0)
+    O.ppo_heap_noop(_p(c), c.shape[0], float(extra_cost), C.byref(same))
+    return bool(same.value)
 
 
 def sampler_generate(bounds6, seed, ribbons4, skip, n):

@@ -746,8 +746,9 @@ def _expand_host_equals_the_step_by_step_calls(torch_cuda, w):
     ("cfg2", 300, 40, False),       # k above the probe's 32 groups: every valid sample is near, the replay runs with 41 lanes
     ("cfg2", 300, 5, True), ("cfg1", 64, 9, True),      # coverage_turning_radius = turning_radius: row 1 stays empty
     ("cfg2", 300, 64, False),       # a heap of k + 1 does not fit a wavefront: no replay, every list keeps ascending length and says so
+    ("cfg1", 6, 64, False),         # ... with fewer entries than k: the one-wave selection fills the slots behind them
 ], ids=["cfg1-64-9", "cfg2-4096-9", "cfg2-300-5", "cfg3-65536-9", "cfg3-20000-20", "cfg3-2000-1", "cfg1-6-9",
-        "cfg2-300-40", "cfg2-300-5-one_radius", "cfg1-64-9-one_radius", "cfg2-300-64"])
+        "cfg2-300-40", "cfg2-300-5-one_radius", "cfg1-64-9-one_radius", "cfg2-300-64", "cfg1-6-64"])
 def test_expand_order_is_the_reference_heap_array(torch_cuda, cfgname, n_samples, k, one_radius):
     """The order in which expand() pushes the k winners of each radius = the array of the reference's max-heap of candidates
     when its nearest-first scan stops (SamplingBasedPlanner.cpp:82-149), replayed on the device (pp_k_expand_order) from the root
@@ -1126,11 +1127,12 @@ def test_wrapper_edges_match_oracle(torch_cuda):
     assert fz.wrapper_leg(rng, ctx, world, w.cfg, verts, pool, cs[:, 0], cs[:, 1], cs[:, 2], False, per_vertex=40)
 
 
-@pytest.mark.parametrize("case", ["short_list", "many_equal", "some_equal", "k_larger_than_list"])
+@pytest.mark.parametrize("case", ["short_list", "many_equal", "some_equal", "k_larger_than_list", "k_300", "k_300_of_120_valid"])
 def test_nearest_selection_corner_cases(torch_cuda, case):
     """ppgpu_select_nearest keeps 'k smallest (length, sample index)' when the two-pass scheme cannot be used as is: fewer
     entries than k threads hold one, thousands of identical samples (more survivors below the bound than its list holds), a
-    few identical samples among many, and k larger than the whole list (unused slots report -1)."""
+    few identical samples among many, k larger than the whole list (unused slots report -1), and k above the 256 minima the first
+    pass ranks (k successive minimum scans), with more and with fewer valid samples than k."""
     from path_planner_amd import api, workloads
     w = workloads.config1()
     ctx = api.Context(0)
@@ -1146,6 +1148,12 @@ def test_nearest_selection_corner_cases(torch_cuda, case):
         n, k = 300, 40
         sx, sy, sh = x0 + rng.uniform(-60, 60, n), y0 + rng.uniform(-60, 60, n), rng.uniform(0, 6.28, n)
         sx[:280], sy[:280] = x0, y0          # closer than the increment: not candidates
+    elif case in ("k_300", "k_300_of_120_valid"):
+        n, k = 1000, 300
+        sx, sy, sh = x0 + rng.uniform(-60, 60, n), y0 + rng.uniform(-60, 60, n), rng.uniform(0, 6.28, n)
+        if case == "k_300_of_120_valid":
+            gone = rng.permutation(n)[:880]
+            sx[gone], sy[gone] = x0, y0      # closer than the increment: not candidates
     elif case == "many_equal":
         n = 5000
         sx, sy, sh = np.full(n, x0 + 12.0), np.full(n, y0 + 7.0), np.full(n, 1.0)
