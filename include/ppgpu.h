@@ -201,6 +201,15 @@ int ppgpu_last_cover_edges(ppgpu_ctx* ctx, int64_t* n_edges);
  * ppgpu_create switches it off.  ppgpu_last_shared_edges: how many edges of the last costing launch took another edge's results
  * (0 with the switch off and on small launches).  Waits for the launch; reads one word per edge back, a measurement aid. */
 int ppgpu_last_shared_edges(ppgpu_ctx* ctx, int64_t* n_edges);
+/* The sweep list.  A launch with shared sweeps packs the positions of the edges that are swept at all (solved, neither malformed nor
+ * co-located, not a class member that takes its head's results) into a list on the device, and the chunk-skip planner, the pose
+ * sweep and the approach prepass walk that list instead of every edge (PPGPU_APPROACH_LIST=0: the approach prepass does not).  The records and child ribbons are the same bytes either way.  PPGPU_SWEEP_LIST=0 in
+ * the environment of ppgpu_create switches it off.  ppgpu_last_swept_edges: the entries of that list, summed over the slices of the
+ * last costing launch; every edge of the launch where it had no list.  Waits for the launch; a measurement aid. */
+int ppgpu_last_swept_edges(ppgpu_ctx* ctx, int64_t* n_edges);
+/* How the last costing launch was cut: the number of workspace slices it ran as, and the edges of the last one (tests of sliced
+ * launches check that they are what they meant to be).  Does not wait. */
+int ppgpu_last_slices(ppgpu_ctx* ctx, int64_t* n_slices, int64_t* last_slice_edges);
 
 /* Device memory for callers that have no HIP toolchain of their own (the C++ host library is built with g++ against this header
  * only): buffers for the `d_` parameters below, on the handle's device, and a blocking copy back to the host that first waits

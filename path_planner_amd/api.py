@@ -56,6 +56,8 @@ def _load():
         "ppgpu_past_timing": (C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_last_cover_edges": (C.c_int, [vp, C.POINTER(i64)]),
         "ppgpu_last_shared_edges": (C.c_int, [vp, C.POINTER(i64)]),
+        "ppgpu_last_swept_edges": (C.c_int, [vp, C.POINTER(i64)]),
+        "ppgpu_last_slices": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "ppgpu_set_config": (C.c_int, [vp, C.POINTER(PpgpuConfig)]),
         "ppgpu_set_grid": (C.c_int, [vp, vp, i32, i32, dbl]),
         "ppgpu_get_grid_clearance": (C.c_int, [vp, vp, i64]),
@@ -119,7 +121,11 @@ def _load():
         "ppgpu_comm_destroy": (C.c_int, [vp]),
         "ppgpu_comm_abort": (C.c_int, [vp]),
     }
+    # measurement aids an older build of the library may lack (tools/ab_libs.sh loads the parent commit's): calling one there raises
+    optional = {"ppgpu_last_swept_edges", "ppgpu_last_slices"}
     for name, (res, args) in sig.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)   # AttributeError here = the library does not export what the header declares
         fn.restype = res
         fn.argtypes = args
@@ -201,6 +207,19 @@ class Context:
         n = C.c_int64()
         self._ck(LIB.ppgpu_last_shared_edges(self._h, C.byref(n)), "ppgpu_last_shared_edges")
         return n.value
+
+    def last_swept_edges(self):
+        """Edges of the last costing launch on its sweep list (the ones the skip planner and the pose sweep walked); every edge of a
+        launch without a list."""
+        n = C.c_int64()
+        self._ck(LIB.ppgpu_last_swept_edges(self._h, C.byref(n)), "ppgpu_last_swept_edges")
+        return n.value
+
+    def last_slices(self):
+        """(workspace slices the last costing launch ran as, edges of the last one)."""
+        n, last = C.c_int64(), C.c_int64()
+        self._ck(LIB.ppgpu_last_slices(self._h, C.byref(n), C.byref(last)), "ppgpu_last_slices")
+        return n.value, last.value
 
     def reserve_samples(self, max_samples, max_vertices=16):
         self._ck(LIB.ppgpu_reserve_samples(self._h, max_samples, max_vertices), "ppgpu_reserve_samples")

@@ -10,8 +10,13 @@ struct __attribute__((aligned(128))) PPLaunchWords {
     unsigned live_count;                      // per slice: entries of live_list (pp_k_approach_events); the host sums the slices
     unsigned hw_count;                        // entries of hw_list (pp_k_cover_finish -> pp_k_heuristic_listed)
     unsigned defer_count[PP_HL_MAX_N + 1];    // [n] = deferred edges with n ribbons, n = 1 .. PP_HL_MAX_N (pp_k_deferred_list -> pp_k_heuristic_lanes)
+    unsigned sweep_count;                     // per slice: entries of sweep_list (pp_k_mark_sweeps -> the skip planner, the pose sweep)
+    unsigned swept_total;                     // ... and their sum over the slices of the launch (ppgpu_last_swept_edges)
 };
 static_assert(sizeof(PPLaunchWords) == 128, "the launch counters share one 128-byte line");
+static_assert(offsetof(PPLaunchWords, sweep_count) % 8 == 0 && offsetof(PPLaunchWords, swept_total) == offsetof(PPLaunchWords, sweep_count) + 4,
+              "pp_k_mark_sweeps adds to sweep_count (low half) and swept_total (high half) with one 64-bit atomic");
+__device__ __forceinline__ unsigned long long* pp_sweep_counters(PPLaunchWords* w) { return reinterpret_cast<unsigned long long*>(&w->sweep_count); }
 
 // Everything a costing launch needs, passed by value (kernarg segment, scalar loads).
 struct PPParams {
@@ -66,7 +71,12 @@ struct PPParams {
     // Shared sweeps (large solved launches, pp_k_solve.h): edges whose whole horizon lies on their first arc are swept once per class
     unsigned* share_head;                // [nverts * PP_SHARE_KEYS] lowest list position of each class, PP_SHARE_NONE: none yet; per LAUNCH (NULL: nothing is shared)
     unsigned* share_of;                  // [list position] the position whose results the edge takes (pp_k_share_fanout), PP_SHARE_NONE: its own
-                                         //                 (between pp_k_solve_edges and pp_k_share_mark: the edge's class, PP_SHARE_NONE: in none)
+                                         //                 (between pp_k_solve_edges and pp_k_mark_sweeps: the edge's class, PP_SHARE_NONE: in none,
+                                         //                 PP_SHARE_UNSWEPT: in none and not to be swept either)
+    int approach_list;                   // pp_k_approach_events walks the sweep list too: pp_k_mark_sweeps writes track_far of the edges off it
+    unsigned* sweep_list;                // [words->sweep_count] slice positions of the edges the skip planner and the pose sweep walk, packed
+                                         // (pp_k_mark_sweeps): the solved edges without a PP_SETUP_NO_SWEEP bit.  NULL: both walk every edge of
+                                         // the slice and leave the others at once (launches without shared sweeps, PPGPU_SWEEP_LIST=0)
 };
 
 // Phase 0 of an edge (Vertex::connect + Edge::computeApproxCost: which vertex/target/configuration, the Dubins word and
@@ -76,10 +86,12 @@ struct PPParams {
 #define PP_SETUP_MALFORMED 1u   // descriptor out of range
 #define PP_SETUP_COLOCATED 2u   // State::isCoLocated(start, end): the reference throws
 #define PP_SETUP_SHARED 4u      // the edge belongs to a class of edges with one and the same sweep (pp_edge_shareable, pp_k_solve.h) and is not its
-                                // head (pp_k_share_mark): no kernel sweeps it, pp_k_share_fanout gives it the head's results
+                                // head (pp_k_mark_sweeps): no kernel sweeps it, pp_k_share_fanout gives it the head's results
 #define PP_SETUP_NO_SWEEP (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED | PP_SETUP_SHARED)   // what the per-edge kernels of a launch leave at once
 #define PP_SHARE_KEYS 8         // classes per vertex: configuration bits (4) x direction of the first arc (2)
 #define PP_SHARE_NONE 0xffffffffu
+#define PP_FAR_DONE (-2)        // PPParams::track_far[e].x of an edge the cover sweep's wave has nothing left to do for (pp_k_cover.h)
+#define PP_SHARE_UNSWEPT 0xfffffffeu   // (no class key: keys are below nverts * PP_SHARE_KEYS < 2^32, a multiple of 8)
 struct PPEdgeSetupBody {
     PPSegBase seg[3];                      // the bases of the curve's three segments (pp_seg_load_uniform / pp_setup_seg_pose make the rest)
     double p0, p1, p2, hi1;                // DubinsPath::param; hi1 = p0 + p1 as the solver rounded it (where segment 2 begins)
@@ -292,9 +304,13 @@ __device__ __forceinline__ long long pp_next_edge(const PPParams& p, PPQueue& s,
     }
     return n;
 }
-// What pp_k_solve_edges (thread e) clears ahead of its slice's kernels: queue heads and live_count per slice, the other counters per launch.
+// What pp_k_solve_edges (thread e) clears ahead of its slice's kernels: queue heads, live_count and sweep_count per slice, the other counters per launch.
 __device__ __forceinline__ void pp_launch_reset(const PPParams& p, long long e) {
     if (!p.reset_words) return;
     if (e < PP_NQ) p.work[(size_t)e * PP_QSTRIDE] = 0ull;
-    if (e == 0) { if (p.e_base == 0) *p.words = PPLaunchWords{}; else p.words->live_count = 0u; }
+    if (p.e_base == 0) {
+        if (e < (long long)(sizeof(PPLaunchWords) / sizeof(unsigned))) reinterpret_cast<unsigned*>(p.words)[e] = 0u;     // the whole line, a word per thread
+    } else if (e == 0) {
+        p.words->live_count = 0u; p.words->sweep_count = 0u;
+    }
 }

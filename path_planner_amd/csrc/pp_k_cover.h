@@ -43,7 +43,7 @@ __device__ __forceinline__ int pp_event_stride(double D, double inc_d, double in
 // the rest of computeTrueCost is scalar work.  The lane does that too (pp_finish_quiet_edge: pp_lane_phase_c from the vertex's own
 // state, the function pp_k_cover_finish runs from a wave's) and marks the edge PP_FAR_DONE; the cover sweep's wave then drops it at
 // once.  Nearly half the edges of config 3.
-#define PP_FAR_DONE (-2)
+// (PP_FAR_DONE itself: pp_k_common.h, pp_k_mark_sweeps stores it too)
 #define PP_FAR_SHARED (-3)      // inside pp_k_approach_events only: a shared edge, stored as PP_FAR_DONE
 // PPParams::track_far[e].y = (last event before the hand-over) + 1 in the low 20 bits, and, when the approach lane has already split the
 // one ribbon the vehicle entered (round 4): PP_FAR_SPLIT, which piece the corridor run that follows moves (6 bits) and which of its ends
@@ -90,11 +90,22 @@ __device__ __forceinline__ PPBoxScan pp_box_scan(RP r, int n, double x, double y
 #ifndef PP_LANE_NEAR_MAX
 #define PP_LANE_NEAR_MAX 8
 #endif
-__global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp_k_approach_events(PPParams p) {
+// LISTED: lane i takes entry i of the sweep list (launches with a list, unless PPGPU_APPROACH_LIST=0; pp_k_mark_sweeps then gives the edges off the list their
+// track_far entry, and the unsolved ones their place on the live list); otherwise edge i of the slice.
+template <bool LISTED>
+__device__ __forceinline__ void pp_approach_events_body(const PPParams& p) {
     __shared__ double s_rec[PP_APPROACH_THREADS * PP_REC_STRIDE];      // quiet edges' records, transposed through LDS (34 KB: four workgroups per CU still fit)
     const long long e0 = (long long)blockIdx.x * PP_APPROACH_THREADS;
-    const long long e = e0 + threadIdx.x;
-    const bool valid = e < p.n_edges;
+    long long eIdx = e0 + threadIdx.x;
+    bool inRange = eIdx < p.n_edges;
+    if (LISTED) {
+        const long long count = (long long)(unsigned)pp_const_i32(&p.words->sweep_count)[0];
+        if (e0 >= count) return;                                       // (the whole workgroup: no barrier met)
+        inRange = eIdx < count;
+        eIdx = inRange ? (long long)p.sweep_list[eIdx] : 0;
+    }
+    const long long e = eIdx;
+    const bool valid = inRange;
     const PPEdgeSetupBody* S = p.setup + p.ws_base + (valid ? e : 0);
     int2 out; out.x = 0; out.y = 0;                 // {first event of the wave, (last event before it) + 1 | PP_FAR_* bits}
     int splitInfo = 0;
@@ -264,6 +275,9 @@ __global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp
         }
     }
 }
+
+__global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp_k_approach_events(PPParams p) { pp_approach_events_body<true>(p); }
+__global__ __launch_bounds__(PP_APPROACH_THREADS, PP_APPROACH_MIN_WAVES) void pp_k_approach_events_direct(PPParams p) { pp_approach_events_body<false>(p); }
 
 // e = the edge's slot in the workspace, eg = its position in the caller's edge list, lds = 256 doubles private to the wave
 #ifndef PP_FUSE_HEUR

@@ -133,8 +133,10 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
         }
     }
     // what depends on the speed, once per record: this lane's own edge, then its fast partner
-    bool member[2] = {false, false};                          // (shared sweeps: the rule, once per record)
-    unsigned key[2] = {0u, 0u}, pos[2] = {0u, 0u};
+    // (shared sweeps: the rule, once per record.  Two of each by name and not arrays: the loop below is not always unrolled, and an array
+    // indexed by k then lives in scratch)
+    bool member0 = false, member1 = false;
+    unsigned key0 = 0u, key1 = 0u, pos0 = 0u, pos1 = 0u;
     for (int k = 0; k < (e2 >= 0 ? 2 : 1); k++) {
         PPEdgeSetup* __restrict__ O = p.setup + p.ws_base + (k ? e2 : e);
         struct { double approx, wStart, wEnd, speed; int type; unsigned vi, cbits, sflags; } S;
@@ -154,12 +156,14 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
             S.type = dub.type;
         }
         if (p.share_head) {
-            // (the class of a member, PP_SHARE_NONE for any other edge: pp_k_share_mark reads it there and puts the edge's head in its place)
+            // (the class of a member, PP_SHARE_NONE for any other edge, PP_SHARE_UNSWEPT for one no kernel sweeps anyway: pp_k_mark_sweeps
+            // reads it there, without a look at the record, and puts the edge's head in its place)
             const long long egk = k ? pp_edge_position(p, p.e_base + e2) : eg;
-            member[k] = pp_edge_shareable(p, cv, S.type, S.sflags, S.cbits, S.wStart, S.wEnd, S.speed);
-            key[k] = member[k] ? pp_share_key(S.vi, S.cbits, S.type) : PP_SHARE_NONE;
-            pos[k] = (unsigned)egk;
-            p.share_of[egk] = key[k];
+            const bool member = pp_edge_shareable(p, cv, S.type, S.sflags, S.cbits, S.wStart, S.wEnd, S.speed);
+            const bool unswept = S.type < 0 || (S.sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) != 0u;
+            const unsigned key = member ? pp_share_key(S.vi, S.cbits, S.type) : PP_SHARE_NONE;
+            if (k) { member1 = member; key1 = key; pos1 = (unsigned)egk; } else { member0 = member; key0 = key; pos0 = (unsigned)egk; }
+            p.share_of[egk] = unswept ? PP_SHARE_UNSWEPT : key;          // (an unswept edge is no member)
         }
         pp_curve_segments(cv, O->seg);
         O->qx = cv.qx; O->qy = cv.qy; O->rho = cv.rho; O->rho_inv = cv.rho_inv; O->length = cv.length;
@@ -190,8 +194,8 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
         O->omask = omask;
     }
     if (p.share_head) {
-        pp_share_elect(p, member[0], key[0], pos[0]);
-        if (__ballot(e2 >= 0) != 0ull) pp_share_elect(p, member[1], key[1], pos[1]);
+        pp_share_elect(p, member0, key0, pos0);
+        if (__ballot(e2 >= 0) != 0ull) pp_share_elect(p, member1, key1, pos1);
     }
 }
 // After the solve of a slice, one lane per edge; every edge that is in no class leaves after one coalesced 4-byte read.  A member of a
@@ -200,23 +204,79 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
 // every per-edge kernel of the launch leaves it at once, and gets a stub record — its own type byte, approx_cost and param[], everything
 // else zero (no flags, no ribbons, h = 0) — so that no kernel that builds a list from the records (pp_k_deferred_list,
 // pp_k_tsp_table_list, the unfused heuristic kernels) takes what the caller's array held for a deferred or overflowed record.
-__global__ __launch_bounds__(256) void pp_k_share_mark(PPParams p) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.n_edges) return;
-    const long long eg = pp_edge_position(p, p.e_base + e);
-    const unsigned key = p.share_of[eg];                       // as pp_k_solve_edges left it
-    if (key == PP_SHARE_NONE) return;
-    const unsigned head = p.share_head[key];
-    if (head == (unsigned)eg) { p.share_of[eg] = PP_SHARE_NONE; return; }
-    p.share_of[eg] = head;
-    PPEdgeSetup* S = p.setup + p.ws_base + e;
-    S->sflags |= PP_SETUP_SHARED;
-    double* r = reinterpret_cast<double*>(p.out + eg);
-    const unsigned info = (unsigned)(S->type & 0xff);
-    r[0] = __hiloint2double((int)info, 0);
-    r[1] = 0.0; r[2] = 0.0; r[3] = S->approx;
-    for (int i = 4; i < 13; i++) r[i] = 0.0;
-    r[13] = S->p0; r[14] = S->p1; r[15] = S->p2;
+//
+// The sweep list.  The same visit decides which edges of the slice are swept at all — the solved ones that are neither malformed, nor
+// co-located, nor (now) shared — and packs their slice positions into p.sweep_list, as pp_k_approach_events packs the live list:
+// ballot and popcount per wave, one atomic per workgroup (which also adds to the launch's total), 32-bit entries; the order of the
+// workgroups in the list is whatever order they got here in.  The skip planner and the pose sweep walk that list and never see the
+// other edges, so those get here what the pose sweep used to leave them: the zeroed summary.  That is all anyone reads of them —
+// pp_k_approach_events leaves such an edge before it looks at its track; the cover sweep's wave and pp_k_cover_finish read limit,
+// blocked and dub_err, and with limit = 0 no step of it executes: no word of track_eq, no chunk sum, no skip byte is asked for; a
+// trace reads the setup records only.  p.sweep_list == NULL: no list (PPGPU_SWEEP_LIST=0), the planner and the sweep walk every edge.
+// With a list, 1 024 edges per workgroup (the host picks the size: without a list it stays at 256, which measures 4 us faster where no
+// workgroup has anything to add up) and ONE atomic for both counters (they share a 64-bit word: the slice's count in its low half, which the
+// add returns, the launch's total in its high half): a line takes an atomic every ~12.5 ns, and 231 of them stay under 3 us where
+// two per 256 edges would be 23.  The kernel's stores all come after its last barrier (a barrier waits for the stores before it).
+#define PP_MARK_THREADS 1024         // with a list
+#define PP_MARK_THREADS_PLAIN 256    // without
+__global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = e < p.n_edges;
+    const long long eg = valid ? pp_edge_position(p, p.e_base + e) : 0;
+    const unsigned key = valid ? p.share_of[eg] : PP_SHARE_UNSWEPT;                  // as pp_k_solve_edges left it
+    unsigned head = PP_SHARE_NONE;                                                   // whose results the edge takes: its own
+    if (key != PP_SHARE_UNSWEPT && key != PP_SHARE_NONE) {
+        head = p.share_head[key];
+        if (head == (unsigned)eg) head = PP_SHARE_NONE;
+    }
+    const bool swept = key != PP_SHARE_UNSWEPT && head == PP_SHARE_NONE;
+    unsigned at = 0u;
+    if (p.sweep_list) {
+        __shared__ unsigned s_cnt[PP_MARK_THREADS / 64];
+        __shared__ unsigned s_base;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const unsigned long long m = __ballot(swept);
+        if (lane == 0) s_cnt[wave] = (unsigned)__popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned tot = 0;
+            for (int w = 0; w < (int)(blockDim.x >> 6); w++) tot += s_cnt[w];
+            // (no carry out of the low half: it is cleared per slice and a slice has fewer than 2^32 edges)
+            s_base = tot ? (unsigned)atomicAdd(pp_sweep_counters(p.words), ((unsigned long long)tot << 32) | tot) : 0u;
+        }
+        __syncthreads();
+        at = s_base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; w++) at += s_cnt[w];
+    }
+    if (!valid) return;
+    if (key != PP_SHARE_NONE) p.share_of[eg] = head;
+    if (head != PP_SHARE_NONE) {
+        PPEdgeSetup* S = p.setup + p.ws_base + e;
+        S->sflags |= PP_SETUP_SHARED;
+        double* r = reinterpret_cast<double*>(p.out + eg);
+        const unsigned info = (unsigned)(S->type & 0xff);
+        r[0] = __hiloint2double((int)info, 0);
+        r[1] = 0.0; r[2] = 0.0; r[3] = S->approx;
+        for (int i = 4; i < 13; i++) r[i] = 0.0;
+        r[13] = S->p0; r[14] = S->p1; r[15] = S->p2;
+    }
+    if (!p.sweep_list) return;
+    if (swept) p.sweep_list[at] = (unsigned)e;                 // (a slice position: below 2^32, as the live list's)
+    else {
+        reinterpret_cast<int4*>(p.track_summary)[p.ws_base + e] = make_int4(0, 0, 0, 0);   // (PPTrackSummary, pp_k_sweep.h: {limit, blocked, dub_err, pad})
+        if (p.approach_list) {
+            // what pp_k_approach_events would have left: a shared edge is done; an edge without a curve goes to the cover sweep's wave
+            // from its step 0 (its record is the wave's to write), so it takes a place on the live list here — a handful per launch
+            if (head != PP_SHARE_NONE) {
+                p.track_far[p.ws_base + e] = make_int2(PP_FAR_DONE, 0);
+            } else {
+                p.track_far[p.ws_base + e] = make_int2(0, 0);
+                const unsigned li = atomicAdd(&p.words->live_count, 1u);
+                p.live_list[2 * (size_t)li] = (unsigned)e;
+                p.live_list[2 * (size_t)li + 1] = (unsigned)eg;
+            }
+        }
+    }
 }
 // Last kernel of the launch, 16 lanes per record (one 128-byte line read, one written): every member takes its head's record but for
 // the three fields that are the edge's own (type byte, approx_cost, param[]: the stub holds them) and, copy_child, the head's child slot.

@@ -34,6 +34,7 @@ struct PPTrackSummary {
     int dub_err;    // some sampled arc length fell outside the curve even after the reference's 1e-5 retry
     int pad;        // (round 3 measured a per-edge hit total here: pose sweep +33 us for -10 elsewhere, not taken)
 };
+static_assert(sizeof(PPTrackSummary) == sizeof(int4), "pp_k_mark_sweeps zeroes the summary of an edge off the sweep list with one 16-byte store");
 
 // What the cover sweep's wave knows when its event loop (Edge.cpp:153-171) is over, for pp_k_cover_finish (one LANE per edge) to go
 // on from: the rest of computeTrueCost (Edge.cpp:177-205) is scalar work per edge — where the loop stopped, two poses, the last
@@ -324,13 +325,30 @@ __device__ __forceinline__ void pp_plan_skips_chunk(const PPParams& p, const PPE
 // into s_obst; the caller's barrier follows.  A thread reads some 40 fields of its record and ten doubles per obstacle it tests;
 // from memory every one of those was a vector load whose lanes hit two or three different lines, ≈ 200 per thread, and the kernel
 // ran at the rate the L1 serves such loads, not at the VALU's (round 3).
-template <bool OBST_LDS>
-__device__ __forceinline__ void pp_plan_stage(const PPParams& p, const long long el0, const int ne, double* s_setup, PPObst* s_obst) {
+// LISTED (a compile-time property: the kernels of a launch without a list are the code they were before there was one): the
+// workgroup's edges are entries el0 .. el0 + ne - 1 of the sweep list (pp_k_mark_sweeps), read once into s_slot; each record is still
+// contiguous.  Otherwise they are those slice positions themselves.
+template <bool LISTED>
+__device__ __forceinline__ long long pp_plan_count(const PPParams& p) {
+    return LISTED ? (long long)(unsigned)pp_const_i32(&p.words->sweep_count)[0] : p.n_edges;
+}
+template <bool OBST_LDS, bool LISTED>
+__device__ __forceinline__ void pp_plan_stage(const PPParams& p, const long long el0, const int ne, double* s_setup, PPObst* s_obst, unsigned* s_slot) {
     const int tid = (int)threadIdx.x;
-    const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
-    for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
-        const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
-        if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
+    if (LISTED) {
+        if (tid < ne) s_slot[tid] = p.sweep_list[el0 + tid];
+        __syncthreads();
+        for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
+            const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
+            const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + (long long)s_slot[ed]);
+            if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[w];
+        }
+    } else {
+        const double* src = reinterpret_cast<const double*>(p.setup + p.ws_base + el0);
+        for (int i = tid; i < ne * PP_SETUP_GLOBAL_WORDS; i += 256) {
+            const int ed = i / PP_SETUP_GLOBAL_WORDS, w = i - ed * PP_SETUP_GLOBAL_WORDS;
+            if (w < PP_SETUP_WORDS) s_setup[ed * PP_SETUP_LDS_STRIDE + w] = src[i];
+        }
     }
     if (OBST_LDS) {
         const double* os = reinterpret_cast<const double*>(p.obst);
@@ -338,17 +356,20 @@ __device__ __forceinline__ void pp_plan_stage(const PPParams& p, const long long
         for (int i = tid; i < p.n_obst * (int)(sizeof(PPObst) / sizeof(double)); i += 256) od[i] = os[i];
     }
 }
-// One workgroup per `epw` consecutive edges (host: as many as give it 256 (edge, chunk) pairs, at most PP_PLAN_EDGES_MAX), one
+// One workgroup per `epw` consecutive entries of the sweep list — or edges of the slice, where the launch has no list; a workgroup
+// whose first entry lies past the list's end leaves as a whole — (host: as many as give it 256 (edge, chunk) pairs, at most PP_PLAN_EDGES_MAX), one
 // THREAD per (edge, chunk) — measured against one lane per edge walking its chunks (0.29 ms at config 3: 24 dependent iterations
 // on 3 700 wavefronts) this mapping took 0.21 ms, most threads of a short edge leaving after two loads.
-template <bool GAUSSIAN, bool OBST_LDS>
+template <bool GAUSSIAN, bool OBST_LDS, bool LISTED>
 __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw) {
     __shared__ double s_setup[PP_PLAN_EDGES_MAX * PP_SETUP_LDS_STRIDE];
     __shared__ PPObst s_obst[OBST_LDS ? PP_WAVE : 1];
+    __shared__ unsigned s_slot[LISTED ? PP_PLAN_EDGES_MAX : 1];
     const int tid = (int)threadIdx.x;
-    const long long el0 = (long long)blockIdx.x * epw;
-    const int ne = (int)((p.n_edges - el0 < (long long)epw) ? (p.n_edges - el0) : (long long)epw);
-    pp_plan_stage<OBST_LDS>(p, el0, ne, s_setup, s_obst);
+    const long long el0 = (long long)blockIdx.x * epw, n = pp_plan_count<LISTED>(p);
+    if (LISTED && el0 >= n) return;                            // (the whole workgroup, past the end of the list: nothing staged, no barrier met)
+    const int ne = (int)((n - el0 < (long long)epw) ? (n - el0) : (long long)epw);
+    pp_plan_stage<OBST_LDS, LISTED>(p, el0, ne, s_setup, s_obst, s_slot);
     __syncthreads();
     // (blockIdx.y: further tiles of 256 chunks when one edge alone has more than 256 of them)
     const int t = (int)blockIdx.y * 256 + tid;
@@ -356,17 +377,22 @@ __device__ __forceinline__ void pp_plan_skips_thread(const PPParams& p, int epw)
     const int el = (int)((unsigned)t / (unsigned)p.nch);
     const int chunk = t - el * p.nch;
     const PPEdgeSetupBody* S = reinterpret_cast<const PPEdgeSetupBody*>(&s_setup[el * PP_SETUP_LDS_STRIDE]);
-    pp_plan_skips_chunk<GAUSSIAN>(p, S, OBST_LDS ? s_obst : p.obst, p.ws_base + el0 + el, chunk);
+    pp_plan_skips_chunk<GAUSSIAN>(p, S, OBST_LDS ? s_obst : p.obst, p.ws_base + (LISTED ? (long long)s_slot[el] : el0 + el), chunk);
 }
 #ifndef PP_PLAN_MIN_WAVES
 #define PP_PLAN_MIN_WAVES 8   // 62 VGPRs, no spills; 0.28 -> 0.27 ms against the compiler's own choice (6 waves)
 #endif
 // the obstacle table in LDS (up to 64 obstacles; PPGPU_PLAN_SPANS=0: the tests compare the span planner below with these, and A/B runs
 // take both from one library) / read from memory (more)
-__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<false, true>(p, epw); }
-__global__ __launch_bounds__(256) void pp_k_plan_skips_many(PPParams p, int epw) { pp_plan_skips_thread<false, false>(p, epw); }
-__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<true, true>(p, epw); }
-__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p, int epw) { pp_plan_skips_thread<true, false>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<false, true, true>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_many(PPParams p, int epw) { pp_plan_skips_thread<false, false, true>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_chunkwise(PPParams p, int epw) { pp_plan_skips_thread<true, true, true>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p, int epw) { pp_plan_skips_thread<true, false, true>(p, epw); }
+// ... and the same four for a launch without a sweep list (`_direct`: they index the slice)
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_chunkwise_direct(PPParams p, int epw) { pp_plan_skips_thread<false, true, false>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_many_direct(PPParams p, int epw) { pp_plan_skips_thread<false, false, false>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_chunkwise_direct(PPParams p, int epw) { pp_plan_skips_thread<true, true, false>(p, epw); }
+__global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many_direct(PPParams p, int epw) { pp_plan_skips_thread<true, false, false>(p, epw); }
 
 // The span caller (up to 64 obstacles, the table in LDS): the same decisions with two pieces of work taken out of the thread.  The
 // workgroup goes through three phases, and every thread stays to the last barrier (what is an early return above is a predicate
@@ -400,17 +426,19 @@ __global__ __launch_bounds__(256) void pp_k_plan_skips_gaussian_many(PPParams p,
 #endif
 static_assert(PP_PLAN_SPAN >= 2 && PP_PLAN_SPAN <= 32 && 256 % PP_PLAN_SPAN == 0, "a span may not straddle a 256-chunk tile of a long edge (and 256 threads clear the span words)");
 #define PP_PLAN_SPANS_MAX (256 / PP_PLAN_SPAN + PP_PLAN_EDGES_MAX)   // epw ceil(nch / SPAN) <= (epw nch + epw (SPAN - 1)) / SPAN < 256 / SPAN + 32
-template <bool GAUSSIAN>
+template <bool GAUSSIAN, bool LISTED>
 __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) {
     constexpr int LOG = __builtin_ctz(PP_PLAN_SPAN);
     __shared__ double s_setup[PP_PLAN_EDGES_MAX * PP_SETUP_LDS_STRIDE];
     __shared__ PPObst s_obst[PP_WAVE];
     __shared__ double s_bx[256], s_by[256];                    // the pose at each thread's first step; x = NaN: none
     __shared__ unsigned long long s_span[PP_PLAN_SPANS_MAX];
+    __shared__ unsigned s_slot[LISTED ? PP_PLAN_EDGES_MAX : 1];
     const int tid = (int)threadIdx.x;
-    const long long el0 = (long long)blockIdx.x * epw;
-    const int ne = (int)((p.n_edges - el0 < (long long)epw) ? (p.n_edges - el0) : (long long)epw);
-    pp_plan_stage<true>(p, el0, ne, s_setup, s_obst);
+    const long long el0 = (long long)blockIdx.x * epw, n = pp_plan_count<LISTED>(p);
+    if (LISTED && el0 >= n) return;                            // (the whole workgroup, past the end of the list: nothing staged, no barrier met)
+    const int ne = (int)((n - el0 < (long long)epw) ? (n - el0) : (long long)epw);
+    pp_plan_stage<true, LISTED>(p, el0, ne, s_setup, s_obst, s_slot);
     if (tid < PP_PLAN_SPANS_MAX) s_span[tid] = 0ull;
     __syncthreads();
     // (blockIdx.y: further tiles of 256 chunks when one edge alone has more than 256 of them)
@@ -476,7 +504,7 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
     // ---- the chunk (no barrier from here on).  The lambdas take what they need from the record again: a value loaded in front of
     // the barriers and captured here stays in a register through the whole decision, and pp_k_plan_skips has none to spare.
     if (!live) return;
-    pp_plan_chunk<GAUSSIAN>(p, S, p.ws_base + el0 + el, chunk, tg, endTime, tF,
+    pp_plan_chunk<GAUSSIAN>(p, S, p.ws_base + (LISTED ? (long long)s_slot[el] : el0 + el), chunk, tg, endTime, tF,
         [&](double, double dL, double& xF, double& yF, double& xE, double& yE, double& tE, double& dE) {
             xF = s_bx[tid]; yF = s_by[tid];                    // (0 <= dF <= dL <= length, so this thread left its pose there)
             // the far end E of the chord: the neighbour's first step, or this chunk's last
@@ -497,8 +525,10 @@ __device__ __forceinline__ void pp_plan_skips_spans(const PPParams& p, int epw) 
             }
         });
 }
-__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips(PPParams p, int epw) { pp_plan_skips_spans<false>(p, epw); }
-__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussian(PPParams p, int epw) { pp_plan_skips_spans<true>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips(PPParams p, int epw) { pp_plan_skips_spans<false, true>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussian(PPParams p, int epw) { pp_plan_skips_spans<true, true>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_direct(PPParams p, int epw) { pp_plan_skips_spans<false, false>(p, epw); }
+__global__ __launch_bounds__(256, PP_PLAN_MIN_WAVES) void pp_k_plan_skips_gaussian_direct(PPParams p, int epw) { pp_plan_skips_spans<true, false>(p, epw); }
 
 // e = the edge's slot in the workspace.  GAUSSIAN: the dynamic obstacles are GaussianDynamicObstaclesManager's (its own
 // instantiation: exp() and the density bookkeeping would otherwise cost the common kernel registers).
@@ -747,13 +777,37 @@ __device__ __forceinline__ void pp_pose_sweep_edge(const PPParams& p, const long
 #ifndef PP_POSE_MIN_WAVES
 #define PP_POSE_MIN_WAVES 6
 #endif
-// n_edges = slice size (ppgpu.hip: launch_cost)
+// n_edges = slice size (ppgpu.hip: launch_cost).  The grid has a wave per edge of the slice either way: the host does not know how
+// many of them are on the sweep list.  pp_k_pose_sweep / _gaussian are the kernels of a launch WITH a list: wave i asks for the count
+// and the list's entry i together (two scalar loads) and leaves at or past the count.  The `_direct` kernels are those of a launch
+// without one: wave i takes edge i, and pp_pose_sweep_edge leaves the edges that are not swept.  Two instantiations and not a branch on
+// the pointer: the branch alone changes how the whole sweep is compiled (60 spilled SGPRs against 46, profiles/sweep_list.txt).
+__device__ __forceinline__ void pp_pose_sweep_listed(const PPParams& p, bool& mine, long long& idx) {
+    const unsigned count = (unsigned)pp_const_i32(&p.words->sweep_count)[0];       // (<= n_edges)
+    const unsigned entry = (unsigned)pp_const_i32(p.sweep_list + idx)[0];          // (the list has room for the grid's last workgroup: in bounds whatever the count)
+    mine = idx < (long long)count;
+    idx = (long long)entry;
+}
 __global__ __launch_bounds__(PP_WPB * 64, PP_POSE_MIN_WAVES) void pp_k_pose_sweep(PPParams p) {
+    int wave;
+    long long idx = pp_wave_edge<PP_WPB>(wave);
+    bool mine;
+    pp_pose_sweep_listed(p, mine, idx);
+    if (mine) pp_pose_sweep_edge<false>(p, p.ws_base + idx);
+}
+__global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian(PPParams p) {
+    int wave;
+    long long idx = pp_wave_edge<PP_WPB>(wave);
+    bool mine;
+    pp_pose_sweep_listed(p, mine, idx);
+    if (mine) pp_pose_sweep_edge<true>(p, p.ws_base + idx);
+}
+__global__ __launch_bounds__(PP_WPB * 64, PP_POSE_MIN_WAVES) void pp_k_pose_sweep_direct(PPParams p) {
     int wave;
     const long long idx = pp_wave_edge<PP_WPB>(wave);
     if (idx < p.n_edges) pp_pose_sweep_edge<false>(p, p.ws_base + idx);
 }
-__global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian(PPParams p) {
+__global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian_direct(PPParams p) {
     int wave;
     const long long idx = pp_wave_edge<PP_WPB>(wave);
     if (idx < p.n_edges) pp_pose_sweep_edge<true>(p, p.ws_base + idx);

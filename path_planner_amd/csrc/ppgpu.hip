@@ -207,6 +207,8 @@ struct ppgpu_ctx {
     bool lane_heuristic = true;         // env PPGPU_LANE_HEURISTIC=0: large launches keep the wave-per-edge enumeration too (tests compare the two)
     long long prepass_min_edges = PP_PREPASS_MIN_EDGES;   // env PPGPU_PREPASS_MIN_EDGES overrides (tests run the prepasses on small launches too)
     bool share_sweeps = true;           // env PPGPU_SHARE_SWEEPS=0: every edge of a large launch is swept itself (A/B runs, and the tests compare the two)
+    bool use_sweep_list = true;         // env PPGPU_SWEEP_LIST=0: the skip planner and the pose sweep walk every edge of a launch with shared sweeps too (A/B runs, and the tests compare the two)
+    bool approach_list = true;          // env PPGPU_APPROACH_LIST=0: pp_k_approach_events walks every edge of a slice although the launch has a sweep list (A/B runs: profiles/sweep_list.txt)
     size_t slice_bytes = PP_SLICE_BYTES; // workspace budget of one costing slice (env PPGPU_SLICE_BYTES overrides: tests)
     DevBuf<PPEdgeSetup> setup;          // workspace of the current costing slice: phase-0 records ...
     DevBuf<unsigned short> track_hits;  // ... and the pose sweep's track (see PPParams)
@@ -219,6 +221,9 @@ struct ppgpu_ctx {
     DevBuf<unsigned> defer_list, live_list, hw_list;
     DevBuf<unsigned> share_head, share_of;   // shared sweeps: the head of each class, and whose results each edge of the launch takes (see PPParams)
     bool last_launch_shared = false;         // the last costing launch ran with shared sweeps (share_of then holds last_launch_edges entries)
+    DevBuf<unsigned> sweep_list;             // ... and the slice positions of the edges the skip planner and the pose sweep walk (pp_k_mark_sweeps)
+    long long last_launch_slices = 0, last_slice_edges = 0;   // how the last costing launch was cut (ppgpu_last_slices)
+    bool last_launch_listed = false;         // the last costing launch ran with that list (words->swept_total then counts its entries over all slices)
     DevBuf<PPCoverState> cover_state;
     DevBuf<unsigned long long> work;    // queue heads of the cover sweep's resident grid (pp_next_edge)
     int n_cu = 0;
@@ -342,6 +347,8 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* aw = std::getenv("PPGPU_SOLVE_ALL_WORDS")) c->solve_all_words = std::atoi(aw) != 0;
     if (const char* ps = std::getenv("PPGPU_PLAN_SPANS")) c->plan_spans = std::atoi(ps) != 0;
     if (const char* ss = std::getenv("PPGPU_SHARE_SWEEPS")) c->share_sweeps = std::atoi(ss) != 0;
+    if (const char* sl = std::getenv("PPGPU_SWEEP_LIST")) c->use_sweep_list = std::atoi(sl) != 0;
+    if (const char* al = std::getenv("PPGPU_APPROACH_LIST")) c->approach_list = std::atoi(al) != 0;
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
@@ -438,6 +445,25 @@ int ppgpu_last_shared_edges(ppgpu_ctx* c, int64_t* n_edges) {
     int64_t n = 0;
     for (unsigned h : of) n += (h != PP_SHARE_NONE);
     *n_edges = n;
+    return PPGPU_OK;
+}
+
+int ppgpu_last_slices(ppgpu_ctx* c, int64_t* n_slices, int64_t* last_slice_edges) {
+    if (!c || !n_slices || !last_slice_edges) return fail(PPGPU_EINVAL, "null argument");
+    *n_slices = c->last_launch_slices; *last_slice_edges = c->last_slice_edges;
+    return PPGPU_OK;
+}
+
+int ppgpu_last_swept_edges(ppgpu_ctx* c, int64_t* n_edges) {
+    if (!c || !n_edges) return fail(PPGPU_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    *n_edges = c->last_launch_edges;
+    if (c->last_launch_listed) {
+        unsigned swept = 0;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(&swept, &c->words.p->swept_total, sizeof(unsigned), hipMemcpyDeviceToHost));
+        *n_edges = (int64_t)swept;
+    }
     return PPGPU_OK;
 }
 
@@ -1310,7 +1336,7 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.heuristic = g.heuristic; p.tsp_k = g.tsp_k; p.h_rho = g.heuristic_turning_radius;
     p.fuse_h = 0;
     p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.words = nullptr; p.reset_words = 0;
-    p.share_head = nullptr; p.share_of = nullptr;
+    p.share_head = nullptr; p.share_of = nullptr; p.sweep_list = nullptr; p.approach_list = 0;
     p.grid = PPGrid{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
     p.obst = c->obst.p; p.n_obst = c->n_obst; p.obst_model = c->obst_model;
     p.verts = c->verts.p; p.ribbons = c->ribbons.p; p.tgrid = c->tgrid.p; p.ng = c->ng; p.nverts = c->nverts;
@@ -1457,6 +1483,7 @@ struct CostLaunch {
     bool forked;         // pp_k_heuristic_listed runs on the side stream
     bool share;          // shared sweeps: one member of each class of edges with the same sweep is swept, the others take its results (pp_k_solve.h)
     bool share_child;    // ... and its child ribbons, where the caller asked for them
+    bool sweep_list;     // ... and the skip planner and the pose sweep walk the packed list of the edges that are swept (pp_k_mark_sweeps)
     int nch, ngp;        // 64-step chunks per edge, and the steps they hold
     long long slice;     // edges per workspace slice (>= p.n_edges: one piece, the setup records of the whole list are still there)
 };
@@ -1496,6 +1523,9 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
     // shared sweeps: large launches of solved curves (a given curve is its caller's); positions and class keys are 32-bit words
     m.share = m.prepasses && m.packed && !p.wedges && c->share_sweeps && (long long)p.nverts * PP_SHARE_KEYS < (1ll << 32);
     m.share_child = m.share && p.child != nullptr;
+    // the sweep list: exactly where sweeps are shared.  Any other launch has a handful of unsweepable edges at most, and the kernel
+    // that builds the list would cost it more than they do
+    m.sweep_list = m.share && c->use_sweep_list;
 }
 
 // Reserves the workspace of the launch and wires it, and the modes the kernels look at, into m.p.
@@ -1545,6 +1575,11 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
         if ((rc = c->share_head.reserve((size_t)p.nverts * PP_SHARE_KEYS, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
         p.share_head = c->share_head.p; p.share_of = c->share_of.p;
     }
+    if (m.sweep_list) {
+        if ((rc = c->sweep_list.reserve(ws + PP_WPB, false, st))) return rc;      // (every wave of the pose sweep's grid reads "its" entry)
+        p.sweep_list = c->sweep_list.p;
+        p.approach_list = c->approach_list ? 1 : 0;       // (m.share: the prepasses run and the live list exists)
+    }
     return PPGPU_OK;
 }
 
@@ -1568,22 +1603,31 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
     hipEvent_t* ev = c->ev_ring[c->ev_slot];
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_BEGIN], st));
     hipLaunchKernelGGL(c->solve_all_words ? pp_k_solve_edges_all_words : pp_k_solve_edges, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);
-    if (m.share) hipLaunchKernelGGL(pp_k_share_mark, dim3((unsigned)((p.n_edges + 255) / 256)), dim3(256), 0, st, p);   // timed with the solve
+    if (m.share) {                                               // timed with the solve
+        const unsigned mark_threads = m.sweep_list ? PP_MARK_THREADS : PP_MARK_THREADS_PLAIN;
+        hipLaunchKernelGGL(pp_k_mark_sweeps, dim3((unsigned)((p.n_edges + mark_threads - 1) / mark_threads)), dim3(mark_threads), 0, st, p);
+    }
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_SOLVED], st));
     if (m.skip_chunks) {                                         // timed with the pose sweep
-        // one workgroup per epw consecutive edges: as many as give it 256 (edge, chunk) threads
+        // one workgroup per epw consecutive edges (of the sweep list, where the launch has one: the grid is then the one for "every
+        // edge of the slice is on it", and the workgroups past the list's end leave at once): as many as give it 256 (edge, chunk) threads
         int epw = 256 / p.nch;
         if (epw < 1) epw = 1;
         if (epw > PP_PLAN_EDGES_MAX) epw = PP_PLAN_EDGES_MAX;
         const unsigned blocks = (unsigned)((p.n_edges + epw - 1) / epw);
         const bool many = p.n_obst > PP_WAVE;
-        void (*planner)(PPParams, int) = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : (c->plan_spans ? pp_k_plan_skips_gaussian : pp_k_plan_skips_gaussian_chunkwise))
-                                                    : (many ? pp_k_plan_skips_many : (c->plan_spans ? pp_k_plan_skips : pp_k_plan_skips_chunkwise));
+        // (each in two instantiations: over the sweep list, or `_direct` over the slice)
+        void (*planner)(PPParams, int);
+        if (m.sweep_list) planner = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many : (c->plan_spans ? pp_k_plan_skips_gaussian : pp_k_plan_skips_gaussian_chunkwise))
+                                               : (many ? pp_k_plan_skips_many : (c->plan_spans ? pp_k_plan_skips : pp_k_plan_skips_chunkwise));
+        else planner = m.gaussian ? (many ? pp_k_plan_skips_gaussian_many_direct : (c->plan_spans ? pp_k_plan_skips_gaussian_direct : pp_k_plan_skips_gaussian_chunkwise_direct))
+                                  : (many ? pp_k_plan_skips_many_direct : (c->plan_spans ? pp_k_plan_skips_direct : pp_k_plan_skips_chunkwise_direct));
         hipLaunchKernelGGL(planner, dim3(blocks, (unsigned)((epw * p.nch + 255) / 256)), dim3(256), 0, st, p, epw);
     }
-    hipLaunchKernelGGL(m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep, dim3((unsigned)((p.n_edges + PP_WPB - 1) / PP_WPB)), dim3(PP_WPB * 64), 0, st, p);   // a wave per edge
+    void (*pose)(PPParams) = m.sweep_list ? (m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep) : (m.gaussian ? pp_k_pose_sweep_gaussian_direct : pp_k_pose_sweep_direct);
+    hipLaunchKernelGGL(pose, dim3((unsigned)((p.n_edges + PP_WPB - 1) / PP_WPB)), dim3(PP_WPB * 64), 0, st, p);   // a wave per edge
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_POSED], st));
-    if (m.prepasses) hipLaunchKernelGGL(pp_k_approach_events, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
+    if (m.prepasses) hipLaunchKernelGGL(p.approach_list ? pp_k_approach_events : pp_k_approach_events_direct, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_APPROACHED], st));
     hipLaunchKernelGGL(m.gaussian ? pp_k_cover_sweep_gaussian : pp_k_cover_sweep, dim3(resident_grid(c, m.gaussian, p.n_edges)), dim3(PP_WPB * 64), 0, st, p);
     if (m.lane_finish)       // (the list's length is on the device: a grid for "every edge of the slice is on it", whose spare workgroups leave at once)
@@ -1676,18 +1720,20 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     if (c->timing) c->ev_slot = (int)(c->ev_launches % PP_TIMING_RING);     // the next set of the ring
     for (double& ms : c->ms_ring[c->ev_slot]) ms = 0;
     c->live_earlier_slices = 0;
-    c->last_launch_shared = false;
+    c->last_launch_shared = false; c->last_launch_listed = false;
     // the heads of the classes: none yet.  Per launch, not per slice: a member in a later slice finds the head of an earlier one
     if (m.share) HIP_TRY(hipMemsetAsync(p.share_head, 0xff, (size_t)p.nverts * PP_SHARE_KEYS * sizeof(unsigned), c->stream));
+    c->last_launch_slices = 0;
     for (long long e0 = 0; e0 < total; e0 += m.slice) {
         p.e_base = e0; p.ws_base = 0; p.n_edges = (total - e0 < m.slice) ? (total - e0) : m.slice;
+        c->last_launch_slices++; c->last_slice_edges = p.n_edges;
         if (c->timing && e0 > 0 && (rc = bank_slice_timing(c, m.packed))) return rc;
         if ((rc = cost_slice(c, m))) return rc;
     }
     p.e_base = 0;
     p.n_edges = total;
     if ((rc = cost_heuristic_tail(c, m))) return rc;
-    c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share;
+    c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share; c->last_launch_listed = m.sweep_list;
     if (c->timing) { HIP_TRY(hipEventRecord(c->ev_ring[c->ev_slot][EV_END], c->stream)); c->ev_launches++; }
     HIP_TRY(hipGetLastError());
     return PPGPU_OK;
