@@ -69,7 +69,8 @@ struct PPParams {
     unsigned* hw_list;                   // edges pp_k_cover_finish leaves to pp_k_heuristic_listed (a TSP enumeration of 7 or 8 ribbons)
     int ngp, nch;                        // steps per edge rounded up to whole 64-step chunks, and that many chunks
     // Shared sweeps (large solved launches, pp_k_solve.h): edges whose whole horizon lies on their first arc are swept once per class
-    unsigned* share_head;                // [nverts * PP_SHARE_KEYS] lowest list position of each class, PP_SHARE_NONE: none yet; per LAUNCH (NULL: nothing is shared)
+    unsigned* share_head;                // [nverts * PP_SHARE_KEYS] lowest list position of each class, PP_SHARE_NONE: none yet; per LAUNCH (NULL: nothing
+                                         // is shared).  One entry per 128-byte line, reached through pp_share_entry only; all-ones between launches
     unsigned* share_of;                  // [list position] the position whose results the edge takes (pp_k_share_fanout), PP_SHARE_NONE: its own
                                          //                 (between pp_k_solve_edges and pp_k_mark_sweeps: the edge's class, PP_SHARE_NONE: in none,
                                          //                 PP_SHARE_UNSWEPT: in none and not to be swept either)
@@ -92,6 +93,11 @@ struct PPParams {
 #define PP_SHARE_NONE 0xffffffffu
 #define PP_FAR_DONE (-2)        // PPParams::track_far[e].x of an edge the cover sweep's wave has nothing left to do for (pp_k_cover.h)
 #define PP_SHARE_UNSWEPT 0xfffffffeu   // (no class key: keys are below nverts * PP_SHARE_KEYS < 2^32, a multiple of 8)
+// The layout of PPParams::share_head: every class has a 128-byte line to itself, so that the atomics of a vertex's eight classes (all
+// that a launch from one vertex has) do not queue on one line.  The host sizes the table with PP_SHARE_STRIDE; every kernel reaches
+// an entry through pp_share_entry.
+#define PP_SHARE_STRIDE 32u     // 32-bit words from one class's entry to the next
+__device__ __forceinline__ unsigned* pp_share_entry(const PPParams& p, unsigned key) { return p.share_head + (size_t)key * PP_SHARE_STRIDE; }
 struct PPEdgeSetupBody {
     PPSegBase seg[3];                      // the bases of the curve's three segments (pp_seg_load_uniform / pp_setup_seg_pose make the rest)
     double p0, p1, p2, hi1;                // DubinsPath::param; hi1 = p0 + p1 as the solver rounded it (where segment 2 begins)

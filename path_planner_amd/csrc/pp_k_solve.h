@@ -39,31 +39,53 @@ __device__ __forceinline__ bool pp_edge_shareable(const PPParams& p, const PPCur
 __device__ __forceinline__ unsigned pp_share_key(unsigned vi, unsigned cbits, int type) {
     return vi * PP_SHARE_KEYS + (cbits & 3u) * 2u + (pp_word_seg_type(type, 0) == 0 ? 0u : 1u);
 }
-// The head of a class is its member with the lowest position in the caller's list.  The lanes of this wave that hold a position
-// below the table's entry (a plain look first: after the first waves of a launch nearly every lane leaves here) take turns by key;
-// for each key ONE lane issues the atomicMin.  It is the lowest such lane, and that lane holds the wave's lowest position of the key:
-// work items of one configuration map to list positions in rising order (pp_edge_position), in explicit lists they are the positions.
-// (One atomic per member would be 70 000 same-address atomics at ~12.5 ns each.)  No lane waits for another wave.
-__device__ __forceinline__ void pp_share_elect(const PPParams& p, bool member, unsigned key, unsigned pos) {
+// The head of a class is its member with the lowest position in the caller's list: the minimum of the positions, whatever order
+// they arrive in.  It is taken in three stages, each of which passes on only what can still lower the table's entry.
+//   1. The wave.  The lanes that hold a position below the entry (a plain look first: in a later slice nearly every lane leaves here)
+//      take turns by key; for each key ONE lane goes on.  It is the lowest such lane, and that lane holds the wave's lowest position
+//      of the key: work items of one configuration map to list positions in rising order (pp_edge_position), in explicit lists they
+//      are the positions.  (One atomic per member would be 70 000 same-address atomics at ~12.5 ns each.)
+//   2. The workgroup (PPElectLds, pp_share_elect_wave).  That lane takes the minimum in LDS, in the slot its key maps to.  A slot holds
+//      one key, the first that claimed it; a lane that finds another key's claim goes to the table itself, so nothing is lost, and a
+//      dense launch, whose workgroup sees the eight classes of a vertex or two, never does.
+//   3. The table (pp_share_elect_flush), after a barrier: one lane per claimed slot looks at the entry and issues the atomicMin where
+//      the slot's position is lower.  At most one atomic per workgroup and class, where every working wave of a launch used to issue
+//      one per class, all resident at once (so the look saw an empty table), all on the one line a vertex's keys shared.
+// No lane waits for another wave's result; every loop is bounded by the lanes of a wave.
+#define PP_ELECT_SLOTS 64
+struct PPElectLds { unsigned key[PP_ELECT_SLOTS], pos[PP_ELECT_SLOTS]; };
+__device__ __forceinline__ void pp_share_elect_wave(const PPParams& p, PPElectLds& lds, bool member, unsigned key, unsigned pos) {
     bool pend = false;
-    if (member) pend = pos < __hip_atomic_load(p.share_head + key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (member) pend = pos < __hip_atomic_load(pp_share_entry(p, key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned long long m;
     while ((m = __ballot(pend)) != 0ull) {
         const int leader = __ffsll((long long)m) - 1;
         const unsigned k0 = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
-        if (pp_lane() == leader) atomicMin(p.share_head + k0, pos);
+        if (pp_lane() == leader) {
+            const unsigned slot = k0 & (PP_ELECT_SLOTS - 1u);
+            const unsigned was = atomicCAS(&lds.key[slot], PP_SHARE_NONE, k0);
+            if (was == PP_SHARE_NONE || was == k0) atomicMin(&lds.pos[slot], pos);
+            else atomicMin(pp_share_entry(p, k0), pos);
+        }
         if (key == k0) pend = false;
     }
 }
+__device__ __forceinline__ void pp_share_elect_flush(const PPParams& p, const PPElectLds& lds) {
+    if (threadIdx.x >= PP_ELECT_SLOTS) return;
+    const unsigned k = lds.key[threadIdx.x], pos = lds.pos[threadIdx.x];
+    if (k == PP_SHARE_NONE) return;
+    if (pos < __hip_atomic_load(pp_share_entry(p, k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(pp_share_entry(p, k), pos);
+}
+// what a lane's records ask of the election: its own edge's (0) and, where it wrote its fast partner's record too, that one's (1)
+struct PPElectAsk { bool member0, member1, two; unsigned key0, key1, pos0, pos1; };
 
 // ALL_WORDS: the solver evaluates all six words correctly rounded and pp_curve_init every base heading (pp_k_solve_edges_all_words,
 // PPGPU_SOLVE_ALL_WORDS=1, for the tests that compare the two); else only the words that can win, and no sin / cos of the curve's
 // bases twice (pp_solve_rank.h, PPSincosMemo): the same records.  Two kernels, so that the test path does not set the registers of
 // the production one.
+// The records of work item e (a lane that has none to write leaves at once), and what they ask of the election.
 template <bool ALL_WORDS>
-__device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    pp_launch_reset(p, e);
+__device__ __forceinline__ void pp_solve_edge_records(const PPParams& p, long long e, PPElectAsk& ask) {
     if (e >= p.n_edges) return;
     // The two speeds of a radius (configurations c and c ^ PPGPU_EDGE_SLOW) run along the same curve: in the dense enumeration the
     // lane of the slow edge solves it once and writes both records, each where its own lane would have put it; the fast edge's lane
@@ -193,9 +215,30 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
         }
         O->omask = omask;
     }
+    ask.member0 = member0; ask.key0 = key0; ask.pos0 = pos0;
+    ask.member1 = member1; ask.key1 = key1; ask.pos1 = pos1;
+    ask.two = e2 >= 0;
+}
+// A workgroup of pp_k_solve_edges: 256 work items.  With shared sweeps every wave reaches both barriers of the election, also the
+// waves whose lanes all left pp_solve_edge_records at once (the fast configurations of a dense launch, the lanes past n_edges).
+template <bool ALL_WORDS>
+__device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
+    __shared__ PPElectLds lds;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    pp_launch_reset(p, e);
     if (p.share_head) {
-        pp_share_elect(p, member0, key0, pos0);
-        if (__ballot(e2 >= 0) != 0ull) pp_share_elect(p, member1, key1, pos1);
+        if (threadIdx.x < PP_ELECT_SLOTS) { lds.key[threadIdx.x] = PP_SHARE_NONE; lds.pos[threadIdx.x] = PP_SHARE_NONE; }
+        __syncthreads();
+    }
+    PPElectAsk ask;
+    ask.member0 = ask.member1 = ask.two = false;
+    ask.key0 = ask.key1 = PP_SHARE_NONE; ask.pos0 = ask.pos1 = 0u;
+    pp_solve_edge_records<ALL_WORDS>(p, e, ask);
+    if (p.share_head) {
+        pp_share_elect_wave(p, lds, ask.member0, ask.key0, ask.pos0);
+        if (__ballot(ask.two) != 0ull) pp_share_elect_wave(p, lds, ask.member1, ask.key1, ask.pos1);
+        __syncthreads();
+        pp_share_elect_flush(p, lds);
     }
 }
 // After the solve of a slice, one lane per edge; every edge that is in no class leaves after one coalesced 4-byte read.  A member of a
@@ -226,7 +269,7 @@ __global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) 
     const unsigned key = valid ? p.share_of[eg] : PP_SHARE_UNSWEPT;                  // as pp_k_solve_edges left it
     unsigned head = PP_SHARE_NONE;                                                   // whose results the edge takes: its own
     if (key != PP_SHARE_UNSWEPT && key != PP_SHARE_NONE) {
-        head = p.share_head[key];
+        head = *pp_share_entry(p, key);
         if (head == (unsigned)eg) head = PP_SHARE_NONE;
     }
     const bool swept = key != PP_SHARE_UNSWEPT && head == PP_SHARE_NONE;
@@ -280,7 +323,13 @@ __global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) 
 }
 // Last kernel of the launch, 16 lanes per record (one 128-byte line read, one written): every member takes its head's record but for
 // the three fields that are the edge's own (type byte, approx_cost, param[]: the stub holds them) and, copy_child, the head's child slot.
+// It also leaves the table of heads as the next launch's solve wants to find it, all-ones: nobody reads the table any more (the
+// kernel itself goes by share_of), so the next launch needs no fill in front of its first kernel.  The host fills the table itself
+// only when it is new, or when a launch ended before this kernel.
 __global__ __launch_bounds__(256) void pp_k_share_fanout(PPParams p, int copy_child) {
+    const unsigned long long n_keys = (unsigned long long)p.nverts * PP_SHARE_KEYS;        // (below 2^32: cost_modes)
+    for (unsigned long long k = (unsigned long long)blockIdx.x * 256u + threadIdx.x; k < n_keys; k += (unsigned long long)gridDim.x * 256u)
+        *pp_share_entry(p, (unsigned)k) = PP_SHARE_NONE;
     const long long eg = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int sub = (int)(threadIdx.x & 15);
     if (eg >= p.n_edges) return;

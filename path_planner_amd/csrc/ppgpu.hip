@@ -220,6 +220,8 @@ struct ppgpu_ctx {
     DevBuf<PPLaunchWords> words;        // the counters the kernels of a launch hand to one another (one 128-byte line)
     DevBuf<unsigned> defer_list, live_list, hw_list;
     DevBuf<unsigned> share_head, share_of;   // shared sweeps: the head of each class, and whose results each edge of the launch takes (see PPParams)
+    bool share_head_stale = true;            // share_head is not known to be all-ones: it is new, or a launch that shares began and did not get as
+                                             // far as pp_k_share_fanout, which leaves it so.  The next launch that shares fills it first
     bool last_launch_shared = false;         // the last costing launch ran with shared sweeps (share_of then holds last_launch_edges entries)
     DevBuf<unsigned> sweep_list;             // ... and the slice positions of the edges the skip planner and the pose sweep walk (pp_k_mark_sweeps)
     long long last_launch_slices = 0, last_slice_edges = 0;   // how the last costing launch was cut (ppgpu_last_slices)
@@ -1520,8 +1522,9 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
 #endif
     m.lane_finish = laneFinishBuilt && m.packed && c->lane_finish && !m.gaussian;
     m.forked = m.lane_finish && m.fuse_h && p.heuristic != PPGPU_H_MAX_DISTANCE;
-    // shared sweeps: large launches of solved curves (a given curve is its caller's); positions and class keys are 32-bit words
-    m.share = m.prepasses && m.packed && !p.wedges && c->share_sweeps && (long long)p.nverts * PP_SHARE_KEYS < (1ll << 32);
+    // shared sweeps: large launches of solved curves (a given curve is its caller's); positions and class keys are 32-bit words, and the
+    // table of heads, a 128-byte line per class, stays within 256 MB (262 144 open vertices: beyond that every edge is swept itself)
+    m.share = m.prepasses && m.packed && !p.wedges && c->share_sweeps && (long long)p.nverts * PP_SHARE_KEYS * PP_SHARE_STRIDE <= (1ll << 26);
     m.share_child = m.share && p.child != nullptr;
     // the sweep list: exactly where sweeps are shared.  Any other launch has a handful of unsweepable edges at most, and the kernel
     // that builds the list would cost it more than they do
@@ -1572,7 +1575,9 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
         p.defer_list = c->defer_list.p;
     }
     if (m.share) {
-        if ((rc = c->share_head.reserve((size_t)p.nverts * PP_SHARE_KEYS, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
+        const unsigned* const table_was = c->share_head.p;
+        if ((rc = c->share_head.reserve((size_t)p.nverts * PP_SHARE_KEYS * PP_SHARE_STRIDE, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
+        if (c->share_head.p != table_was) c->share_head_stale = true;      // (a grown table is a new one: nothing is kept)
         p.share_head = c->share_head.p; p.share_of = c->share_of.p;
     }
     if (m.sweep_list) {
@@ -1721,8 +1726,13 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     for (double& ms : c->ms_ring[c->ev_slot]) ms = 0;
     c->live_earlier_slices = 0;
     c->last_launch_shared = false; c->last_launch_listed = false;
-    // the heads of the classes: none yet.  Per launch, not per slice: a member in a later slice finds the head of an earlier one
-    if (m.share) HIP_TRY(hipMemsetAsync(p.share_head, 0xff, (size_t)p.nverts * PP_SHARE_KEYS * sizeof(unsigned), c->stream));
+    // the heads of the classes: none yet.  Per launch, not per slice: a member in a later slice finds the head of an earlier one.
+    // The launch before left the table so (pp_k_share_fanout, its last kernel); only a table that is new, or that a launch which
+    // failed between its slices may have left with heads in it, is filled here, all of it.  Stale until this launch's fan-out is queued.
+    if (m.share) {
+        if (c->share_head_stale) HIP_TRY(hipMemsetAsync(c->share_head.p, 0xff, c->share_head.cap * sizeof(unsigned), c->stream));
+        c->share_head_stale = true;
+    }
     c->last_launch_slices = 0;
     for (long long e0 = 0; e0 < total; e0 += m.slice) {
         p.e_base = e0; p.ws_base = 0; p.n_edges = (total - e0 < m.slice) ? (total - e0) : m.slice;
@@ -1736,6 +1746,7 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share; c->last_launch_listed = m.sweep_list;
     if (c->timing) { HIP_TRY(hipEventRecord(c->ev_ring[c->ev_slot][EV_END], c->stream)); c->ev_launches++; }
     HIP_TRY(hipGetLastError());
+    if (m.share) c->share_head_stale = false;             // (pp_k_share_fanout is in the stream)
     return PPGPU_OK;
 }
 
