@@ -708,6 +708,15 @@ __device__ __forceinline__ bool pp_line_distance_lt(double num, double sqL, doub
     return (fabs(num) / sqrt(sqL)) < lim;
 }
 
+// What the rounding of Ribbon::distance's numerator (Ribbon.h:118-121) can amount to: its four products and three sums round at the
+// size of ex * sy and ey * sx (3e9 around (1e5, -3e4): 1e-6, i.e. 1e-8 m of line distance).  A corridor run evaluates it on the piece
+// as the run found it, the reference on the piece with the moved endpoint, so the two values differ by up to twice 8 ulp of the sum
+// of the magnitudes; the run adds this to |num| before it calls a step "inside": a relative guard on w / 2 alone does not cover it
+// (tests/test_gpu_cover_pieces.py, the knife-edge runs).  Pieces that do not move are measured on the same line by both sides.
+__device__ __forceinline__ double pp_line_num_slack(double dxr, double dyr, double x, double y, double sx, double sy, double ex, double ey) {
+    return 2e-15 * (fabs(dyr * x) + fabs(dxr * y) + fabs(ex * sy) + fabs(ey * sx));
+}
+
 // One coverage event of Edge::computeTrueCost (Edge.cpp:158-161), lane i holding ribbon i (i < n):
 //   D = RibbonManager::minDistanceFrom(x, y)                    (RibbonManager.cpp:142-152)
 //   if (doCover) RibbonManager::cover(x, y, strict = true)      (RibbonManager.cpp:14-22, Ribbon::split
@@ -829,8 +838,10 @@ __device__ inline int pp_ribbons_event(PPRibbon& r, int n, double w, double x, d
 // chain re-derives the line from the moved start each step; the two differ by rounding only, ~1e-14 m), and every
 // decision the reference would take (containsProjection with its 1e-5 tolerance, strict distance, front covered,
 // rest not covered, no other piece anywhere near) must hold with a guard of 1e-9 — a step that does not clear the
-// guard ends the run and goes through the exact per-event code.  Flags therefore cannot differ; the moved start
-// differs from the sequential value by rounding noise (<= 1e-12 m).
+// guard ends the run and goes through the exact per-event code (the strict distance also clears pp_line_num_slack, the rounding of
+// its numerator, which at coordinates of 1e5 m is larger than that guard).  Flags therefore cannot differ; the moved start
+// differs from the sequential value by rounding noise, a few ulp of the coordinate: measured <= 4.8e-12 m around (100, 100) and
+// <= 1.3e-10 m around (1e5, -3e4), where one ulp is 1.5e-11 m (tests/test_gpu_cover_pieces.py; the tests hold it to 1e-9 m).
 //
 // lanes = steps of the current chunk; `first` is the first candidate step, `limit` the end of the executable range.
 // moveEnd = false: the piece's START follows the vehicle (front part vanishes each step); true: its END does (the
@@ -894,7 +905,8 @@ __device__ inline int pp_corridor_run(const PPRibbon& r, int n, double w, int ad
     // with the same margin, being the next sample's partner).
     const double sag = (ell > 0.0) ? (ell * sinDt * 0.125) * (1.0 + 1e-9) + 1e-9 : 0.0;
     const double lim = w / 2.0 - sag;
-    bool strictOk = (lim > 0.0) & ((num * num) < ((lim * lim) * sqL) * (1.0 - g));
+    const double numIn = fabs(num) + pp_line_num_slack(dxr, dyr, x, y, Sx, Sy, Ex, Ey);
+    bool strictOk = (lim > 0.0) & ((numIn * numIn) < ((lim * lim) * sqL) * (1.0 - g));
     if (ell > 0.0) {                                              // wave-uniform
         const bool prevOk = __shfl_up((int)strictOk, 1, PP_WAVE) != 0;
         strictOk = strictOk & ((lane == first) | prevOk);
