@@ -733,6 +733,83 @@ int ppgpu_ribbon_reach_host(ppgpu_ctx* ctx, int32_t n, const double* h_ribbons4,
  * not timed since ppgpu_enable_timing.  PPGPU_ESTATE with timing off.  Waits for the stream. */
 int ppgpu_last_reach_timing(ppgpu_ctx* ctx, double* ms_labels, double* ms_reach_gap, double* ms_ribbons);
 
+/* ---------------------------------------------------------------- distance by water */
+
+/* How far it is by water from a pose (a plan's start) to every cell of the chart and to every ribbon: the planner's heuristics measure
+ * straight lines (Vertex::computeApproxToGo), and a breakwater between the start and a survey line makes those arbitrarily optimistic.
+ * Everything is exact in integers except where a ribbon's sample points are placed.
+ * GRAPH.  The nodes are the free cells of the effective grid (what ppgpu_get_grid_blocked returns: the grid as set at limit2 0); the
+ * edges are the 8-neighbour steps the component labels use, a diagonal step allowed whatever the two cells beside it hold (the
+ * reasoning under COMPONENTS, "reachable water", applies unchanged).  A row or column step costs PPGPU_WATER_STEP = 12, a diagonal
+ * step PPGPU_WATER_DIAG = 17.
+ * WATER DISTANCE.  wd(cell) is the cost of the cheapest path from the seed's cell, a uint32_t: 0 on the seed's cell, PPGPU_WATER_NONE
+ * on a blocked cell and on a free cell of another component.  The map is canonical: any correct algorithm writes the same bytes.
+ * wd(cell) != NONE if and only if label(cell) == label(seed's cell), with the labels of ppgpu_get_grid_labels.
+ *   Why 12 and 17: 17 / 12 > sqrt(2), so the polyline through the cell centres of a cheapest path is at most resolution * wd / 12
+ *   metres long, and a route of that length or less through free cells therefore exists.  That is what a value certifies: an UPPER
+ *   bound on the shortest route through cell centres, at most 0.18 % above its octile length.  It is NOT a lower bound on what a
+ *   Dubins vehicle must travel: the turning radius can make the vehicle go farther, and a route between cell centres can be shorter.
+ * THE SEED'S CELL is the one Map::isBlocked puts the pose in (GridWorldMap.cpp:84-93), as for the reach seed.  A seed that is blocked
+ * or outside the grid gives PPGPU_WATER_SEED_BLOCKED and a map that is all NONE; the base Map (rows == 0) gives PPGPU_WATER_NO_MAP.
+ * The water seed is independent of the reach seed.
+ * A RIBBON'S SAMPLES are those of the reach report: the same len, n, k / n, clamp and cell rule ("reachable water"), and
+ * lim2 = ppgpu_keepout_limit2(resolution, ribbon_width + 0.25 * resolution).
+ * APPROACH DISTANCE of a sample in cell A: ad(A) = min of wd(B) over the cells B of the grid with gap2(A, B) < lim2, gap2 as under
+ * "chart clearance" (max(|dr| - 1, 0)^2 + max(|dc| - 1, 0)^2); NONE when no such cell has a distance.  It is the distance by water to
+ * the nearest cell from which the reach report would let the sample be covered: ad(A) != NONE if and only if the reach report, seeded
+ * at the same pose, does not call the sample OUT.  The sample's own cell would not do: a ribbon inside a keep-out band lies on
+ * blocked cells and can still be covered from beside them.  lim2 > PPGPU_WATER_MAX_LIM2 (a window of at most 67 x 67 cells) is refused.
+ * OVERFLOW.  17 * rows * cols must stay below 2^32 - 1 (no path cost can then reach NONE): PPGPU_EINVAL otherwise.
+ * Lazy, like the labels: ppgpu_set_grid and a changed keep-out limit only mark the map stale, the first call below that needs it builds
+ * it, and a seed in the cell of the cached map costs no launch.  A handle that never makes these calls allocates and launches
+ * nothing for them.  The build relaxes 32 x 32 tiles in rounds, one launch per round (pp_k_water.h); `rounds` says how many had work
+ * to do, and may differ between two builds of the same map (the bytes of the map do not). */
+#define PPGPU_WATER_NONE 0xFFFFFFFFu
+#define PPGPU_WATER_STEP 12
+#define PPGPU_WATER_DIAG 17
+#define PPGPU_WATER_TILE 32     /* the relaxation's tile edge in cells (tests place their shapes around it) */
+#define PPGPU_WATER_MAX_LIM2 1024u
+#define PPGPU_WATER_SEED_BLOCKED 0x1u  /* the seed's cell is blocked or outside the grid: the map is all NONE */
+#define PPGPU_WATER_NO_MAP       0x2u  /* base Map (rows == 0): nothing is charted; the counts are 0 */
+typedef struct ppgpu_water_info {          /* 32 bytes */
+    uint64_t wet_cells;                    /* cells with a distance */
+    uint32_t max_wd, farthest_cell;        /* the largest distance and the lowest row-major index that attains it (0, NONE when nothing is wet) */
+    uint32_t seed_cell, flags;             /* row-major index (NONE for a blocked seed); PPGPU_WATER_* */
+    uint32_t rounds, builds;               /* relaxation rounds of the last build; maps this handle has built so far */
+} ppgpu_water_info;
+/* The seed of the map (a plan's start).  Builds the map when it is stale or the seed's cell is not that of the cached one.  out may
+ * be NULL.  PPGPU_EINVAL for a NaN and for 17 * rows * cols >= 2^32 - 1; PPGPU_ECAPACITY if a relaxation loop ran into its cap (it
+ * cannot).  Synchronous. */
+int ppgpu_set_water_seed(ppgpu_ctx* ctx, double x, double y, ppgpu_water_info* out);
+/* For tests and tools: the map of the current seed, rows*cols values.  PPGPU_ESTATE without a seed; PPGPU_EINVAL without a grid
+ * (rows == 0) or when capacity < rows*cols.  Synchronous. */
+int ppgpu_get_grid_water(ppgpu_ctx* ctx, uint32_t* h_out, int64_t capacity);
+/* The map at n points {x, y} of h_xy2 (the cell Map::isBlocked puts each in): h_metres[i] = resolution * wd / 12, +infinity where wd is
+ * NONE or the point is outside the grid; h_wd[i] = wd, NONE likewise; either output may be NULL.  The base Map: +infinity and NONE.
+ * PPGPU_ESTATE without a seed.  Synchronous. */
+int ppgpu_water_distance_at(ppgpu_ctx* ctx, int64_t n, const double* h_xy2, double* h_metres, uint32_t* h_wd);
+#define PPGPU_RW_ANY_DRY    0x01u  /* some sample has no approach distance */
+#define PPGPU_RW_WHOLE_DRY  0x02u  /* none has */
+#define PPGPU_RW_DEGENERATE 0x10u  /* len == 0: one sample, pitch 0 */
+#define PPGPU_RW_NO_SEED    0x40u  /* the seed is blocked: nothing judged, wet_samples 0, the sample indices -1, the distances NONE, +infinity metres */
+#define PPGPU_RW_NO_MAP     0x80u  /* base Map: nothing judged, as above */
+typedef struct ppgpu_ribbon_water_record { /* 64 bytes */
+    double length, pitch;                  /* len, len / n (0 for a degenerate ribbon) */
+    uint32_t samples, wet_samples;         /* n + 1 (1 for a degenerate ribbon); wet: ad != NONE */
+    int32_t nearest_sample, farthest_sample;   /* lowest index attaining min_ad / max_ad over the wet samples; -1 without one */
+    uint32_t min_ad, max_ad, start_ad, end_ad; /* NONE where there is none; start/end = sample 0 / the last sample */
+    uint32_t lim2, flags;                  /* PPGPU_RW_* */
+    double nearest_metres;                 /* resolution * min_ad / 12; +infinity without a wet sample */
+} ppgpu_ribbon_water_record;
+/* One record per ribbon of h_ribbons4 (n rows of {sx, sy, ex, ey}) against the map of the current seed.  PPGPU_ESTATE without a seed.
+ * PPGPU_EINVAL for a NaN anywhere, a ribbon with more than 2^22 samples, ribbon_width + resolution / 4 above 255 cells and
+ * lim2 > PPGPU_WATER_MAX_LIM2.  Synchronous. */
+int ppgpu_ribbon_water_host(ppgpu_ctx* ctx, int32_t n, const double* h_ribbons4, double ribbon_width, ppgpu_ribbon_water_record* h_records);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds of the last build of the map (from the fill to the totals:
+ * the host's reads of the rounds' active counts between the batches of launches are inside) and of the last ribbon walk; -1 for each
+ * that was not timed since ppgpu_enable_timing.  PPGPU_ESTATE with timing off.  Waits for the stream. */
+int ppgpu_last_water_timing(ppgpu_ctx* ctx, double* ms_map, double* ms_ribbons);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

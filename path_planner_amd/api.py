@@ -110,6 +110,11 @@ def _load():
         "ppgpu_get_grid_reach_gap": (C.c_int, [vp, vp, i64]),
         "ppgpu_ribbon_reach_host": (C.c_int, [vp, i32, vp, dbl, vp]),
         "ppgpu_last_reach_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
+        "ppgpu_set_water_seed": (C.c_int, [vp, dbl, dbl, vp]),
+        "ppgpu_get_grid_water": (C.c_int, [vp, vp, i64]),
+        "ppgpu_water_distance_at": (C.c_int, [vp, i64, vp, vp, vp]),
+        "ppgpu_ribbon_water_host": (C.c_int, [vp, i32, vp, dbl, vp]),
+        "ppgpu_last_water_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -628,6 +633,45 @@ class Context:
         enable_timing."""
         t = [C.c_double() for _ in range(3)]
         self._ck(LIB.ppgpu_last_reach_timing(self._h, *[C.byref(x) for x in t]), "ppgpu_last_reach_timing")
+        return tuple(x.value for x in t)
+
+    # ---- distance by water: how far it is through free cells from a seed to every cell, and to every ribbon
+    def set_water_seed(self, x, y):
+        """The pose the distances are measured from; returns the WATER_INFO_DTYPE block (flags: WATER_SEED_BLOCKED, WATER_NO_MAP).
+        Builds the map unless the cached one is that of the seed's cell."""
+        from .types import WATER_INFO_DTYPE
+        info = np.zeros(1, dtype=WATER_INFO_DTYPE)
+        self._ck(LIB.ppgpu_set_water_seed(self._h, float(x), float(y), _ptr(info)), "ppgpu_set_water_seed")
+        return info[0]
+
+    def get_grid_water(self, rows, cols):
+        """wd per cell, rows x cols uint32: the cost of the cheapest 8-connected path from the seed's cell (12 per row or column
+        step, 17 per diagonal step), WATER_NONE on blocked cells and other components; for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint32)
+        self._ck(LIB.ppgpu_get_grid_water(self._h, _ptr(out), out.size), "ppgpu_get_grid_water")
+        return out
+
+    def water_distance_at(self, xy):
+        """(metres, wd) of the map at n points {x, y}: resolution * wd / 12 and wd; +inf and WATER_NONE where there is no distance or
+        the point is outside the grid."""
+        pts = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        metres, wd = np.zeros(pts.shape[0], dtype=np.float64), np.zeros(pts.shape[0], dtype=np.uint32)
+        self._ck(LIB.ppgpu_water_distance_at(self._h, pts.shape[0], _ptr(pts), _ptr(metres), _ptr(wd)), "ppgpu_water_distance_at")
+        return metres, wd
+
+    def ribbon_water(self, ribbons4, ribbon_width):
+        """One RIBBON_WATER_DTYPE record per ribbon {sx, sy, ex, ey}: how far by water the nearest and the farthest of its samples can
+        be approached.  An upper bound on a route through cell centres, not a lower bound on what a Dubins vehicle travels."""
+        from .types import RIBBON_WATER_DTYPE
+        rb = np.ascontiguousarray(ribbons4, dtype=np.float64).reshape(-1, 4)
+        out = np.zeros(rb.shape[0], dtype=RIBBON_WATER_DTYPE)
+        self._ck(LIB.ppgpu_ribbon_water_host(self._h, rb.shape[0], _ptr(rb), float(ribbon_width), _ptr(out)), "ppgpu_ribbon_water_host")
+        return out
+
+    def last_water_timing(self):
+        """(map build, ribbon walk) device milliseconds of the last of each, -1 where none was timed since enable_timing."""
+        t = [C.c_double() for _ in range(2)]
+        self._ck(LIB.ppgpu_last_water_timing(self._h, *[C.byref(x) for x in t]), "ppgpu_last_water_timing")
         return tuple(x.value for x in t)
 
     @staticmethod

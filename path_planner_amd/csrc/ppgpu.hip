@@ -161,6 +161,20 @@ struct ppgpu_ctx {
     DevBuf<double> reach_ribbons;       // {sx, sy, ex, ey, len, n} per ribbon of the last ppgpu_ribbon_reach_host
     DevBuf<ppgpu_ribbon_reach_record> reach_records;
     TraceTimer t_reach_labels, t_reach_gap, t_reach_ribbons;   // (events made by the first timed use, like t_keepout's)
+    // distance by water (ppgpu.h): nothing here is allocated, launched or timed before the first call of that section
+    DevBuf<uint32_t> water_wd;          // the map of water_map_cell, built by the first call that needs it ...
+    bool water_built = false;           // ... after a ppgpu_set_grid, a changed keep-out limit or a seed in another cell (water_ready)
+    DevBuf<uint32_t> water_ctl;         // [2][tiles] dirty flags (this round's, the next round's), then water_batch words of active tiles
+    DevBuf<unsigned long long> water_words;   // PP_WW_*
+    unsigned* water_pinned = nullptr;   // the active counts of a batch of rounds, read back in one copy
+    int water_batch = 16;               // rounds issued between two reads (PPGPU_WATER_BATCH, 1 .. 64): the map does not depend on it
+    bool water_have_seed = false;       // ppgpu_set_water_seed was called: the seed stays across grids and limits
+    double water_seed_x = 0, water_seed_y = 0;
+    uint32_t water_map_cell = PPGPU_WATER_NONE;   // the seed's cell of the map as built (NONE: a blocked seed, all NONE)
+    ppgpu_water_info water_info{};      // of the map as built; builds counts on
+    DevBuf<double> water_ribbons;       // {sx, sy, ex, ey, len, n} per ribbon of the last ppgpu_ribbon_water_host
+    DevBuf<ppgpu_ribbon_water_record> water_records;
+    TraceTimer t_water_map, t_water_ribbons;
     // dynamic obstacles
     DevBuf<PPObst> obst;
     int n_obst = 0;
@@ -263,10 +277,11 @@ struct ppgpu_ctx {
     DevBuf<unsigned long long> tsp_words;   // [0] lists answered, [1] lists refused, [2] length of the list of the launch under way
 
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
-        for (void* pinned : {(void*)pinned_counts, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
+        for (void* pinned : {(void*)pinned_counts, (void*)water_pinned, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1],
-                             t_reach_labels.ev[0], t_reach_labels.ev[1], t_reach_gap.ev[0], t_reach_gap.ev[1], t_reach_ribbons.ev[0], t_reach_ribbons.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+                             t_reach_labels.ev[0], t_reach_labels.ev[1], t_reach_gap.ev[0], t_reach_gap.ev[1], t_reach_ribbons.ev[0], t_reach_ribbons.ev[1],
+                             t_water_map.ev[0], t_water_map.ev[1], t_water_ribbons.ev[0], t_water_ribbons.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -351,6 +366,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* ss = std::getenv("PPGPU_SHARE_SWEEPS")) c->share_sweeps = std::atoi(ss) != 0;
     if (const char* sl = std::getenv("PPGPU_SWEEP_LIST")) c->use_sweep_list = std::atoi(sl) != 0;
     if (const char* al = std::getenv("PPGPU_APPROACH_LIST")) c->approach_list = std::atoi(al) != 0;
+    if (const char* wb = std::getenv("PPGPU_WATER_BATCH")) c->water_batch = std::min(64, std::max(1, std::atoi(wb)));
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
         if (v > 0) c->slice_bytes = (size_t)v;
@@ -388,6 +404,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     }
     c->t_keepout.timed = false;         // (its events are made by the first timed change of the keep-out: apply_keepout)
     c->t_reach_labels.timed = c->t_reach_gap.timed = c->t_reach_ribbons.timed = false;   // (... by the first timed build or walk)
+    c->t_water_map.timed = c->t_water_ribbons.timed = false;
     c->timing = on != 0;
     c->ev_launches = 0;
     return PPGPU_OK;
@@ -606,6 +623,7 @@ int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t col
     HIP_TRY(hipSetDevice(c->device));
     c->grid_dist_built = false;
     c->reach_labels_built = false;                      // (stale: the first call that needs the labels builds them)
+    c->water_built = false;                             // (likewise the distance by water)
     if (rows == 0) { c->rows = c->cols = c->wpr = 0; c->res = 0; return PPGPU_OK; }
     if (!cells || rows < 0 || cols <= 0 || !(res > 0)) return fail(PPGPU_EINVAL, "grid: bad shape or resolution");
     int wpr = (cols + 31) / 32;
@@ -732,6 +750,7 @@ static int apply_keepout(ppgpu_ctx* c) {
     hipStream_t st = c->stream;
     int rc = PPGPU_OK;
     c->reach_labels_built = false;                      // the labels are those of the effective grid
+    c->water_built = false;                             // ... and so is the distance by water
     if (c->keepout_limit2) {
         const unsigned ctiles = (unsigned)((c->cols + 255) / 256);
         if (ctiles > 65535u) return fail(PPGPU_ECAPACITY, "keep-out: the grid is too wide for the kernel's launch shape");
@@ -1012,6 +1031,251 @@ int ppgpu_last_reach_timing(ppgpu_ctx* c, double* ms_labels, double* ms_reach_ga
     TraceTimer* tms[3] = {&c->t_reach_labels, &c->t_reach_gap, &c->t_reach_ribbons};
     double* outs[3] = {ms_labels, ms_reach_gap, ms_ribbons};
     for (int i = 0; i < 3; i++) {
+        *outs[i] = -1.0;
+        if (!tms[i]->timed) continue;
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(tms[i]->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, tms[i]->ev[0], tms[i]->ev[1]));
+        *outs[i] = ms;
+    }
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ distance by water
+// What every call of this section refuses on a grid (rows > 0): a path cost must stay below PPGPU_WATER_NONE.
+static int water_check_size(const ppgpu_ctx* c, const char* who) {
+    if ((unsigned long long)PPGPU_WATER_DIAG * (unsigned long long)c->rows * (unsigned long long)c->cols >= 0xFFFFFFFFull)
+        return fail(PPGPU_EINVAL, std::string(who) + ": 17 * rows * cols must be below 2^32 - 1 (a water distance is 32 bits)");
+    return PPGPU_OK;
+}
+// The cell Map::isBlocked puts the seed in (GridWorldMap.cpp:84-93), PPGPU_WATER_NONE outside the grid (rows > 0).
+static uint32_t water_seed_cell(const ppgpu_ctx* c) {
+    const double x = c->water_seed_x, y = c->water_seed_y;
+    if (x < 0 || x / c->res >= (double)c->cols || y < 0 || y / c->res >= (double)c->rows) return PPGPU_WATER_NONE;
+    return (uint32_t)((size_t)(y / c->res) * (size_t)c->cols + (size_t)(x / c->res));
+}
+
+// The map of the current seed on the effective grid as it stands (rows > 0, a seed is set, the size was checked): nothing when the
+// cached map is that of the seed's cell.  Otherwise the fill, the seed, rounds of pp_k_water_round in batches of water_batch launches
+// (the rounds' active counts come back in one copy per batch; a round past the last one that had work is a grid of workgroups that
+// return), and the totals.  The seed's cell is looked up in the effective bits: a blocked seed leaves the map all NONE.
+static int water_ready(ppgpu_ctx* c) {
+    hipStream_t st = c->stream;
+    uint32_t cell = water_seed_cell(c);
+    const size_t ncell = (size_t)c->rows * c->cols;
+    if (c->water_built && c->water_map_cell != PPGPU_WATER_NONE && cell == c->water_map_cell) return PPGPU_OK;
+    if (cell != PPGPU_WATER_NONE) {                     // blocked in the effective grid?
+        uint32_t word = 0;
+        const size_t r = cell / (size_t)c->cols, x = cell % (size_t)c->cols;
+        HIP_TRY(hipMemcpyAsync(&word, grid_bits(c) + r * c->wpr + (x >> 5), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((word >> (x & 31)) & 1u) cell = PPGPU_WATER_NONE;
+    }
+    if (c->water_built && cell == c->water_map_cell) return PPGPU_OK;      // (a blocked seed on a map that is all NONE already)
+    const unsigned tx = (unsigned)((c->cols + PP_WATER_TILE - 1) / PP_WATER_TILE), ty = (unsigned)((c->rows + PP_WATER_TILE - 1) / PP_WATER_TILE);
+    if (ty > 65535u) return fail(PPGPU_ECAPACITY, "water map: the grid is too tall for the tile kernel's launch shape");
+    const size_t tiles = (size_t)tx * ty;
+    const int batch = c->water_batch;
+    int rc;
+    if ((rc = c->water_wd.reserve(ncell, false, st)) || (rc = c->water_ctl.reserve(2 * tiles + 64, false, st)) || (rc = c->water_words.reserve(PP_WW_COUNT, false, st)))
+        return rc;
+    if (!c->water_pinned) {
+        GrowthTimer growth;
+        HIP_TRY(hipHostMalloc((void**)&c->water_pinned, 64 * sizeof(unsigned), hipHostMallocDefault));
+    }
+    c->water_built = false;
+    TraceTimer& tm = c->t_water_map;
+    if ((rc = reach_timer_begin(c, tm))) return rc;
+    HIP_TRY(hipMemsetAsync(c->water_wd.p, 0xFF, ncell * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(c->water_words.p, 0, PP_WW_COUNT * sizeof(unsigned long long), st));
+    uint32_t* flags = c->water_ctl.p;
+    unsigned* counts = (unsigned*)(c->water_ctl.p + 2 * tiles);
+    unsigned long long rounds = 0;
+    if (cell != PPGPU_WATER_NONE) {
+        HIP_TRY(hipMemsetAsync(flags, 0, 2 * tiles * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(pp_k_water_seed, dim3(1), dim3(64), 0, st, c->water_wd.p, cell, c->cols, (int)tx, (int)ty, flags);
+        const unsigned long long cap = (unsigned long long)ncell + 1ull;          // a round that has work lowers a cell: it cannot take more
+        bool done = false;
+        for (unsigned long long issued = 0; !done; issued += (unsigned)batch) {
+            if (issued >= cap) return fail(PPGPU_ECAPACITY, "water map: the relaxation ran into its cap of rows * cols + 1 rounds");
+            HIP_TRY(hipMemsetAsync(counts, 0, (size_t)batch * sizeof(unsigned), st));
+            for (int k = 0; k < batch; k++) {
+                const unsigned long long round = issued + (unsigned)k;
+                hipLaunchKernelGGL(pp_k_water_round, dim3(tx, ty), dim3(PP_WATER_TILE * PP_WATER_TILE), 0, st, grid_bits(c), c->rows, c->cols, c->wpr, c->water_wd.p,
+                                   flags + (round & 1ull) * tiles, flags + ((round + 1ull) & 1ull) * tiles, counts + k, c->water_words.p);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c->water_pinned, counts, (size_t)batch * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (int k = 0; k < batch && !done; k++) {
+                if (c->water_pinned[k] == 0u) done = true;                        // (no tile was dirty: none is in any later round)
+                else rounds++;
+            }
+        }
+        hipLaunchKernelGGL(pp_k_water_totals, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, c->water_wd.p, (long long)ncell, c->water_words.p);
+    }
+    if ((rc = reach_timer_end(c, tm))) return rc;
+    unsigned long long w[PP_WW_COUNT];
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(w, c->water_words.p, sizeof w, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (w[PP_WW_ERROR]) return fail(PPGPU_ECAPACITY, "water map: a tile's relaxation ran into its cap of sweeps");
+    ppgpu_water_info& info = c->water_info;
+    info.wet_cells = w[PP_WW_WET];
+    info.max_wd = info.wet_cells ? (uint32_t)(w[PP_WW_FARTHEST] >> 32) : 0u;
+    info.farthest_cell = info.wet_cells ? ~(uint32_t)w[PP_WW_FARTHEST] : PPGPU_WATER_NONE;
+    info.seed_cell = cell;
+    info.flags = cell == PPGPU_WATER_NONE ? PPGPU_WATER_SEED_BLOCKED : 0u;
+    info.rounds = (uint32_t)rounds;
+    info.builds++;
+    c->water_map_cell = cell;
+    c->water_built = true;
+    return PPGPU_OK;
+}
+
+int ppgpu_set_water_seed(ppgpu_ctx* c, double x, double y, ppgpu_water_info* out) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (x != x || y != y) return fail(PPGPU_EINVAL, "set_water_seed: the seed is not a number");
+    if (c->rows > 0) {
+        const int rc = water_check_size(c, "set_water_seed");
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+    }
+    const bool had = c->water_have_seed;
+    const double was_x = c->water_seed_x, was_y = c->water_seed_y;
+    c->water_have_seed = true;
+    c->water_seed_x = x; c->water_seed_y = y;
+    ppgpu_water_info info{};
+    if (c->rows == 0) {                                 // the base Map charts nothing
+        info.farthest_cell = info.seed_cell = PPGPU_WATER_NONE;
+        info.flags = PPGPU_WATER_NO_MAP;
+        info.builds = c->water_info.builds;
+    } else {
+        const int rc = water_ready(c);
+        if (rc) { c->water_have_seed = had; c->water_seed_x = was_x; c->water_seed_y = was_y; return rc; }
+        info = c->water_info;
+    }
+    if (out) *out = info;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_water(ppgpu_ctx* c, uint32_t* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, "grid water: null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, "grid water: no grid is set");
+    if (capacity < (int64_t)c->rows * c->cols) return fail(PPGPU_EINVAL, "grid water: capacity below rows * cols");
+    int rc = water_check_size(c, "grid water");
+    if (rc) return rc;
+    if (!c->water_have_seed) return fail(PPGPU_ESTATE, "grid water: ppgpu_set_water_seed must be called first");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = water_ready(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out, c->water_wd.p, (size_t)c->rows * c->cols * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_water_distance_at(ppgpu_ctx* c, int64_t n, const double* h_xy2, double* h_metres, uint32_t* h_wd) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n < 0 || (n > 0 && !h_xy2)) return fail(PPGPU_EINVAL, "water_distance_at: bad arguments");
+    if (!c->water_have_seed) return fail(PPGPU_ESTATE, "water_distance_at: ppgpu_set_water_seed must be called first");
+    if (n == 0 || (!h_metres && !h_wd)) return PPGPU_OK;
+    if (c->rows == 0) {                             // the base Map charts nothing
+        for (int64_t i = 0; i < n; i++) {
+            if (h_metres) h_metres[i] = INFINITY;
+            if (h_wd) h_wd[i] = PPGPU_WATER_NONE;
+        }
+        return PPGPU_OK;
+    }
+    int rc = water_check_size(c, "water_distance_at");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if ((rc = water_ready(c)) || (rc = c->tmp_lengths.reserve((size_t)n * 2, false, st)) || (h_metres && (rc = c->tmp_len_out.reserve((size_t)n, false, st))) ||
+        (h_wd && (rc = c->tmp_counts.reserve((size_t)n, false, st))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->tmp_lengths.p, h_xy2, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    const PPGrid g{nullptr, c->rows, c->cols, c->wpr, c->res, 1.0 / c->res, nullptr};
+    hipLaunchKernelGGL(pp_k_water_distance_at, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, c->water_wd.p, (long long)n, c->tmp_lengths.p,
+                       h_metres ? c->tmp_len_out.p : nullptr, h_wd ? (unsigned*)c->tmp_counts.p : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (h_metres) HIP_TRY(hipMemcpyAsync(h_metres, c->tmp_len_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (h_wd) HIP_TRY(hipMemcpyAsync(h_wd, c->tmp_counts.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PPGPU_OK;
+}
+
+int ppgpu_ribbon_water_host(ppgpu_ctx* c, int32_t n, const double* h_ribbons4, double ribbon_width, ppgpu_ribbon_water_record* h_records) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n < 0 || (n > 0 && (!h_ribbons4 || !h_records))) return fail(PPGPU_EINVAL, "ribbon_water: bad arguments");
+    if (ribbon_width != ribbon_width) return fail(PPGPU_EINVAL, "ribbon_water: the ribbon width is not a number");
+    if (!c->water_have_seed) return fail(PPGPU_ESTATE, "ribbon_water: ppgpu_set_water_seed must be called first");
+    const bool nomap = c->rows == 0;
+    uint32_t lim2 = 0;
+    if (!nomap) {
+        const int rc = water_check_size(c, "ribbon_water");
+        if (rc) return rc;
+        if (ppgpu_keepout_limit2(c->res, ribbon_width + 0.25 * c->res, &lim2)) return fail(PPGPU_EINVAL, "ribbon_water: ribbon_width + resolution / 4 above 255 cells");
+        if (lim2 > PPGPU_WATER_MAX_LIM2) return fail(PPGPU_EINVAL, "ribbon_water: lim2 above PPGPU_WATER_MAX_LIM2 (the window of a sample would exceed 67 x 67 cells)");
+    }
+    // len and n of every ribbon, by the rule ppgpu.h states under "reachable water" (the base Map has no resolution: one sample per ribbon end)
+    std::vector<double> rib((size_t)n * 6);
+    for (int32_t i = 0; i < n; i++) {
+        const double* q = h_ribbons4 + 4 * (size_t)i;
+        for (int j = 0; j < 4; j++)
+            if (q[j] != q[j]) return fail(PPGPU_EINVAL, "ribbon_water: a ribbon coordinate is not a number");
+        const double dx = q[2] - q[0], dy = q[3] - q[1];
+        const double len = std::sqrt(dx * dx + dy * dy);
+        double nd = nomap ? 1.0 : std::ceil(len / (0.5 * c->res));
+        if (!(nd >= 1.0)) nd = 1.0;
+        if (!(nd < 4194304.0)) return fail(PPGPU_EINVAL, "ribbon_water: a ribbon has more than 2^22 samples");
+        double* o = rib.data() + 6 * (size_t)i;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; o[4] = len; o[5] = nd;
+    }
+    if (n == 0) return PPGPU_OK;
+    if (!nomap) {
+        HIP_TRY(hipSetDevice(c->device));
+        const int rc = water_ready(c);
+        if (rc) return rc;
+    }
+    if (nomap || c->water_map_cell == PPGPU_WATER_NONE) {            // nothing is judged
+        for (int32_t i = 0; i < n; i++) {
+            const double len = rib[6 * (size_t)i + 4], nd = rib[6 * (size_t)i + 5];
+            ppgpu_ribbon_water_record r{};
+            r.length = len;
+            r.pitch = len == 0.0 ? 0.0 : len / nd;
+            r.samples = len == 0.0 ? 1u : (uint32_t)nd + 1u;
+            r.nearest_sample = r.farthest_sample = -1;
+            r.min_ad = r.max_ad = r.start_ad = r.end_ad = PPGPU_WATER_NONE;
+            r.lim2 = lim2;
+            r.flags = (nomap ? PPGPU_RW_NO_MAP : PPGPU_RW_NO_SEED) | (len == 0.0 ? PPGPU_RW_DEGENERATE : 0u);
+            r.nearest_metres = INFINITY;
+            h_records[i] = r;
+        }
+        return PPGPU_OK;
+    }
+    int reach = 0;                                                   // the largest d with (d - 1)^2 < lim2: |dr|, |dc| of a window cell (0 for lim2 0)
+    while ((unsigned)(reach * reach) < lim2) reach++;
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = c->water_ribbons.reserve((size_t)n * 6, false, st)) || (rc = c->water_records.reserve((size_t)n, false, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->water_ribbons.p, rib.data(), rib.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const PPGrid g{nullptr, c->rows, c->cols, c->wpr, c->res, 1.0 / c->res, nullptr};
+    if ((rc = reach_timer_begin(c, c->t_water_ribbons))) return rc;
+    hipLaunchKernelGGL(pp_k_water_ribbons, dim3((unsigned)((n + PP_WATER_WPB - 1) / PP_WATER_WPB)), dim3(PP_WATER_WPB * 64), 0, st, g, c->water_wd.p, (int)n,
+                       c->water_ribbons.p, lim2, reach, c->water_records.p);
+    if ((rc = reach_timer_end(c, c->t_water_ribbons))) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_records, c->water_records.p, (size_t)n * sizeof(ppgpu_ribbon_water_record), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PPGPU_OK;
+}
+
+int ppgpu_last_water_timing(ppgpu_ctx* c, double* ms_map, double* ms_ribbons) {
+    if (!c || !ms_map || !ms_ribbons) return fail(PPGPU_EINVAL, "last_water_timing: null argument");
+    if (!c->timing) return fail(PPGPU_ESTATE, "last_water_timing: timing is off (ppgpu_enable_timing)");
+    HIP_TRY(hipSetDevice(c->device));
+    TraceTimer* tms[2] = {&c->t_water_map, &c->t_water_ribbons};
+    double* outs[2] = {ms_map, ms_ribbons};
+    for (int i = 0; i < 2; i++) {
         *outs[i] = -1.0;
         if (!tms[i]->timed) continue;
         float ms = 0;

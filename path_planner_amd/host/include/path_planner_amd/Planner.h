@@ -163,6 +163,32 @@ public:
             double OutMetres = 0;                              // the records' outLength summed
         };
         ReachReport Reach;
+        // PlannerConfig::setPlanWater: how far it is by water from the call's start (ppgpu.h, "distance by water"), after the keep-out
+        // margin was applied.  WetCells .. Builds are ppgpu_water_info's, Ribbons the fields of ppgpu_ribbon_water_record, one per ribbon
+        // of the call's RibbonManager in its order.  resolution * wd / 12 metres is an upper bound on the shortest route through the
+        // centres of free cells, NOT a lower bound on what the vehicle must travel.  Certified as in ReachReport (collision checking
+        // increment <= resolution): a ribbon that is dry can then not be approached at all; otherwise the report makes no claim about
+        // that.  With the switch off Valid is false and nothing was asked.
+        struct WaterReport {
+            enum : uint32_t { SeedBlocked = 0x1, NoMap = 0x2 };                                 // PPGPU_WATER_*
+            enum : uint32_t { AnyDry = 0x01, WholeDry = 0x02, Degenerate = 0x10, NoSeed = 0x40, RibbonNoMap = 0x80 };   // PPGPU_RW_*
+            static constexpr uint32_t None = 0xFFFFFFFFu;                                       // PPGPU_WATER_NONE
+            struct Ribbon {
+                double length = 0, pitch = 0, nearestMetres = 0;
+                uint32_t samples = 0, wetSamples = 0;
+                int32_t nearestSample = -1, farthestSample = -1;
+                uint32_t minAd = None, maxAd = None, startAd = None, endAd = None, lim2 = 0, flags = 0;
+            };
+            bool Valid = false, Certified = false;
+            uint64_t WetCells = 0;
+            uint32_t MaxWd = 0, FarthestCell = None, SeedCell = None, Flags = 0, Rounds = 0, Builds = 0;
+            double Resolution = 0, MaxMetres = 0;              // of the grid the map was built on; Resolution * MaxWd / 12
+            std::vector<Ribbon> Ribbons;
+            int RibbonsDry = 0;                                // no sample can be approached
+            int NearestRibbon = -1;                            // the smallest minAd (the lowest index on a tie); -1 without a wet ribbon
+            double NearestWaterMetres = -1, NearestStraightMetres = -1;   // its nearestMetres; the straight line from the start to its nearestSample point
+        };
+        WaterReport Water;
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
         struct PreviousLeg { double g, collisionPenalty; bool infeasible; };
         std::vector<PreviousLeg> PreviousPlanLegs;
@@ -364,6 +390,7 @@ public:
         Planner::Stats::ClearanceReport clearance;       // PlannerConfig::setPlanClearance: the costed legs merged (Stats::mergeClearance)
         Planner::Stats::KeepoutReport keepout;           // PlannerConfig::setKeepoutMargin as the call applied it (the same for every plan)
         Planner::Stats::ReachReport reach;               // PlannerConfig::setPlanReach: what the call's start can reach (the same for every plan)
+        Planner::Stats::WaterReport water;               // PlannerConfig::setPlanWater: how far it is by water from the call's start (likewise)
     };
     // AStarPlanner::plan's walk over a previous plan (AStarPlanner.cpp:46-59) for ANY number of candidate plans, all from `start`,
     // in one device call (ppgpu_cost_plans_host).  Legs are filtered as plan() filters them (:49-50); a leg at a radius the
@@ -434,6 +461,7 @@ private:
     DeviceCounters deviceCounters() const;
     Node beginCall(const RibbonManager& ribbonManager, const State& start);      // shared with evaluatePlans
     void reportReach(const State& start);                                         // ... PlannerConfig::planReach from the first context (after applyKeepout)
+    void reportWater(const State& start);                                         // ... PlannerConfig::planWater, likewise
     void applyKeepout(const State& start);                                        // ... PlannerConfig::keepoutMargin on every context
     void initSampler(const State& start, unsigned long seed);
     struct WalkedLegs;                     // the previous-plan leg filter

@@ -270,6 +270,15 @@ public:
     // nothing: plan() returns the same plan with it on.  Off by default; with it off nothing changes.
     bool planReach() const { return m_PlanReach; }
     void setPlanReach(bool on) { m_PlanReach = on; }
+    // How far it is by water from the call's start to every cell of the chart and to every ribbon (Planner::Stats::Water,
+    // GpuAStarPlanner::PlanEvaluation::water): the cheapest 8-connected path through the free cells of the effective grid (the keep-out
+    // margin applied), 12 per row or column step and 17 per diagonal step, and one record per ribbon of the call, from the first context
+    // (ppgpu.h, "distance by water").  The planner's heuristics measure straight lines; a breakwater between the start and a line makes
+    // them arbitrarily optimistic, and this says by how much.  The first call after a new grid, a changed margin or a start in another
+    // cell builds the map; the report reads the world and changes nothing: plan() returns the same plan with it on.  Off by default;
+    // with it off nothing changes.
+    bool planWater() const { return m_PlanWater; }
+    void setPlanWater(bool on) { m_PlanWater = on; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -292,7 +301,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false, m_PlanReach = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false, m_PlanReach = false, m_PlanWater = false;
     double m_PlanClearanceMargin = 0, m_KeepoutMargin = 0;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;

@@ -1317,6 +1317,44 @@ void GpuAStarPlanner::reportReach(const State& start) {
     m_Stats.Reach = std::move(r);
 }
 
+// Stats::Water of the call: the start as the seed of the distance by water, the call's ribbons against its map, on the first context.
+// The straight line to the nearest ribbon goes to the sample point the header's rule places: (sx + dx * (k / n), sy + dy * (k / n)).
+void GpuAStarPlanner::reportWater(const State& start) {
+    Stats::WaterReport r;
+    ppgpu_water_info info;
+    check(ppgpu_set_water_seed(m_Ctx->handle(), start.x(), start.y(), &info), "ppgpu_set_water_seed");
+    r.Valid = true;
+    const double res = m_Ctx->gridResolution;
+    r.Certified = res > 0 && m_Config.collisionCheckingIncrement() <= res;
+    r.WetCells = info.wet_cells; r.MaxWd = info.max_wd; r.FarthestCell = info.farthest_cell; r.SeedCell = info.seed_cell;
+    r.Flags = info.flags; r.Rounds = info.rounds; r.Builds = info.builds;
+    r.Resolution = res;
+    r.MaxMetres = res * (double)info.max_wd / (double)PPGPU_WATER_STEP;
+    const int n = m_RibbonManager.count();
+    std::vector<ppgpu_ribbon_water_record> recs((size_t)n);
+    check(ppgpu_ribbon_water_host(m_Ctx->handle(), n, m_RibbonManager.rows(), Ribbon::RibbonWidth, recs.data()), "ppgpu_ribbon_water_host");
+    r.Ribbons.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ppgpu_ribbon_water_record& d = recs[(size_t)i];
+        Stats::WaterReport::Ribbon& o = r.Ribbons[(size_t)i];
+        o.length = d.length; o.pitch = d.pitch; o.nearestMetres = d.nearest_metres;
+        o.samples = d.samples; o.wetSamples = d.wet_samples; o.nearestSample = d.nearest_sample; o.farthestSample = d.farthest_sample;
+        o.minAd = d.min_ad; o.maxAd = d.max_ad; o.startAd = d.start_ad; o.endAd = d.end_ad; o.lim2 = d.lim2; o.flags = d.flags;
+        if (d.flags & PPGPU_RW_WHOLE_DRY) r.RibbonsDry++;
+        if (d.wet_samples && (r.NearestRibbon < 0 || d.min_ad < recs[(size_t)r.NearestRibbon].min_ad)) r.NearestRibbon = i;
+    }
+    if (r.NearestRibbon >= 0) {
+        const ppgpu_ribbon_water_record& d = recs[(size_t)r.NearestRibbon];
+        const double* q = m_RibbonManager.rows() + 4 * (size_t)r.NearestRibbon;
+        const double dx = q[2] - q[0], dy = q[3] - q[1];
+        const double t = d.length == 0.0 ? 0.0 : (double)d.nearest_sample / (double)(d.samples - 1u);
+        const double px = q[0] + dx * t - start.x(), py = q[1] + dy * t - start.y();
+        r.NearestWaterMetres = d.nearest_metres;
+        r.NearestStraightMetres = std::sqrt(px * px + py * py);
+    }
+    m_Stats.Water = std::move(r);
+}
+
 GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonManager, const State& start) {
     m_Config.setStartStateTime(start.time());
     m_RibbonManager = ribbonManager;
@@ -1327,6 +1365,8 @@ GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonMana
     applyKeepout(start);
     if (m_Config.planReach()) reportReach(start);
     else m_Stats.Reach = Stats::ReachReport();          // (evaluatePlans keeps the planner's Stats: no report of an earlier call)
+    if (m_Config.planWater()) reportWater(start);
+    else m_Stats.Water = Stats::WaterReport();
     // PlannerConfig::deviceTspTable on every context, on or off: contexts outlive planners, and the last call's range must not serve this one
     for (const auto& ctx : m_Ctxs) {
         const int ribbons = m_Config.deviceTspTable();
@@ -1392,6 +1432,7 @@ std::vector<GpuAStarPlanner::PlanEvaluation> GpuAStarPlanner::evaluatePlans(cons
         e.legsCosted = costed[i];
         e.keepout = m_Stats.Keepout;
         e.reach = m_Stats.Reach;
+        e.water = m_Stats.Water;
         e.stop = (PlanEvaluation::Stop)why[i];
         e.goalReached = why[i] == PPGPU_CHAIN_GOAL;
         e.ribbons = root.ribbons;

@@ -16,6 +16,10 @@
 //                  reach_free_cells, reach_cells, reach_components, reach_certified, reach_seed_blocked, ribbons_out_of_reach,
 //                  ribbons_partly_out_of_reach and out_of_reach_metres to the JSON, and to every plan under evaluate) |
 //                  plan_reach_file path (with cfg plan_reach 1: one line per ribbon of the call) |
+//                  cfg plan_water 1 (PlannerConfig::setPlanWater: how far it is by water from the start to the chart's cells and to every
+//                  ribbon; adds water_cells, water_max_metres, water_seed_blocked, water_rounds, ribbons_dry, nearest_ribbon_by_water,
+//                  nearest_ribbon_water_metres and nearest_ribbon_straight_metres to the JSON, and to every plan under evaluate) |
+//                  plan_water_file path (with cfg plan_water 1: one line per ribbon of the call) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -80,6 +84,18 @@ static std::string reachKeys(const Planner::Stats::ReachReport& r) {
     return buf;
 }
 
+// ", water_cells ..., ..., nearest_ribbon_straight_metres ..." of a call's Stats::Water: the cells with a distance by water from the start,
+// the largest of them in metres, the rounds the build took, the ribbons that cannot be approached, and the ribbon nearest by water with
+// its distance by water and in a straight line (-1 for all three without one)
+static std::string waterKeys(const Planner::Stats::WaterReport& w) {
+    char buf[420];
+    std::snprintf(buf, sizeof buf, ", \"water_cells\": %llu, \"water_max_metres\": %.17g, \"water_seed_blocked\": %s, \"water_rounds\": %u, "
+                  "\"ribbons_dry\": %d, \"nearest_ribbon_by_water\": %d, \"nearest_ribbon_water_metres\": %.17g, \"nearest_ribbon_straight_metres\": %.17g",
+                  (unsigned long long)w.WetCells, w.MaxMetres, (w.Flags & Planner::Stats::WaterReport::SeedBlocked) ? "true" : "false", w.Rounds, w.RibbonsDry,
+                  w.NearestRibbon, w.NearestWaterMetres, w.NearestStraightMetres);
+    return buf;
+}
+
 // One report file: rows(f, s) prints the lines of segment s.  No path, no file; -> false (and the complaint) when it cannot be written.
 template <class Rows>
 static bool writeReport(const std::string& path, size_t segments, Rows rows) {
@@ -115,7 +131,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planReachPath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planReachPath, planWaterPath, planLogPath;
     bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -144,6 +160,7 @@ int main(int argc, char** argv) {
             else if (name == "plan_clearance_margin") config.setPlanClearanceMargin(v);
             else if (name == "keepout_margin") config.setKeepoutMargin(v);
             else if (name == "plan_reach") config.setPlanReach(v != 0);
+            else if (name == "plan_water") config.setPlanWater(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -177,6 +194,7 @@ int main(int argc, char** argv) {
         } else if (k == "plan_contacts_file") { s >> planContactsPath;   // segment mmsi hit_steps first_hit_time last_hit_time cpa_distance cpa_time exposure peak
         } else if (k == "plan_clearance_file") { s >> planClearancePath;   // segment clearance time x y step gap2 below_steps first_below_time flags
         } else if (k == "plan_reach_file") { s >> planReachPath;   // ribbon length pitch samples out_samples first_out last_out min_rgap2 max_rgap2 lim2 out_length flags
+        } else if (k == "plan_water_file") { s >> planWaterPath;   // ribbon length pitch samples wet_samples nearest_sample farthest_sample min_ad max_ad start_ad end_ad lim2 flags nearest_metres
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -250,6 +268,7 @@ int main(int argc, char** argv) {
                 std::printf("]%s%s", config.planContacts() ? contactKeys(e.contacts).c_str() : "", config.planClearance() ? clearanceKeys(e.clearance).c_str() : "");
                 if (config.keepoutMargin() != 0) std::printf("%s", keepoutKeys(e.keepout).c_str());
                 if (config.planReach()) std::printf("%s", reachKeys(e.reach).c_str());
+                if (config.planWater()) std::printf("%s", waterKeys(e.water).c_str());
                 std::printf("}");
             }
             std::printf("]}\n");
@@ -460,6 +479,14 @@ int main(int argc, char** argv) {
                     const auto& r = st.Reach.Ribbons[rb];
                     std::fprintf(f, "%zu %.17g %.17g %u %u %d %d %u %u %u %.17g %u\n", rb, r.length, r.pitch, r.samples, r.outSamples, r.firstOut, r.lastOut, r.minRgap2,
                                  r.maxRgap2, r.lim2, r.outLength, r.flags);
+                })) return 2;
+        }
+        if (config.planWater()) {                 // (likewise)
+            tail += waterKeys(st.Water);
+            if (!writeReport(planWaterPath, st.Water.Ribbons.size(), [&](FILE* f, size_t rb) {
+                    const auto& r = st.Water.Ribbons[rb];
+                    std::fprintf(f, "%zu %.17g %.17g %u %u %d %d %u %u %u %u %u %u %.17g\n", rb, r.length, r.pitch, r.samples, r.wetSamples, r.nearestSample,
+                                 r.farthestSample, r.minAd, r.maxAd, r.startAd, r.endAd, r.lim2, r.flags, r.nearestMetres);
                 })) return 2;
         }
         if (config.planTrace()) {

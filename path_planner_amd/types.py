@@ -120,6 +120,21 @@ RIBBON_REACH_DTYPE = np.dtype([
 ])
 assert RIBBON_REACH_DTYPE.itemsize == 64
 
+# distance by water (ppgpu_set_water_seed, ppgpu_get_grid_water, ppgpu_water_distance_at, ppgpu_ribbon_water_host): struct
+# ppgpu_water_info, 32 bytes, and struct ppgpu_ribbon_water_record, 64 bytes, per ribbon.  WATER_TILE is the relaxation's tile edge
+WATER_NONE, WATER_STEP, WATER_DIAG, WATER_TILE, WATER_MAX_LIM2 = 0xFFFFFFFF, 12, 17, 32, 1024
+WATER_SEED_BLOCKED, WATER_NO_MAP = 0x1, 0x2
+WATER_INFO_DTYPE = np.dtype([
+    ("wet_cells", "<u8"), ("max_wd", "<u4"), ("farthest_cell", "<u4"), ("seed_cell", "<u4"), ("flags", "<u4"), ("rounds", "<u4"), ("builds", "<u4"),
+])
+assert WATER_INFO_DTYPE.itemsize == 32
+RW_ANY_DRY, RW_WHOLE_DRY, RW_DEGENERATE, RW_NO_SEED, RW_NO_MAP = 0x01, 0x02, 0x10, 0x40, 0x80
+RIBBON_WATER_DTYPE = np.dtype([
+    ("length", "<f8"), ("pitch", "<f8"), ("samples", "<u4"), ("wet_samples", "<u4"), ("nearest_sample", "<i4"), ("farthest_sample", "<i4"),
+    ("min_ad", "<u4"), ("max_ad", "<u4"), ("start_ad", "<u4"), ("end_ad", "<u4"), ("lim2", "<u4"), ("flags", "<u4"), ("nearest_metres", "<f8"),
+])
+assert RIBBON_WATER_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
