@@ -205,8 +205,28 @@ int ppgpu_last_shared_edges(ppgpu_ctx* ctx, int64_t* n_edges);
  * co-located, not a class member that takes its head's results) into a list on the device, and the chunk-skip planner, the pose
  * sweep and the approach prepass walk that list instead of every edge (PPGPU_APPROACH_LIST=0: the approach prepass does not).  The records and child ribbons are the same bytes either way.  PPGPU_SWEEP_LIST=0 in
  * the environment of ppgpu_create switches it off.  ppgpu_last_swept_edges: the entries of that list, summed over the slices of the
- * last costing launch; every edge of the launch where it had no list.  Waits for the launch; a measurement aid. */
+ * last costing launch; every edge of the launch where it had no list.  With shared tracks (below) the number includes the edges
+ * that took their track from a head: it stays "edges - shared - unsolved".  Waits for the launch; a measurement aid. */
 int ppgpu_last_swept_edges(ppgpu_ctx* ctx, int64_t* n_edges);
+/* Shared tracks.  The first arc of a curve depends on the open vertex, the radius, the speed and the turn direction alone, so all
+ * edges of one (open vertex, configuration, direction) sample the same poses while they are on it.  Where that arc crosses a
+ * blocked cell of the grid at step kb of the vertex's collision-check time row, every edge of the class that is still on its first
+ * arc at that step stops there, with the same track (hits, heading bits, stop) up to it.  A launch with a sweep list walks each
+ * class's arc once per set of vertices, grid, keep-out limit and configuration (pp_k_arc_stops, in front of the first such launch
+ * after any of them changed), and per class and workspace slice ONE such edge, the head, goes through the chunk-skip planner and the
+ * pose sweep; the others, the stop members, get a copy of its track and are costed from there like any swept edge: their end state,
+ * g, h and ribbons are their own.  The records and child ribbons are the same bytes either way.  Given curves, the Gaussian obstacle
+ * model, launches without a grid or without a sweep list and the traces' own solves form no stop classes.  PPGPU_SHARE_TRACKS=0 in
+ * the environment of ppgpu_create switches it off: a launch then builds the lists and runs the kernels it ran before there were stop
+ * classes.
+ * ppgpu_last_stop_members: how many edges of the last costing launch took their track from a head, summed over its slices (0 with
+ * the switch off).  A stop member is not a shared edge (ppgpu_last_shared_edges does not count it) and it is a swept one:
+ * ppgpu_last_swept_edges, "edges - shared - unsolved", counts it although the planner and the pose sweep did not walk it.  Waits for
+ * the launch; a measurement aid. */
+int ppgpu_last_stop_members(ppgpu_ctx* ctx, int64_t* n_edges);
+/* Measurement aid: with timing on (ppgpu_enable_timing), the milliseconds pp_k_arc_stops took the last time a costing launch queued
+ * it (HIP events around the kernel alone).  PPGPU_ESTATE when none was timed since timing was switched on. */
+int ppgpu_last_arc_stops_timing(ppgpu_ctx* ctx, double* ms_arc_stops);
 /* How the last costing launch was cut: the number of workspace slices it ran as, and the edges of the last one (tests of sliced
  * launches check that they are what they meant to be).  Does not wait. */
 int ppgpu_last_slices(ppgpu_ctx* ctx, int64_t* n_slices, int64_t* last_slice_edges);

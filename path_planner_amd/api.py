@@ -57,6 +57,8 @@ def _load():
         "ppgpu_last_cover_edges": (C.c_int, [vp, C.POINTER(i64)]),
         "ppgpu_last_shared_edges": (C.c_int, [vp, C.POINTER(i64)]),
         "ppgpu_last_swept_edges": (C.c_int, [vp, C.POINTER(i64)]),
+        "ppgpu_last_stop_members": (C.c_int, [vp, C.POINTER(i64)]),
+        "ppgpu_last_arc_stops_timing": (C.c_int, [vp, C.POINTER(dbl)]),
         "ppgpu_last_slices": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "ppgpu_set_config": (C.c_int, [vp, C.POINTER(PpgpuConfig)]),
         "ppgpu_set_grid": (C.c_int, [vp, vp, i32, i32, dbl]),
@@ -127,7 +129,7 @@ def _load():
         "ppgpu_comm_abort": (C.c_int, [vp]),
     }
     # measurement aids an older build of the library may lack (tools/ab_libs.sh loads the parent commit's): calling one there raises
-    optional = {"ppgpu_last_swept_edges", "ppgpu_last_slices"}
+    optional = {"ppgpu_last_swept_edges", "ppgpu_last_slices", "ppgpu_last_stop_members", "ppgpu_last_arc_stops_timing"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -219,6 +221,19 @@ class Context:
         n = C.c_int64()
         self._ck(LIB.ppgpu_last_swept_edges(self._h, C.byref(n)), "ppgpu_last_swept_edges")
         return n.value
+
+    def last_stop_members(self):
+        """Edges of the last costing launch that took their track from the head of their stop class (PPGPU_SHARE_TRACKS); they count
+        as swept edges, not as shared ones."""
+        n = C.c_int64()
+        self._ck(LIB.ppgpu_last_stop_members(self._h, C.byref(n)), "ppgpu_last_stop_members")
+        return n.value
+
+    def last_arc_stops_timing(self):
+        """Milliseconds of the last timed pp_k_arc_stops (enable_timing, then a launch after new vertices, grid, keep-out or config)."""
+        ms = C.c_double()
+        self._ck(LIB.ppgpu_last_arc_stops_timing(self._h, C.byref(ms)), "ppgpu_last_arc_stops_timing")
+        return ms.value
 
     def last_slices(self):
         """(workspace slices the last costing launch ran as, edges of the last one)."""

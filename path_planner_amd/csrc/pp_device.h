@@ -398,21 +398,28 @@ struct PPCurve {
     double s0, c0, s1, c1, s2, c2;             // sin/cos of the three base headings
 };
 
-// MEMO: with the repeated evaluations left out (a CSC curve then takes two, a CCC curve three, instead of five)
+// What a curve has before its word is known: where it starts, its radius, and the base of segment 0, {0, 0, qth, s0, c0}.  None of
+// it depends on the target, so every edge of one (vertex, radius) starts from these bits: pp_curve_init goes on from here, and
+// pp_k_arc_stops (pp_k_sweep.h) walks the first arc of a class from here without solving anything.
 template <bool CR = false, bool MEMO = false>
-__device__ inline void pp_curve_init(PPCurve& c, double qx, double qy, double qth, double rho, const PPDubins& d) {
+__device__ __forceinline__ void pp_curve_base(PPCurve& c, double qx, double qy, double qth, double rho, PPSincosMemo& m) {
     c.qx = qx; c.qy = qy; c.qth = qth; c.rho = rho;
     {
         int ex;
         c.rho_inv = (frexp(rho, &ex) == 0.5) ? (1.0 / rho) : 0.0;
     }
+    m.have = false;
+    pp_dub_sincos_memo<CR, MEMO>(m, qth, &c.s0, &c.c0);
+}
+// MEMO: with the repeated evaluations left out (a CSC curve then takes two, a CCC curve three, instead of five)
+template <bool CR = false, bool MEMO = false>
+__device__ inline void pp_curve_init(PPCurve& c, double qx, double qy, double qth, double rho, const PPDubins& d) {
+    PPSincosMemo m;
+    pp_curve_base<CR, MEMO>(c, qx, qy, qth, rho, m);
     c.p0 = d.p0; c.p1 = d.p1; c.p2 = d.p2;
     c.length = pp_dubins_length(d, rho);
     int w = d.type < 0 ? 0 : d.type;
     c.t0 = pp_seg_type(w, 0); c.t1 = pp_seg_type(w, 1); c.t2 = pp_seg_type(w, 2);
-    PPSincosMemo m;
-    m.have = false;
-    pp_dub_sincos_memo<CR, MEMO>(m, qth, &c.s0, &c.c0);
     pp_segment<CR, MEMO>(c.t0, d.p0, 0.0, 0.0, qth, c.s0, c.c0, c.b1x, c.b1y, c.b1th, m);
     pp_dub_sincos_memo<CR, MEMO>(m, c.b1th, &c.s1, &c.c1);
     pp_segment<CR, MEMO>(c.t1, d.p1, c.b1x, c.b1y, c.b1th, c.s1, c.c1, c.b2x, c.b2y, c.b2th, m);

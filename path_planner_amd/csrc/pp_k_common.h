@@ -11,12 +11,17 @@ struct __attribute__((aligned(128))) PPLaunchWords {
     unsigned hw_count;                        // entries of hw_list (pp_k_cover_finish -> pp_k_heuristic_listed)
     unsigned defer_count[PP_HL_MAX_N + 1];    // [n] = deferred edges with n ribbons, n = 1 .. PP_HL_MAX_N (pp_k_deferred_list -> pp_k_heuristic_lanes)
     unsigned sweep_count;                     // per slice: entries of sweep_list (pp_k_mark_sweeps -> the skip planner, the pose sweep)
-    unsigned swept_total;                     // ... and their sum over the slices of the launch (ppgpu_last_swept_edges)
+    unsigned swept_total;                     // ... and their sum over the slices of the launch, stop members included (ppgpu_last_swept_edges)
+    unsigned stop_count;                      // per slice: entries of stop_list (pp_k_mark_sweeps -> pp_k_track_fanout, which puts them behind the sweep list's prefix for pp_k_approach_events)
+    unsigned stop_total;                      // ... and their sum over the slices of the launch (ppgpu_last_stop_members)
 };
 static_assert(sizeof(PPLaunchWords) == 128, "the launch counters share one 128-byte line");
 static_assert(offsetof(PPLaunchWords, sweep_count) % 8 == 0 && offsetof(PPLaunchWords, swept_total) == offsetof(PPLaunchWords, sweep_count) + 4,
               "pp_k_mark_sweeps adds to sweep_count (low half) and swept_total (high half) with one 64-bit atomic");
+static_assert(offsetof(PPLaunchWords, stop_count) % 8 == 0 && offsetof(PPLaunchWords, stop_total) == offsetof(PPLaunchWords, stop_count) + 4,
+              "... and to stop_count (low half) and stop_total (high half) with another");
 __device__ __forceinline__ unsigned long long* pp_sweep_counters(PPLaunchWords* w) { return reinterpret_cast<unsigned long long*>(&w->sweep_count); }
+__device__ __forceinline__ unsigned long long* pp_stop_counters(PPLaunchWords* w) { return reinterpret_cast<unsigned long long*>(&w->stop_count); }
 
 // Everything a costing launch needs, passed by value (kernarg segment, scalar loads).
 struct PPParams {
@@ -78,6 +83,12 @@ struct PPParams {
     unsigned* sweep_list;                // [words->sweep_count] slice positions of the edges the skip planner and the pose sweep walk, packed
                                          // (pp_k_mark_sweeps): the solved edges without a PP_SETUP_NO_SWEEP bit.  NULL: both walk every edge of
                                          // the slice and leave the others at once (launches without shared sweeps, PPGPU_SWEEP_LIST=0)
+    // Shared tracks (pp_k_solve.h): edges that a blocked cell stops on their class's first arc take their track from one of them
+    int* arc_stop;                       // [nverts * PP_SHARE_KEYS] the first step of the vertex's time row at which the class's first arc is blocked,
+                                         // -1: at none before the horizon (pp_k_arc_stops).  NULL: the launch forms no stop classes
+    unsigned* stop_list;                 // [words->stop_count] slice positions of the stop members, packed (pp_k_mark_sweeps).  pp_k_track_fanout copies them
+                                         // to sweep_list[sweep_count ...], behind the prefix the skip planner and the pose sweep have walked by then
+    unsigned* stop_of;                   // [slice position] of a stop member: the slice position of its head (pp_k_mark_sweeps -> pp_k_track_fanout)
 };
 
 // Phase 0 of an edge (Vertex::connect + Edge::computeApproxCost: which vertex/target/configuration, the Dubins word and
@@ -92,7 +103,10 @@ struct PPParams {
 #define PP_SHARE_KEYS 8         // classes per vertex: configuration bits (4) x direction of the first arc (2)
 #define PP_SHARE_NONE 0xffffffffu
 #define PP_FAR_DONE (-2)        // PPParams::track_far[e].x of an edge the cover sweep's wave has nothing left to do for (pp_k_cover.h)
-#define PP_SHARE_UNSWEPT 0xfffffffeu   // (no class key: keys are below nverts * PP_SHARE_KEYS < 2^32, a multiple of 8)
+#define PP_SHARE_UNSWEPT 0xfffffffeu   // (no class key: keys are below 2 * nverts * PP_SHARE_KEYS < 2^32, a multiple of 8)
+// A stop class (pp_edge_stopped_on_arc) has the key of the horizon class of the same (vertex, configuration, direction) plus
+// nverts * PP_SHARE_KEYS: the second half of share_head, elected per SLICE (a track lives in the slice's workspace).
+__device__ __forceinline__ unsigned pp_stop_key_base(int nverts) { return (unsigned)nverts * PP_SHARE_KEYS; }
 // The layout of PPParams::share_head: every class has a 128-byte line to itself, so that the atomics of a vertex's eight classes (all
 // that a launch from one vertex has) do not queue on one line.  The host sizes the table with PP_SHARE_STRIDE; every kernel reaches
 // an entry through pp_share_entry.
@@ -237,6 +251,13 @@ __device__ __forceinline__ long long pp_edge_position(const PPParams& p, long lo
     const long long r = w / Q;
     return (w - r * Q) * p.per + (p.per - 1 - r);
 }
+// ... and back: the slice position (work item - e_base) of the edge at list position eg, which lies in the current slice.
+__device__ __forceinline__ long long pp_edge_slice_position(const PPParams& p, long long eg) {
+    if (p.wedges || p.edges) return eg - p.e_base;
+    const long long Q = p.total_edges / p.per;
+    const long long q = eg / p.per, r = p.per - 1 - (eg - q * p.per);
+    return q + r * Q - p.e_base;
+}
 
 // Which (vertex, target, configuration) edge `e` of the launch is: wrapper list, explicit list or dense enumeration.
 __device__ __forceinline__ void pp_edge_decode(const PPParams& p, long long e, unsigned& vi, unsigned& target, unsigned& cbits) {
@@ -310,13 +331,13 @@ __device__ __forceinline__ long long pp_next_edge(const PPParams& p, PPQueue& s,
     }
     return n;
 }
-// What pp_k_solve_edges (thread e) clears ahead of its slice's kernels: queue heads, live_count and sweep_count per slice, the other counters per launch.
+// What pp_k_solve_edges (thread e) clears ahead of its slice's kernels: queue heads, live_count, sweep_count and stop_count per slice, the other counters per launch.
 __device__ __forceinline__ void pp_launch_reset(const PPParams& p, long long e) {
     if (!p.reset_words) return;
     if (e < PP_NQ) p.work[(size_t)e * PP_QSTRIDE] = 0ull;
     if (p.e_base == 0) {
         if (e < (long long)(sizeof(PPLaunchWords) / sizeof(unsigned))) reinterpret_cast<unsigned*>(p.words)[e] = 0u;     // the whole line, a word per thread
     } else if (e == 0) {
-        p.words->live_count = 0u; p.words->sweep_count = 0u;
+        p.words->live_count = 0u; p.words->sweep_count = 0u; p.words->stop_count = 0u;
     }
 }

@@ -99,7 +99,9 @@ __device__ __forceinline__ void pp_approach_events_body(const PPParams& p) {
     long long eIdx = e0 + threadIdx.x;
     bool inRange = eIdx < p.n_edges;
     if (LISTED) {
-        const long long count = (long long)(unsigned)pp_const_i32(&p.words->sweep_count)[0];
+        // (both parts of the list: the prefix the pose sweep walked, then the stop members, which pp_k_track_fanout gave their head's
+        // track and put behind the prefix)
+        const long long count = (long long)(unsigned)pp_const_i32(&p.words->sweep_count)[0] + (long long)(unsigned)pp_const_i32(&p.words->stop_count)[0];
         if (e0 >= count) return;                                       // (the whole workgroup: no barrier met)
         inRange = eIdx < count;
         eIdx = inRange ? (long long)p.sweep_list[eIdx] : 0;

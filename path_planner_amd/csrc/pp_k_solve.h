@@ -39,6 +39,40 @@ __device__ __forceinline__ bool pp_edge_shareable(const PPParams& p, const PPCur
 __device__ __forceinline__ unsigned pp_share_key(unsigned vi, unsigned cbits, int type) {
     return vi * PP_SHARE_KEYS + (cbits & 3u) * 2u + (pp_word_seg_type(type, 0) == 0 ? 0u : 1u);
 }
+// Shared tracks.  The first arc of a class is one curve whatever the target, so the first step kb of the vertex's time row at which
+// that arc lies on a blocked cell is a property of the class (pp_k_arc_stops, PPParams::arc_stop).  An edge that is still on the arc
+// at step kb stops there: its pose sweep ends with limit = kb and blocked = 1, and everything the sweep leaves up to that step — hits,
+// heading bits, skip bytes — is the same for every such edge of the class.  Its RECORD is not: after the break the end state is sampled
+// at endTime on the edge's own curve (Edge.cpp:177-203), so g, h and the last cover are the edge's.  So one such edge per class and
+// slice, the head, goes through the skip planner and the pose sweep, pp_k_track_fanout copies its track to the others, the members,
+// and every kernel after that treats a member as the swept edge it is.
+//
+// The rule (pp_edge_stopped_on_arc), on the record as the sweeps will read it, with bound = horizon + 1e-12 + sst and
+// t_kb = tgrid[kb] of the edge's vertex:
+//   * the edge is solved (type >= 0, neither malformed nor co-located), cbits < 4, and pp_edge_shareable does not hold;
+//   * its class has a kb;
+//   * t_kb < min(bound, wEnd): the edge's own loop reaches step kb;
+//   * the pose at t_kb, in pp_window_pose's own arithmetic, lies strictly inside segment 0: dist = (t_kb - wStart) * speed has
+//     dist <= length, and tprime = dist * rho_inv (or dist / rho where rho_inv is 0) has tprime < p0.
+// Why the one test at t_kb covers every step up to kb: the time row never falls (each entry is the one before plus a positive
+// increment, rounded), so a step k <= kb has t_k <= t_kb < endTime — the sweep samples it — and t -> (t - wStart) * speed -> tprime
+// is the chain of roundings of non-decreasing functions of the horizon rule above: dist(t_k) <= dist(t_kb) <= length, so the retry and
+// the clamp of DubinsWrapper::sample can only fire for dist < 0, where they do not look at the curve, and tprime(t_k) <=
+// tprime(t_kb) < p0 picks segment 0.  There the pose is pp_curve_seg on the base {0, 0, qth, s0, c0} with qx, qy, rho, rho_inv,
+// wStart and speed: the bits pp_k_arc_stops walked (pp_curve_base forms them for both).  It found no blocked cell before kb and one
+// at kb, no obstacle stops a sweep, and a chunk the skip planner spares the grid test provably has no blocked pose: limit = kb.
+__device__ __forceinline__ bool pp_edge_stopped_on_arc(const PPParams& p, const PPCurve& cv, int type, unsigned sflags, unsigned vi, unsigned cbits,
+                                                       double wStart, double wEnd, double speed) {
+    if (type < 0 || (sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) || cbits >= 4u) return false;
+    const int kb = p.arc_stop[pp_share_key(vi, cbits, type)];
+    if (kb < 0) return false;
+    const double t_kb = p.tgrid[(size_t)vi * p.ng + kb];
+    if (!(t_kb < fmin(p.horizon + 1e-12 + p.sst, wEnd))) return false;
+    const double dist = (t_kb - wStart) * speed;
+    if (!(dist <= cv.length)) return false;
+    const double tprime = (cv.rho_inv != 0.0) ? dist * cv.rho_inv : dist / cv.rho;
+    return tprime < cv.p0;
+}
 // The head of a class is its member with the lowest position in the caller's list: the minimum of the positions, whatever order
 // they arrive in.  It is taken in three stages, each of which passes on only what can still lower the table's entry.
 //   1. The wave.  The lanes that hold a position below the entry (a plain look first: in a later slice nearly every lane leaves here)
@@ -47,7 +81,9 @@ __device__ __forceinline__ unsigned pp_share_key(unsigned vi, unsigned cbits, in
 //      are the positions.  (One atomic per member would be 70 000 same-address atomics at ~12.5 ns each.)
 //   2. The workgroup (PPElectLds, pp_share_elect_wave).  That lane takes the minimum in LDS, in the slot its key maps to.  A slot holds
 //      one key, the first that claimed it; a lane that finds another key's claim goes to the table itself, so nothing is lost, and a
-//      dense launch, whose workgroup sees the eight classes of a vertex or two, never does.
+//      dense launch, whose workgroup sees the classes of a vertex or two — eight of each kind, the stop classes half the slots away —
+//      does not unless its vertex count puts the two kinds on the same slots (nverts * 8 = 32 mod 64): then the loser's atomic goes to
+//      the table, one per wave and key, and the result is the same.
 //   3. The table (pp_share_elect_flush), after a barrier: one lane per claimed slot looks at the entry and issues the atomicMin where
 //      the slot's position is lower.  At most one atomic per workgroup and class, where every working wave of a launch used to issue
 //      one per class, all resident at once (so the look saw an empty table), all on the one line a vertex's keys shared.
@@ -62,7 +98,9 @@ __device__ __forceinline__ void pp_share_elect_wave(const PPParams& p, PPElectLd
         const int leader = __ffsll((long long)m) - 1;
         const unsigned k0 = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
         if (pp_lane() == leader) {
-            const unsigned slot = k0 & (PP_ELECT_SLOTS - 1u);
+            // (a stop class sits 32 slots from the horizon class of the same vertex, configuration and direction: their keys differ by
+            // nverts * 8, which is 0 mod 64 for the 64 open vertices of a dense launch)
+            const unsigned slot = (k0 + (k0 >= pp_stop_key_base(p.nverts) ? PP_ELECT_SLOTS / 2u : 0u)) & (PP_ELECT_SLOTS - 1u);
             const unsigned was = atomicCAS(&lds.key[slot], PP_SHARE_NONE, k0);
             if (was == PP_SHARE_NONE || was == k0) atomicMin(&lds.pos[slot], pos);
             else atomicMin(pp_share_entry(p, k0), pos);
@@ -181,9 +219,14 @@ __device__ __forceinline__ void pp_solve_edge_records(const PPParams& p, long lo
             // (the class of a member, PP_SHARE_NONE for any other edge, PP_SHARE_UNSWEPT for one no kernel sweeps anyway: pp_k_mark_sweeps
             // reads it there, without a look at the record, and puts the edge's head in its place)
             const long long egk = k ? pp_edge_position(p, p.e_base + e2) : eg;
-            const bool member = pp_edge_shareable(p, cv, S.type, S.sflags, S.cbits, S.wStart, S.wEnd, S.speed);
+            bool member = pp_edge_shareable(p, cv, S.type, S.sflags, S.cbits, S.wStart, S.wEnd, S.speed);
             const bool unswept = S.type < 0 || (S.sflags & (PP_SETUP_MALFORMED | PP_SETUP_COLOCATED)) != 0u;
-            const unsigned key = member ? pp_share_key(S.vi, S.cbits, S.type) : PP_SHARE_NONE;
+            unsigned key = member ? pp_share_key(S.vi, S.cbits, S.type) : PP_SHARE_NONE;
+            // (shared tracks: an edge of neither kind of class stays PP_SHARE_NONE; the stop classes have the table's second half)
+            if (p.arc_stop && !member && pp_edge_stopped_on_arc(p, cv, S.type, S.sflags, S.vi, S.cbits, S.wStart, S.wEnd, S.speed)) {
+                member = true;
+                key = pp_stop_key_base(p.nverts) + pp_share_key(S.vi, S.cbits, S.type);
+            }
             if (k) { member1 = member; key1 = key; pos1 = (unsigned)egk; } else { member0 = member; key0 = key; pos0 = (unsigned)egk; }
             p.share_of[egk] = unswept ? PP_SHARE_UNSWEPT : key;          // (an unswept edge is no member)
         }
@@ -260,6 +303,11 @@ __device__ __forceinline__ void pp_solve_edges_body(const PPParams& p) {
 // workgroup has anything to add up) and ONE atomic for both counters (they share a 64-bit word: the slice's count in its low half, which the
 // add returns, the launch's total in its high half): a line takes an atomic every ~12.5 ns, and 231 of them stay under 3 us where
 // two per 256 edges would be 23.  The kernel's stores all come after its last barrier (a barrier waits for the stores before it).
+//
+// Shared tracks.  A member of a stop class that is not the class's head of this slice is a swept edge whose track comes from that
+// head: it is packed into stop_list — stop_count counts the entries (a second 64-bit atomic, only in a workgroup that has some) — which
+// pp_k_track_fanout appends to the sweep list behind the prefix that sweep_count bounds, and stop_of holds its head's slice position.  Its
+// share_of entry becomes PP_SHARE_NONE like the head's: a stop member is not a shared edge.
 #define PP_MARK_THREADS 1024         // with a list
 #define PP_MARK_THREADS_PLAIN 256    // without
 __global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) {
@@ -268,28 +316,35 @@ __global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) 
     const long long eg = valid ? pp_edge_position(p, p.e_base + e) : 0;
     const unsigned key = valid ? p.share_of[eg] : PP_SHARE_UNSWEPT;                  // as pp_k_solve_edges left it
     unsigned head = PP_SHARE_NONE;                                                   // whose results the edge takes: its own
+    unsigned trackHead = PP_SHARE_NONE;                                              // whose track it takes (a stop member): its own
     if (key != PP_SHARE_UNSWEPT && key != PP_SHARE_NONE) {
         head = *pp_share_entry(p, key);
         if (head == (unsigned)eg) head = PP_SHARE_NONE;
+        // (a stop class: its head is swept like any edge, its members keep their own results; no launch without p.arc_stop has such a key)
+        if (key >= pp_stop_key_base(p.nverts)) { trackHead = head; head = PP_SHARE_NONE; }
     }
-    const bool swept = key != PP_SHARE_UNSWEPT && head == PP_SHARE_NONE;
-    unsigned at = 0u;
+    const bool stopMember = trackHead != PP_SHARE_NONE;
+    const bool swept = key != PP_SHARE_UNSWEPT && head == PP_SHARE_NONE && !stopMember;
+    unsigned at = 0u, atStop = 0u;
     if (p.sweep_list) {
-        __shared__ unsigned s_cnt[PP_MARK_THREADS / 64];
-        __shared__ unsigned s_base;
+        __shared__ unsigned s_cnt[PP_MARK_THREADS / 64], s_cntStop[PP_MARK_THREADS / 64];
+        __shared__ unsigned s_base, s_baseStop;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const unsigned long long m = __ballot(swept);
-        if (lane == 0) s_cnt[wave] = (unsigned)__popcll(m);
+        const unsigned long long m = __ballot(swept), ms = __ballot(stopMember);
+        if (lane == 0) { s_cnt[wave] = (unsigned)__popcll(m); s_cntStop[wave] = (unsigned)__popcll(ms); }
         __syncthreads();
         if (threadIdx.x == 0) {
-            unsigned tot = 0;
-            for (int w = 0; w < (int)(blockDim.x >> 6); w++) tot += s_cnt[w];
-            // (no carry out of the low half: it is cleared per slice and a slice has fewer than 2^32 edges)
-            s_base = tot ? (unsigned)atomicAdd(pp_sweep_counters(p.words), ((unsigned long long)tot << 32) | tot) : 0u;
+            unsigned tot = 0, totStop = 0;
+            for (int w = 0; w < (int)(blockDim.x >> 6); w++) { tot += s_cnt[w]; totStop += s_cntStop[w]; }
+            // (no carry out of the low half: it is cleared per slice and a slice has fewer than 2^32 edges.  The launch's total counts the
+            // stop members too: they are swept edges that took their track from a head)
+            s_base = (tot + totStop) ? (unsigned)atomicAdd(pp_sweep_counters(p.words), ((unsigned long long)(tot + totStop) << 32) | tot) : 0u;
+            s_baseStop = totStop ? (unsigned)atomicAdd(pp_stop_counters(p.words), ((unsigned long long)totStop << 32) | totStop) : 0u;
         }
         __syncthreads();
         at = s_base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; w++) at += s_cnt[w];
+        atStop = s_baseStop + (unsigned)__popcll(ms & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; w++) { at += s_cnt[w]; atStop += s_cntStop[w]; }
     }
     if (!valid) return;
     if (key != PP_SHARE_NONE) p.share_of[eg] = head;
@@ -305,7 +360,12 @@ __global__ __launch_bounds__(PP_MARK_THREADS) void pp_k_mark_sweeps(PPParams p) 
     }
     if (!p.sweep_list) return;
     if (swept) p.sweep_list[at] = (unsigned)e;                 // (a slice position: below 2^32, as the live list's)
-    else {
+    else if (stopMember) {
+        // on a list of its own, which pp_k_track_fanout puts behind the prefix once the skip planner and the pose sweep have walked that.
+        // That kernel gives the edge its summary and its track, pp_k_approach_events its track_far: nothing of either is written here
+        p.stop_list[atStop] = (unsigned)e;
+        p.stop_of[e] = (unsigned)pp_edge_slice_position(p, (long long)trackHead);
+    } else {
         reinterpret_cast<int4*>(p.track_summary)[p.ws_base + e] = make_int4(0, 0, 0, 0);   // (PPTrackSummary, pp_k_sweep.h: {limit, blocked, dub_err, pad})
         if (p.approach_list) {
             // what pp_k_approach_events would have left: a shared edge is done; an edge without a curve goes to the cover sweep's wave

@@ -812,3 +812,107 @@ __global__ __launch_bounds__(PP_WPB * 64, 4) void pp_k_pose_sweep_gaussian_direc
     const long long idx = pp_wave_edge<PP_WPB>(wave);
     if (idx < p.n_edges) pp_pose_sweep_edge<true>(p, p.ws_base + idx);
 }
+
+// ------------------------------------------------------------------------------------------
+// Shared tracks (the rule and its proof: pp_k_solve.h).
+//
+// pp_k_arc_stops: one wave per class (pp_share_key), 64 steps of the vertex's time row per trip, the pose sweep's own arithmetic on
+// the one thing every edge of the class has in common: segment 0.  Its base is {0, 0, qth, s0, c0} with qx, qy, rho and rho_inv as
+// pp_curve_init forms them for every edge of the class (pp_curve_base, one piece of code for both), the segment is given the whole
+// line (-inf, +inf) and the curve no end (length = +inf), so pp_window_pose stays on it whatever the step.  Only steps with
+// t < horizon + 1e-12 + sst count, only the grid stops a sweep.  The entry is the first blocked step, or -1: none before the horizon,
+// no grid, or an arc the bounded sine and cosine could not follow (no edge the solver accepts gets that far on its first arc; -1 only
+// ever costs a class its sharing).  The loop is bounded by the row's length and no wave waits for another.
+// The table changes with the vertices, the grid, the keep-out limit and the configuration: the host queues the kernel in front of
+// the first launch that shares tracks after any of them changed, and not otherwise.
+__global__ __launch_bounds__(PP_WPB * 64) void pp_k_arc_stops(PPParams p) {
+    int wave;
+    const long long key = pp_wave_edge<PP_WPB>(wave);
+    if (key >= (long long)p.nverts * PP_SHARE_KEYS) return;
+    const int lane = pp_lane();
+    const unsigned vi = (unsigned)(key / PP_SHARE_KEYS), cbits = ((unsigned)key & (PP_SHARE_KEYS - 1u)) >> 1;
+    const int segType = ((unsigned)key & 1u) ? 2 : 0;                    // (pp_share_key: 0 = a left arc, 1 = a right one)
+    const ppgpu_vertex* V = p.verts + vi;
+    const double rho = (cbits & PPGPU_EDGE_COVERAGE) ? p.rho_cov : p.rho;             // Edge.cpp:73-76
+    const double speed = (cbits & PPGPU_EDGE_SLOW) ? p.slow_speed : p.max_speed;
+    PPCurve cv;
+    PPSincosMemo memo;
+    pp_curve_base<PP_CR_SOLVE>(cv, V->x, V->y, pp_yaw(V->heading), rho, memo);
+    const PPCurveHot hot = {V->time, speed, INFINITY, cv.rho, cv.rho_inv, cv.qx, cv.qy};
+    PPSeg cs = PPSeg{0.0, 0.0, cv.qth, cv.s0, cv.c0, -INFINITY, INFINITY, 0.0, 0.0, segType};
+    int cur = 0;
+    const double bound = p.horizon + 1e-12 + p.sst;
+    const double* tg = p.tgrid + (size_t)vi * p.ng;
+    int kb = -1;
+    if (p.grid.rows != 0) {
+        double tNext = (lane < p.ng) ? tg[lane] : INFINITY;
+        for (int k0 = 0; k0 < p.ng; k0 += PP_WAVE) {
+            const double t = tNext;
+            tNext = (k0 + PP_WAVE + lane < p.ng) ? tg[k0 + PP_WAVE + lane] : INFINITY;   // (the next trip's times travel during this one's poses)
+            const double tFirst = pp_readlane(t, 0);
+            if (!(tFirst < bound)) break;
+            const bool valid = t < bound;
+            {
+                // (as pp_window_pose is about to form it: a tprime that is no number, or beyond what the solver lets a curve reach, ends the walk)
+                const double d = ((valid ? t : tFirst) - hot.wStart) * hot.speed;
+                const double tp = (hot.rho_inv != 0.0) ? d * hot.rho_inv : d / hot.rho;
+                if (__ballot(!(fabs(cv.qth) + fabs(tp) < 9.0e4)) != 0ull) break;
+            }
+            double x, y, uth;
+            bool dubErr = false;
+            pp_window_pose(p.setup, hot, cur, cs, t, tFirst, valid, x, y, uth, dubErr);   // (the record is never looked at: tprime lies in the segment's interval)
+            const PPCellRef cell = pp_blocked_cell(p.grid, x, y);
+            const uint32_t word = p.grid.bits[cell.word];
+            const unsigned long long bm = __ballot(valid & pp_blocked_test(cell, word));
+            if (bm != 0ull) { kb = k0 + __ffsll((long long)bm) - 1; break; }
+            if (__ballot(valid) != ~0ull) break;
+        }
+    }
+    if (lane == 0) p.arc_stop[key] = kb;
+}
+
+// pp_k_track_fanout: after the pose sweep of a slice and before its approach kernel, PP_TF_LANES lanes per stop member (entry j of
+// stop_list).  The count is on the device: the grid has at most PP_TF_GRID workgroups, which stride over the members, and the
+// workgroups past the count leave at once.  The member goes onto the sweep list, behind the prefix the skip planner and the pose
+// sweep have walked (pp_k_approach_events walks both parts as one list), and gets a copy of what those two left its head, as far
+// as anyone reads it: the summary (limit = kb, blocked = 1); for the chunks 0 .. kb >> 6 the chunk's hit sum, its skip byte and, on an edge that may
+// not cover while turning, its heading bits; and the 128-byte row of per-step hits of each of those chunks that was sampled and
+// whose sum is not zero (the only rows a reader looks at: pp_lane_hit_sum).  The readers then find the member's track where they
+// find any edge's, with no indirection.
+// The kernel also leaves the stop classes' half of the table of heads all-ones for the next slice's solve: pp_k_mark_sweeps was its
+// last reader (this kernel goes by stop_of).
+#define PP_TF_LANES 16
+#define PP_TF_GRID 2048       // workgroups at most: 32 768 members a pass
+static_assert(PP_TF_LANES * sizeof(unsigned long long) == PP_WAVE * sizeof(unsigned short), "a row of per-step hits is one 8-byte word per lane");
+__global__ __launch_bounds__(256) void pp_k_track_fanout(PPParams p) {
+    const unsigned long long n_keys = (unsigned long long)p.nverts * PP_SHARE_KEYS;
+    for (unsigned long long k = (unsigned long long)blockIdx.x * 256u + threadIdx.x; k < n_keys; k += (unsigned long long)gridDim.x * 256u)
+        *pp_share_entry(p, pp_stop_key_base(p.nverts) + (unsigned)k) = PP_SHARE_NONE;
+    const int sub = (int)(threadIdx.x % PP_TF_LANES);
+    const long long count = (long long)(unsigned)pp_const_i32(&p.words->stop_count)[0], swept = (long long)(unsigned)pp_const_i32(&p.words->sweep_count)[0];
+    for (long long j = (long long)blockIdx.x * (256 / PP_TF_LANES) + (threadIdx.x / PP_TF_LANES); j < count; j += (long long)gridDim.x * (256 / PP_TF_LANES)) {
+        const unsigned slot = p.stop_list[j];
+        if (sub == 0) p.sweep_list[swept + j] = slot;                   // (swept + count <= n_edges: within the list)
+        const long long e = p.ws_base + (long long)slot;
+        const long long h = p.ws_base + (long long)p.stop_of[e - p.ws_base];
+        const int4 sum = reinterpret_cast<const int4*>(p.track_summary)[h];
+        if (sub == 0) reinterpret_cast<int4*>(p.track_summary)[e] = sum;
+        const bool cov = (p.setup[e].cbits & PPGPU_EDGE_COVERAGE) != 0;
+        int nchunks = (sum.x >> 6) + 1;                                 // (limit = kb: the chunk of the blocked step is the last one read)
+        if (nchunks > p.nch) nchunks = p.nch;
+        const size_t rowE = (size_t)e * p.nch, rowH = (size_t)h * p.nch;
+        for (int c = sub; c < nchunks; c += PP_TF_LANES) {
+            p.track_chunk_hits[rowE + c] = p.track_chunk_hits[rowH + c];
+            if (p.track_skip) p.track_skip[rowE + c] = p.track_skip[rowH + c];
+            if (!cov) p.track_eq[rowE + c] = p.track_eq[rowH + c];
+        }
+        if (p.n_obst <= 0) continue;
+        for (int c = 0; c < nchunks; c++) {
+            const bool skipped = p.track_skip && (p.track_skip[rowH + c] & PP_SKIP_ALL) != 0;
+            if (skipped || p.track_chunk_hits[rowH + c] == 0u) continue;
+            const unsigned long long* src = reinterpret_cast<const unsigned long long*>(p.track_hits + (size_t)h * p.ngp + (size_t)c * PP_WAVE);
+            unsigned long long* dst = reinterpret_cast<unsigned long long*>(p.track_hits + (size_t)e * p.ngp + (size_t)c * PP_WAVE);
+            dst[sub] = src[sub];
+        }
+    }
+}

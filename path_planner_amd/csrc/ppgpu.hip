@@ -213,6 +213,7 @@ struct ppgpu_ctx {
     TraceTimer t_tsp;                   // around the table pass (tsp_table_pass)
     TraceTimer t_dist;                  // around the two passes of the distance map (grid_distance)
     TraceTimer t_keepout;               // around pp_k_keepout_bits and the rebuild of grid_clear (apply_keepout)
+    TraceTimer t_arc_stops;             // around pp_k_arc_stops (launch_cost; events made by the first timed use, like t_keepout's)
     bool quiet_finish = true;           // env PPGPU_QUIET_FINISH=0: every edge's phase C stays with its wave
     bool solve_all_words = false;       // env PPGPU_SOLVE_ALL_WORDS=1: the solver evaluates all six words correctly rounded (tests compare the two)
     bool lane_split = true;             // env PPGPU_LANE_SPLIT=0: the wave makes every split itself (tests compare the two)
@@ -240,6 +241,12 @@ struct ppgpu_ctx {
     DevBuf<unsigned> sweep_list;             // ... and the slice positions of the edges the skip planner and the pose sweep walk (pp_k_mark_sweeps)
     long long last_launch_slices = 0, last_slice_edges = 0;   // how the last costing launch was cut (ppgpu_last_slices)
     bool last_launch_listed = false;         // the last costing launch ran with that list (words->swept_total then counts its entries over all slices)
+    bool share_tracks = true;                // env PPGPU_SHARE_TRACKS=0: no stop classes, every swept edge is planned and posed itself (A/B runs, and the tests compare the two)
+    DevBuf<int> arc_stop;                    // shared tracks: per class the step at which its first arc is blocked (pp_k_arc_stops; see PPParams) ...
+    bool arc_stops_stale = true;             // ... which is not known to hold for the vertices, grid, keep-out limit and configuration now set:
+                                             // the next launch that shares tracks queues pp_k_arc_stops first
+    DevBuf<unsigned> stop_list, stop_of;     // ... and the stop members of the current slice, packed, and per member its head (pp_k_mark_sweeps)
+    bool last_launch_tracks = false;         // the last costing launch shared tracks (words->stop_total then counts its stop members)
     DevBuf<PPCoverState> cover_state;
     DevBuf<unsigned long long> work;    // queue heads of the cover sweep's resident grid (pp_next_edge)
     int n_cu = 0;
@@ -279,7 +286,7 @@ struct ppgpu_ctx {
     __attribute__((visibility("hidden"))) ~ppgpu_ctx() {          // (the library exports nothing new)
         for (void* pinned : {(void*)pinned_counts, (void*)water_pinned, stage_in, stage_out}) if (pinned) (void)hipHostFree(pinned);
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1],
+        for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1], t_arc_stops.ev[0], t_arc_stops.ev[1],
                              t_reach_labels.ev[0], t_reach_labels.ev[1], t_reach_gap.ev[0], t_reach_gap.ev[1], t_reach_ribbons.ev[0], t_reach_ribbons.ev[1],
                              t_water_map.ev[0], t_water_map.ev[1], t_water_ribbons.ev[0], t_water_ribbons.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
@@ -366,6 +373,7 @@ int ppgpu_create(int device, ppgpu_ctx** out) {
     if (const char* ss = std::getenv("PPGPU_SHARE_SWEEPS")) c->share_sweeps = std::atoi(ss) != 0;
     if (const char* sl = std::getenv("PPGPU_SWEEP_LIST")) c->use_sweep_list = std::atoi(sl) != 0;
     if (const char* al = std::getenv("PPGPU_APPROACH_LIST")) c->approach_list = std::atoi(al) != 0;
+    if (const char* tr = std::getenv("PPGPU_SHARE_TRACKS")) c->share_tracks = std::atoi(tr) != 0;
     if (const char* wb = std::getenv("PPGPU_WATER_BATCH")) c->water_batch = std::min(64, std::max(1, std::atoi(wb)));
     if (const char* sb = std::getenv("PPGPU_SLICE_BYTES")) {
         const long long v = std::atoll(sb);
@@ -403,6 +411,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
         tm->timed = false;
     }
     c->t_keepout.timed = false;         // (its events are made by the first timed change of the keep-out: apply_keepout)
+    c->t_arc_stops.timed = false;       // (... by the first timed walk of the classes' arcs: launch_cost)
     c->t_reach_labels.timed = c->t_reach_gap.timed = c->t_reach_ribbons.timed = false;   // (... by the first timed build or walk)
     c->t_water_map.timed = c->t_water_ribbons.timed = false;
     c->timing = on != 0;
@@ -482,6 +491,19 @@ int ppgpu_last_swept_edges(ppgpu_ctx* c, int64_t* n_edges) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(&swept, &c->words.p->swept_total, sizeof(unsigned), hipMemcpyDeviceToHost));
         *n_edges = (int64_t)swept;
+    }
+    return PPGPU_OK;
+}
+
+int ppgpu_last_stop_members(ppgpu_ctx* c, int64_t* n_edges) {
+    if (!c || !n_edges) return fail(PPGPU_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    *n_edges = 0;
+    if (c->last_launch_tracks) {
+        unsigned members = 0;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(&members, &c->words.p->stop_total, sizeof(unsigned), hipMemcpyDeviceToHost));
+        *n_edges = (int64_t)members;
     }
     return PPGPU_OK;
 }
@@ -605,6 +627,7 @@ int ppgpu_set_config(ppgpu_ctx* c, const ppgpu_config* cfg) {
     c->have_cfg = true;
     c->ng = (int)steps + 8;
     c->nverts = 0;  // time grids depend on the config: vertices must be set again
+    c->arc_stops_stale = true;
     return PPGPU_OK;
 }
 
@@ -622,6 +645,7 @@ int ppgpu_set_grid(ppgpu_ctx* c, const uint8_t* cells, int32_t rows, int32_t col
     if (!c) return fail(PPGPU_EINVAL, "null context");
     HIP_TRY(hipSetDevice(c->device));
     c->grid_dist_built = false;
+    c->arc_stops_stale = true;                          // (the first launch that shares tracks walks the classes' arcs over the new grid)
     c->reach_labels_built = false;                      // (stale: the first call that needs the labels builds them)
     c->water_built = false;                             // (likewise the distance by water)
     if (rows == 0) { c->rows = c->cols = c->wpr = 0; c->res = 0; return PPGPU_OK; }
@@ -749,6 +773,7 @@ int ppgpu_keepout_limit2(double resolution, double margin, uint32_t* limit2) {
 static int apply_keepout(ppgpu_ctx* c) {
     hipStream_t st = c->stream;
     int rc = PPGPU_OK;
+    c->arc_stops_stale = true;                          // the arcs stop on the effective grid
     c->reach_labels_built = false;                      // the labels are those of the effective grid
     c->water_built = false;                             // ... and so is the distance by water
     if (c->keepout_limit2) {
@@ -1375,6 +1400,7 @@ int ppgpu_set_vertices(ppgpu_ctx* c, int32_t n, const ppgpu_vertex* hv, int32_t 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));  // the host arrays may go away after return
     c->nverts = n; c->nribbons = n_ribbons; c->max_vertex_ribbons = maxr;
+    c->arc_stops_stale = true;
     return PPGPU_OK;
 }
 
@@ -1603,6 +1629,7 @@ static void fill_params(ppgpu_ctx* c, PPParams& p) {
     p.fuse_h = 0;
     p.lane_split = 0; p.defer_h = 0; p.defer_list = nullptr; p.quiet_finish = 0; p.live_list = nullptr; p.cover_state = nullptr; p.hw_list = nullptr; p.words = nullptr; p.reset_words = 0;
     p.share_head = nullptr; p.share_of = nullptr; p.sweep_list = nullptr; p.approach_list = 0;
+    p.arc_stop = nullptr; p.stop_of = nullptr; p.stop_list = nullptr;
     p.grid = PPGrid{grid_bits(c), c->rows, c->cols, c->wpr, c->res, c->res > 0 ? 1.0 / c->res : 0.0, c->rows > 0 ? c->grid_clear.p : nullptr};
     p.obst = c->obst.p; p.n_obst = c->n_obst; p.obst_model = c->obst_model;
     p.verts = c->verts.p; p.ribbons = c->ribbons.p; p.tgrid = c->tgrid.p; p.ng = c->ng; p.nverts = c->nverts;
@@ -1750,6 +1777,7 @@ struct CostLaunch {
     bool share;          // shared sweeps: one member of each class of edges with the same sweep is swept, the others take its results (pp_k_solve.h)
     bool share_child;    // ... and its child ribbons, where the caller asked for them
     bool sweep_list;     // ... and the skip planner and the pose sweep walk the packed list of the edges that are swept (pp_k_mark_sweeps)
+    bool tracks;         // shared tracks: edges that a blocked cell stops on their class's first arc take their track from one of them (pp_k_solve.h)
     int nch, ngp;        // 64-step chunks per edge, and the steps they hold
     long long slice;     // edges per workspace slice (>= p.n_edges: one piece, the setup records of the whole list are still there)
 };
@@ -1793,6 +1821,9 @@ static void cost_modes(const ppgpu_ctx* c, CostLaunch& m) {
     // the sweep list: exactly where sweeps are shared.  Any other launch has a handful of unsweepable edges at most, and the kernel
     // that builds the list would cost it more than they do
     m.sweep_list = m.share && c->use_sweep_list;
+    // shared tracks: where there is a list to put the members behind, a grid to stop on, and room for the stop classes' half of the
+    // table of heads.  The Gaussian model has its own track arrays and forms no stop classes
+    m.tracks = m.sweep_list && c->share_tracks && !m.gaussian && c->rows > 0 && (long long)p.nverts * 2 * PP_SHARE_KEYS * PP_SHARE_STRIDE <= (1ll << 26);
 }
 
 // Reserves the workspace of the launch and wires it, and the modes the kernels look at, into m.p.
@@ -1840,7 +1871,8 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
     }
     if (m.share) {
         const unsigned* const table_was = c->share_head.p;
-        if ((rc = c->share_head.reserve((size_t)p.nverts * PP_SHARE_KEYS * PP_SHARE_STRIDE, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
+        // (with shared tracks the table has a second half, the stop classes')
+        if ((rc = c->share_head.reserve((size_t)p.nverts * (m.tracks ? 2 : 1) * PP_SHARE_KEYS * PP_SHARE_STRIDE, false, st)) || (rc = c->share_of.reserve(total, false, st))) return rc;
         if (c->share_head.p != table_was) c->share_head_stale = true;      // (a grown table is a new one: nothing is kept)
         p.share_head = c->share_head.p; p.share_of = c->share_of.p;
     }
@@ -1848,6 +1880,12 @@ static int cost_workspace(ppgpu_ctx* c, CostLaunch& m) {
         if ((rc = c->sweep_list.reserve(ws + PP_WPB, false, st))) return rc;      // (every wave of the pose sweep's grid reads "its" entry)
         p.sweep_list = c->sweep_list.p;
         p.approach_list = c->approach_list ? 1 : 0;       // (m.share: the prepasses run and the live list exists)
+    }
+    if (m.tracks) {
+        const int* const stops_was = c->arc_stop.p;
+        if ((rc = c->arc_stop.reserve((size_t)p.nverts * PP_SHARE_KEYS, false, st)) || (rc = c->stop_of.reserve(ws, false, st)) || (rc = c->stop_list.reserve(ws, false, st))) return rc;
+        if (c->arc_stop.p != stops_was) c->arc_stops_stale = true;
+        p.arc_stop = c->arc_stop.p; p.stop_of = c->stop_of.p; p.stop_list = c->stop_list.p;
     }
     return PPGPU_OK;
 }
@@ -1895,6 +1933,11 @@ static int cost_slice(ppgpu_ctx* c, const CostLaunch& m) {
     }
     void (*pose)(PPParams) = m.sweep_list ? (m.gaussian ? pp_k_pose_sweep_gaussian : pp_k_pose_sweep) : (m.gaussian ? pp_k_pose_sweep_gaussian_direct : pp_k_pose_sweep_direct);
     hipLaunchKernelGGL(pose, dim3((unsigned)((p.n_edges + PP_WPB - 1) / PP_WPB)), dim3(PP_WPB * 64), 0, st, p);   // a wave per edge
+    // (timed with the pose sweep: the stop members take their head's track; the count is on the device, the grid strides over it)
+    if (m.tracks) {
+        const long long need = (p.n_edges + 256 / PP_TF_LANES - 1) / (256 / PP_TF_LANES);
+        hipLaunchKernelGGL(pp_k_track_fanout, dim3((unsigned)(need < PP_TF_GRID ? need : PP_TF_GRID)), dim3(256), 0, st, p);
+    }
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_POSED], st));
     if (m.prepasses) hipLaunchKernelGGL(p.approach_list ? pp_k_approach_events : pp_k_approach_events_direct, dim3((unsigned)((p.n_edges + PP_APPROACH_THREADS - 1) / PP_APPROACH_THREADS)), dim3(PP_APPROACH_THREADS), 0, st, p);
     if (c->timing) HIP_TRY(hipEventRecord(ev[EV_APPROACHED], st));
@@ -1989,13 +2032,28 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     if (c->timing) c->ev_slot = (int)(c->ev_launches % PP_TIMING_RING);     // the next set of the ring
     for (double& ms : c->ms_ring[c->ev_slot]) ms = 0;
     c->live_earlier_slices = 0;
-    c->last_launch_shared = false; c->last_launch_listed = false;
+    c->last_launch_shared = false; c->last_launch_listed = false; c->last_launch_tracks = false;
     // the heads of the classes: none yet.  Per launch, not per slice: a member in a later slice finds the head of an earlier one.
     // The launch before left the table so (pp_k_share_fanout, its last kernel); only a table that is new, or that a launch which
     // failed between its slices may have left with heads in it, is filled here, all of it.  Stale until this launch's fan-out is queued.
     if (m.share) {
         if (c->share_head_stale) HIP_TRY(hipMemsetAsync(c->share_head.p, 0xff, c->share_head.cap * sizeof(unsigned), c->stream));
         c->share_head_stale = true;
+    }
+    // the stops of the classes' first arcs, where the vertices, the grid, the keep-out limit or the configuration changed since they
+    // were last walked (a wave per class; a planner's round trip pays it once per vertex set, a loop over one vertex set once)
+    if (m.tracks && c->arc_stops_stale) {
+        TraceTimer& tm = c->t_arc_stops;
+        tm.ms_earlier = 0;
+        tm.timed = false;
+        if (c->timing) {
+            if (!tm.ev[0])
+                for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&tm.ev[i]));
+            HIP_TRY(hipEventRecord(tm.ev[0], c->stream));
+        }
+        hipLaunchKernelGGL(pp_k_arc_stops, dim3((unsigned)(((long long)p.nverts * PP_SHARE_KEYS + PP_WPB - 1) / PP_WPB)), dim3(PP_WPB * 64), 0, c->stream, p);
+        if (c->timing) { HIP_TRY(hipEventRecord(tm.ev[1], c->stream)); tm.timed = true; }
+        c->arc_stops_stale = false;
     }
     c->last_launch_slices = 0;
     for (long long e0 = 0; e0 < total; e0 += m.slice) {
@@ -2007,7 +2065,7 @@ static int launch_cost(ppgpu_ctx* c, const PPParams& asked, CostLaunch* done = n
     p.e_base = 0;
     p.n_edges = total;
     if ((rc = cost_heuristic_tail(c, m))) return rc;
-    c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share; c->last_launch_listed = m.sweep_list;
+    c->last_launch_edges = total; c->last_launch_packed = m.packed; c->last_launch_shared = m.share; c->last_launch_listed = m.sweep_list; c->last_launch_tracks = m.tracks;
     if (c->timing) { HIP_TRY(hipEventRecord(c->ev_ring[c->ev_slot][EV_END], c->stream)); c->ev_launches++; }
     HIP_TRY(hipGetLastError());
     if (m.share) c->share_head_stale = false;             // (pp_k_share_fanout is in the stream)
@@ -2198,6 +2256,7 @@ int ppgpu_last_contact_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace
 int ppgpu_last_clearance_trace_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_clearance, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_grid_distance_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_dist, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_keepout_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_keepout, ms) : fail(PPGPU_EINVAL, "null argument"); }
+int ppgpu_last_arc_stops_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_arc_stops, ms) : fail(PPGPU_EINVAL, "null argument"); }
 int ppgpu_last_tsp_table_timing(ppgpu_ctx* c, double* ms) { return c ? trace_timing(c, c->t_tsp, ms) : fail(PPGPU_EINVAL, "null argument"); }
 
 // A device list in, device records out: cost the list, then trace it.
@@ -2479,6 +2538,7 @@ int ppgpu_expand_host(ppgpu_ctx* c, int32_t nv, const ppgpu_vertex* hv, int32_t 
     hipLaunchKernelGGL(pp_k_expand_unpack, dim3((unsigned)((in_bytes / 8 + nv + 255) / 256)), dim3(256), 0, st, c->dstage_in.p, nv, n_ribbons,
                        c->verts.p, c->ribbons.p, c->sx.p + ns, c->sy.p + ns, c->sh.p + ns, c->s_bytes.p, c->expand.fallbacks.p);
     c->nverts = nv; c->nribbons = n_ribbons; c->max_vertex_ribbons = maxr; c->n_extra = nv;
+    c->arc_stops_stale = true;
     hipLaunchKernelGGL(pp_k_time_grid, dim3((unsigned)nv), dim3(64), 0, st, c->verts.p, nv, c->cfg.start_state_time,
                        c->cfg.collision_checking_increment, c->cfg.max_speed, c->ng, c->tgrid.p);
     // ---- k nearest per (vertex, radius), on the device
@@ -2591,6 +2651,7 @@ int ppgpu_cost_plans_host(ppgpu_ctx* c, int32_t n_plans, const int32_t* offs, co
         const int nNow = nAt[(size_t)d], nNext = d + 1 < maxLegs ? nAt[(size_t)d + 1] : 0;
         PPParams p = list_params(c, nNow, nullptr, d_legs + at[(size_t)d], d_results + at[(size_t)d], d_child + at[(size_t)d] * (size_t)stride * 4, stride);
         p.nverts = run0 + n1;                             // the running vertices count as open ones
+        c->arc_stops_stale = true;                        // (given curves form no stop classes; the vertices past run0 change under the table all the same)
         if ((rc = launch_cost(c, p))) return rc;
         PPChainArgs a;
         a.results = p.out; a.child = p.child; a.stride = stride;

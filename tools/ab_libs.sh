@@ -28,6 +28,8 @@ ms=[json.loads(l)['ms_per_step'] for l in open(os.environ["out"]+f"/ab_{sys.argv
 run={k:round(d[k],1) for k in ('pp_k_cover_sweep','pp_k_pose_sweep','pp_k_plan_skips','pp_k_approach_events','pp_k_cover_finish')}
 # the head of a launch (profiles/solve_icache.txt): the solve, the marking, the fan-out, and the table's reset where a library still has one
 run.update({k:round(d.get(k,0.0),1) for k in ('pp_k_solve_edges','pp_k_mark_sweeps','pp_k_share_fanout')})
+# shared tracks (profiles/arc_stops.txt): the members' copy per launch, and the arc walk, which a run's first launch alone queues
+run.update({k:round(d.get(k,0.0),1) for k in ('pp_k_track_fanout','pp_k_arc_stops')})
 run['fill']=round(sum(v for k,v in d.items() if 'fillBuffer' in k),1)
 run['solve+mark+fanout+fill']=round(run['pp_k_solve_edges']+run['pp_k_mark_sweeps']+run['pp_k_share_fanout']+run['fill'],1)
 print(sys.argv[1], run, 'ms_per_step', ms)
