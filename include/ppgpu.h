@@ -830,6 +830,66 @@ int ppgpu_ribbon_water_host(ppgpu_ctx* ctx, int32_t n, const double* h_ribbons4,
  * that was not timed since ppgpu_enable_timing.  PPGPU_ESTATE with timing off.  Waits for the stream. */
 int ppgpu_last_water_timing(ppgpu_ctx* ctx, double* ms_map, double* ms_ribbons);
 
+/* ---------------------------------------------------------------- route by water */
+
+/* Which way the distance by water goes: the cheapest path that the water map of the current seed (above) holds implicitly, made
+ * explicit as a step map and walked on the device per query point.  Per route: its length, its turning points, its narrowest place
+ * and the direction in which it leaves the seed.  Everything is exact in integers; the only floating point is in the two metres fields.
+ * STEP CODES.  Codes 0 .. 7 stand for the offsets (dr, dc) = N(-1,0), S(+1,0), W(0,-1), E(0,+1), NW(-1,-1), NE(-1,+1), SW(+1,-1), SE(+1,+1);
+ * the cost is PPGPU_WATER_STEP for codes 0-3 and PPGPU_WATER_DIAG for codes 4-7.  The opposite of a code: N<->S, W<->E, NW<->SE, NE<->SW.
+ * STEP MAP, one byte per cell over the water map wd: dir(cell) = PPGPU_ROUTE_NONE where wd == PPGPU_WATER_NONE, PPGPU_ROUTE_SEED on the
+ * seed's cell, otherwise the LOWEST code k whose neighbour lies in the grid, has a distance and satisfies
+ * wd(neighbour) + cost(k) == wd(cell).  One such neighbour always exists (wd is the fixed point of the relaxation); the lowest code
+ * prefers a straight step on a tie.  The map is canonical: any correct algorithm writes the same bytes.
+ * APPROACH CELL of a query point with limit lim2: A is the cell Map::isBlocked puts the point in (GridWorldMap.cpp:84-93); a point
+ * outside the grid has none.  With lim2 == 0, B = A.  With lim2 >= 1, B is the cell of the grid with gap2(A, B) < lim2 (gap2 as under
+ * "chart clearance") that has the smallest wd; on a tie the lowest row-major index wins.  lim2 > PPGPU_WATER_MAX_LIM2 is refused.  For a
+ * ribbon's sample, wd(B) is its approach distance ad.
+ * ROUTE.  The cells from B to the seed's cell, following dir: wd falls by the step's cost at every step, so the route ends after at most
+ * wd(B) / 12 steps.  A TURN is a cell of the route, other than its two ends, whose incoming and outgoing codes differ.  The VERTICES are
+ * the seed's cell, the turns and B, listed FROM THE SEED: turns + 2 of them, 1 when B is the seed's cell, 0 without an approach cell.
+ * RECORD.  first_dir = code | flags << 8: the code of the first step leaving the seed (the opposite of the walk's last code),
+ * PPGPU_ROUTE_SEED when B is the seed's cell, 0xFF for a dry record; the PPGPU_WR_* flags are in bits 8-15.  min_gap2 is the smallest
+ * value of the distance map of the occupancy grid AS SET (ppgpu_get_grid_distance, built on first use) over all cells of the route,
+ * both ends included; min_gap2_cell the cell that attains it, on a tie the one nearest the seed along the route.  A dry record has
+ * metres and narrowest_metres +infinity, min_gap2 and min_gap2_cell NONE, wd and from_cell NONE and all counts 0.
+ * VERTICES ARRAY: n * vertex_stride cell indices; slot i * vertex_stride + j holds vertex j of route i, seed first, for
+ * j < vertices_written = min(vertices, vertex_stride); the other slots are left as they were.  A truncated route keeps the end near
+ * the seed, which is where the vehicle goes first.
+ * Lazy and derived: the step map (one byte per cell) is built by the first call below after the water map was built or rebuilt; a
+ * moved seed, a new grid and a changed keep-out limit make it stale through the water map.  A handle that never makes these calls
+ * allocates and launches nothing for them. */
+#define PPGPU_ROUTE_NONE 0xFFu
+#define PPGPU_ROUTE_SEED 8u
+#define PPGPU_WR_DRY       0x01u  /* no approach cell has a distance */
+#define PPGPU_WR_OUTSIDE   0x02u  /* the point is outside the grid (implies PPGPU_WR_DRY) */
+#define PPGPU_WR_AT_SEED   0x04u  /* B is the seed's cell */
+#define PPGPU_WR_TRUNCATED 0x08u  /* vertices > vertex_stride */
+#define PPGPU_WR_NO_SEED   0x40u  /* the seed is blocked: nothing judged, cells NONE, counts 0, +infinity metres */
+#define PPGPU_WR_NO_MAP    0x80u  /* base Map: nothing judged, as above */
+typedef struct ppgpu_water_route_record {  /* 64 bytes */
+    uint32_t point_cell, from_cell;        /* A and B, row-major; PPGPU_WATER_NONE where there is none */
+    uint32_t wd, lim2;                     /* wd(B) (NONE without B); the limit as passed */
+    uint32_t straight_steps, diagonal_steps;   /* 12 * straight + 17 * diagonal == wd */
+    uint32_t turns, vertices;              /* vertices: the total, whatever the stride */
+    uint32_t vertices_written, first_dir;  /* min(vertices, vertex_stride); first_dir = code | flags << 8 (above) */
+    uint32_t min_gap2, min_gap2_cell;      /* above */
+    double metres;                         /* resolution * ((double)straight + (double)diagonal * sqrt(2)) */
+    double narrowest_metres;               /* resolution * sqrt((double)min_gap2) */
+} ppgpu_water_route_record;
+/* For tests and tools: the step map of the current seed, rows*cols bytes.  PPGPU_ESTATE without a seed; PPGPU_EINVAL without a grid
+ * (rows == 0) or when capacity < rows*cols.  Synchronous. */
+int ppgpu_get_grid_water_dirs(ppgpu_ctx* ctx, uint8_t* h_out, int64_t capacity);
+/* One record per point {x, y} of h_xy2 and up to vertex_stride vertices per route into h_vertices (may be NULL with vertex_stride 0).
+ * PPGPU_ESTATE without a water seed.  PPGPU_EINVAL for a NaN, n < 0, vertex_stride < 0, vertex_stride > 0 with h_vertices == NULL and
+ * lim2 > PPGPU_WATER_MAX_LIM2.  n == 0 is a no-op.  A blocked seed or the base Map gives records with PPGPU_WR_NO_SEED or
+ * PPGPU_WR_NO_MAP and no launch.  PPGPU_ECAPACITY if a walk ran into its bound of wd(B) / 12 + 2 rounds (it cannot).  Synchronous. */
+int ppgpu_water_routes_host(ppgpu_ctx* ctx, int64_t n, const double* h_xy2, uint32_t lim2, int32_t vertex_stride,
+                            ppgpu_water_route_record* h_records, uint32_t* h_vertices);
+/* Measurement aid: with timing on, the milliseconds of the last build of the step map and of the last route walk; -1 for each that
+ * was not timed since ppgpu_enable_timing.  PPGPU_ESTATE with timing off.  Waits for the stream. */
+int ppgpu_last_water_route_timing(ppgpu_ctx* ctx, double* ms_dirs, double* ms_routes);
+
 /* Number of edges a dense launch with these arguments produces. */
 int64_t ppgpu_dense_edge_count(int32_t nv, int64_t ns, uint32_t cfg_mask);
 

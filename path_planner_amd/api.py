@@ -117,6 +117,9 @@ def _load():
         "ppgpu_water_distance_at": (C.c_int, [vp, i64, vp, vp, vp]),
         "ppgpu_ribbon_water_host": (C.c_int, [vp, i32, vp, dbl, vp]),
         "ppgpu_last_water_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
+        "ppgpu_get_grid_water_dirs": (C.c_int, [vp, vp, i64]),
+        "ppgpu_water_routes_host": (C.c_int, [vp, i64, vp, u32, i32, vp, vp]),
+        "ppgpu_last_water_route_timing": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
         "ppgpu_dense_edge_count": (i64, [i32, i64, u32]),
         "ppgpu_best_edge": (C.c_int, [vp, i64, vp, i32, u64, vp]),
         "ppgpu_key_min": (C.c_int, [vp, i32, vp, vp]),
@@ -687,6 +690,35 @@ class Context:
         """(map build, ribbon walk) device milliseconds of the last of each, -1 where none was timed since enable_timing."""
         t = [C.c_double() for _ in range(2)]
         self._ck(LIB.ppgpu_last_water_timing(self._h, *[C.byref(x) for x in t]), "ppgpu_last_water_timing")
+        return tuple(x.value for x in t)
+
+    # ---- route by water: which way the distance by water goes, per query point
+    def get_grid_water_dirs(self, rows, cols):
+        """dir per cell, rows x cols uint8: the code of the step towards the seed (0..7 = N, S, W, E, NW, NE, SW, SE; the lowest
+        code on a tie), ROUTE_SEED on the seed's cell, ROUTE_NONE where there is no distance; for tests and tools."""
+        out = np.zeros((rows, cols), dtype=np.uint8)
+        self._ck(LIB.ppgpu_get_grid_water_dirs(self._h, _ptr(out), out.size), "ppgpu_get_grid_water_dirs")
+        return out
+
+    def water_routes(self, xy, lim2=0, vertex_stride=0, vertices=None):
+        """(records, vertices): one WATER_ROUTE_DTYPE record per point {x, y} and an (n, vertex_stride) uint32 array whose row i holds
+        the first vertices_written vertices of route i, the seed's cell first.  `vertices`: an array to write into (its other slots
+        are left as they were); a new one, filled with WATER_NONE, otherwise."""
+        from .types import WATER_ROUTE_DTYPE, WATER_NONE
+        pts = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n, stride = pts.shape[0], int(vertex_stride)
+        recs = np.zeros(n, dtype=WATER_ROUTE_DTYPE)
+        if vertices is None:
+            vertices = np.full((n, max(stride, 0)), WATER_NONE, dtype=np.uint32)
+        assert vertices.dtype == np.uint32 and vertices.flags.c_contiguous and vertices.size >= n * max(stride, 0)
+        self._ck(LIB.ppgpu_water_routes_host(self._h, n, _ptr(pts), int(lim2), stride, _ptr(recs), _ptr(vertices) if stride > 0 else None),
+                 "ppgpu_water_routes_host")
+        return recs, vertices
+
+    def last_water_route_timing(self):
+        """(step map build, route walk) device milliseconds of the last of each, -1 where none was timed since enable_timing."""
+        t = [C.c_double() for _ in range(2)]
+        self._ck(LIB.ppgpu_last_water_route_timing(self._h, *[C.byref(x) for x in t]), "ppgpu_last_water_route_timing")
         return tuple(x.value for x in t)
 
     @staticmethod

@@ -17,6 +17,7 @@
 #include "pp_k_keepout.h"      // pp_k_keepout_bits: the distance map thresholded into the effective grid of a keep-out margin
 #include "pp_k_reach.h"        // pp_k_reach_tiles / _merge / _flatten, pp_k_reach_bits, pp_k_reach_ribbons: which water a seed can reach
 #include "pp_k_water.h"        // pp_k_water_seed / _round / _totals, pp_k_water_distance_at, pp_k_water_ribbons: how far it is by water from a seed
+#include "pp_k_route.h"        // pp_k_water_dirs, pp_k_water_routes: which way the distance by water goes, per query point
 #include "pp_k_chain.h"        // pp_k_chain_advance
 #include "pp_k_tsp_table.h"    // pp_k_tsp_table_list, pp_k_tsp_table
 #include "pp_k_expand.h"       // pp_k_dubins_lengths, pp_k_select_nearest, the push-order pipeline, the round trip's pack / unpack

@@ -175,6 +175,13 @@ struct ppgpu_ctx {
     DevBuf<double> water_ribbons;       // {sx, sy, ex, ey, len, n} per ribbon of the last ppgpu_ribbon_water_host
     DevBuf<ppgpu_ribbon_water_record> water_records;
     TraceTimer t_water_map, t_water_ribbons;
+    // route by water (ppgpu.h): derived from the water map; nothing here is allocated, launched or timed before the first call of that section
+    DevBuf<uint8_t> route_dirs;         // the step map of the water map whose build number is route_dirs_build (0: none yet)
+    uint32_t route_dirs_build = 0;
+    DevBuf<double> route_points;        // {x, y} per query of the last ppgpu_water_routes_host
+    DevBuf<ppgpu_water_route_record> route_records;
+    DevBuf<uint32_t> route_vertices;    // [n][vertex_stride]
+    TraceTimer t_route_dirs, t_routes;
     // dynamic obstacles
     DevBuf<PPObst> obst;
     int n_obst = 0;
@@ -288,7 +295,8 @@ struct ppgpu_ctx {
         for (auto& set : ev_ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {t_steps.ev[0], t_steps.ev[1], t_cover.ev[0], t_cover.ev[1], t_contacts.ev[0], t_contacts.ev[1], t_clearance.ev[0], t_clearance.ev[1], t_tsp.ev[0], t_tsp.ev[1], t_dist.ev[0], t_dist.ev[1], t_keepout.ev[0], t_keepout.ev[1], t_arc_stops.ev[0], t_arc_stops.ev[1],
                              t_reach_labels.ev[0], t_reach_labels.ev[1], t_reach_gap.ev[0], t_reach_gap.ev[1], t_reach_ribbons.ev[0], t_reach_ribbons.ev[1],
-                             t_water_map.ev[0], t_water_map.ev[1], t_water_ribbons.ev[0], t_water_ribbons.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+                             t_water_map.ev[0], t_water_map.ev[1], t_water_ribbons.ev[0], t_water_ribbons.ev[1],
+                             t_route_dirs.ev[0], t_route_dirs.ev[1], t_routes.ev[0], t_routes.ev[1], ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {side_stream, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -414,6 +422,7 @@ int ppgpu_enable_timing(ppgpu_ctx* c, int32_t on) {
     c->t_arc_stops.timed = false;       // (... by the first timed walk of the classes' arcs: launch_cost)
     c->t_reach_labels.timed = c->t_reach_gap.timed = c->t_reach_ribbons.timed = false;   // (... by the first timed build or walk)
     c->t_water_map.timed = c->t_water_ribbons.timed = false;
+    c->t_route_dirs.timed = c->t_routes.timed = false;
     c->timing = on != 0;
     c->ev_launches = 0;
     return PPGPU_OK;
@@ -1300,6 +1309,113 @@ int ppgpu_last_water_timing(ppgpu_ctx* c, double* ms_map, double* ms_ribbons) {
     HIP_TRY(hipSetDevice(c->device));
     TraceTimer* tms[2] = {&c->t_water_map, &c->t_water_ribbons};
     double* outs[2] = {ms_map, ms_ribbons};
+    for (int i = 0; i < 2; i++) {
+        *outs[i] = -1.0;
+        if (!tms[i]->timed) continue;
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(tms[i]->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, tms[i]->ev[0], tms[i]->ev[1]));
+        *outs[i] = ms;
+    }
+    return PPGPU_OK;
+}
+
+// ------------------------------------------------------------------------------ route by water
+// The step map of the water map as it stands (rows > 0, a seed is set, the size was checked): water_ready first, then nothing when the
+// step map is that of the water map's build; otherwise one launch of pp_k_water_dirs.  A rebuilt water map has a new build number,
+// whatever made it stale (a moved seed, a new grid, a changed keep-out limit).
+static int route_dirs_ready(ppgpu_ctx* c) {
+    int rc = water_ready(c);
+    if (rc) return rc;
+    if (c->route_dirs_build == c->water_info.builds) return PPGPU_OK;
+    hipStream_t st = c->stream;
+    const size_t ncell = (size_t)c->rows * c->cols;
+    if ((rc = c->route_dirs.reserve(ncell, false, st))) return rc;
+    if ((rc = reach_timer_begin(c, c->t_route_dirs))) return rc;
+    hipLaunchKernelGGL(pp_k_water_dirs, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, c->water_wd.p, c->rows, c->cols, (long long)ncell, c->route_dirs.p);
+    if ((rc = reach_timer_end(c, c->t_route_dirs))) return rc;
+    HIP_TRY(hipGetLastError());
+    c->route_dirs_build = c->water_info.builds;
+    return PPGPU_OK;
+}
+
+int ppgpu_get_grid_water_dirs(ppgpu_ctx* c, uint8_t* h_out, int64_t capacity) {
+    if (!c || !h_out) return fail(PPGPU_EINVAL, "grid water dirs: null argument");
+    if (c->rows == 0) return fail(PPGPU_EINVAL, "grid water dirs: no grid is set");
+    if (capacity < (int64_t)c->rows * c->cols) return fail(PPGPU_EINVAL, "grid water dirs: capacity below rows * cols");
+    int rc = water_check_size(c, "grid water dirs");
+    if (rc) return rc;
+    if (!c->water_have_seed) return fail(PPGPU_ESTATE, "grid water dirs: ppgpu_set_water_seed must be called first");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = route_dirs_ready(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_out, c->route_dirs.p, (size_t)c->rows * c->cols, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PPGPU_OK;
+}
+
+int ppgpu_water_routes_host(ppgpu_ctx* c, int64_t n, const double* h_xy2, uint32_t lim2, int32_t vertex_stride, ppgpu_water_route_record* h_records,
+                            uint32_t* h_vertices) {
+    if (!c) return fail(PPGPU_EINVAL, "null context");
+    if (n < 0 || (n > 0 && (!h_xy2 || !h_records))) return fail(PPGPU_EINVAL, "water_routes: bad arguments");
+    if (vertex_stride < 0 || (vertex_stride > 0 && !h_vertices)) return fail(PPGPU_EINVAL, "water_routes: a vertex stride without a vertices array, or below 0");
+    if (lim2 > PPGPU_WATER_MAX_LIM2) return fail(PPGPU_EINVAL, "water_routes: lim2 above PPGPU_WATER_MAX_LIM2 (the window of a point would exceed 67 x 67 cells)");
+    for (int64_t i = 0; i < 2 * n; i++)
+        if (h_xy2[i] != h_xy2[i]) return fail(PPGPU_EINVAL, "water_routes: a point is not a number");
+    if (!c->water_have_seed) return fail(PPGPU_ESTATE, "water_routes: ppgpu_set_water_seed must be called first");
+    if (n == 0) return PPGPU_OK;
+    const bool nomap = c->rows == 0;
+    if (!nomap) {
+        int rc = water_check_size(c, "water_routes");
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = water_ready(c))) return rc;
+    }
+    if (nomap || c->water_map_cell == PPGPU_WATER_NONE) {            // nothing is judged
+        ppgpu_water_route_record r{};
+        r.point_cell = r.from_cell = r.wd = r.min_gap2 = r.min_gap2_cell = PPGPU_WATER_NONE;
+        r.lim2 = lim2;
+        r.first_dir = PPGPU_ROUTE_NONE | ((nomap ? PPGPU_WR_NO_MAP : PPGPU_WR_NO_SEED) << 8);
+        r.metres = r.narrowest_metres = INFINITY;
+        for (int64_t i = 0; i < n; i++) h_records[i] = r;
+        return PPGPU_OK;
+    }
+    int reach = 0;                                                   // as for the ribbon walk: |dr|, |dc| of a window cell (0 for lim2 0)
+    while ((unsigned)(reach * reach) < lim2) reach++;
+    hipStream_t st = c->stream;
+    const size_t stride = (size_t)vertex_stride;
+    int rc;
+    if ((rc = grid_distance(c)) || (rc = route_dirs_ready(c)) || (rc = c->route_points.reserve((size_t)n * 2, false, st)) ||
+        (rc = c->route_records.reserve((size_t)n, false, st)) || (stride && (rc = c->route_vertices.reserve((size_t)n * stride, false, st))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->route_points.p, h_xy2, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    const PPGrid g{nullptr, c->rows, c->cols, c->wpr, c->res, 1.0 / c->res, nullptr};
+    if ((rc = reach_timer_begin(c, c->t_routes))) return rc;
+    hipLaunchKernelGGL(pp_k_water_routes, dim3((unsigned)((n + PP_WATER_WPB - 1) / PP_WATER_WPB)), dim3(PP_WATER_WPB * 64), 0, st, g, c->water_wd.p, c->route_dirs.p,
+                       c->grid_dist.p, (long long)n, c->route_points.p, c->water_map_cell, lim2, reach, (unsigned)vertex_stride, c->route_records.p,
+                       stride ? c->route_vertices.p : nullptr, c->water_words.p);
+    if ((rc = reach_timer_end(c, c->t_routes))) return rc;
+    HIP_TRY(hipGetLastError());
+    // the vertices come back whole and only the slots a route wrote are handed on: the others stay as the caller left them
+    std::vector<uint32_t> verts((size_t)n * stride);
+    unsigned long long error_word = 0;
+    HIP_TRY(hipMemcpyAsync(h_records, c->route_records.p, (size_t)n * sizeof(ppgpu_water_route_record), hipMemcpyDeviceToHost, st));
+    if (stride) HIP_TRY(hipMemcpyAsync(verts.data(), c->route_vertices.p, verts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&error_word, c->water_words.p + PP_WW_ERROR, sizeof error_word, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (error_word) return fail(PPGPU_ECAPACITY, "water_routes: a walk ran into its bound of wd / 12 + 2 rounds");
+    for (int64_t i = 0; i < n && stride; i++) {
+        const size_t count = std::min((size_t)h_records[i].vertices_written, stride);
+        std::copy_n(verts.data() + (size_t)i * stride, count, h_vertices + (size_t)i * stride);
+    }
+    return PPGPU_OK;
+}
+
+int ppgpu_last_water_route_timing(ppgpu_ctx* c, double* ms_dirs, double* ms_routes) {
+    if (!c || !ms_dirs || !ms_routes) return fail(PPGPU_EINVAL, "last_water_route_timing: null argument");
+    if (!c->timing) return fail(PPGPU_ESTATE, "last_water_route_timing: timing is off (ppgpu_enable_timing)");
+    HIP_TRY(hipSetDevice(c->device));
+    TraceTimer* tms[2] = {&c->t_route_dirs, &c->t_routes};
+    double* outs[2] = {ms_dirs, ms_routes};
     for (int i = 0; i < 2; i++) {
         *outs[i] = -1.0;
         if (!tms[i]->timed) continue;

@@ -68,6 +68,8 @@ public:
     void setPlanReach(bool on) { m_PlannerConfig.setPlanReach(on); }
     // PlannerConfig::setPlanWater: every cycle's Stats say how far it is by water from the start to every ribbon
     void setPlanWater(bool on) { m_PlannerConfig.setPlanWater(on); }
+    // PlannerConfig::setPlanWaterRoute: ... and which way round the breakwater that distance goes (with setPlanWater(true) only)
+    void setPlanWaterRoute(bool on) { m_PlannerConfig.setPlanWaterRoute(on); }
     // What the loop decided for a cycle, handed to an observer right before that cycle's plan() call (called on the planning
     // thread): the state it plans from (executive.cpp:114-118,217-268), how much of the last plan it hands back (:144-146), the
     // horizon after any back-off (:270-287), the time budget (:189-190), the ribbons left.  tests/test_gpu_mission.py compares these

@@ -27,6 +27,8 @@ struct ppgpu_ctx;
 struct ppgpu_edge_result;   // include/ppgpu.h
 struct ppgpu_vertex;
 struct ppgpu_wrapper_edge;
+struct ppgpu_ribbon_water_record;
+struct ppgpu_water_route_record;
 
 namespace ppamd {
 
@@ -187,6 +189,19 @@ public:
             int RibbonsDry = 0;                                // no sample can be approached
             int NearestRibbon = -1;                            // the smallest minAd (the lowest index on a tie); -1 without a wet ribbon
             double NearestWaterMetres = -1, NearestStraightMetres = -1;   // its nearestMetres; the straight line from the start to its nearestSample point
+            // PlannerConfig::setPlanWaterRoute (ppgpu.h, "route by water"): which way those distances go.  One route per ribbon, to the
+            // approach cell of its nearestSample point (sample 0, and a dry route, without a wet sample): the fields of
+            // ppgpu_water_route_record, flags and the code of firstDir taken apart, and the vertices (the seed's cell, the turns, the
+            // approach cell; at most 256, the seed's end kept) as the centres of their cells.  Empty with that switch off.
+            struct RouteReport {
+                enum : uint32_t { Dry = 0x01, Outside = 0x02, AtSeed = 0x04, Truncated = 0x08, NoSeed = 0x40, RouteNoMap = 0x80 };   // PPGPU_WR_*
+                uint32_t pointCell = None, fromCell = None, wd = None, lim2 = 0, straightSteps = 0, diagonalSteps = 0, turns = 0, vertices = 0;
+                uint32_t verticesWritten = 0, firstDir = 0xFF, flags = 0, minGap2 = None, minGap2Cell = None;
+                double metres = 0, narrowestMetres = 0;
+                std::vector<std::pair<double, double>> Vertices;   // (x, y) = ((c + 0.5) * resolution, (r + 0.5) * resolution), from the seed
+            };
+            std::vector<RouteReport> Routes;
+            int NearestRoute = -1;                             // the index into Routes of NearestRibbon; -1 without one or with the switch off
         };
         WaterReport Water;
         // The vertices the walk over the previous plan made (AStarPlanner.cpp:46-59), in order: what each leg costs in this cycle's world
@@ -341,6 +356,10 @@ public:
     const void* gridOf = nullptr;
     unsigned long gridVersion = 0;
     double gridResolution = 0;             // cell size of the grid the device holds (0: the base Map, no grid), whichever call uploaded it
+    int gridRows = 0, gridCols = 0;        // ... and its shape
+    // ppgpu_water_routes_host against the water map of the handle's current seed: one record per point {x, y} and up to `stride`
+    // vertices per route in vertices[i * stride ...] (slots no route wrote hold PPGPU_WATER_NONE).  Throws std::runtime_error.
+    std::vector<ppgpu_water_route_record> waterRoutes(const std::vector<double>& pointsXY, uint32_t lim2, int stride, std::vector<uint32_t>& vertices);
     // round-trip result blocks not referred to by any planner any more are handed out again (used by this context's thread only)
     std::vector<std::shared_ptr<TripBlock>> tripPool;
     std::shared_ptr<TripBlock> takeTripBlock(size_t nEdges, size_t childDoubles);
@@ -462,6 +481,7 @@ private:
     Node beginCall(const RibbonManager& ribbonManager, const State& start);      // shared with evaluatePlans
     void reportReach(const State& start);                                         // ... PlannerConfig::planReach from the first context (after applyKeepout)
     void reportWater(const State& start);                                         // ... PlannerConfig::planWater, likewise
+    void reportWaterRoutes(Stats::WaterReport& r, const std::vector<ppgpu_ribbon_water_record>& recs);   // ... PlannerConfig::planWaterRoute, into reportWater's report
     void applyKeepout(const State& start);                                        // ... PlannerConfig::keepoutMargin on every context
     void initSampler(const State& start, unsigned long seed);
     struct WalkedLegs;                     // the previous-plan leg filter

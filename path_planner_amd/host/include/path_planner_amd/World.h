@@ -279,6 +279,12 @@ public:
     // with it off nothing changes.
     bool planWater() const { return m_PlanWater; }
     void setPlanWater(bool on) { m_PlanWater = on; }
+    // Which way the distance by water goes (Planner::Stats::WaterReport::Routes): per ribbon the cheapest route through free cells from
+    // the start to where its nearest sample can be approached, with its length, its turning points, its narrowest place and the
+    // direction in which it leaves the start (ppgpu.h, "route by water").  It has effect only together with setPlanWater(true); it
+    // reads the world and changes nothing: plan() returns the same plan and every other statistic with it on.  Off by default.
+    bool planWaterRoute() const { return m_PlanWaterRoute; }
+    void setPlanWaterRoute(bool on) { m_PlanWaterRoute = on; }
     // The previous plan (AStarPlanner.cpp:46-59) costed by ONE device call (ppgpu_cost_plans_host: every leg starts from the vertex
     // the leg before left on the device) instead of one upload and one costing round trip per leg.  Same nodes, same search.  Off by
     // default.
@@ -301,7 +307,7 @@ private:
     bool m_UseBrownPaths = false;
     bool m_DeadlineGuard = true;
     bool m_Visualizations = false;
-    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false, m_PlanReach = false, m_PlanWater = false;
+    bool m_DeviceTrajectories = false, m_PlanTrace = false, m_PlanCoverage = false, m_PlanContacts = false, m_PlanClearance = false, m_ChainedPreviousPlan = false, m_PlanReach = false, m_PlanWater = false, m_PlanWaterRoute = false;
     double m_PlanClearanceMargin = 0, m_KeepoutMargin = 0;
     int m_DeviceTspTable = 0;
     Visualizer::SharedPtr m_Visualizer;

@@ -446,6 +446,7 @@ static bool uploadSnapshot(const std::vector<std::shared_ptr<GpuContext>>& ctxs,
             ctx->gridOf = nullptr; ctx->gridVersion = 0;       // until the upload below has succeeded
             check(ppgpu_set_grid(h, rows ? cells.data() : nullptr, rows, cols, res), "ppgpu_set_grid");
             ctx->gridResolution = rows ? res : 0;
+            ctx->gridRows = rows; ctx->gridCols = rows ? cols : 0;
             if (mapVersion != 0) { ctx->gridOf = (const void*)map; ctx->gridVersion = mapVersion; }
         }
         if (om.deviceModel() == PPGPU_OBST_GAUSSIAN)
@@ -1352,7 +1353,55 @@ void GpuAStarPlanner::reportWater(const State& start) {
         r.NearestWaterMetres = d.nearest_metres;
         r.NearestStraightMetres = std::sqrt(px * px + py * py);
     }
+    if (m_Config.planWaterRoute()) reportWaterRoutes(r, recs);
     m_Stats.Water = std::move(r);
+}
+
+std::vector<ppgpu_water_route_record> GpuContext::waterRoutes(const std::vector<double>& pointsXY, uint32_t lim2, int stride, std::vector<uint32_t>& vertices) {
+    const size_t n = pointsXY.size() / 2;
+    std::vector<ppgpu_water_route_record> recs(n);
+    vertices.assign(n * (size_t)std::max(stride, 0), PPGPU_WATER_NONE);
+    check(ppgpu_water_routes_host(m_Handle, (int64_t)n, pointsXY.data(), lim2, stride, recs.data(), vertices.empty() ? nullptr : vertices.data()), "ppgpu_water_routes_host");
+    return recs;
+}
+
+// WaterReport::Routes: ONE device call, query i = ribbon i's nearestSample point (sample 0 without a wet one), clamped to the grid as
+// the ribbon walk clamps it (the coordinates into [0, width] x [0, height], then the cell's indices to the last row and column) and
+// handed over as the centre of that cell.  The limit is the records' lim2, the stride 256.
+void GpuAStarPlanner::reportWaterRoutes(Stats::WaterReport& r, const std::vector<ppgpu_ribbon_water_record>& recs) {
+    const int n = (int)recs.size();
+    if (n == 0) return;
+    const double res = m_Ctx->gridResolution;
+    const int rows = m_Ctx->gridRows, cols = m_Ctx->gridCols;
+    std::vector<double> points((size_t)n * 2, 0.0);
+    for (int i = 0; i < n && rows > 0; i++) {
+        const ppgpu_ribbon_water_record& d = recs[(size_t)i];
+        const double* q = m_RibbonManager.rows() + 4 * (size_t)i;
+        const double t = d.samples > 1u ? (double)std::max(d.nearest_sample, 0) / (double)(d.samples - 1u) : 0.0;
+        const double w = (double)cols * res, h = (double)rows * res;
+        const double x = std::min(std::max(q[0] + (q[2] - q[0]) * t, 0.0), w), y = std::min(std::max(q[1] + (q[3] - q[1]) * t, 0.0), h);
+        const size_t c = std::min((size_t)(x / res), (size_t)cols - 1), rw = std::min((size_t)(y / res), (size_t)rows - 1);
+        points[2 * (size_t)i] = ((double)c + 0.5) * res;
+        points[2 * (size_t)i + 1] = ((double)rw + 0.5) * res;
+    }
+    constexpr int kStride = 256;
+    std::vector<uint32_t> vertices;
+    const std::vector<ppgpu_water_route_record> routes = m_Ctx->waterRoutes(points, recs[0].lim2, kStride, vertices);
+    r.Routes.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ppgpu_water_route_record& d = routes[(size_t)i];
+        Stats::WaterReport::RouteReport& o = r.Routes[(size_t)i];
+        o.pointCell = d.point_cell; o.fromCell = d.from_cell; o.wd = d.wd; o.lim2 = d.lim2;
+        o.straightSteps = d.straight_steps; o.diagonalSteps = d.diagonal_steps; o.turns = d.turns; o.vertices = d.vertices;
+        o.verticesWritten = d.vertices_written; o.firstDir = d.first_dir & 0xFFu; o.flags = d.first_dir >> 8;
+        o.minGap2 = d.min_gap2; o.minGap2Cell = d.min_gap2_cell; o.metres = d.metres; o.narrowestMetres = d.narrowest_metres;
+        o.Vertices.reserve(d.vertices_written);
+        for (uint32_t j = 0; j < d.vertices_written; j++) {
+            const uint32_t v = vertices[(size_t)i * kStride + j];
+            o.Vertices.emplace_back(((double)(v % (uint32_t)cols) + 0.5) * res, ((double)(v / (uint32_t)cols) + 0.5) * res);
+        }
+    }
+    r.NearestRoute = r.NearestRibbon;
 }
 
 GpuAStarPlanner::Node GpuAStarPlanner::beginCall(const RibbonManager& ribbonManager, const State& start) {

@@ -74,6 +74,7 @@ int main(int argc, char** argv) {
     int flags[3] = {0, 0, 0};
     double planningTime = 0.1, maxSeconds = 60, keepoutMargin = 0;
     int speculation = 16;
+    bool planWater = false, planWaterRoute = false;
     std::vector<int> devices;
     std::string line;
     while (std::getline(in, line)) {
@@ -90,6 +91,11 @@ int main(int argc, char** argv) {
         else if (k == "speculation") s >> speculation;
         else if (k == "keepout_margin") s >> keepoutMargin;      // metres (Executive::setKeepoutMargin)
         else if (k == "devices") { int d; while (s >> d) devices.push_back(d); }
+        else if (k == "cfg") {                                   // cfg plan_water 0|1, cfg plan_water_route 0|1 (Executive::setPlanWater, ::setPlanWaterRoute)
+            std::string name; double v = 0; s >> name >> v;
+            if (name == "plan_water") planWater = v != 0;
+            else if (name == "plan_water_route") planWaterRoute = v != 0;
+        }
     }
     SimulatedVehicle vehicle(start);
     vehicle.setLookahead(planningTime);
@@ -98,6 +104,8 @@ int main(int argc, char** argv) {
     exec.setSpeculation(speculation);
     if (!devices.empty()) exec.setDevices(devices);
     exec.setKeepoutMargin(keepoutMargin);
+    exec.setPlanWater(planWater);
+    exec.setPlanWaterRoute(planWaterRoute);
     exec.setConfiguration(cfg[0], cfg[1], cfg[2], cfg[3], cfg[4], (int)cfg[5], (int)cfg[6], cfg[7], cfg[8], cfg[9], (int)cfg[10], flags[0] != 0, flags[1] != 0,
                           flags[2] != 0, false);
     if (!mapFile.empty()) exec.refreshMap(mapFile, 0, 0);

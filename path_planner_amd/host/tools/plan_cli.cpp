@@ -20,6 +20,10 @@
 //                  ribbon; adds water_cells, water_max_metres, water_seed_blocked, water_rounds, ribbons_dry, nearest_ribbon_by_water,
 //                  nearest_ribbon_water_metres and nearest_ribbon_straight_metres to the JSON, and to every plan under evaluate) |
 //                  plan_water_file path (with cfg plan_water 1: one line per ribbon of the call) |
+//                  cfg plan_water_route 1 (PlannerConfig::setPlanWaterRoute, with cfg plan_water 1: which way the distance by water goes;
+//                  adds water_route_metres, water_route_turns, water_route_vertices, water_route_truncated, water_route_narrowest_metres
+//                  and water_route_first_dir of the ribbon nearest by water to the JSON, and to every plan under evaluate) |
+//                  plan_water_route_file path (with both: one line per vertex of every ribbon's route, from the start) |
 //                  time_remaining T | prev qi0 qi1 qi2 p0 p1 p2 rho type speed start end | repeat n |
 //                  sharded_batch attempts seed   (instead of plan(): one iteration's batch, sample-sharded over `devices`: ShardedIteration)
 //                  cfg chained_previous_plan 0|1 (PlannerConfig::setChainedPreviousPlan; naming it at all adds round_trips, prologue_trips,
@@ -96,6 +100,23 @@ static std::string waterKeys(const Planner::Stats::WaterReport& w) {
     return buf;
 }
 
+// ", water_route_metres ..., ..., water_route_first_dir ..." of the route to the ribbon nearest by water (Stats::Water.Routes[NearestRoute]):
+// its length, its turns, its vertices and whether the list was cut, its narrowest place and the code of the step that leaves the start
+// (-1 for the numbers, false, without a wet ribbon)
+static std::string waterRouteKeys(const Planner::Stats::WaterReport& w) {
+    char buf[420];
+    if (w.NearestRoute < 0) {
+        std::snprintf(buf, sizeof buf, ", \"water_route_metres\": -1, \"water_route_turns\": -1, \"water_route_vertices\": -1, \"water_route_truncated\": false, "
+                      "\"water_route_narrowest_metres\": -1, \"water_route_first_dir\": -1");
+        return buf;
+    }
+    const auto& r = w.Routes[(size_t)w.NearestRoute];
+    std::snprintf(buf, sizeof buf, ", \"water_route_metres\": %.17g, \"water_route_turns\": %u, \"water_route_vertices\": %u, \"water_route_truncated\": %s, "
+                  "\"water_route_narrowest_metres\": %.17g, \"water_route_first_dir\": %u",
+                  r.metres, r.turns, r.vertices, (r.flags & Planner::Stats::WaterReport::RouteReport::Truncated) ? "true" : "false", r.narrowestMetres, r.firstDir);
+    return buf;
+}
+
 // One report file: rows(f, s) prints the lines of segment s.  No path, no file; -> false (and the complaint) when it cannot be written.
 template <class Rows>
 static bool writeReport(const std::string& path, size_t segments, Rows rows) {
@@ -131,7 +152,7 @@ int main(int argc, char** argv) {
     long long shardedAttempts = 0;
     unsigned long shardedSeed = 7;
     int failShard = -1;
-    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planReachPath, planWaterPath, planLogPath;
+    std::string cycleLogPath, planTracePath, planCoveragePath, planContactsPath, planClearancePath, planReachPath, planWaterPath, planWaterRoutePath, planLogPath;
     bool chainNamed = false, tableNamed = false, evaluate = false, inBlock = false;
     std::vector<DubinsPlan> candidates;
     long replanClockCalls = 0;
@@ -161,6 +182,7 @@ int main(int argc, char** argv) {
             else if (name == "keepout_margin") config.setKeepoutMargin(v);
             else if (name == "plan_reach") config.setPlanReach(v != 0);
             else if (name == "plan_water") config.setPlanWater(v != 0);
+            else if (name == "plan_water_route") config.setPlanWaterRoute(v != 0);
             else if (name == "device_trajectories") config.setDeviceTrajectories(v != 0);
             else if (name == "chained_previous_plan") { config.setChainedPreviousPlan(v != 0); chainNamed = true; }
             else if (name == "device_tsp_table") { config.setDeviceTspTable((int)v); tableNamed = true; }
@@ -195,6 +217,7 @@ int main(int argc, char** argv) {
         } else if (k == "plan_clearance_file") { s >> planClearancePath;   // segment clearance time x y step gap2 below_steps first_below_time flags
         } else if (k == "plan_reach_file") { s >> planReachPath;   // ribbon length pitch samples out_samples first_out last_out min_rgap2 max_rgap2 lim2 out_length flags
         } else if (k == "plan_water_file") { s >> planWaterPath;   // ribbon length pitch samples wet_samples nearest_sample farthest_sample min_ad max_ad start_ad end_ad lim2 flags nearest_metres
+        } else if (k == "plan_water_route_file") { s >> planWaterRoutePath;   // ribbon j x y
         } else if (k == "plan_log") { s >> planLogPath;
         } else if (k == "replan_clock_calls") { s >> replanClockCalls;
         } else if (k == "evaluate") { evaluate = true;
@@ -269,6 +292,7 @@ int main(int argc, char** argv) {
                 if (config.keepoutMargin() != 0) std::printf("%s", keepoutKeys(e.keepout).c_str());
                 if (config.planReach()) std::printf("%s", reachKeys(e.reach).c_str());
                 if (config.planWater()) std::printf("%s", waterKeys(e.water).c_str());
+                if (config.planWater() && config.planWaterRoute()) std::printf("%s", waterRouteKeys(e.water).c_str());
                 std::printf("}");
             }
             std::printf("]}\n");
@@ -488,6 +512,13 @@ int main(int argc, char** argv) {
                     std::fprintf(f, "%zu %.17g %.17g %u %u %d %d %u %u %u %u %u %u %.17g\n", rb, r.length, r.pitch, r.samples, r.wetSamples, r.nearestSample,
                                  r.farthestSample, r.minAd, r.maxAd, r.startAd, r.endAd, r.lim2, r.flags, r.nearestMetres);
                 })) return 2;
+            if (config.planWaterRoute()) {
+                tail += waterRouteKeys(st.Water);
+                if (!writeReport(planWaterRoutePath, st.Water.Routes.size(), [&](FILE* f, size_t rb) {
+                        const auto& vs = st.Water.Routes[rb].Vertices;
+                        for (size_t j = 0; j < vs.size(); j++) std::fprintf(f, "%zu %zu %.17g %.17g\n", rb, j, vs[j].first, vs[j].second);
+                    })) return 2;
+            }
         }
         if (config.planTrace()) {
             size_t nSteps = 0;

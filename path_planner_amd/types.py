@@ -135,6 +135,17 @@ RIBBON_WATER_DTYPE = np.dtype([
 ])
 assert RIBBON_WATER_DTYPE.itemsize == 64
 
+# route by water (ppgpu_get_grid_water_dirs, ppgpu_water_routes_host): the step map's codes 0..7 = N, S, W, E, NW, NE, SW, SE, and
+# struct ppgpu_water_route_record, 64 bytes, per query point.  first_dir = code | WR_* << 8
+ROUTE_NONE, ROUTE_SEED = 0xFF, 8
+WR_DRY, WR_OUTSIDE, WR_AT_SEED, WR_TRUNCATED, WR_NO_SEED, WR_NO_MAP = 0x01, 0x02, 0x04, 0x08, 0x40, 0x80
+WATER_ROUTE_DTYPE = np.dtype([
+    ("point_cell", "<u4"), ("from_cell", "<u4"), ("wd", "<u4"), ("lim2", "<u4"), ("straight_steps", "<u4"), ("diagonal_steps", "<u4"),
+    ("turns", "<u4"), ("vertices", "<u4"), ("vertices_written", "<u4"), ("first_dir", "<u4"), ("min_gap2", "<u4"), ("min_gap2_cell", "<u4"),
+    ("metres", "<f8"), ("narrowest_metres", "<f8"),
+])
+assert WATER_ROUTE_DTYPE.itemsize == 64
+
 
 def edge_pack(vertex, target, cfg):
     """ppgpu_edge_pack()."""
